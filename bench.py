@@ -8,6 +8,11 @@ of B utterances per GPU.  N>1: one process per GPU (torch.distributed, RCCL), ut
 independent so ranks shard them with no data-path collective (weak scaling).
 
 Prints ONE JSON line on rank 0.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times the K steps of the headline and prints
+its line.  `--full` adds everything else the default run measures: the CPU baseline, the write-fill ceiling, the
+ragged-M1 and M1' variants and the train-step, decode and MBR-step legs.  `--dump-outputs DIR` writes what the last
+timed step returned (costs and a fixed, seeded sample of the gradient) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -88,6 +93,26 @@ def make_inputs(B, T, U, V, dev, seed):
     tl = torch.full((B,), T, dtype=torch.int32, device=dev)
     ul = torch.full((B,), U, dtype=torch.int32, device=dev)
     return lp, labels, tl, ul
+
+
+DUMP_SAMPLE = 1 << 21      # elements kept of an output larger than that: 8 MB of float32 (+ 16 MB of float64 positions)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the arrays the timed path returned in its last step, as DIR/<name>.npy in float32 (float64 stays
+    float64).  An output of more than DUMP_SAMPLE elements is written as a sample of its flattened elements at positions
+    drawn from a fixed seed -- the same positions in every run of the same shape -- next to those positions
+    (DIR/<name>_index.npy, float64, exact below 2^53)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(20240613)
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g, dtype=torch.int64).sort().values
+            np.save(os.path.join(dirname, name + "_index.npy"), idx.numpy().astype(np.float64))
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
 
 
 def cpu_baseline(lp, labels, tl, ul, n_utts, min_seconds=10.0):
@@ -846,8 +871,10 @@ class Ranks(object):
         return r
 
 
-def leg_rnnt_loss_m1(args, R_, ragged=False):
-    """Headline: RNNTLoss.apply(...).sum().backward() on a resident (B,T,U+1,V) fp32 lattice."""
+def leg_rnnt_loss_m1(args, R_, ragged=False, dump_dir=None):
+    """Headline: RNNTLoss.apply(...).sum().backward() on a resident (B,T,U+1,V) fp32 lattice.  dump_dir:
+    rank 0 writes the last timed step's costs and d/dlog-probs there (dump_outputs).  The write-fill ceiling and the CPU
+    baseline take runs of their own: --full only."""
     from warp_rnnt import RNNTLoss  # the drop-in import the reference scripts use
     from pika_amd import rnnt as R
     dev, rank, world = R_.dev, R_.rank, R_.world
@@ -882,16 +909,20 @@ def leg_rnnt_loss_m1(args, R_, ragged=False):
         cells = T * (U + 1)
         bytes_per_utt = cells * V * 4 + 2 * cells * 4 + 4 * cells * 4
         achieved = bytes_per_utt * B / (bwd_ms * 1e-3) / 1e9
-        # measured ceiling for a pure write stream of the same size (hipMemsetAsync)
-        gbuf = lp.grad
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(3):
-            gbuf.zero_()
-        e1.record()
-        torch.cuda.synchronize()
-        fill_gbps = gbuf.numel() * 4 * 3 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+        if dump_dir is not None:        # before anything below overwrites the gradient
+            dump_outputs(dump_dir, {"costs": costs, "grad_log_probs": lp.grad})
+        fill_gbps = None
+        if args.full:
+            # measured ceiling for a pure write stream of the same size (hipMemsetAsync)
+            gbuf = lp.grad
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(3):
+                gbuf.zero_()
+            e1.record()
+            torch.cuda.synchronize()
+            fill_gbps = gbuf.numel() * 4 * 3 / (e0.elapsed_time(e1) * 1e-3) / 1e9
         traffic, traffic_src = None, None
         pmc = os.path.join(ROOT, "profiles", "rnnt_grad_pmc.json")
         if os.path.exists(pmc) and (T, U, V) == (1000, 50, 5000) and not ragged:
@@ -915,7 +946,7 @@ def leg_rnnt_loss_m1(args, R_, ragged=False):
                          "traffic": traffic, "traffic_source": traffic_src, "bytes_per_launch": bytes_per_utt * B,
                          "kernel_ms": bwd_ms, "forward_ms": fwd_ms, "measured_fill_GBps": fill_gbps},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb, c_cpu = cpu_baseline(lp.detach(), labels, tl, ul, min(args.cpu_utts, B))
             out["cpu_baseline"] = cb
             c_gpu = costs.detach()[:len(c_cpu)].cpu().numpy()
@@ -1374,7 +1405,7 @@ def leg_mbr(args, R_, with_cpu, steps=4, warmup=3):      # (warm-up: an eager st
     return d
 
 
-def run_m1p(args, R_, steps, warmup):
+def run_m1p(args, R_, steps, warmup, dump_dir=None):
     """SURVEY 8d M1': fused boundary logits -> (costs, d/dlogits); no log-prob tensor, no dense lp gradient.  Returns the
     JSON object of the workload on rank 0 (None elsewhere)."""
     from warp_rnnt import RNNTLoss
@@ -1414,6 +1445,8 @@ def run_m1p(args, R_, steps, warmup):
     el = float(t.item()) / steps
     if rank != 0:
         return None
+    if dump_dir is not None:
+        dump_outputs(dump_dir, {"costs": costs, "grad_logits": logits.grad})
     fwd_ms = float(np.mean([a.elapsed_time(b) for a, b in ev["fwd"]]))
     bwd_ms = float(np.mean([a.elapsed_time(b) for a, b in ev["bwd"]]))
     bytes_per_launch = 3.0 * B * T * (U + 1) * V * 4          # SURVEY 8d M1': 3X
@@ -1507,7 +1540,18 @@ def main():
     ap.add_argument("--no-decode-pipeline", action="store_true",
                     help="decode leg of the default run: skip the FST-fused search + LAS rescoring measurement")
     ap.add_argument("--no-fp32-leg", action="store_true", help="skip the fp32-split timing inside the train-step leg")
+    ap.add_argument("--full", action="store_true",
+                    help="default workload: also the CPU baseline, the write-fill ceiling and the secondary legs (ragged M1 "
+                         "and M1', train step, decode, MBR step; each can still be skipped with its --no-* switch).  "
+                         "Without it the run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(rnnt_loss_M1 and rnnt_loss_M1p workloads)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and args.workload not in ("rnnt_loss_M1", "rnnt_loss_M1p"):
+        ap.error("--dump-outputs: only the rnnt_loss_M1 and rnnt_loss_M1p workloads write their outputs")
 
     dry_run = os.environ.get("PIKA_BENCH_DRYRUN") == "1"     # tests: launch/timing plumbing only, NO product compute
     env_world = os.environ.get("WORLD_SIZE")
@@ -1553,7 +1597,7 @@ def main():
         R_.finish()
         return
     if args.workload == "rnnt_loss_M1p":
-        d = run_m1p(args, R_, args.steps, args.warmup)
+        d = run_m1p(args, R_, args.steps, args.warmup, dump_dir=args.dump_outputs)
         if rank == 0:
             print(json.dumps(d), flush=True)
         if world > 1:
@@ -1610,14 +1654,14 @@ def main():
             print(json.dumps(out), flush=True)
         R_.finish()
         return
-    out = leg_rnnt_loss_m1(args, R_, ragged=args.ragged)
+    out = leg_rnnt_loss_m1(args, R_, ragged=args.ragged, dump_dir=args.dump_outputs)
     if rank == 0 and R_.selfcheck is not None:
         out["rccl_selfcheck"] = R_.selfcheck
-    if not args.no_m1_variants and not args.ragged:
+    if args.full and not args.no_m1_variants and not args.ragged:
         extra = leg_m1_variants(args, R_)
         if rank == 0:
             out.update(extra)
-    if not args.no_train_step:
+    if args.full and not args.no_train_step:
         ts = leg_train_step(args, R_, max(5, min(args.steps, 10)), 2, world == 1 and not args.no_cpu_baseline)
         if rank == 0:
             out["train_step"] = ts
@@ -1642,11 +1686,11 @@ def main():
                                            "SLOWER than xGMI (%.1fx the one-link ring bound: PCIe / sockets?)" % (
                                                sc["all_reduce_ms"] / sc["bound_ring_ms"])),
                              "error": sc.get("error")}}
-    if not args.no_decode:
+    if args.full and not args.no_decode:
         d = leg_decode(args, R_, world == 1 and not args.no_cpu_baseline)
         if rank == 0:
             out["decode"] = d
-    if not args.no_mbr:
+    if args.full and not args.no_mbr:
         m = leg_mbr(args, R_, world == 1 and not args.no_cpu_baseline)
         if rank == 0:
             out["mbr_step"] = m

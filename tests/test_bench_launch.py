@@ -8,6 +8,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -83,8 +85,8 @@ def test_eight_rank_line_on_one_gpu_carries_what_a_scaling_record_is_judged_by(h
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "PIKA_BENCH_DRYRUN"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--batch", "2", "--frames", "300",
-                        "--labels", "8", "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--no-decode", "--no-mbr",
-                        "--no-m1-variants"], env=env, capture_output=True, text=True, timeout=1500)
+                        "--labels", "8", "--steps", "5", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-decode",
+                        "--no-mbr", "--no-m1-variants"], env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -100,3 +102,48 @@ def test_eight_rank_line_on_one_gpu_carries_what_a_scaling_record_is_judged_by(h
     sm = d["scaling_summary"]
     assert sm["train_step_vs_n1"] == ts["vs_n1"] and sm["bmuf_all_reduce_ms"] == bm["all_reduce_ms"]
     assert "independent kernels" in sm["headline"] and sm["rccl"]["backend"] == "gloo"
+
+
+def test_plain_run_arguments_are_checked_before_any_work():
+    """--steps sets the number of timed steps, so it cannot be 0; --dump-outputs names the workloads that write outputs."""
+    for argv, what in ((["--steps", "0"], "--steps"), (["--workload", "decode", "--dump-outputs", "x"], "--dump-outputs")):
+        env = dict(os.environ, PIKA_BENCH_DRYRUN="1")
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, env=env, capture_output=True,
+                           text=True, timeout=300)
+        assert r.returncode != 0 and what in r.stderr, r.stderr[-2000:]
+
+
+@pytest.mark.gpu
+def test_plain_line_times_the_headline_only_and_dumps_its_outputs(hip_device, tmp_path):
+    """A plain run: the headline's timed steps and its line, none of the --full legs; --dump-outputs writes the last timed
+    step's costs and d/dlog-probs, which the oracle reproduces from the same seeded inputs (bench.make_inputs)."""
+    B, T, U, V = 2, 50, 12, 100
+    env = dict(os.environ, PIKA_BENCH_WATCHDOG="600")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "PIKA_BENCH_DRYRUN"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", str(B), "--frames", str(T), "--labels",
+                        str(U), "--vocab", str(V), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "utterances/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - B / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for k in ("cpu_baseline", "rnnt_loss_M1_ragged", "rnnt_loss_M1p", "train_step", "decode", "mbr_step"):
+        assert k not in d, k
+    costs, grad = np.load(tmp_path / "costs.npy"), np.load(tmp_path / "grad_log_probs.npy")
+    assert costs.dtype == np.float32 and grad.dtype == np.float32
+    saved = list(sys.path)
+    try:
+        sys.path.insert(0, ROOT)
+        import bench            # puts the drop-in packages first on sys.path: not for the tests after this one
+    finally:
+        sys.path[:] = saved
+    from oracle import rnnt as O
+    lp, labels, tl, ul = bench.make_inputs(B, T, U, V, hip_device, 1234)
+    c64, g64 = O.rnnt_loss(*[a.cpu().numpy() for a in (lp, labels, tl, ul)])
+    assert np.allclose(costs, c64, rtol=1e-5), (costs, c64)
+    assert grad.shape == g64.shape
+    assert np.all(np.abs(grad - g64) <= 1e-4 * np.abs(g64) + 1e-5)     # the budget of tests/test_rnnt_loss_gpu.py

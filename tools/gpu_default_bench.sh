@@ -1,10 +1,10 @@
 #!/bin/bash
-# the default `python bench.py` line of the tree -> gpurun_out/bench_default.json (copy to profiles/rN_bench_default_run.json)
-cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out
-timeout 900 python bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err
+# the full default `python bench.py --full` line of the tree -> $OUT/bench_default.json (copy to profiles/rN_bench_default_run.json)
+cd "$(dirname "$0")/.."; export OUT=${OUT:-bench_out}; mkdir -p "$OUT"
+timeout 900 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 python - <<'PY'
-import json
-d = json.loads(open("gpurun_out/bench_default.json").read().strip().splitlines()[-1])
+import json, os
+d = json.loads(open(os.path.join(os.environ["OUT"], "bench_default.json")).read().strip().splitlines()[-1])
 print("M1", d["value"], d["ms_per_step"], d["roofline"]["frac"])
 print("M1p", d["rnnt_loss_M1p"]["ms_per_step"], d["rnnt_loss_M1p"]["roofline"]["frac"])
 ts = d["train_step"]; print("train", ts["ms_per_step"], ts["roofline"]["frac"], "lstm", ts["lstm_prediction_net"]["ms_per_step"])

@@ -1,11 +1,11 @@
 #!/bin/bash
-# full GPU suite + the default bench line (what the driver runs at round end)
-cd /root/repo; mkdir -p gpurun_out
-timeout 2400 python -m pytest tests/ -x -q -m gpu 2>&1 | tail -6 > gpurun_out/v_pytest.txt; cat gpurun_out/v_pytest.txt
-timeout 1200 python bench.py > gpurun_out/v_bench.json 2> gpurun_out/v_bench.err; tail -3 gpurun_out/v_bench.err | cut -c1-300
+# full GPU suite + the full default bench line -> $OUT
+cd "$(dirname "$0")/.."; export OUT=${OUT:-bench_out}; mkdir -p "$OUT"
+timeout 2400 python -m pytest tests/ -x -q -m gpu 2>&1 | tail -6 > "$OUT/v_pytest.txt"; cat "$OUT/v_pytest.txt"
+timeout 1200 python bench.py --full > "$OUT/v_bench.json" 2> "$OUT/v_bench.err"; tail -3 "$OUT/v_bench.err" | cut -c1-300
 python - <<'PY'
-import json
-for l in open('gpurun_out/v_bench.json'):
+import json, os
+for l in open(os.path.join(os.environ["OUT"], 'v_bench.json')):
     l=l.strip()
     if l.startswith('{'):
         d=json.loads(l)

@@ -1,11 +1,11 @@
 #!/bin/bash
-cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out
+cd "$(dirname "$0")/.."; export OUT=${OUT:-bench_out}; mkdir -p "$OUT"
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-PIKA_BENCH_DEVICE=0 PIKA_BENCH_BACKEND=gloo PIKA_BENCH_WATCHDOG=900 timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 2 --no-cpu-baseline > gpurun_out/r6_n2.json 2> gpurun_out/r6_n2.err
-tail -3 gpurun_out/r6_n2.err | cut -c1-300
+PIKA_BENCH_DEVICE=0 PIKA_BENCH_BACKEND=gloo PIKA_BENCH_WATCHDOG=900 timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 2 --full --no-cpu-baseline > "$OUT/r6_n2.json" 2> "$OUT/r6_n2.err"
+tail -3 "$OUT/r6_n2.err" | cut -c1-300
 python - <<'PY'
-import json
-for l in open('gpurun_out/r6_n2.json'):
+import json, os
+for l in open(os.path.join(os.environ["OUT"], 'r6_n2.json')):
     l=l.strip()
     if l.startswith('{'):
         d=json.loads(l)
