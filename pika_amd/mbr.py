@@ -81,8 +81,9 @@ class RiskFn(torch.autograd.Function):
     def backward(ctx, g):
         lp, sym, val = ctx.saved_tensors
         rows, V = lp.shape
-        v = (val * g).float().contiguous()
+        v = val * g
         if lp.is_cuda:
+            v = v.float().contiguous()
             with torch.cuda.device(lp.device):
                 _lib.check(_lib.lib().pika_mbr_risk_grad_rows(
                     lp.data_ptr(), sym.data_ptr(), v.data_ptr(), rows, V, V, ctx.scale,
@@ -131,10 +132,13 @@ def hyp_arrays(hyps, nonblk, pad, blk, S=None, Umax=None):
     return y_h, sym_h, slen_h
 
 
-def risk_surrogate(model, enc, y, sym, slen, seq_grad, blk, sm_scale):
+def risk_surrogate(model, enc, y, sym, slen, seq_grad, blk, sm_scale, t_enc=None):
     """:197-235 as a differentiable scalar: sum over the live trajectory rows of val * log_softmax(sm_scale * logits)[sym]
     with val = seq_grad of the row's hypothesis (blank rows / T).  Its gradient IS what `out.backward(mbr_grad)` of the
-    reference back-propagates.  Device tensors in, no host reads: capturable (GraphedMbrStep)."""
+    reference back-propagates.  Device tensors in, no host reads: capturable (GraphedMbrStep).
+    t_enc: a (1,) integer device tensor, the frames of data of an `enc` whose time axis is padded beyond them (the graphed
+    step's buckets); T of the reference (`x.size()[1]` of the unpadded batch, :140) is then t_enc, not enc.shape[1] -- the
+    1/T of the blank rows and the last frame a trajectory may read.  Default: the whole time axis."""
     bb, S = sym.shape
     B = enc.shape[0]
     beam = bb // B
@@ -145,7 +149,8 @@ def risk_surrogate(model, enc, y, sym, slen, seq_grad, blk, sm_scale):
     is_blk = sym.eq(blk)
     steps = torch.arange(S, device=dev).unsqueeze(0)
     live = steps < slen.unsqueeze(1)
-    t_idx = (torch.cumsum(is_blk & live, 1) - (is_blk & live).long()).clamp(max=T - 1)
+    t_idx = torch.cumsum(is_blk & live, 1) - (is_blk & live).long()
+    t_idx = t_idx.clamp(max=T - 1) if t_enc is None else torch.minimum(t_idx, t_enc.long() - 1)
     u_idx = torch.cumsum(~is_blk & live, 1) - (~is_blk & live).long()
     rows_b = torch.arange(B, device=dev).repeat_interleave(beam).unsqueeze(1).expand(-1, S)
     rows_r = torch.arange(bb, device=dev).unsqueeze(1).expand(-1, S)
@@ -159,8 +164,10 @@ def risk_surrogate(model, enc, y, sym, slen, seq_grad, blk, sm_scale):
     h = torch.tanh(z1) * torch.sigmoid(zg)
     logits = ops.linear(h.reshape(-1, H), model.fc2.weight, model.fc2.bias)
     val = seq_grad.reshape(-1, 1).expand(-1, S) * live
-    val = torch.where(is_blk, val / float(T), val)
-    return RiskFn.apply(logits, sym.reshape(-1).int(), val.reshape(-1).float().contiguous(), sm_scale)
+    val = torch.where(is_blk, val / (float(T) if t_enc is None else t_enc.to(val.dtype)), val)
+    # (float64 on the CPU path, the tests' oracle arithmetic; the device kernels take fp32)
+    val = val.reshape(-1).to(logits.dtype if not logits.is_cuda else torch.float32).contiguous()
+    return RiskFn.apply(logits, sym.reshape(-1).int(), val, sm_scale)
 
 
 def mbr_backward(model, enc, hyps, seq_grad, nonblk, blk, sm_scale):
@@ -202,7 +209,10 @@ class GraphedMbrStep(object):
     A batch also rides a graph whose time axis is up to `t_bucket` - 1 frames and whose label axis is up to `l_bucket` - 1
     labels longer than its own (padding frames masked through the encoder's `valid_frames`, labels padded with the padding
     index, as pika_amd.train_graph does for the plain step), and a bucket of t_bucket x l_bucket that has shown two different
-    shapes is captured at its upper boundary: a corpus whose batch shapes never recur still gets graphs.
+    shapes is captured at its upper boundary: a corpus whose batch shapes never recur still gets graphs.  On such a padded
+    axis the risk term's T (the 1/T of its blank rows, the last frame a trajectory reads) is the batch's own encoder length,
+    derived on the device from the same word (`encoder.valid_out`), not the graph's: every call of the graph, the capture
+    call included, leaves the gradients of the unpadded batch.
     Dropout: the device-side salt word of pika_amd.train_graph, re-drawn before every replay."""
 
     def __init__(self, model, rnnt_scale=1.0, sm_scale=1.0, blk=0, max_graphs=16, min_seen=2, s_bucket=32, u_bucket=8,
@@ -294,7 +304,10 @@ class GraphedMbrStep(object):
                     pred = model.predict(torch.cat((sos, e.labels), dim=1))
                     lp = ops.joint(enc, pred, model.fc1, model.fc_gate, model.fc2, log_softmax=True, labels=e.labels)
                     rnnt = self.rnnt_scale * self.loss(lp, e.labels32, e.x_len, e.ali).sum()
-                    surrogate = risk_surrogate(model, enc, e.y, e.sym, e.slen, e.seq_grad, self.blk, self.sm_scale)
+                    # (a padded time axis: the risk term's T is the encoder's frames of data, read from the device word)
+                    t_enc = None if e.t_valid is None else model.encoder.valid_out(e.t_valid)
+                    surrogate = risk_surrogate(model, enc, e.y, e.sym, e.slen, e.seq_grad, self.blk, self.sm_scale,
+                                               t_enc=t_enc)
                     grads = torch.autograd.grad((rnnt + surrogate,), [aliases[n] for n, _ in named], allow_unused=True)
                     grads = [g if g is None or (g.dtype == p.dtype and g.is_contiguous() and g.shape == p.shape)
                              else g.to(p.dtype).expand_as(p).contiguous() for g, (_, p) in zip(grads, named)]

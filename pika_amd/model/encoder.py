@@ -56,9 +56,7 @@ class Net(nn.Module):
             to_transformer = (i + 1) % 3 == 0
             span, stride = conv.dilation[0] * (self.filter_size - 1), conv.stride[0]
             t_out = (h.shape[1] - span - 1) // stride + 1
-            # data frames after a valid convolution: (v - span - 1) // stride + 1 = (v - span - 1 + stride) // stride
-            assert div == 1, "only the last time-delay layer strides"
-            sub, div = sub + span + 1 - stride, stride
+            sub, div = self._after(conv, sub, div)
             if ops.tdnn_bn_ok(h, conv.weight, bn):
                 nxt_ok = (not to_transformer and i + 1 < n_layers)
                 with valid(valid_frames, t_out, sub, div):
@@ -80,6 +78,21 @@ class Net(nn.Module):
             h = ops.batch_norm(h.reshape(-1, C), self.bn_final)
         h = ops.linear(h, self.fc_out.weight, self.fc_out.bias).view(B, -1, self.output_dim)
         return h[:, frame_offset:, :]
+
+    def _after(self, conv, sub, div):
+        """(sub, div) of the data frames behind `conv`, given those in front of it: data frames = (V - sub) // div."""
+        span, stride = conv.dilation[0] * (self.filter_size - 1), conv.stride[0]
+        # data frames after a valid convolution: (v - span - 1) // stride + 1 = (v - span - 1 + stride) // stride
+        assert div == 1, "only the last time-delay layer strides"
+        return sub + span + 1 - stride, stride
+
+    def valid_out(self, valid_frames):
+        """The frames of data at the output of `forward(x, valid_frames=valid_frames)`: a device tensor of the dtype of
+        `valid_frames` (capturable), by the formula the forward's masks use."""
+        sub, div = 0, 1
+        for conv in self.hidden_conv:
+            sub, div = self._after(conv, sub, div)
+        return torch.div(valid_frames - sub, div, rounding_mode="floor")
 
 
 class _NoValid(object):
