@@ -4,13 +4,15 @@
 //   /root/reference/trainer/train_transducer_bmuf_otfaug.py:58,97-99
 // (SURVEY.md 8a row 10).  From-scratch CDNA4 design, not a hipify:
 //
-//   gather    : one thread per lattice cell pulls the TWO log-probs the cell needs (blank, next
-//               label) out of the (B,T,U1,V) tensor into two compact planes stored SKEWED:
-//               cell (t,u) lives at [t+u][u], so every anti-diagonal is one contiguous row.
+//   gather    : one wave per anti-diagonal row (lane = u) pulls the TWO log-probs each cell
+//               needs (blank, next label) out of the (B,T,U1,V) tensor into two compact planes
+//               stored SKEWED: cell (t,u) lives at [t+u][u], so every anti-diagonal is one
+//               contiguous row and a wave writes it with one store per plane.
 //   alpha/beta: one 64-lane wavefront per utterance and direction walks the anti-diagonals;
 //               lane = u, the neighbour term moves one lane with a single DPP wave-shift (no
-//               LDS, no barrier); log-probs of the next 8 diagonals are prefetched into
-//               registers while the current 8 are consumed (the recurrence is latency-bound).
+//               LDS, no barrier); log-probs are prefetched into registers ahead of use (the
+//               recurrence is latency-bound).  With one wave, the band of diagonals where every
+//               live lane is inside the lattice runs branch-free (see the kernel).
 //               Every 16 diagonals the wave subtracts its running maximum and accumulates it
 //               in fp64 ("offsets"), so the fp32 lattice values stay O(100) however long the
 //               utterance is -- the absolute error of a plain fp32 log-space lattice grows
@@ -32,6 +34,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "pika_rnnt.h"
 #include "pika_internal.h"
@@ -137,30 +141,48 @@ __device__ inline float wave_max(float v) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// gather: (B,T,U1,V) -> two skewed planes
+// gather: (B,T,U1,V) -> two skewed planes.  A wave owns GATHER_ROWS consecutive rows d of one
+// utterance and 64 columns u (lane = u), so each plane store is one contiguous 256-byte row piece;
+// the lane's label is loaded once for all its rows, and every blank load is issued before the
+// first wait.  Cells outside the (Tn, Un+1) sub-lattice (and columns >= U1) get NEG.
+// grid = (ceil(D / (4 * GATHER_ROWS)), Wp / 64, B), block = 256.
 // ---------------------------------------------------------------------------------------------
+constexpr int GATHER_ROWS = 4;
+
 __global__ __launch_bounds__(256) void rnnt_gather_kernel(
     const float *__restrict__ lp, const int *__restrict__ labels, const int *__restrict__ Tn_,
     const int *__restrict__ Un_, int B, int T, int U1, int V, int blank, float *__restrict__ lpb,
     float *__restrict__ lpe, int Wp, int D) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t total = (size_t)B * T * U1;
-    if (idx >= total) return;
-    const int u = (int)(idx % U1);
-    const int t = (int)((idx / U1) % T);
-    const int b = (int)(idx / ((size_t)U1 * T));
+    const int b = blockIdx.z;
+    const int d0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * GATHER_ROWS;
+    const int u = blockIdx.y * 64 + (threadIdx.x & 63);
+    if (d0 >= D) return;
     const int Tn = clampi(Tn_[b], 1, T), Un = clampi(Un_[b], 0, U1 - 1);
-    if (t >= Tn || u > Un) return;
-    const float *row = lp + idx * (size_t)V;
-    const float vb = fmaxf(row[blank], NEG);
-    float ve = NEG;
-    if (u < Un) {
-        const int y = labels[(size_t)b * (U1 - 1) + u];
-        if (y >= 0 && y < V) ve = fmaxf(row[y], NEG);
+    const int y = u < Un ? labels[(size_t)b * (U1 - 1) + u] : -1;
+    const bool emits = y >= 0 && y < V;
+    float vb[GATHER_ROWS], ve[GATHER_ROWS];
+#pragma unroll
+    for (int r = 0; r < GATHER_ROWS; ++r) {
+        const int t = d0 + r - u;
+        vb[r] = NEG;
+        if (u <= Un && t >= 0 && t < Tn)
+            vb[r] = fmaxf(lp[(((size_t)b * T + t) * U1 + u) * V + blank], NEG);
     }
-    const size_t o = ((size_t)b * D + (t + u)) * Wp + u;
-    lpb[o] = vb;
-    lpe[o] = ve;
+#pragma unroll
+    for (int r = 0; r < GATHER_ROWS; ++r) {
+        const int t = d0 + r - u;
+        ve[r] = NEG;
+        if (emits && t >= 0 && t < Tn)
+            ve[r] = fmaxf(lp[(((size_t)b * T + t) * U1 + u) * V + y], NEG);
+    }
+#pragma unroll
+    for (int r = 0; r < GATHER_ROWS; ++r) {
+        if (d0 + r < D) {
+            const size_t o = ((size_t)b * D + d0 + r) * Wp + u;
+            lpb[o] = vb[r];
+            lpe[o] = ve[r];
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -228,11 +250,41 @@ __global__ __launch_bounds__(NW * 64) void rnnt_alpha_beta_kernel(
     const float *lpe = lpe_ + base;
 
     // cell (d-u, u) is inside the sub-lattice
-    auto inside = [&](int d) { const int t = d - u; return t >= 0 && t < Tn && u <= Un; };
+    auto inside = [&](int d) __attribute__((always_inline)) { const int t = d - u; return t >= 0 && t < Tn && u <= Un; };
 
     float pbv[2][UNR], pev[2][UNR];
     double off = 0.0;  // sum of subtracted maxima (identical in every thread)
 
+    // One wave (NW == 1): for d in [Un, Tn-1] the cell (d-u, u) of every lane u <= Un is inside
+    // and lanes u > Un never are.  Whole renormalisation groups of 16 diagonals in that band run
+    // a "bulk" loop with no per-step masks or guards: lanes > Un are held at NEG by one
+    // loop-invariant select and load column Un (real plane data, never garbage), addresses are a
+    // uniform row pointer plus a fixed lane offset, offs[] goes out once per group, and the next
+    // group's rows are loaded one step at a time, 16 diagonals ahead.  The masked code below walks
+    // the head and the tail; inside-cell arithmetic and renorm points are the same in both.
+    // The masked walker is inlined three times per direction (head, tail, and the whole walk when
+    // there is no bulk): each copy is straight-line code of ~1k instructions, so the kernel grows
+    // by a few KB of instruction cache -- one resident wave per utterance and direction, and the
+    // bulk loop it spends ~90 % of its diagonals in is a single ~5 KB body.
+    constexpr int G = RENORM;
+    constexpr int ROWB = NW * 64 * 4;  // bytes per plane row (Wp == NW * 64)
+    const bool live = u <= Un;
+    const int lcol = (live ? u : Un) * 4;  // byte offset of the column loaded
+    const int scol = u * 4;                // byte offset of the column stored
+    // buffer descriptors over this utterance's rows of each plane (uniform: kernargs + blockIdx)
+    const size_t plane_b = (size_t)b * D * (NW * 64);
+    auto rsrc = [&](const float *plane) __attribute__((always_inline)) {
+        return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(plane + plane_b), 0, D * ROWB,
+                                                 0x00020000);
+    };
+    auto ldb = [](__amdgpu_buffer_rsrc_t r, int voff, int soff) __attribute__((always_inline)) {
+        return __uint_as_float(
+            __builtin_amdgcn_raw_buffer_load_b32(r, voff, __builtin_amdgcn_readfirstlane(soff), 0));
+    };
+    auto stb = [](float v, __amdgpu_buffer_rsrc_t r, int voff, int soff) __attribute__((always_inline)) {
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff,
+                                              __builtin_amdgcn_readfirstlane(soff), 0);
+    };
     if (blockIdx.x == 0) {
         // ----- alpha: A_d[u] = lae(A_{d-1}[u] + lpb_{d-1}[u], A_{d-1}[u-1] + lpe_{d-1}[u-1]) -----
         float *alpha = alpha_ + base;
@@ -240,7 +292,7 @@ __global__ __launch_bounds__(NW * 64) void rnnt_alpha_beta_kernel(
         float a = (u == 0) ? 0.0f : NEG;
         alpha[0] = a;
         if (u == 0) offs[0] = 0.0;
-        auto load = [&](int buf, int d0) {  // rows d0-1 .. d0+UNR-2
+        auto load = [&](int buf, int d0) __attribute__((always_inline)) {  // rows d0-1 .. d0+UNR-2
 #pragma unroll
             for (int i = 0; i < UNR; ++i) {
                 const int r = min(d0 + i - 1, D - 1);
@@ -250,15 +302,16 @@ __global__ __launch_bounds__(NW * 64) void rnnt_alpha_beta_kernel(
                 pev[buf][i] = ok ? ve : 0.0f;
             }
         };
-        auto steps = [&](int buf, int d0) {
+        // diagonals d0 .. d0+UNR-1 (<= dlast); d0 = 1 (mod RENORM) at the first half of a group
+        auto steps = [&](int buf, int d0, int dlast, auto second_half) __attribute__((always_inline)) {
 #pragma unroll
             for (int i = 0; i < UNR; ++i) {
                 const int d = d0 + i;
-                if (d <= dend) {  // workgroup-uniform
+                if (d <= dlast) {  // workgroup-uniform
                     const float x = a + pbv[buf][i];
                     const float y = xc.up(a + pev[buf][i], d);
                     a = inside(d) ? lae(x, y) : NEG;
-                    if ((d0 + i) % RENORM == 0) {  // d0 = 1 (mod UNR): compile-time per i
+                    if (decltype(second_half)::value && i == UNR - 1) {  // d = 0 (mod RENORM)
                         const float m = xc.max_all(a, d);
                         a = a > NEG_HALF ? a - m : NEG;
                         off += (double)m;
@@ -268,12 +321,59 @@ __global__ __launch_bounds__(NW * 64) void rnnt_alpha_beta_kernel(
                 }
             }
         };
-        load(0, 1);
-        for (int d0 = 1; d0 <= dend; d0 += 2 * UNR) {
-            load(1, d0 + UNR);
-            steps(0, d0);
-            load(0, d0 + 2 * UNR);
-            steps(1, d0 + UNR);
+        auto masked = [&](int dfirst, int dlast) __attribute__((always_inline)) {  // dfirst = 1 (mod RENORM)
+            load(0, dfirst);
+            for (int d0 = dfirst; d0 <= dlast; d0 += 2 * UNR) {
+                load(1, d0 + UNR);
+                steps(0, d0, dlast, std::false_type{});
+                load(0, d0 + 2 * UNR);
+                steps(1, d0 + UNR, dlast, std::true_type{});
+            }
+        };
+        // bulk groups [G*g+1, G*g+G]: rows read G*g .. G*g+G-1 >= Un, last diagonal <= Tn-1
+        const int g0 = (Un + G - 1) / G, g1 = NW == 1 ? (Tn - 1) / G : 0;
+        if (NW == 1 && g1 > g0) {
+            masked(1, G * g0);
+            const auto rb = rsrc(lpb_), re = rsrc(lpe_), ra = rsrc(alpha_);
+            float qb[2][G], qe[2][G];
+            auto fetch = [&](int buf, int i, int g) __attribute__((always_inline)) {  // row G*g+i
+                qb[buf][i] = ldb(rb, lcol + i * ROWB, G * g * ROWB);
+                qe[buf][i] = ldb(re, lcol + i * ROWB, G * g * ROWB);
+            };
+            // diagonals G*g+1 .. G*g+G from qb/qe[buf]; step i also fetches row i of group g+1
+            // (the last group fetches itself again) into 1-buf
+            auto group = [&](int buf, int g) __attribute__((always_inline)) {
+                const int gn = min(g + 1, g1 - 1);
+                const double off0 = off;
+#pragma unroll
+                for (int i = 0; i < G; ++i) {
+                    const float x = a + qb[buf][i];
+                    const float y = wave_shr1(a + qe[buf][i], NEG);
+                    const float v = lae(x, y);
+                    a = live ? v : NEG;
+                    if (i == G - 1) {
+                        const float m = wave_max(a);
+                        a = a > NEG_HALF ? a - m : NEG;
+                        off += (double)m;
+                    }
+                    stb(a, ra, scol + i * ROWB, (G * g + 1) * ROWB);
+                    fetch(1 - buf, i, gn);
+                    __builtin_amdgcn_sched_barrier(0);  // keep the prefetch where it is
+                }
+                if (u < G) offs[G * g + 1 + u] = u == G - 1 ? off : off0;
+            };
+#pragma unroll
+            for (int i = 0; i < G; ++i) fetch(0, i, g0);
+            group(0, g0);  // peeled: the loop is entered in its steady state of pending loads
+            int g = g0 + 1;
+            for (; g + 1 < g1; g += 2) {
+                group(1, g);
+                group(0, g + 1);
+            }
+            if (g < g1) group(1, g);
+            masked(G * g1 + 1, dend);
+        } else {
+            masked(1, dend);
         }
         if (u == Un) ll_a_[b] = (double)a + off + (double)fmaxf(lpb[(size_t)dend * Wp], NEG);
     } else {
@@ -281,7 +381,7 @@ __global__ __launch_bounds__(NW * 64) void rnnt_alpha_beta_kernel(
         float *beta = beta_ + base;
         double *offs = off_b_ + (size_t)b * D;
         float bt = NEG;
-        auto load = [&](int buf, int d0) {  // rows d0, d0-1, ..., d0-UNR+1
+        auto load = [&](int buf, int d0) __attribute__((always_inline)) {  // rows d0, d0-1, ..., d0-UNR+1
 #pragma unroll
             for (int i = 0; i < UNR; ++i) {
                 const int r = max(d0 - i, 0);
@@ -291,12 +391,13 @@ __global__ __launch_bounds__(NW * 64) void rnnt_alpha_beta_kernel(
                 pev[buf][i] = ok ? ve : 0.0f;
             }
         };
-        int k = 0;  // steps taken, for the renormalisation cadence
-        auto steps = [&](int buf, int d0) {
+        // diagonals d0, d0-1, ..., d0-UNR+1 (>= dstop); renormalised after every RENORM steps
+        // counted from dend (the last step of a second half)
+        auto steps = [&](int buf, int d0, int dstop, auto second_half) __attribute__((always_inline)) {
 #pragma unroll
             for (int i = 0; i < UNR; ++i) {
                 const int d = d0 - i;
-                if (d >= 0) {
+                if (d >= dstop) {
                     const int t = d - u;
                     const float dn = xc.down(bt, d);
                     const float x = bt + pbv[buf][i];
@@ -304,8 +405,8 @@ __global__ __launch_bounds__(NW * 64) void rnnt_alpha_beta_kernel(
                     float nb = lae(x, y);
                     if (t == Tn - 1 && u == Un) nb = pbv[buf][i];  // terminal blank
                     bt = inside(d) ? nb : NEG;
-                    if (i == UNR - 1 && (k & (RENORM / UNR - 1)) == RENORM / UNR - 1) {
-                        const float m = xc.max_all(bt, k * UNR);
+                    if (decltype(second_half)::value && i == UNR - 1) {
+                        const float m = xc.max_all(bt, d);
                         bt = bt > NEG_HALF ? bt - m : NEG;
                         off += (double)m;
                     }
@@ -313,14 +414,63 @@ __global__ __launch_bounds__(NW * 64) void rnnt_alpha_beta_kernel(
                     if (u == 0) offs[d] = off;
                 }
             }
-            ++k;
         };
-        load(0, dend);
-        for (int d0 = dend; d0 >= 0; d0 -= 2 * UNR) {
-            load(1, d0 - UNR);
-            steps(0, d0);
-            load(0, d0 - 2 * UNR);
-            steps(1, d0 - UNR);
+        auto masked = [&](int dfirst, int dstop) __attribute__((always_inline)) {  // dend - dfirst = 0 (mod RENORM)
+            load(0, dfirst);
+            for (int d0 = dfirst; d0 >= dstop; d0 -= 2 * UNR) {
+                load(1, d0 - UNR);
+                steps(0, d0, dstop, std::false_type{});
+                load(0, d0 - 2 * UNR);
+                steps(1, d0 - UNR, dstop, std::true_type{});
+            }
+        };
+        // bulk groups: steps j = dend-d in [G*n, G*n+G-1] with Un <= d <= Tn-1 and j >= 1 (the
+        // terminal cell, j = 0, stays in the masked head)
+        const int n0 = (max(Un, 1) + G - 1) / G, n1 = NW == 1 ? Tn / G : 0;
+        if (NW == 1 && n1 > n0) {
+            masked(dend, dend - G * n0 + 1);
+            const auto rb = rsrc(lpb_), re = rsrc(lpe_), rbt = rsrc(beta_);
+            float qb[2][G], qe[2][G];
+            // group n's rows dend-G*n .. dend-G*n-G+1, addressed from its lowest one
+            auto fetch = [&](int buf, int i, int n) __attribute__((always_inline)) {  // row dend-G*n-i
+                const int r0 = (dend - G * n - (G - 1)) * ROWB;
+                qb[buf][i] = ldb(rb, lcol + (G - 1 - i) * ROWB, r0);
+                qe[buf][i] = ldb(re, lcol + (G - 1 - i) * ROWB, r0);
+            };
+            auto group = [&](int buf, int n) __attribute__((always_inline)) {
+                const int nn = min(n + 1, n1 - 1);
+                const int r0 = (dend - G * n - (G - 1)) * ROWB;
+                const double off0 = off;
+#pragma unroll
+                for (int i = 0; i < G; ++i) {
+                    const float dn = wave_shl1(bt, NEG);
+                    const float x = bt + qb[buf][i];
+                    const float y = dn + qe[buf][i];
+                    const float v = lae(x, y);
+                    bt = live ? v : NEG;
+                    if (i == G - 1) {
+                        const float m = wave_max(bt);
+                        bt = bt > NEG_HALF ? bt - m : NEG;
+                        off += (double)m;
+                    }
+                    stb(bt, rbt, scol + (G - 1 - i) * ROWB, r0);
+                    fetch(1 - buf, i, nn);
+                    __builtin_amdgcn_sched_barrier(0);  // keep the prefetch where it is
+                }
+                if (u < G) offs[dend - G * n - u] = u == G - 1 ? off : off0;
+            };
+#pragma unroll
+            for (int i = 0; i < G; ++i) fetch(0, i, n0);
+            group(0, n0);  // peeled: the loop is entered in its steady state of pending loads
+            int n = n0 + 1;
+            for (; n + 1 < n1; n += 2) {
+                group(1, n);
+                group(0, n + 1);
+            }
+            if (n < n1) group(1, n);
+            masked(dend - G * n1, 0);
+        } else {
+            masked(dend, 0);
         }
         if (u == 0) {
             const double ll = (double)bt + off;
@@ -932,8 +1082,9 @@ int pika_rnnt_loss_forward(const float *log_probs, const int *labels, const int 
     if (U1 > 1 && !labels) return PIKA_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Lattice L = carve(workspace, B, T, U1);
-    const size_t cells = (size_t)B * T * U1;
-    hipLaunchKernelGGL(rnnt_gather_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s,
+    const dim3 grid((unsigned)((L.D + 4 * GATHER_ROWS - 1) / (4 * GATHER_ROWS)), (unsigned)(L.Wp / 64),
+                    (unsigned)B);
+    hipLaunchKernelGGL(rnnt_gather_kernel, grid, dim3(256), 0, s,
                        log_probs, labels, frames_lengths, labels_lengths, B, T, U1, V, blank, L.lpb,
                        L.lpe, L.Wp, L.D);
     return run_alpha_beta(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
