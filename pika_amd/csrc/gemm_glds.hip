@@ -685,8 +685,10 @@ __global__ __launch_bounds__(512) void gemm_pp(PPArgs P) {
                 if (rl >= 0 && !(rl & ~51) && g_lab < N) P.g_out[2LL * m + 1] = pick(rl);
             }
             // the next 16-row block of this lane: 16 lattice cells further
-            g_u += 16;
-            while (g_u >= P.g_U1) { g_u -= P.g_U1; if (++g_t == P.g_T) { g_t = 0; ++g_b; } }
+            if (P.g_out) {
+                g_u += 16;
+                while (g_u >= P.g_U1) { g_u -= P.g_U1; if (++g_t == P.g_T) { g_t = 0; ++g_b; } }
+            }
         }
         if constexpr (EPI == 1 || EPI == 2 || EPI == 4) {
             if (wide16) {    // (wave-uniform; every lane of the wave takes part in the swaps: rows m >= M only skip the store)
@@ -1350,6 +1352,7 @@ extern "C" int pika_gemm_bf16_nt_lse_f16(const void *A, long long lda, const voi
     P.out16 = static_cast<__bf16 *>(out16); P.ldo16 = ldo;
     P.lse_pm = pmax; P.lse_ps = psum; P.lse_np = n_part;
     P.g_labels = labels; P.g_out = gathered; P.g_T = T; P.g_U1 = U1; P.g_blank = blank;
+    if (!gathered) P.g_T = P.g_U1 = 1;     // ignored then (pika_gemm.h); kept legal for the epilogue's lattice walk
     return launch_pp_epi<4>(P, static_cast<hipStream_t>(stream));
 }
 

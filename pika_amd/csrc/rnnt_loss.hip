@@ -837,15 +837,16 @@ __global__ __launch_bounds__(256) void rnnt_dlogits_compact8_kernel(const TI *__
         if (live) {
             // (their logits in fp32 where the forward product's epilogue kept them: `gathered`; the fp16 copy is 2^-11 of
             // |logit| off, percents of a softmax value at |logit| ~ 30 -- and these two entries carry the gradient's own terms.
-            // The column sums took the bulk value above: they get the difference.)
-            if (lane == gb_lane && m.gb != 0.f) {
+            // The column sums took the bulk value above: they get the difference.  Patched in every live row, also where
+            // the row's own term is zero -- gb on the last frame -- since the softmax part still takes the fp32 logit.)
+            if (lane == gb_lane) {
                 const float vb = k * __builtin_amdgcn_exp2f(__builtin_fmaf((float)lrow[blank], LOG2E, nl2));
                 const float v = (gathered && g_blank == blank) ? k * __builtin_amdgcn_exp2f(__builtin_fmaf(gathered[2 * r], LOG2E, nl2)) : vb;
                 orow[blank] = (__bf16)(v + scale * m.gb);
                 cs_blank += scale * m.gb + (v - vb);
             }
             const int ye = m.ye;
-            if (ye >= 0 && m.ge != 0.f && lane == ((ye >> 3) & 63)) {
+            if (ye >= 0 && lane == ((ye >> 3) & 63)) {
                 const float vb = k * __builtin_amdgcn_exp2f(__builtin_fmaf((float)lrow[ye], LOG2E, nl2));
                 // (the gathered label logit belongs to the label the PRODUCT was given for this row: used where it is the loss')
                 const int u = (int)(r % U1);
