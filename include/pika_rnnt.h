@@ -70,6 +70,16 @@ int pika_rnnt_loss_backward(const int *labels, const int *frames_lengths,
                             const float *grad_costs, const void *workspace,
                             float *grads, void *stream);
 
+/* pika_rnnt_loss_backward with FastEmit (Yu et al. 2021, arXiv:2010.11148): every label-emission entry
+ * (n, t, u, y_{u+1}), u < U_n, of the gradient is multiplied by 1 + fastemit_lambda; blank entries, the costs
+ * and the zeros outside the sub-lattice are unchanged.  fastemit_lambda must be finite and >= 0 (PIKA_EINVAL
+ * otherwise); 0 gives exactly pika_rnnt_loss_backward.  The factor is part of the row metadata left in
+ * `workspace`, so with grads == NULL every reader of it -- pika_rnnt_loss_dense_grads and the d(logits) calls
+ * below -- gets the FastEmit gradient. */
+int pika_rnnt_loss_backward_fe(const int *labels, const int *frames_lengths, const int *labels_lengths,
+                               int B, int T, int U1, int V, int blank, const float *grad_costs,
+                               const void *workspace, float *grads, float fastemit_lambda, void *stream);
+
 /* The streaming pass of pika_rnnt_loss_backward on its own: dense (B,T,U1,V) gradient from the row metadata a
  * pika_rnnt_loss_backward call (with or without `grads`) left in `workspace`. */
 int pika_rnnt_loss_dense_grads(const void *workspace, int B, int T, int U1, int V, int blank,
@@ -144,6 +154,46 @@ int pika_rnnt_fused_backward(const float *logits, const float *lse, const int *l
                              const int *frames_lengths, const int *labels_lengths, int B, int T, int U1, int V,
                              int blank, const float *grad_costs, const void *workspace, void *grad_logits,
                              int out_dtype, long long ld_out, void *stream);
+
+/* pika_rnnt_fused_backward with FastEmit (as pika_rnnt_loss_backward_fe): the label entry of g is scaled before
+ * the softmax backward, out = g~ - p * sum g~. */
+int pika_rnnt_fused_backward_fe(const float *logits, const float *lse, const int *labels,
+                                const int *frames_lengths, const int *labels_lengths, int B, int T, int U1, int V,
+                                int blank, const float *grad_costs, const void *workspace, void *grad_logits,
+                                int out_dtype, long long ld_out, float fastemit_lambda, void *stream);
+
+/* Packed (compact) layout: a ragged batch without padding.
+ *   log_probs / logits f32 (N, V), N = sum_n T_n (U_n + 1); row off_n + t (U_n + 1) + u holds cell (n, t, u)
+ *   labels         i32 (sum_n U_n,)  the utterances' labels concatenated
+ *   frames_lengths i32 (B,)          T_n >= 1
+ *   labels_lengths i32 (B,)          U_n >= 0, U_n + 1 <= U1_max
+ *   row_offsets    i32 (B,)          off_n: exclusive prefix sum of T_n (U_n + 1)
+ *   label_offsets  i32 (B,)          exclusive prefix sum of U_n (may be NULL, with labels, when U1_max == 1)
+ *   T_max, U1_max  the largest T_n and U_n + 1 (host values; the lattice planes and the workspace are those of a
+ *                  padded (B, T_max, U1_max) batch: pika_rnnt_workspace_bytes(B, T_max, U1_max), whose metadata
+ *                  region of B*T_max*U1_max rows covers N)
+ *   costs          f32 (B,);  grads / grad_logits (N, V) (pitch ld_out for the fused call), every element written.
+ * The lengths, offsets and N must agree: the calls read only what they describe, and cannot check that on the host
+ * (stream-ordered, no synchronisation).  N <= 0, N > B*T_max*U1_max: PIKA_EINVAL; N > 0x7fffffff: PIKA_ETOOBIG.
+ * The fused pair takes RAW logits (V % 4 == 0, V <= 8192, as pika_rnnt_fused_forward) and lse (N,). */
+int pika_rnnt_packed_forward(const float *log_probs, const int *labels, const int *frames_lengths,
+                             const int *labels_lengths, const int *row_offsets, const int *label_offsets, int B,
+                             int T_max, int U1_max, long long N, int V, int blank, float *costs, void *workspace,
+                             void *stream);
+/* grads == NULL: row metadata only, as pika_rnnt_loss_backward. */
+int pika_rnnt_packed_backward(const int *labels, const int *frames_lengths, const int *labels_lengths,
+                              const int *row_offsets, const int *label_offsets, int B, int T_max, int U1_max,
+                              long long N, int V, int blank, const float *grad_costs, const void *workspace,
+                              float *grads, float fastemit_lambda, void *stream);
+int pika_rnnt_packed_fused_forward(const float *logits, const int *labels, const int *frames_lengths,
+                                   const int *labels_lengths, const int *row_offsets, const int *label_offsets, int B,
+                                   int T_max, int U1_max, long long N, int V, int blank, float *costs, float *lse,
+                                   void *workspace, void *stream);
+int pika_rnnt_packed_fused_backward(const float *logits, const float *lse, const int *labels,
+                                    const int *frames_lengths, const int *labels_lengths, const int *row_offsets,
+                                    const int *label_offsets, int B, int T_max, int U1_max, long long N, int V,
+                                    int blank, const float *grad_costs, const void *workspace, void *grad_logits,
+                                    int out_dtype, long long ld_out, float fastemit_lambda, void *stream);
 
 #ifdef __cplusplus
 }

@@ -7,9 +7,9 @@ import os
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libpika_amd.so")
-ABI_VERSION = 22
+ABI_VERSION = 23
 
-_vp, _i, _sz, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_longlong
+_vp, _i, _sz, _ll, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_float
 
 # name -> (restype, argtypes); mirrors include/*.h one to one
 SIGNATURES = {
@@ -28,6 +28,13 @@ SIGNATURES = {
     "pika_rnnt_dlogits_compact_bf16_f16in": (_i, [_vp, _ll, _vp, _vp, _i, _i, _i, _i, _i, _vp, _ll, ctypes.c_float, _vp, _vp, _vp,
                                                    _i, _vp]),
     "pika_rnnt_export_lattice": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "pika_rnnt_loss_backward_fe": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp]),
+    "pika_rnnt_fused_backward_fe": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _ll, _f, _vp]),
+    "pika_rnnt_packed_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _ll, _i, _i, _vp, _vp, _vp]),
+    "pika_rnnt_packed_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _ll, _i, _i, _vp, _vp, _vp, _f, _vp]),
+    "pika_rnnt_packed_fused_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _ll, _i, _i, _vp, _vp, _vp, _vp]),
+    "pika_rnnt_packed_fused_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _ll, _i, _i, _vp, _vp, _vp, _i,
+                                              _ll, _f, _vp]),
     # include/pika_bmuf.h
     "pika_bmuf_delta": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "pika_bmuf_nan_flag": (_i, [_vp, _sz, _vp, _vp]),

@@ -145,20 +145,28 @@ __device__ inline float wave_max(float v) {
 // utterance and 64 columns u (lane = u), so each plane store is one contiguous 256-byte row piece;
 // the lane's label is loaded once for all its rows, and every blank load is issued before the
 // first wait.  Cells outside the (Tn, Un+1) sub-lattice (and columns >= U1) get NEG.
+// PACKED: log_probs are the (N, V) rows of the packed layout -- cell (t, u) of utterance b is row
+// roff[b] + t (Un+1) + u, its label labels[loff[b] + u] -- and the planes are the same as above.
 // grid = (ceil(D / (4 * GATHER_ROWS)), Wp / 64, B), block = 256.
 // ---------------------------------------------------------------------------------------------
 constexpr int GATHER_ROWS = 4;
 
+template <bool PACKED = false>
 __global__ __launch_bounds__(256) void rnnt_gather_kernel(
     const float *__restrict__ lp, const int *__restrict__ labels, const int *__restrict__ Tn_,
     const int *__restrict__ Un_, int B, int T, int U1, int V, int blank, float *__restrict__ lpb,
-    float *__restrict__ lpe, int Wp, int D) {
+    float *__restrict__ lpe, int Wp, int D, const int *__restrict__ roff = nullptr,
+    const int *__restrict__ loff = nullptr) {
     const int b = blockIdx.z;
     const int d0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * GATHER_ROWS;
     const int u = blockIdx.y * 64 + (threadIdx.x & 63);
     if (d0 >= D) return;
     const int Tn = clampi(Tn_[b], 1, T), Un = clampi(Un_[b], 0, U1 - 1);
-    const int y = u < Un ? labels[(size_t)b * (U1 - 1) + u] : -1;
+    // row of cell (0, u) and the row step of t
+    const size_t r0 = PACKED ? (size_t)roff[b] + u : (size_t)b * T * U1 + u;
+    const size_t rt = PACKED ? (size_t)(Un + 1) : (size_t)U1;
+    const int *lab = PACKED ? labels + loff[b] : labels + (size_t)b * (U1 - 1);
+    const int y = u < Un ? lab[u] : -1;
     const bool emits = y >= 0 && y < V;
     float vb[GATHER_ROWS], ve[GATHER_ROWS];
 #pragma unroll
@@ -166,14 +174,14 @@ __global__ __launch_bounds__(256) void rnnt_gather_kernel(
         const int t = d0 + r - u;
         vb[r] = NEG;
         if (u <= Un && t >= 0 && t < Tn)
-            vb[r] = fmaxf(lp[(((size_t)b * T + t) * U1 + u) * V + blank], NEG);
+            vb[r] = fmaxf(lp[(r0 + (size_t)t * rt) * V + blank], NEG);
     }
 #pragma unroll
     for (int r = 0; r < GATHER_ROWS; ++r) {
         const int t = d0 + r - u;
         ve[r] = NEG;
         if (emits && t >= 0 && t < Tn)
-            ve[r] = fmaxf(lp[(((size_t)b * T + t) * U1 + u) * V + y], NEG);
+            ve[r] = fmaxf(lp[(r0 + (size_t)t * rt) * V + y], NEG);
     }
 #pragma unroll
     for (int r = 0; r < GATHER_ROWS; ++r) {
@@ -481,23 +489,49 @@ __global__ __launch_bounds__(NW * 64) void rnnt_alpha_beta_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------
-// rowmeta: the two non-zeros of every V-row of the gradient
+// rowmeta: the two non-zeros of every V-row of the gradient.  The label entry carries the FastEmit
+// factor lscale = 1 + lambda (Yu et al. 2021: d/d lp of every emission scaled, costs unchanged);
+// 1.0f leaves it exact.  PACKED: row r of the (N, V) packed layout, utterance found by a binary
+// search over the row offsets roff (T_n >= 1: strictly increasing).
 // ---------------------------------------------------------------------------------------------
+__device__ inline int packed_utterance(const int *__restrict__ roff, int B, long r) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (roff[mid] <= r) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+template <bool PACKED = false>
 __global__ __launch_bounds__(256) void rnnt_rowmeta_kernel(
     const int *__restrict__ labels, const int *__restrict__ Tn_, const int *__restrict__ Un_,
     int B, int T, int U1, int V, const float *__restrict__ grad_costs,
     const float *__restrict__ lpb, const float *__restrict__ lpe, const float *__restrict__ alpha,
     const float *__restrict__ beta, const double *__restrict__ off_a,
     const double *__restrict__ off_b, const double *__restrict__ ll, int Wp, int D,
-    RowMeta *__restrict__ meta) {
+    RowMeta *__restrict__ meta, float lscale, const int *__restrict__ roff = nullptr,
+    const int *__restrict__ loff = nullptr, long npacked = 0) {
     const long row = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long nrows = (long)B * T * U1;
+    const long nrows = PACKED ? npacked : (long)B * T * U1;
     if (row >= nrows) return;
     float gb = 0.f, ge = 0.f;
     int ye = -1;
-    const int u = (int)(row % U1);
-    const int t = (int)((row / U1) % T);
-    const int b = (int)(row / ((long)U1 * T));
+    int u, t, b;
+    const int *lab;
+    if constexpr (PACKED) {
+        b = packed_utterance(roff, B, row);
+        const int w = clampi(Un_[b], 0, U1 - 1) + 1;
+        const int i = (int)(row - roff[b]);
+        t = i / w;
+        u = i - t * w;
+        lab = labels + loff[b];
+    } else {
+        u = (int)(row % U1);
+        t = (int)((row / U1) % T);
+        b = (int)(row / ((long)U1 * T));
+        lab = labels + (size_t)b * (U1 - 1);
+    }
     const int Tn = clampi(Tn_[b], 1, T), Un = clampi(Un_[b], 0, U1 - 1);
     if (t < Tn && u <= Un) {
         const int d = t + u;
@@ -512,10 +546,10 @@ __global__ __launch_bounds__(256) void rnnt_rowmeta_kernel(
         else if (u == Un)
             gb = -sc * __expf((float)base + (a + lpb[o]));
         if (u < Un) {
-            const int y = labels[(size_t)b * (U1 - 1) + u];
+            const int y = lab[u];
             if (y >= 0 && y < V) {
                 ye = y;
-                ge = -sc * __expf(k1 + (a + beta[o + Wp + 1] + lpe[o]));
+                ge = -sc * lscale * __expf(k1 + (a + beta[o + Wp + 1] + lpe[o]));
             }
         }
     }
@@ -914,17 +948,32 @@ __device__ inline float fwave_sum(float v) {
     return v;
 }
 
-template <int CQ>
+// PACKED: `logits` are the (N, V) rows of the packed layout (rows = N, roff / loff the row and label offsets of the
+// utterances, B of them): the wave's utterance comes from a binary search over roff, everything else is the same.
+template <int CQ, bool PACKED = false>
 __global__ __launch_bounds__(256) void rnnt_lse_gather_kernel(
     const float *__restrict__ logits, const int *__restrict__ labels, const int *__restrict__ Tn_,
     const int *__restrict__ Un_, long long rows, int T, int U1, int V, int blank, float *__restrict__ lse,
-    float *__restrict__ lpb, float *__restrict__ lpe, int Wp, int D) {
+    float *__restrict__ lpb, float *__restrict__ lpe, int Wp, int D, const int *__restrict__ roff = nullptr,
+    const int *__restrict__ loff = nullptr, int B = 0) {
     const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
     const int lane = threadIdx.x & 63, c4 = V >> 2;
-    const int u = (int)(r % U1);
-    const int t = (int)((r / U1) % T);
-    const int b = (int)(r / ((long long)U1 * T));
+    int u, t, b;
+    const int *lab;
+    if constexpr (PACKED) {   // rows < 2^31 (host check); the search runs on wave-uniform values
+        b = packed_utterance(roff, B, __builtin_amdgcn_readfirstlane((int)r));
+        const int w = clampi(Un_[b], 0, U1 - 1) + 1;
+        const int i = (int)r - roff[b];
+        t = i / w;
+        u = i - t * w;
+        lab = labels + loff[b];
+    } else {
+        u = (int)(r % U1);
+        t = (int)((r / U1) % T);
+        b = (int)(r / ((long long)U1 * T));
+        lab = labels + (size_t)b * (U1 - 1);
+    }
     const int Tn = clampi(Tn_[b], 1, T), Un = clampi(Un_[b], 0, U1 - 1);
     if (t >= Tn || u > Un) {            // outside the sub-lattice: no gradient, nothing to gather
         if (lane == 0) lse[r] = 0.f;
@@ -936,7 +985,7 @@ __global__ __launch_bounds__(256) void rnnt_lse_gather_kernel(
     // (label -> row[label], row[blank] -> three stores on one lane) was a chain of dependent round trips as long as the
     // streaming part, with the whole wave's registers parked behind it (7.4 ms for one 32.6 GB read = 4.4 TB/s).
     int y = -1;
-    if (u < Un) y = labels[(size_t)b * (U1 - 1) + u];
+    if (u < Un) y = lab[u];
     f32x4 v[CQ];
 #pragma unroll
     for (int q = 0; q < CQ; ++q)
@@ -1068,7 +1117,7 @@ __global__ __launch_bounds__(256) void rnnt_dlogits_fused_kernel(const float *__
 
 extern "C" {
 
-int pika_amd_abi_version(void) { return 22; }
+int pika_amd_abi_version(void) { return 23; }
 
 size_t pika_rnnt_workspace_bytes(int B, int T, int U1) {
     if (B <= 0 || T <= 0 || U1 <= 0 || U1 > 1024) return 0;
@@ -1085,16 +1134,15 @@ int pika_rnnt_loss_forward(const float *log_probs, const int *labels, const int 
     const Lattice L = carve(workspace, B, T, U1);
     const dim3 grid((unsigned)((L.D + 4 * GATHER_ROWS - 1) / (4 * GATHER_ROWS)), (unsigned)(L.Wp / 64),
                     (unsigned)B);
-    hipLaunchKernelGGL(rnnt_gather_kernel, grid, dim3(256), 0, s,
+    hipLaunchKernelGGL(rnnt_gather_kernel<false>, grid, dim3(256), 0, s,
                        log_probs, labels, frames_lengths, labels_lengths, B, T, U1, V, blank, L.lpb,
                        L.lpe, L.Wp, L.D);
     return run_alpha_beta(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
 }
 
 namespace {
-// the streaming pass: dense (B,T,U1,V) gradient from the row metadata in the workspace
-int write_dense_grads(const Lattice &L, int B, int T, int U1, int V, int blank, float *grads, hipStream_t s) {
-    const size_t nrows = (size_t)B * T * U1;
+// the streaming pass: dense (nrows, V) gradient from the row metadata in the workspace (nrows = B*T*U1 padded, N packed)
+int write_dense_grads(const Lattice &L, size_t nrows, int V, int blank, float *grads, hipStream_t s) {
     const size_t n = nrows * (size_t)V;
     const bool vec4 = (V % 4 == 0) && ((reinterpret_cast<uintptr_t>(grads) & 15) == 0);
     if (vec4) {
@@ -1118,22 +1166,66 @@ int write_dense_grads(const Lattice &L, int B, int T, int U1, int V, int blank, 
     }
     return (int)hipGetLastError();
 }
+
+// FastEmit lambda -> the factor of the label entries of the row metadata (finite, >= 0; NaN fails the compare)
+int label_scale(float fastemit_lambda, float *lscale) {
+    if (!(fastemit_lambda >= 0.0f && fastemit_lambda <= 3.4e38f)) return PIKA_EINVAL;
+    *lscale = 1.0f + fastemit_lambda;
+    return PIKA_OK;
+}
+
+// row metadata of the B*T*U1 rows of a padded batch
+void launch_rowmeta(const Lattice &L, const int *labels, const int *Tn, const int *Un, int B, int T, int U1, int V,
+                    const float *grad_costs, float lscale, hipStream_t s) {
+    const size_t nrows = (size_t)B * T * U1;
+    hipLaunchKernelGGL(rnnt_rowmeta_kernel<false>, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s,
+                       labels, Tn, Un, B, T, U1, V, grad_costs, L.lpb, L.lpe,
+                       L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, L.meta, lscale,
+                       static_cast<const int *>(nullptr), static_cast<const int *>(nullptr), 0L);
+}
+
+// ... and of the N rows of a packed one
+void launch_rowmeta_packed(const Lattice &L, const int *labels, const int *Tn, const int *Un, const int *roff,
+                           const int *loff, int B, int T, int U1, long long N, int V, const float *grad_costs,
+                           float lscale, hipStream_t s) {
+    hipLaunchKernelGGL(rnnt_rowmeta_kernel<true>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s,
+                       labels, Tn, Un, B, T, U1, V, grad_costs, L.lpb, L.lpe,
+                       L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, L.meta, lscale, roff, loff, (long)N);
+}
+
+// the packed calls' shared checks: (B, T_max, U1_max) as check_dims, 0 < N <= B*T_max*U1_max (the metadata region) and
+// N < 2^31; the offsets are required, the labels and their offsets when some utterance has a label (U1_max > 1)
+int check_packed(int B, int T, int U1, long long N, int V, int blank, const int *labels, const int *frames_lengths,
+                 const int *labels_lengths, const int *roff, const int *loff) {
+    if (int rc = check_dims(B, T, U1, V, blank)) return rc;
+    if (!frames_lengths || !labels_lengths || !roff || N <= 0) return PIKA_EINVAL;
+    if (U1 > 1 && (!labels || !loff)) return PIKA_EINVAL;
+    if (N > 0x7fffffffLL) return PIKA_ETOOBIG;
+    if (N > (long long)B * T * U1) return PIKA_EINVAL;
+    return PIKA_OK;
+}
 }  // namespace
+
+int pika_rnnt_loss_backward_fe(const int *labels, const int *frames_lengths, const int *labels_lengths,
+                               int B, int T, int U1, int V, int blank, const float *grad_costs,
+                               const void *workspace, float *grads, float fastemit_lambda, void *stream) {
+    if (int rc = check_dims(B, T, U1, V, blank)) return rc;
+    if (!frames_lengths || !labels_lengths || !workspace) return PIKA_EINVAL;
+    if (U1 > 1 && !labels) return PIKA_EINVAL;
+    float lscale;
+    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
+    launch_rowmeta(L, labels, frames_lengths, labels_lengths, B, T, U1, V, grad_costs, lscale, s);
+    if (!grads) return (int)hipGetLastError();   // row metadata only (pika_rnnt.h)
+    return write_dense_grads(L, (size_t)B * T * U1, V, blank, grads, s);
+}
 
 int pika_rnnt_loss_backward(const int *labels, const int *frames_lengths, const int *labels_lengths,
                             int B, int T, int U1, int V, int blank, const float *grad_costs,
                             const void *workspace, float *grads, void *stream) {
-    if (int rc = check_dims(B, T, U1, V, blank)) return rc;
-    if (!frames_lengths || !labels_lengths || !workspace) return PIKA_EINVAL;
-    if (U1 > 1 && !labels) return PIKA_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
-    const size_t nrows = (size_t)B * T * U1;
-    hipLaunchKernelGGL(rnnt_rowmeta_kernel, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s,
-                       labels, frames_lengths, labels_lengths, B, T, U1, V, grad_costs, L.lpb, L.lpe,
-                       L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, L.meta);
-    if (!grads) return (int)hipGetLastError();   // row metadata only (pika_rnnt.h)
-    return write_dense_grads(L, B, T, U1, V, blank, grads, s);
+    return pika_rnnt_loss_backward_fe(labels, frames_lengths, labels_lengths, B, T, U1, V, blank, grad_costs, workspace,
+                                      grads, 0.0f, stream);
 }
 
 int pika_rnnt_loss_dense_grads(const void *workspace, int B, int T, int U1, int V, int blank, float *grads,
@@ -1141,7 +1233,7 @@ int pika_rnnt_loss_dense_grads(const void *workspace, int B, int T, int U1, int 
     if (int rc = check_dims(B, T, U1, V, blank)) return rc;
     if (!workspace || !grads) return PIKA_EINVAL;
     const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
-    return write_dense_grads(L, B, T, U1, V, blank, grads, static_cast<hipStream_t>(stream));
+    return write_dense_grads(L, (size_t)B * T * U1, V, blank, grads, static_cast<hipStream_t>(stream));
 }
 
 int pika_rnnt_loss_fwd_bwd(const float *log_probs, const int *labels, const int *frames_lengths,
@@ -1306,25 +1398,10 @@ int pika_rnnt_dlogits_compact_bf16_f16in(const void *logits16, long long ld_in, 
     return (int)hipGetLastError();
 }
 
-int pika_rnnt_fused_backward(const float *logits, const float *lse, const int *labels,
-                             const int *frames_lengths, const int *labels_lengths, int B, int T, int U1, int V,
-                             int blank, const float *grad_costs, const void *workspace, void *grad_logits,
-                             int out_dtype, long long ld_out, void *stream) {
-    if (int rc = check_dims(B, T, U1, V, blank)) return rc;
-    if (!logits || !lse || !frames_lengths || !labels_lengths || !workspace || !grad_logits) return PIKA_EINVAL;
-    if (U1 > 1 && !labels) return PIKA_EINVAL;
-    if ((V & 3) || V > V_MAX || ld_out < V || (ld_out & 3) || ld_out > V_MAX ||
-        (reinterpret_cast<uintptr_t>(logits) & 15))
-        return PIKA_EINVAL;
-    if (out_dtype != 0 && out_dtype != 1) return PIKA_EINVAL;   // PIKA_F32 / PIKA_BF16 (pika_gemm.h)
-    if (reinterpret_cast<uintptr_t>(grad_logits) & (out_dtype == 0 ? 15 : 7)) return PIKA_EINVAL;
-    const long long rows = (long long)B * T * U1;
-    if (rows > 0x7fffffffLL) return PIKA_ETOOBIG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
-    hipLaunchKernelGGL(rnnt_rowmeta_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s,
-                       labels, frames_lengths, labels_lengths, B, T, U1, V, grad_costs, L.lpb, L.lpe,
-                       L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, L.meta);
+namespace {
+// d(logits) of the fused route over `rows` rows, from the row metadata in L
+int launch_dlogits_fused(const Lattice &L, const float *logits, const float *lse, long long rows, int V, int blank,
+                         void *grad_logits, int out_dtype, long long ld_out, hipStream_t s) {
     const dim3 grid((unsigned)((rows + 3) / 4));
     if (out_dtype == 0)
         PIKA_CQ(ld_out, hipLaunchKernelGGL((rnnt_dlogits_fused_kernel<float, CQ>), grid, dim3(256), 0, s, logits, lse, L.meta,
@@ -1333,6 +1410,118 @@ int pika_rnnt_fused_backward(const float *logits, const float *lse, const int *l
         PIKA_CQ(ld_out, hipLaunchKernelGGL((rnnt_dlogits_fused_kernel<__bf16, CQ>), grid, dim3(256), 0, s, logits, lse, L.meta,
                                            static_cast<__bf16 *>(grad_logits), rows, V, ld_out, blank));
     return (int)hipGetLastError();
+}
+
+// the d(logits) arguments of the fused backward calls
+int check_dlogits_out(const float *logits, int V, const void *grad_logits, int out_dtype, long long ld_out) {
+    if ((V & 3) || V > V_MAX || ld_out < V || (ld_out & 3) || ld_out > V_MAX ||
+        (reinterpret_cast<uintptr_t>(logits) & 15))
+        return PIKA_EINVAL;
+    if (out_dtype != 0 && out_dtype != 1) return PIKA_EINVAL;   // PIKA_F32 / PIKA_BF16 (pika_gemm.h)
+    if (reinterpret_cast<uintptr_t>(grad_logits) & (out_dtype == 0 ? 15 : 7)) return PIKA_EINVAL;
+    return PIKA_OK;
+}
+}  // namespace
+
+int pika_rnnt_fused_backward_fe(const float *logits, const float *lse, const int *labels,
+                                const int *frames_lengths, const int *labels_lengths, int B, int T, int U1, int V,
+                                int blank, const float *grad_costs, const void *workspace, void *grad_logits,
+                                int out_dtype, long long ld_out, float fastemit_lambda, void *stream) {
+    if (int rc = check_dims(B, T, U1, V, blank)) return rc;
+    if (!logits || !lse || !frames_lengths || !labels_lengths || !workspace || !grad_logits) return PIKA_EINVAL;
+    if (U1 > 1 && !labels) return PIKA_EINVAL;
+    if (int rc = check_dlogits_out(logits, V, grad_logits, out_dtype, ld_out)) return rc;
+    float lscale;
+    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
+    const long long rows = (long long)B * T * U1;
+    if (rows > 0x7fffffffLL) return PIKA_ETOOBIG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
+    launch_rowmeta(L, labels, frames_lengths, labels_lengths, B, T, U1, V, grad_costs, lscale, s);
+    return launch_dlogits_fused(L, logits, lse, rows, V, blank, grad_logits, out_dtype, ld_out, s);
+}
+
+int pika_rnnt_fused_backward(const float *logits, const float *lse, const int *labels,
+                             const int *frames_lengths, const int *labels_lengths, int B, int T, int U1, int V,
+                             int blank, const float *grad_costs, const void *workspace, void *grad_logits,
+                             int out_dtype, long long ld_out, void *stream) {
+    return pika_rnnt_fused_backward_fe(logits, lse, labels, frames_lengths, labels_lengths, B, T, U1, V, blank, grad_costs,
+                                       workspace, grad_logits, out_dtype, ld_out, 0.0f, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// packed layout (pika_rnnt.h): the lattice planes, alpha/beta and the workspace of a padded
+// (B, T_max, U1_max) batch; gather, row metadata and the row passes address the N packed rows
+// ---------------------------------------------------------------------------------------------
+int pika_rnnt_packed_forward(const float *log_probs, const int *labels, const int *frames_lengths,
+                             const int *labels_lengths, const int *row_offsets, const int *label_offsets, int B,
+                             int T_max, int U1_max, long long N, int V, int blank, float *costs, void *workspace,
+                             void *stream) {
+    if (int rc = check_packed(B, T_max, U1_max, N, V, blank, labels, frames_lengths, labels_lengths, row_offsets,
+                              label_offsets))
+        return rc;
+    if (!log_probs || !costs || !workspace) return PIKA_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Lattice L = carve(workspace, B, T_max, U1_max);
+    const dim3 grid((unsigned)((L.D + 4 * GATHER_ROWS - 1) / (4 * GATHER_ROWS)), (unsigned)(L.Wp / 64),
+                    (unsigned)B);
+    hipLaunchKernelGGL(rnnt_gather_kernel<true>, grid, dim3(256), 0, s, log_probs, labels, frames_lengths,
+                       labels_lengths, B, T_max, U1_max, V, blank, L.lpb, L.lpe, L.Wp, L.D, row_offsets, label_offsets);
+    return run_alpha_beta(L, frames_lengths, labels_lengths, costs, B, T_max, U1_max, s);
+}
+
+int pika_rnnt_packed_backward(const int *labels, const int *frames_lengths, const int *labels_lengths,
+                              const int *row_offsets, const int *label_offsets, int B, int T_max, int U1_max,
+                              long long N, int V, int blank, const float *grad_costs, const void *workspace,
+                              float *grads, float fastemit_lambda, void *stream) {
+    if (int rc = check_packed(B, T_max, U1_max, N, V, blank, labels, frames_lengths, labels_lengths, row_offsets,
+                              label_offsets))
+        return rc;
+    if (!workspace) return PIKA_EINVAL;
+    float lscale;
+    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Lattice L = carve(const_cast<void *>(workspace), B, T_max, U1_max);
+    launch_rowmeta_packed(L, labels, frames_lengths, labels_lengths, row_offsets, label_offsets, B, T_max, U1_max, N, V,
+                          grad_costs, lscale, s);
+    if (!grads) return (int)hipGetLastError();
+    return write_dense_grads(L, (size_t)N, V, blank, grads, s);
+}
+
+int pika_rnnt_packed_fused_forward(const float *logits, const int *labels, const int *frames_lengths,
+                                   const int *labels_lengths, const int *row_offsets, const int *label_offsets, int B,
+                                   int T_max, int U1_max, long long N, int V, int blank, float *costs, float *lse,
+                                   void *workspace, void *stream) {
+    if (int rc = check_packed(B, T_max, U1_max, N, V, blank, labels, frames_lengths, labels_lengths, row_offsets,
+                              label_offsets))
+        return rc;
+    if (!logits || !costs || !lse || !workspace) return PIKA_EINVAL;
+    if ((V & 3) || V > V_MAX || (reinterpret_cast<uintptr_t>(logits) & 15)) return PIKA_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Lattice L = carve(workspace, B, T_max, U1_max);
+    PIKA_CQ(V, hipLaunchKernelGGL((rnnt_lse_gather_kernel<CQ, true>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, logits,
+                                  labels, frames_lengths, labels_lengths, N, T_max, U1_max, V, blank, lse, L.lpb, L.lpe, L.Wp,
+                                  L.D, row_offsets, label_offsets, B));
+    return run_alpha_beta(L, frames_lengths, labels_lengths, costs, B, T_max, U1_max, s);
+}
+
+int pika_rnnt_packed_fused_backward(const float *logits, const float *lse, const int *labels,
+                                    const int *frames_lengths, const int *labels_lengths, const int *row_offsets,
+                                    const int *label_offsets, int B, int T_max, int U1_max, long long N, int V,
+                                    int blank, const float *grad_costs, const void *workspace, void *grad_logits,
+                                    int out_dtype, long long ld_out, float fastemit_lambda, void *stream) {
+    if (int rc = check_packed(B, T_max, U1_max, N, V, blank, labels, frames_lengths, labels_lengths, row_offsets,
+                              label_offsets))
+        return rc;
+    if (!logits || !lse || !workspace || !grad_logits) return PIKA_EINVAL;
+    if (int rc = check_dlogits_out(logits, V, grad_logits, out_dtype, ld_out)) return rc;
+    float lscale;
+    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Lattice L = carve(const_cast<void *>(workspace), B, T_max, U1_max);
+    launch_rowmeta_packed(L, labels, frames_lengths, labels_lengths, row_offsets, label_offsets, B, T_max, U1_max, N, V,
+                          grad_costs, lscale, s);
+    return launch_dlogits_fused(L, logits, lse, N, V, blank, grad_logits, out_dtype, ld_out, s);
 }
 
 }  // extern "C"

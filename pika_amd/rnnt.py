@@ -16,7 +16,18 @@ by autograd's grad_output -- warp_rnnt instead materialises it in forward and mu
 again in backward (3 extra passes over 32 GB at the benchmark shape).  When log_probs came out of
 this package's own joint network, the gradient goes back as a LazyDenseGrad: the joint's backward
 reads the loss workspace and the dense tensor is written only if anything else touches it.
+
+Two options of warp_rnnt's keyword surface (README "RNN-T loss"):
+  fastemit_lambda  FastEmit (Yu et al. 2021, arXiv:2010.11148): the costs are unchanged, the gradient of every
+                   label-emission entry (n, t, u, y_{u+1}), u < U_n, is multiplied by 1 + lambda.  The factor lives in
+                   the row metadata of the loss workspace, so every backward route (dense, lazy, fused) carries it.
+  compact=True     the packed layout: log_probs (N, V) with N = sum_n T_n (U_n + 1), rows utterance-major then t then u,
+                   labels (sum_n U_n,) concatenated; gradient (N, V).  No padding is read or written.  It costs ONE
+                   device-to-host copy of the two length vectors (T_max, U1_max and N size the launch), so it cannot run
+                   under stream capture; the padded layout never synchronises.
 """
+import math
+
 import torch
 
 from . import _lib
@@ -228,9 +239,16 @@ class LazyLogProbs(torch.Tensor):
         return func(*tree_map(un, args), **tree_map(un, kwargs or {}))
 
 
+def _check_lambda(fastemit_lambda):
+    lam = float(fastemit_lambda)
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError("fastemit_lambda must be finite and >= 0, got %r" % (fastemit_lambda,))
+    return lam
+
+
 class _RNNTLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, log_probs, labels, frames_lengths, labels_lengths, blank=0):
+    def forward(ctx, log_probs, labels, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0):
         wide = getattr(log_probs, "_pika_labels", None)
         if wide is not None and labels.dim() == 2 and log_probs.dim() == 4 and labels.shape[1] < log_probs.shape[2] - 1 \
                 and wide.shape == (labels.shape[0], log_probs.shape[2] - 1):
@@ -301,32 +319,34 @@ class _RNNTLossFn(torch.autograd.Function):
         # to the joint's backward while its buffer is still raw, which that backward checks itself
         ctx.save_for_backward(labels, frames_lengths, labels_lengths, ws, lse)
         ctx.dims = (B, T, U1, V, blank)
+        ctx.fastemit_lambda = fastemit_lambda
         return costs
 
     @staticmethod
     def backward(ctx, grad_costs):
         labels, frames_lengths, labels_lengths, ws, lse = ctx.saved_tensors
         B, T, U1, V, blank = ctx.dims
+        lam = ctx.fastemit_lambda
         lib = _lib.lib()
         gc = grad_costs.to(torch.float32).contiguous()
         if ctx.lazy:
             with torch.cuda.device(ws.device):
-                _lib.check(lib.pika_rnnt_loss_backward(
+                _lib.check(lib.pika_rnnt_loss_backward_fe(
                     _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank,
-                    _ptr(gc), _ptr(ws), None, _stream()), "pika_rnnt_loss_backward")
+                    _ptr(gc), _ptr(ws), None, lam, _stream()), "pika_rnnt_loss_backward_fe")
             compact = CompactGrad.__new__(CompactGrad)
             compact.ws, compact.dims, compact.ptr, compact.version = ws, (B, T, U1, V, blank), 0, 0
             lazy = LazyDenseGrad(compact, labels, frames_lengths, labels_lengths, width=ctx.width)
             lazy.lse = lse
-            return lazy, None, None, None, None
+            return lazy, None, None, None, None, None
         with torch.cuda.device(ws.device):
             grads = torch.empty((B, T, U1, V), dtype=torch.float32, device=ws.device)
             with _timed("bwd"):
-                _lib.check(lib.pika_rnnt_loss_backward(
+                _lib.check(lib.pika_rnnt_loss_backward_fe(
                     _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank,
-                    _ptr(gc), _ptr(ws), _ptr(grads), _stream()), "pika_rnnt_loss_backward")
+                    _ptr(gc), _ptr(ws), _ptr(grads), lam, _stream()), "pika_rnnt_loss_backward_fe")
         grads._pika_compact = CompactGrad(ws, (B, T, U1, V, blank), grads)
-        return grads, None, None, None, None
+        return grads, None, None, None, None, None
 
 
 class _FusedLogitsLossFn(torch.autograd.Function):
@@ -335,7 +355,7 @@ class _FusedLogitsLossFn(torch.autograd.Function):
     log-prob tensor and its dense gradient never exist: 3 tensor passes instead of 6."""
 
     @staticmethod
-    def forward(ctx, logits, labels, frames_lengths, labels_lengths, blank=0):
+    def forward(ctx, logits, labels, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0):
         _check_inputs(logits, labels, frames_lengths, labels_lengths, blank)
         lib = _lib.lib()
         x = logits.contiguous()
@@ -351,6 +371,7 @@ class _FusedLogitsLossFn(torch.autograd.Function):
                     _ptr(costs), _ptr(lse), _ptr(ws), _stream()), "pika_rnnt_fused_forward")
         ctx.save_for_backward(x, labels, frames_lengths, labels_lengths, ws, lse)
         ctx.dims = (B, T, U1, V, blank)
+        ctx.fastemit_lambda = fastemit_lambda
         return costs
 
     @staticmethod
@@ -361,22 +382,172 @@ class _FusedLogitsLossFn(torch.autograd.Function):
         with torch.cuda.device(x.device):
             grads = torch.empty_like(x)
             with _timed("bwd"):
-                _lib.check(_lib.lib().pika_rnnt_fused_backward(
+                _lib.check(_lib.lib().pika_rnnt_fused_backward_fe(
                     _ptr(x), _ptr(lse), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V,
-                    blank, _ptr(gc), _ptr(ws), _ptr(grads), 0, V, _stream()), "pika_rnnt_fused_backward")
-        return grads, None, None, None, None
+                    blank, _ptr(gc), _ptr(ws), _ptr(grads), 0, V, ctx.fastemit_lambda, _stream()),
+                    "pika_rnnt_fused_backward_fe")
+        return grads, None, None, None, None, None
 
 
-def rnnt_loss_from_logits(logits, labels, frames_lengths, labels_lengths, blank=0):
+class _Packed(object):
+    """Host description of a packed batch: B, T_max, U1_max, N and the device row / label offsets."""
+
+    __slots__ = ("B", "T", "U1", "N", "roff", "loff")
+
+
+def _check_packed(x, labels, frames_lengths, labels_lengths, blank, what):
+    """Validate a packed call before any launch; ONE device-to-host copy of the two length vectors."""
+    if not x.is_cuda:
+        raise RuntimeError("pika_amd RNNTLoss: %s must live on a HIP device" % what)
+    if x.dtype != torch.float32:
+        raise TypeError("%s must be float32, got %s" % (what, x.dtype))
+    for name, t in (("labels", labels), ("frames_lengths", frames_lengths), ("labels_lengths", labels_lengths)):
+        if t.dtype != torch.int32:
+            raise TypeError("%s must be int32, got %s" % (name, t.dtype))
+        if t.device != x.device:
+            raise RuntimeError("%s is on %s but %s is on %s" % (name, t.device, what, x.device))
+    if x.dim() != 2:
+        raise ValueError("compact=True: %s must be (N, V), got %s" % (what, tuple(x.shape)))
+    if labels.dim() != 1:
+        raise ValueError("compact=True: labels must be (sum U_n,), got %s" % (tuple(labels.shape),))
+    if frames_lengths.dim() != 1 or labels_lengths.shape != frames_lengths.shape or frames_lengths.numel() == 0:
+        raise ValueError("compact=True: frames_lengths / labels_lengths must be (B,) with B >= 1")
+    N, V = x.shape
+    if not 0 <= blank < V:
+        raise ValueError("blank=%d outside [0,%d)" % (blank, V))
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("rnnt_loss(compact=True) reads the length vectors on the host (T_max, U1_max, N) and cannot "
+                           "run under stream capture; capture the padded layout instead")
+    lens = torch.stack([frames_lengths, labels_lengths]).to("cpu", torch.int64)   # the packed call's one host sync
+    tl, ul = lens[0], lens[1]
+    if bool((tl < 1).any()):
+        raise ValueError("compact=True: every frames_lengths entry must be >= 1, got %s" % (tl.tolist(),))
+    if bool((ul < 0).any()):
+        raise ValueError("compact=True: every labels_lengths entry must be >= 0, got %s" % (ul.tolist(),))
+    if int(ul.max()) + 1 > 1024:
+        raise ValueError("compact=True: U_n + 1 = %d > 1024 not supported" % (int(ul.max()) + 1))
+    rows = tl * (ul + 1)
+    if int(rows.sum()) != N:
+        raise ValueError("compact=True: %s has %d rows, sum_n T_n (U_n + 1) = %d" % (what, N, int(rows.sum())))
+    if int(ul.sum()) != labels.numel():
+        raise ValueError("compact=True: labels has %d entries, sum_n U_n = %d" % (labels.numel(), int(ul.sum())))
+    if N > 0x7fffffff:
+        raise ValueError("compact=True: N = %d rows > 2^31 - 1" % N)
+    p = _Packed()
+    p.B, p.T, p.U1, p.N = int(tl.numel()), int(tl.max()), int(ul.max()) + 1, int(N)
+    # offsets on the device, from the device copies of the lengths (exclusive prefix sums)
+    r = frames_lengths.to(torch.int64) * (labels_lengths.to(torch.int64) + 1)
+    u = labels_lengths.to(torch.int64)
+    p.roff = (torch.cumsum(r, 0) - r).to(torch.int32)
+    p.loff = (torch.cumsum(u, 0) - u).to(torch.int32)
+    return p
+
+
+class _PackedLossFn(torch.autograd.Function):
+    """RNN-T costs of a packed batch of log-probs (N, V); gradient (N, V)."""
+
+    @staticmethod
+    def forward(ctx, log_probs, labels, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0):
+        p = _check_packed(log_probs, labels, frames_lengths, labels_lengths, blank, "log_probs")
+        lib = _lib.lib()
+        lp = log_probs.contiguous()
+        labels, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, frames_lengths, labels_lengths))
+        V = lp.shape[1]
+        with torch.cuda.device(lp.device):
+            costs = torch.empty(p.B, dtype=torch.float32, device=lp.device)
+            ws = torch.empty(lib.pika_rnnt_workspace_bytes(p.B, p.T, p.U1), dtype=torch.uint8, device=lp.device)
+            with _timed("fwd"):
+                _lib.check(lib.pika_rnnt_packed_forward(
+                    _ptr(lp), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(p.roff), _ptr(p.loff),
+                    p.B, p.T, p.U1, p.N, V, blank, _ptr(costs), _ptr(ws), _stream()), "pika_rnnt_packed_forward")
+        ctx.save_for_backward(labels, frames_lengths, labels_lengths, ws, p.roff, p.loff)
+        ctx.dims = (p.B, p.T, p.U1, p.N, V, blank)
+        ctx.fastemit_lambda = fastemit_lambda
+        return costs
+
+    @staticmethod
+    def backward(ctx, grad_costs):
+        labels, frames_lengths, labels_lengths, ws, roff, loff = ctx.saved_tensors
+        B, T, U1, N, V, blank = ctx.dims
+        gc = grad_costs.to(torch.float32).contiguous()
+        with torch.cuda.device(ws.device):
+            grads = torch.empty((N, V), dtype=torch.float32, device=ws.device)
+            with _timed("bwd"):
+                _lib.check(_lib.lib().pika_rnnt_packed_backward(
+                    _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(roff), _ptr(loff), B, T, U1, N, V,
+                    blank, _ptr(gc), _ptr(ws), _ptr(grads), ctx.fastemit_lambda, _stream()), "pika_rnnt_packed_backward")
+        return grads, None, None, None, None, None
+
+
+class _PackedLogitsLossFn(torch.autograd.Function):
+    """_FusedLogitsLossFn on a packed batch of raw logits (N, V)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0):
+        p = _check_packed(logits, labels, frames_lengths, labels_lengths, blank, "logits")
+        lib = _lib.lib()
+        x = logits.contiguous()
+        labels, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, frames_lengths, labels_lengths))
+        V = x.shape[1]
+        if V % 4 or V > MAX_FUSED_V:
+            raise ValueError("rnnt_loss_from_logits: V = %d must be a multiple of 4 and <= %d" % (V, MAX_FUSED_V))
+        with torch.cuda.device(x.device):
+            costs = torch.empty(p.B, dtype=torch.float32, device=x.device)
+            lse = torch.empty(p.N, dtype=torch.float32, device=x.device)
+            ws = torch.empty(lib.pika_rnnt_workspace_bytes(p.B, p.T, p.U1), dtype=torch.uint8, device=x.device)
+            with _timed("fwd"):
+                _lib.check(lib.pika_rnnt_packed_fused_forward(
+                    _ptr(x), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(p.roff), _ptr(p.loff),
+                    p.B, p.T, p.U1, p.N, V, blank, _ptr(costs), _ptr(lse), _ptr(ws), _stream()),
+                    "pika_rnnt_packed_fused_forward")
+        ctx.save_for_backward(x, labels, frames_lengths, labels_lengths, ws, lse, p.roff, p.loff)
+        ctx.dims = (p.B, p.T, p.U1, p.N, V, blank)
+        ctx.fastemit_lambda = fastemit_lambda
+        return costs
+
+    @staticmethod
+    def backward(ctx, grad_costs):
+        x, labels, frames_lengths, labels_lengths, ws, lse, roff, loff = ctx.saved_tensors
+        B, T, U1, N, V, blank = ctx.dims
+        gc = grad_costs.to(torch.float32).contiguous()
+        with torch.cuda.device(x.device):
+            grads = torch.empty_like(x)
+            with _timed("bwd"):
+                _lib.check(_lib.lib().pika_rnnt_packed_fused_backward(
+                    _ptr(x), _ptr(lse), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(roff), _ptr(loff),
+                    B, T, U1, N, V, blank, _ptr(gc), _ptr(ws), _ptr(grads), 0, V, ctx.fastemit_lambda, _stream()),
+                    "pika_rnnt_packed_fused_backward")
+        return grads, None, None, None, None, None
+
+
+def rnnt_loss_from_logits(logits, labels, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0,
+                          compact=False):
     """Per-utterance costs of log_softmax(logits) under the RNN-T loss, differentiable w.r.t. the logits,
-    without materialising the log-probabilities (V % 4 == 0, V <= 8192)."""
-    return _FusedLogitsLossFn.apply(logits, labels, frames_lengths, labels_lengths, blank)
+    without materialising the log-probabilities (V % 4 == 0, V <= 8192).
+
+    fastemit_lambda: FastEmit (module docstring); d(logits) = g~ - softmax * sum(g~) with the scaled gradient g~.
+    compact=True: packed raw logits (N, V) and labels (sum U_n,) as in `rnnt_loss`, one host sync."""
+    lam = _check_lambda(fastemit_lambda)
+    fn = _PackedLogitsLossFn if compact else _FusedLogitsLossFn
+    return fn.apply(logits, labels, frames_lengths, labels_lengths, blank, lam)
 
 
 def rnnt_loss(log_probs, labels, frames_lengths, labels_lengths, average_frames=False,
-              reduction=None, blank=0):
-    """Functional form (same keyword surface as warp_rnnt.rnnt_loss)."""
-    costs = _RNNTLossFn.apply(log_probs, labels, frames_lengths, labels_lengths, blank)
+              reduction=None, blank=0, gather=False, fastemit_lambda=0.0, compact=False):
+    """Functional form, with warp_rnnt.rnnt_loss's keywords.
+
+    gather: accepted for compatibility; it changes no value -- the kernels only ever read the blank and label
+      columns of a cell (warp_rnnt's `gather=True` saving is what they always do).
+    fastemit_lambda: FastEmit regularisation, finite and >= 0 (Yu et al. 2021).  Costs unchanged; in the gradient every
+      label-emission entry (n, t, u, y_{u+1}), u < U_n, is multiplied by 1 + fastemit_lambda.  0 is exactly the plain loss.
+    compact: the packed layout.  log_probs (N, V) with N = sum_n T_n (U_n + 1), row off_n + t (U_n + 1) + u holding cell
+      (n, t, u) (off_n the exclusive prefix sum of T_n (U_n + 1)); labels (sum_n U_n,) int32 concatenated; lengths (B,)
+      int32 with T_n >= 1, U_n >= 0, U_n + 1 <= 1024, and the two sums equal to N and labels.numel() (ValueError before
+      any launch otherwise: nothing is clamped).  Costs (B,), gradient (N, V).  Costs ONE device-to-host copy of the
+      lengths, so it raises under stream capture; the padded layout keeps its no-sync behaviour."""
+    lam = _check_lambda(fastemit_lambda)
+    fn = _PackedLossFn if compact else _RNNTLossFn
+    costs = fn.apply(log_probs, labels, frames_lengths, labels_lengths, blank, lam)
     if average_frames:
         costs = costs / frames_lengths.to(costs)
     if reduction == "sum":
@@ -391,17 +562,19 @@ def rnnt_loss(log_probs, labels, frames_lengths, labels_lengths, average_frames=
 class RNNTLoss(object):
     """`RNNTLoss(blank=0, reduction='sum').apply(...)` exactly as the reference scripts use it.
 
-    As with the binding the reference imports, constructor keywords other than `blank` do not
-    change what `.apply` returns: per-utterance costs (B,), which the caller reduces itself
-    (train_transducer_bmuf_otfaug.py:99 `loss = loss.sum()`).
+    As with the binding the reference imports, `reduction` does not change what `.apply` returns:
+    per-utterance costs (B,), which the caller reduces itself (train_transducer_bmuf_otfaug.py:99
+    `loss = loss.sum()`).  `fastemit_lambda` (finite, >= 0) scales the label-emission entries of the
+    gradient by 1 + lambda, as in `rnnt_loss`.
     """
 
-    def __init__(self, blank=0, reduction="sum", **unused):
+    def __init__(self, blank=0, reduction="sum", fastemit_lambda=0.0, **unused):
         self.blank = int(blank)
         self.reduction = reduction
+        self.fastemit_lambda = _check_lambda(fastemit_lambda)
 
     def apply(self, log_probs, labels, frames_lengths, labels_lengths):
-        return _RNNTLossFn.apply(log_probs, labels, frames_lengths, labels_lengths, self.blank)
+        return _RNNTLossFn.apply(log_probs, labels, frames_lengths, labels_lengths, self.blank, self.fastemit_lambda)
 
     __call__ = apply
 
