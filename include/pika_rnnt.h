@@ -195,6 +195,29 @@ int pika_rnnt_packed_fused_backward(const float *logits, const float *lse, const
                                     int blank, const float *grad_costs, const void *workspace, void *grad_logits,
                                     int out_dtype, long long ld_out, float fastemit_lambda, void *stream);
 
+/* Forced alignment: the single best path of every utterance's lattice (Viterbi, max-plus),
+ *   delta(0,0) = 0,  delta(t,u) = max(delta(t-1,u) + lpb(t-1,u), delta(t,u-1) + lpe(t,u-1)),
+ *   scores[n] = delta(T_n-1, U_n) + lpb(T_n-1, U_n)            (<= -costs[n])
+ * with lpb / lpe the blank and label log-probs of a cell.  Reads ONLY those two planes of a `workspace` left by any
+ * forward call above -- pika_rnnt_loss_forward, pika_rnnt_fused_forward (and its _partials / _gathered forms),
+ * pika_rnnt_packed_forward, pika_rnnt_packed_fused_forward -- with the same (B, T, U1) (packed: T_max, U1_max) and
+ * lengths, and leaves it untouched: forward -> align -> backward gives the gradients of forward -> backward.
+ *   scores        f32 (B,)
+ *   emit_frames   i32; label_offsets == NULL: (B, U1-1), entry [n][u], u < U_n, the frame t at which the best path
+ *                 emits label u (takes the emission edge out of cell (t, u)), entries u >= U_n set to -1;
+ *                 label_offsets (the packed layout's exclusive prefix sum of U_n) given: (sum_n U_n,), utterance
+ *                 n's U_n frames at label_offsets[n], nothing else written.  May be NULL when U1 == 1.
+ *                 Non-decreasing in u, in [0, T_n-1].  Ties go to the blank predecessor (t-1, u) in the back-trace
+ *                 from (T_n-1, U_n), i.e. to the earliest emission.  A label outside [0, V) (an infeasible
+ *                 transcript, -1e30 in the plane) still yields a valid monotone path; its score is <= -1e30.
+ *   scratch       pika_rnnt_align_scratch_bytes(B, T, U1) bytes (one back-pointer bit per cell of the skewed
+ *                 lattice); 0 is returned for dimensions the call refuses.
+ * One launch, values accumulated in fp32.  PIKA_EINVAL / PIKA_ETOOBIG as above, before any launch. */
+size_t pika_rnnt_align_scratch_bytes(int B, int T, int U1);
+int pika_rnnt_align(const void *workspace, const int *frames_lengths, const int *labels_lengths,
+                    const int *label_offsets, int B, int T, int U1, float *scores, int *emit_frames,
+                    void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -671,6 +671,141 @@ void launch_ab(const Lattice &L, const int *Tn, const int *Un, float *costs, int
                        L.D);
 }
 
+// ---------------------------------------------------------------------------------------------
+// forced alignment: the max-plus (Viterbi) recurrence over the same skewed planes,
+//   delta_d[u] = max(delta_{d-1}[u] + lpb_{d-1}[u], delta_{d-1}[u-1] + lpe_{d-1}[u-1]),
+// one workgroup per utterance, lane = u, the neighbour term by Xchg<NW>::up as in the alpha sweep.
+// Plain fp32 accumulation: max picks one of its operands, so a cell's value is the fp32 running sum
+// of ONE path's edges -- T_n + U_n rounded additions, no transcendental, nothing to renormalise.
+// The decision of a cell (1 = came over the emission edge from (t, u-1); a tie is 0, the blank
+// predecessor) is one __ballot bit: row d of the back-pointers is NW 64-bit words, written to the
+// LDS buffer by lane 0 of every wave when the utterance's T_n+U_n-1 rows fit its ALIGN_WORDS / NW
+// (the benchmark's 1049 do), to the caller's scratch otherwise.  Back-trace, same workgroup: thread 0
+// walks the rows from (T_n-1, U_n) down; rows in scratch are staged through LDS a chunk at a time.  Every step lowers d = t + u by one, so the row read
+// does not depend on the walk (for NW == 1 the loads of an unrolled batch all issue at once) and
+// only the column u is carried.  u == 0 forces the blank edge and t == 0 the emission edge (the sweep
+// writes both into the bits), so the walk stays inside the sub-lattice and ends in (0, 0) whatever
+// the planes hold (a label outside [0, V) leaves NEG there).
+// grid = B, block = NW * 64.  frames: (B, U1-1) padded with -1, or -- loff given -- utterance b's
+// U_n entries at frames + loff[b].
+// ---------------------------------------------------------------------------------------------
+constexpr int ALIGN_WORDS = 1536;  // 12 KB of LDS; a multiple of every instantiated NW
+constexpr int AUNR = 8;            // diagonals prefetched per register batch of the alignment sweep
+
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void rnnt_align_kernel(
+    const float *__restrict__ lpb_, const float *__restrict__ lpe_, const int *__restrict__ Tn_,
+    const int *__restrict__ Un_, const int *__restrict__ loff, float *__restrict__ scores,
+    int *__restrict__ frames, unsigned long long *__restrict__ bp_, int T, int U1, int Wp, int D) {
+    __shared__ float lds[2 * (NW + 1) + 2 * NW];
+    __shared__ unsigned long long bits[ALIGN_WORDS];
+    __shared__ int fr[NW * 64 + 1];
+    Xchg<NW> xc{lds, lds + 2 * (NW + 1)};
+    if constexpr (NW > 1) {
+        if (threadIdx.x < 2 * (NW + 1) + 2 * NW) lds[threadIdx.x] = NEG;
+        __syncthreads();
+    }
+    const int b = blockIdx.x;
+    const int u = threadIdx.x;
+    const int Tn = clampi(Tn_[b], 1, T), Un = clampi(Un_[b], 0, U1 - 1);
+    const int dend = Tn - 1 + Un;
+    const size_t base = (size_t)b * D * Wp + u;
+    const float *lpb = lpb_ + base;
+    unsigned long long *bp = bp_ + (size_t)b * D * NW;  // row d: bp[d * NW + wave]
+    // an utterance whose dend rows fit the LDS buffer keeps them there (row d at bits[(d-1) * NW + wave]): no global
+    // store shares the loads' counter in the sweep, and the walk needs no staging
+    constexpr int ROWS = ALIGN_WORDS / NW;
+    const bool fits = dend <= ROWS;  // workgroup-uniform
+
+    // Rows come in by buffer loads at a uniform row offset plus the lane's fixed column (a row past the planes reads
+    // 0), unmasked: the planes hold garbage outside the sub-lattice, but a cell inside it never consumes any -- its
+    // value is selected by the decision bit, which the borders force, and both operands of an interior cell come
+    // from cells inside.
+    constexpr int ROWB = NW * 64 * 4;  // bytes per plane row (Wp == NW * 64)
+    const size_t plane_b = (size_t)b * D * (NW * 64);
+    const auto rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(lpb_ + plane_b), 0, D * ROWB, 0x00020000);
+    const auto re = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(lpe_ + plane_b), 0, D * ROWB, 0x00020000);
+    float pbv[2][AUNR], pev[2][AUNR];
+    float v = (u == 0) ? 0.0f : NEG;
+    auto load = [&](int buf, int d0) __attribute__((always_inline)) {  // rows d0-1 .. d0+AUNR-2
+        const int soff = __builtin_amdgcn_readfirstlane((d0 - 1) * ROWB);
+#pragma unroll
+        for (int i = 0; i < AUNR; ++i) {
+            pbv[buf][i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rb, u * 4 + i * ROWB, soff, 0));
+            pev[buf][i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(re, u * 4 + i * ROWB, soff, 0));
+        }
+    };
+    // (bitwise & and |: no exec-mask branches in the dependent chain; the compare that makes the bit also selects the
+    //  maximum; the eight words of a batch go out under one lane-0 branch)
+    const bool live = u <= Un;
+    auto steps = [&](int buf, int d0) __attribute__((always_inline)) {  // diagonals d0 .. d0+AUNR-1 (<= dend)
+        unsigned long long m[AUNR];
+#pragma unroll
+        for (int i = 0; i < AUNR; ++i) {
+            const int d = d0 + i;
+            if (d <= dend) {  // workgroup-uniform
+                const float x = v + pbv[buf][i];
+                const float y = xc.up(v + pev[buf][i], d);
+                // a tie is the blank predecessor; u == 0 has no emission edge and t == 0 no blank one, whatever the
+                // values say
+                const bool emit = (u > 0) & ((y > x) | (d == u));
+                m[i] = __ballot(emit);
+                const bool in = ((unsigned)(d - u) < (unsigned)Tn) & live;
+                v = in ? (emit ? y : x) : NEG;
+            }
+        }
+        if ((u & 63) == 0) {
+#pragma unroll
+            for (int i = 0; i < AUNR; ++i)
+                if (d0 + i <= dend) {
+                    if (fits) bits[(d0 + i - 1) * NW + (u >> 6)] = m[i];
+                    else bp[(size_t)(d0 + i) * NW + (u >> 6)] = m[i];
+                }
+        }
+    };
+    load(0, 1);
+    for (int d0 = 1; d0 <= dend; d0 += 2 * AUNR) {
+        load(1, d0 + AUNR);
+        steps(0, d0);
+        load(0, d0 + 2 * AUNR);
+        steps(1, d0 + AUNR);
+    }
+    if (u == Un) scores[b] = v + fmaxf(lpb[(size_t)dend * Wp], NEG);
+
+    // back-trace.  The sweep already forced the two borders into the bits, so a step is
+    //   e = bit(d, cu);  fr[cu] = d - cu;  cu -= e
+    // with no branch: the last value a column c >= 1 receives is the frame at which the walk leaves it over
+    // the emission edge, which is emit_frames[c - 1]; the workgroup copies fr out at the end.
+    int cu = Un;  // thread 0: the walk's column; its cell on diagonal d is (d - cu, cu)
+    for (int dhi = dend; dhi >= 1; dhi -= ROWS) {  // workgroup-uniform
+        const int dlo = max(dhi - ROWS + 1, 1);
+        __syncthreads();  // the sweep's rows are written; the previous chunk is walked
+        if (!fits) {
+            for (int i = threadIdx.x; i < (dhi - dlo + 1) * NW; i += NW * 64) bits[i] = bp[(size_t)dlo * NW + i];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+#pragma unroll 8
+            for (int d = dhi; d >= dlo; --d) {
+                const unsigned long long w = bits[(d - dlo) * NW + (NW == 1 ? 0 : cu >> 6)];
+                fr[cu] = d - cu;
+                cu -= (int)((w >> (cu & 63)) & 1ull);
+            }
+        }
+    }
+    __syncthreads();
+    int *out = loff ? frames + loff[b] : frames + (size_t)b * (U1 - 1);
+    if (u < Un) out[u] = fr[u + 1];
+    else if (!loff && u < U1 - 1) out[u] = -1;
+}
+
+template <int NW>
+void launch_align(const Lattice &L, const int *Tn, const int *Un, const int *loff, float *scores, int *frames,
+                  void *scratch, int B, int T, int U1, hipStream_t s) {
+    hipLaunchKernelGGL((rnnt_align_kernel<NW>), dim3(B), dim3(NW * 64), 0, s, L.lpb, L.lpe, Tn, Un, loff, scores,
+                       frames, static_cast<unsigned long long *>(scratch), T, U1, L.Wp, L.D);
+}
+
 // d(logits) of log_softmax(scale * logits) under the RNN-T gradient WITHOUT reading the dense gradient:
 // row r of it has at most two non-zeros, kept in meta[r] by the backward call; with s = gb + ge
 //   out[r, v] = scale * ((v == blank) * gb + (v == ye) * ge - exp(lp[r, v]) * s)      (bf16, zero-padded)
@@ -1117,7 +1252,7 @@ __global__ __launch_bounds__(256) void rnnt_dlogits_fused_kernel(const float *__
 
 extern "C" {
 
-int pika_amd_abi_version(void) { return 23; }
+int pika_amd_abi_version(void) { return 24; }
 
 size_t pika_rnnt_workspace_bytes(int B, int T, int U1) {
     if (B <= 0 || T <= 0 || U1 <= 0 || U1 > 1024) return 0;
@@ -1522,6 +1657,37 @@ int pika_rnnt_packed_fused_backward(const float *logits, const float *lse, const
     launch_rowmeta_packed(L, labels, frames_lengths, labels_lengths, row_offsets, label_offsets, B, T_max, U1_max, N, V,
                           grad_costs, lscale, s);
     return launch_dlogits_fused(L, logits, lse, N, V, blank, grad_logits, out_dtype, ld_out, s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// forced alignment (pika_rnnt.h): Viterbi over the lpb / lpe planes any forward call left
+// ---------------------------------------------------------------------------------------------
+size_t pika_rnnt_align_scratch_bytes(int B, int T, int U1) {
+    if (B <= 0 || T <= 0 || U1 <= 0 || U1 > 1024) return 0;
+    return (size_t)B * (size_t)(T + U1 - 1) * (size_t)(lattice_width(U1) / 64) * sizeof(unsigned long long);
+}
+
+int pika_rnnt_align(const void *workspace, const int *frames_lengths, const int *labels_lengths,
+                    const int *label_offsets, int B, int T, int U1, float *scores, int *emit_frames, void *scratch,
+                    void *stream) {
+    if (B <= 0 || T <= 0 || U1 <= 0) return PIKA_EINVAL;
+    if (U1 > 1024) return PIKA_ETOOBIG;
+    if (!workspace || !frames_lengths || !labels_lengths || !scores || !scratch) return PIKA_EINVAL;
+    if (U1 > 1 && !emit_frames) return PIKA_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
+    switch (L.Wp / 64) {
+        case 1: launch_align<1>(L, frames_lengths, labels_lengths, label_offsets, scores, emit_frames, scratch, B, T, U1, s); break;
+        case 2: launch_align<2>(L, frames_lengths, labels_lengths, label_offsets, scores, emit_frames, scratch, B, T, U1, s); break;
+        case 3: launch_align<3>(L, frames_lengths, labels_lengths, label_offsets, scores, emit_frames, scratch, B, T, U1, s); break;
+        case 4: launch_align<4>(L, frames_lengths, labels_lengths, label_offsets, scores, emit_frames, scratch, B, T, U1, s); break;
+        case 6: launch_align<6>(L, frames_lengths, labels_lengths, label_offsets, scores, emit_frames, scratch, B, T, U1, s); break;
+        case 8: launch_align<8>(L, frames_lengths, labels_lengths, label_offsets, scores, emit_frames, scratch, B, T, U1, s); break;
+        case 12: launch_align<12>(L, frames_lengths, labels_lengths, label_offsets, scores, emit_frames, scratch, B, T, U1, s); break;
+        case 16: launch_align<16>(L, frames_lengths, labels_lengths, label_offsets, scores, emit_frames, scratch, B, T, U1, s); break;
+        default: return PIKA_ETOOBIG;
+    }
+    return (int)hipGetLastError();
 }
 
 }  // extern "C"

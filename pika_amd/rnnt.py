@@ -559,6 +559,128 @@ def rnnt_loss(log_probs, labels, frames_lengths, labels_lengths, average_frames=
     raise ValueError("Unknown reduction: %r" % (reduction,))
 
 
+def _align_call(lib, ws, frames_lengths, labels_lengths, loff, B, T, U1, n_frames, device):
+    """pika_rnnt_align on a workspace a forward call has just filled: (scores (B,), emit_frames)."""
+    scores = torch.empty(B, dtype=torch.float32, device=device)
+    frames = torch.empty(n_frames, dtype=torch.int32, device=device)
+    scratch = torch.empty(lib.pika_rnnt_align_scratch_bytes(B, T, U1), dtype=torch.uint8, device=device)
+    _lib.check(lib.pika_rnnt_align(_ptr(ws), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(loff), B, T, U1,
+                                   _ptr(scores), _ptr(frames) if n_frames else None, _ptr(scratch), _stream()),
+               "pika_rnnt_align")
+    return scores, frames
+
+
+def _align_packed(x, labels, frames_lengths, labels_lengths, blank, fused):
+    p = _check_packed(x, labels, frames_lengths, labels_lengths, blank, "logits" if fused else "log_probs")
+    lib = _lib.lib()
+    x = x.detach().contiguous()
+    labels, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, frames_lengths, labels_lengths))
+    V = x.shape[1]
+    if fused and (V % 4 or V > MAX_FUSED_V):
+        raise ValueError("rnnt_align_from_logits: V = %d must be a multiple of 4 and <= %d" % (V, MAX_FUSED_V))
+    with torch.cuda.device(x.device):
+        costs = torch.empty(p.B, dtype=torch.float32, device=x.device)
+        ws = torch.empty(lib.pika_rnnt_workspace_bytes(p.B, p.T, p.U1), dtype=torch.uint8, device=x.device)
+        if fused:
+            lse = torch.empty(p.N, dtype=torch.float32, device=x.device)
+            _lib.check(lib.pika_rnnt_packed_fused_forward(
+                _ptr(x), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(p.roff), _ptr(p.loff),
+                p.B, p.T, p.U1, p.N, V, blank, _ptr(costs), _ptr(lse), _ptr(ws), _stream()),
+                "pika_rnnt_packed_fused_forward")
+        else:
+            _lib.check(lib.pika_rnnt_packed_forward(
+                _ptr(x), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(p.roff), _ptr(p.loff),
+                p.B, p.T, p.U1, p.N, V, blank, _ptr(costs), _ptr(ws), _stream()), "pika_rnnt_packed_forward")
+        return _align_call(lib, ws, frames_lengths, labels_lengths, p.loff, p.B, p.T, p.U1, labels.numel(), x.device)
+
+
+def _fused_v_ok(V):
+    return V % 4 == 0 and V <= MAX_FUSED_V
+
+
+def rnnt_align(log_probs, labels, frames_lengths, labels_lengths, blank=0, compact=False):
+    """Forced alignment of every transcript against its lattice: the single best (Viterbi) path.
+
+    Returns (scores, emit_frames), both detached: scores (B,) f32, the log-probability of the best alignment
+    (scores[n] <= -cost_n); emit_frames i32 (B, U) -- entry [n][u], u < U_n, is the encoder frame at which that path
+    emits label u (non-decreasing in u, in [0, T_n - 1]), entries u >= U_n are -1 -- or, compact=True, (sum U_n,) in
+    the order of the packed labels.  Ties go to the earliest emission.  Inputs, checks and length clamping are those
+    of `rnnt_loss` (a LazyLogProbs of this package's joint is read the way the loss reads it); no autograd.  The
+    padded form never synchronises the host and can be captured in a graph; compact=True pays the packed layout's
+    one length copy and raises under stream capture."""
+    if compact:
+        return _align_packed(log_probs, labels, frames_lengths, labels_lengths, blank, False)
+    _check_inputs(log_probs, labels, frames_lengths, labels_lengths, blank)
+    lib = _lib.lib()
+    labels, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, frames_lengths, labels_lengths))
+    B, T, U1, V = log_probs.shape
+    state = log_probs.state if isinstance(log_probs, LazyLogProbs) else None
+    if state is not None:
+        V = log_probs.buf.shape[-1]
+        if not (state.raw and state.scale == 1.0 and _fused_v_ok(V)
+                and (state.gathered is None or state.partials is not None)):
+            state = None
+    if state is not None:
+        # raw logits of this package's joint: the planes come from the buffer as it is (the partial statistics, which
+        # the loss uses once, stay for it)
+        x, part = log_probs.buf, state.partials
+        with torch.cuda.device(x.device):
+            costs = torch.empty(B, dtype=torch.float32, device=x.device)
+            lse = torch.empty(B * T * U1, dtype=torch.float32, device=x.device)
+            ws = torch.empty(lib.pika_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8, device=x.device)
+            if state.gathered is not None:
+                gath, g_labels, g_blank = state.gathered
+                _lib.check(lib.pika_rnnt_fused_forward_gathered(
+                    _ptr(x), x.stride(-2), _ptr(gath), _ptr(g_labels), int(g_blank), part[0].data_ptr(),
+                    part[1].data_ptr(), part.shape[2], _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths),
+                    B, T, U1, V, blank, _ptr(costs), _ptr(lse), _ptr(ws), _stream()),
+                    "pika_rnnt_fused_forward_gathered")
+            elif part is not None:
+                _lib.check(lib.pika_rnnt_fused_forward_partials(
+                    _ptr(x), part[0].data_ptr(), part[1].data_ptr(), part.shape[2], _ptr(labels),
+                    _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank, _ptr(costs), _ptr(lse),
+                    _ptr(ws), _stream()), "pika_rnnt_fused_forward_partials")
+            else:
+                _lib.check(lib.pika_rnnt_fused_forward(
+                    _ptr(x), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank,
+                    _ptr(costs), _ptr(lse), _ptr(ws), _stream()), "pika_rnnt_fused_forward")
+            scores, frames = _align_call(lib, ws, frames_lengths, labels_lengths, None, B, T, U1, B * (U1 - 1), x.device)
+    else:
+        lp = log_probs.dense() if isinstance(log_probs, LazyLogProbs) else log_probs
+        lp = lp.detach().contiguous()
+        with torch.cuda.device(lp.device):
+            costs = torch.empty(B, dtype=torch.float32, device=lp.device)
+            ws = torch.empty(lib.pika_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8, device=lp.device)
+            _lib.check(lib.pika_rnnt_loss_forward(
+                _ptr(lp), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, lp.shape[-1], blank,
+                _ptr(costs), _ptr(ws), _stream()), "pika_rnnt_loss_forward")
+            scores, frames = _align_call(lib, ws, frames_lengths, labels_lengths, None, B, T, U1, B * (U1 - 1), lp.device)
+    return scores, frames.view(B, U1 - 1)
+
+
+def rnnt_align_from_logits(logits, labels, frames_lengths, labels_lengths, blank=0, compact=False):
+    """`rnnt_align` of log_softmax(logits) without materialising the log-probabilities (V % 4 == 0, V <= 8192):
+    the planes come from the one read of the raw logits `rnnt_loss_from_logits` makes."""
+    if compact:
+        return _align_packed(logits, labels, frames_lengths, labels_lengths, blank, True)
+    _check_inputs(logits, labels, frames_lengths, labels_lengths, blank)
+    lib = _lib.lib()
+    x = logits.detach().contiguous()
+    labels, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, frames_lengths, labels_lengths))
+    B, T, U1, V = x.shape
+    if not _fused_v_ok(V):
+        raise ValueError("rnnt_align_from_logits: V = %d must be a multiple of 4 and <= %d" % (V, MAX_FUSED_V))
+    with torch.cuda.device(x.device):
+        costs = torch.empty(B, dtype=torch.float32, device=x.device)
+        lse = torch.empty(B * T * U1, dtype=torch.float32, device=x.device)
+        ws = torch.empty(lib.pika_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8, device=x.device)
+        _lib.check(lib.pika_rnnt_fused_forward(
+            _ptr(x), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank,
+            _ptr(costs), _ptr(lse), _ptr(ws), _stream()), "pika_rnnt_fused_forward")
+        scores, frames = _align_call(lib, ws, frames_lengths, labels_lengths, None, B, T, U1, B * (U1 - 1), x.device)
+    return scores, frames.view(B, U1 - 1)
+
+
 class RNNTLoss(object):
     """`RNNTLoss(blank=0, reduction='sum').apply(...)` exactly as the reference scripts use it.
 
