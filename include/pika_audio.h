@@ -17,13 +17,14 @@ extern "C" {
 
 /* Speed + volume perturbation.  pcm int16 [in_off[B]] -> out f32 [out_off[B]] holding
  * int16-valued samples (what Kaldi receives).  Utterance b: m = out_off[b+1]-out_off[b] output
- * samples; if m != n: linear interpolation at x_i = i*n/(m-1) (np.interp on linspace(0,n,m),
- * clamped to the last sample) in fp64; gain = 10^(min(300, target_db[b] - rms_db)/20) with
+ * samples; if resample[b] != 0 (the host's "rate != 1"; int32, device) or m != n: linear interpolation at
+ * x_i = i*n/(m-1) (np.interp on linspace(0,n,m), clamped to the last sample) in fp64, else the samples as they
+ * are.  A rate close to 1 can give m == n and still resamples in the reference, hence the flag.  gain = 10^(min(300, target_db[b] - rms_db)/20) with
  * rms_db = 10 log10(max(1e-20, mean(x^2))); result trunc(clip(x*gain*32768, -32768, 32767)).
  * sumsq: B doubles of scratch (zeroed by the call). */
 int pika_audio_perturb(const short *pcm, const long long *in_off, const long long *out_off,
-                       const double *target_db, int B, long long max_out, float *out,
-                       double *sumsq, void *stream);
+                       const double *target_db, const int *resample, int B, long long max_out,
+                       float *out, double *sumsq, void *stream);
 
 /* Kaldi-compatible log-mel filterbank.  wave f32 [wave_off[B]] -> feats f32 [frame_off[B]][num_bins],
  * frames per utterance = 1 + (n - frame_len)/frame_shift (snip-edges; frame_off from the host).

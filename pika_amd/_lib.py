@@ -7,7 +7,7 @@ import os
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libpika_amd.so")
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 _vp, _i, _sz, _ll, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_float
 
@@ -147,7 +147,7 @@ SIGNATURES = {
     "pika_audio_sumsq": (_i, [_vp, _ll, _vp, _vp]),
     "pika_audio_axpby": (_i, [_vp, _vp, _ll, ctypes.c_float, ctypes.c_float, _vp]),
     "pika_audio_convolve_same": (_i, [_vp, _ll, _vp, _i, _vp, _vp]),
-    "pika_audio_perturb": (_i, [_vp, _vp, _vp, _vp, _i, _ll, _vp, _vp, _vp]),
+    "pika_audio_perturb": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _ll, _vp, _vp, _vp]),
     "pika_fbank": (_i, [_vp, _vp, _vp, _i, _ll, _i, _i, _i, ctypes.c_float, ctypes.c_float,
                         ctypes.c_ulonglong, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pika_splice_pad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),

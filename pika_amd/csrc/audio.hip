@@ -9,8 +9,10 @@
 namespace {
 
 // ---------------- speed / volume perturbation ----------------------------------------------
-__device__ inline double resampled(const short *__restrict__ p, long long n, long long m, long long i) {
-    if (m == n) return (double)((float)p[i] * (1.0f / 32768.0f));
+// `copy`: the utterance keeps its speed (rate == 1, decided by the host: the kernel cannot tell a rate close to 1,
+// where int(n / rate) == n and the reference still interpolates on linspace(0, n, n), from an unchanged one)
+__device__ inline double resampled(const short *__restrict__ p, long long n, long long m, long long i, bool copy) {
+    if (copy) return (double)((float)p[i] * (1.0f / 32768.0f));
     // np.linspace(0, n, m)[i] = i * (n / (m-1)); np.interp clamps beyond the last sample
     const double step = m > 1 ? (double)n / (double)(m - 1) : 0.0;
     const double x = (i == m - 1 && m > 1) ? (double)n : (double)i * step;
@@ -24,14 +26,16 @@ __device__ inline double resampled(const short *__restrict__ p, long long n, lon
 __global__ __launch_bounds__(256) void perturb_sumsq_kernel(const short *__restrict__ pcm,
                                                             const long long *__restrict__ in_off,
                                                             const long long *__restrict__ out_off,
+                                                            const int *__restrict__ resample,
                                                             double *__restrict__ sumsq) {
     __shared__ double part[4];
     const int b = blockIdx.y;
     const long long n = in_off[b + 1] - in_off[b], m = out_off[b + 1] - out_off[b];
     const short *p = pcm + in_off[b];
+    const bool copy = !resample[b] && m == n;   // a cleared flag on m != n still interpolates: p[i] stays in bounds
     double s = 0.0;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < m; i += (long long)gridDim.x * 256) {
-        const double v = resampled(p, n, m, i);
+        const double v = resampled(p, n, m, i, copy);
         s += v * v;
     }
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
@@ -44,22 +48,24 @@ __global__ __launch_bounds__(256) void perturb_apply_kernel(const short *__restr
                                                             const long long *__restrict__ in_off,
                                                             const long long *__restrict__ out_off,
                                                             const double *__restrict__ target_db,
+                                                            const int *__restrict__ resample,
                                                             const double *__restrict__ sumsq,
                                                             float *__restrict__ out) {
     const int b = blockIdx.y;
     const long long n = in_off[b + 1] - in_off[b], m = out_off[b + 1] - out_off[b];
     if (m <= 0) return;
     const short *p = pcm + in_off[b];
+    const bool copy = !resample[b] && m == n;
     const double ms = fmax(1e-20, sumsq[b] / (double)m);
     const double rms_db = 10.0 * log10(ms);
     const double gain = pow(10.0, fmin(300.0, target_db[b] - rms_db) / 20.0);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < m; i += (long long)gridDim.x * 256) {
         double v;
-        if (m == n) {  // unchanged speed: the reference stays in float32 (in-place *= on f32)
+        if (copy) {  // unchanged speed: the reference stays in float32 (in-place *= on f32)
             const float f = (float)p[i] * (1.0f / 32768.0f);
             v = (double)((f * (float)gain) * 32768.0f);
         } else {
-            v = resampled(p, n, m, i) * gain * 32768.0;
+            v = resampled(p, n, m, i, false) * gain * 32768.0;
         }
         v = fmin(fmax(v, -32768.0), 32767.0);
         out[out_off[b] + i] = (float)trunc(v);  // astype(int16) truncates toward zero
@@ -234,17 +240,18 @@ __global__ __launch_bounds__(256) void aug_convolve_same_kernel(const float *__r
 extern "C" {
 
 int pika_audio_perturb(const short *pcm, const long long *in_off, const long long *out_off,
-                       const double *target_db, int B, long long max_out, float *out, double *sumsq,
-                       void *stream) {
-    if (!pcm || !in_off || !out_off || !target_db || !out || !sumsq || B <= 0 || max_out <= 0)
+                       const double *target_db, const int *resample, int B, long long max_out, float *out,
+                       double *sumsq, void *stream) {
+    if (!pcm || !in_off || !out_off || !target_db || !resample || !out || !sumsq || B <= 0 || max_out <= 0)
         return PIKA_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipError_t e = hipMemsetAsync(sumsq, 0, sizeof(double) * B, s);
     if (e != hipSuccess) return (int)e;
     const int gx = (int)((max_out + 256 * 8 - 1) / (256 * 8));
-    hipLaunchKernelGGL(perturb_sumsq_kernel, dim3(gx, B), dim3(256), 0, s, pcm, in_off, out_off, sumsq);
+    hipLaunchKernelGGL(perturb_sumsq_kernel, dim3(gx, B), dim3(256), 0, s, pcm, in_off, out_off, resample,
+                       sumsq);
     hipLaunchKernelGGL(perturb_apply_kernel, dim3(gx, B), dim3(256), 0, s, pcm, in_off, out_off,
-                       target_db, sumsq, out);
+                       target_db, resample, sumsq, out);
     return (int)hipGetLastError();
 }
 

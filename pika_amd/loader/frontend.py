@@ -193,15 +193,18 @@ class GpuFrontEnd(object):
         out_off = np.concatenate(([0], np.cumsum(n_out))).astype(np.int64)
         frames = [cfg.num_frames(n) for n in n_out]
         fr_off = np.concatenate(([0], np.cumsum(frames))).astype(np.int64)
-        # staging layout (bytes): [3 x (B+1) i64 offsets][B f64 target dB][int16 samples]
+        # staging layout (bytes): [3 x (B+1) i64 offsets][B f64 target dB][B i32 "rate != 1"][int16 samples]
         n_samp = int(in_off[-1])
         o_db = 3 * (B + 1) * 8
-        o_pcm = o_db + B * 8
+        o_rs = o_db + B * 8
+        o_pcm = o_rs + B * 4
         nbytes = o_pcm + 2 * n_samp
         host, up_ev = self._stage(nbytes)
         hv = host.numpy()
         hv[:o_db].view(np.int64).reshape(3, B + 1)[:] = (in_off, out_off, fr_off)
-        hv[o_db:o_pcm].view(np.float64)[:] = np.asarray(list(target_dbs), np.float64)[:B] if B else 0.0
+        hv[o_db:o_rs].view(np.float64)[:] = np.asarray(list(target_dbs), np.float64)[:B] if B else 0.0
+        # the reference resamples whenever rate != 1.0, also where int(n / rate) == n: the kernel cannot tell from the lengths
+        hv[o_rs:o_pcm].view(np.int32)[:] = [int(perturb and r != 1.0) for r in rates][:B] if B else 0
         if B:
             np.concatenate(pcms, out=hv[o_pcm:nbytes].view(np.int16))
         cur = torch.cuda.current_stream(dev)
@@ -216,8 +219,8 @@ class GpuFrontEnd(object):
             wave = torch.empty(max(int(out_off[-1]), 1), dtype=torch.float32, device=dev)
             if perturb:
                 sumsq = torch.empty(B, dtype=torch.float64, device=dev)
-                _lib.check(lib.pika_audio_perturb(base + o_pcm, p_in, p_out, base + o_db, B, max(n_out), wave.data_ptr(),
-                                                  sumsq.data_ptr(), st), "pika_audio_perturb")
+                _lib.check(lib.pika_audio_perturb(base + o_pcm, p_in, p_out, base + o_db, base + o_rs, B, max(n_out),
+                                                  wave.data_ptr(), sumsq.data_ptr(), st), "pika_audio_perturb")
             else:
                 wave[:int(out_off[-1])] = stage_d[o_pcm:nbytes].view(torch.int16).float()
             total = int(fr_off[-1])

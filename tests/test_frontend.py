@@ -52,6 +52,29 @@ def test_fbank_conf_parser(tmp_path):
     assert (cfg.num_mel_bins, cfg.low_freq, cfg.high_freq, cfg.dither) == (80, 40.0, -200.0, 1.0)
 
 
+def test_fbank_conf_refuses_other_windows(tmp_path):
+    from pika_amd.loader.frontend import FbankConfig
+    for text in ("--window-type=povey\n--num-mel-bins=80\n", "--num-mel-bins=80\n"):     # Kaldi's default is povey
+        p = tmp_path / "fbank.conf"
+        p.write_text(text)
+        with pytest.raises(NotImplementedError):
+            FbankConfig.from_file(str(p))
+
+
+def test_parity_inputs_meet_their_conditions():
+    """The CPU-side conditions tests/test_frontend_parity_gpu.py checks before it compares anything, without a GPU."""
+    sys.path.insert(0, HERE)
+    import frontend_common as C
+    wide = C.check_restatement_condition()
+    assert [w[:2] for w in wide] == [("short_window", "square"), ("short_window", "chirp")]
+    for name in C.CONFIGS:
+        cfg = C.fbank_config(name)
+        assert (cfg.frame_len, cfg.shift, cfg.nfft) == C.GEOMETRY[name]
+    rng = np.random.default_rng(9000)
+    pcm = C._i16(rng.standard_normal(48000) * 9000)
+    assert 0.1 < C.assert_clipping_case_is_not_vacuous(*C.perturb_expected(pcm, 1.1, -3.0)) < 0.2
+
+
 @pytest.mark.gpu
 def test_gpu_perturb_matches_reference_golden(hip_device):
     from pika_amd.loader.frontend import FbankConfig, GpuFrontEnd

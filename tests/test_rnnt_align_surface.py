@@ -85,9 +85,9 @@ def test_dropin_has_no_align():
         sys.path.pop(0)
 
 
-def test_abi_version_is_24():
+def test_abi_version_is_25():
     from pika_amd import _lib
-    assert _lib.ABI_VERSION == 24 and _lib.lib().pika_amd_abi_version() == 24
+    assert _lib.ABI_VERSION == 25 and _lib.lib().pika_amd_abi_version() == 25
 
 
 def test_align_scratch_bytes():
