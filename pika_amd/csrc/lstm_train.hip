@@ -461,7 +461,8 @@ static int run(bool bwd, const float *in, const void *packed, float *out, float 
     p.xbuf = reinterpret_cast<unsigned *>(static_cast<char *>(work) + 256);
     p.S = S; p.B = B; p.H = H; p.nq = nq; p.ng = ng;
     hipError_t e = hipMemsetAsync(work, 0, 256, st);
-    if (e == hipSuccess && S > 1 && !armed)
+    // (a single step exchanges nothing: the forward leaves its scratch alone, the backward still owes an armed one)
+    if (e == hipSuccess && !armed && (bwd || S > 1))
         e = hipMemsetAsync(p.xbuf, 0xff, (size_t)(bwd ? bwd_words(S, nq, ng) : fwd_words(S, nq, H)) * 4, st);
     if (e != hipSuccess) return (int)e;
 #define PIKA_LSTM_LAUNCH(K)                                                                          \
