@@ -35,7 +35,9 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <initializer_list>
 #include <type_traits>
+#include <utility>
 
 #include "pika_rnnt.h"
 #include "pika_internal.h"
@@ -51,14 +53,27 @@ constexpr int RENORM = 16; // diagonals between renormalisations (multiple of UN
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
+// The wave counts the per-utterance kernels (alpha/beta, alignment) are instantiated for: THE list -- lattice_width
+// searches it, dispatch_nw turns a run-time count into the compile-time one.
+using Waves = std::integer_sequence<int, 1, 2, 3, 4, 6, 8, 12, 16>;
+
 // Width (in lanes) of one skewed lattice row = threads of the alpha/beta workgroup: the
 // smallest instantiated wave count that covers U1 label columns.
-inline int lattice_width(int U1) {
-    static const int kWaves[] = {1, 2, 3, 4, 6, 8, 12, 16};
-    for (int nw : kWaves)
+template <int... NW>
+inline int lattice_width(int U1, std::integer_sequence<int, NW...>) {
+    for (int nw : {NW...})
         if (nw * 64 >= U1) return nw * 64;
     return 0;
 }
+inline int lattice_width(int U1) { return lattice_width(U1, Waves{}); }
+
+// f(std::integral_constant<int, NW>{}) for the instantiated NW == nw; false when there is none
+template <class F, int... NW>
+inline bool dispatch_nw(int nw, F f, std::integer_sequence<int, NW...>) {
+    return ((nw == NW && (f(std::integral_constant<int, NW>{}), true)) || ...);
+}
+template <class F>
+inline bool dispatch_nw(int nw, F f) { return dispatch_nw(nw, f, Waves{}); }
 
 struct RowMeta {  // 16 bytes per lattice cell
     float gb;     // gradient at [.., blank]
@@ -657,19 +672,21 @@ __global__ __launch_bounds__(256) void rnnt_export_kernel(
     if (out_b) out_b[idx] = ok ? (float)((double)beta[o] + off_b[(size_t)b * D + t + u]) : NEG;
 }
 
-int check_dims(int B, int T, int U1, int V, int blank) {
-    if (B <= 0 || T <= 0 || U1 <= 0 || V <= 0 || blank < 0 || blank >= V) return PIKA_EINVAL;
+// the lattice alone (the calls that take no vocabulary) ...
+int check_lattice_dims(int B, int T, int U1) {
+    if (B <= 0 || T <= 0 || U1 <= 0) return PIKA_EINVAL;
     if (U1 > 1024) return PIKA_ETOOBIG;
     return PIKA_OK;
 }
 
-template <int NW>
-void launch_ab(const Lattice &L, const int *Tn, const int *Un, float *costs, int B, int T, int U1,
-               hipStream_t s) {
-    hipLaunchKernelGGL((rnnt_alpha_beta_kernel<NW>), dim3(2, B), dim3(NW * 64), 0, s, L.lpb, L.lpe,
-                       L.alpha, L.beta, L.off_a, L.off_b, Tn, Un, L.ll, L.ll_a, costs, T, U1, L.Wp,
-                       L.D);
+// ... and with V and blank: a bad V or blank is PIKA_EINVAL even where U1 > 1024 would be PIKA_ETOOBIG
+int check_dims(int B, int T, int U1, int V, int blank) {
+    if (V <= 0 || blank < 0 || blank >= V) return PIKA_EINVAL;
+    return check_lattice_dims(B, T, U1);
 }
+
+// B*T*U1 rows (N packed) index the row kernels as an int
+constexpr long long ROWS_MAX = 0x7fffffffLL;
 
 // ---------------------------------------------------------------------------------------------
 // forced alignment: the max-plus (Viterbi) recurrence over the same skewed planes,
@@ -799,13 +816,6 @@ __global__ __launch_bounds__(NW * 64) void rnnt_align_kernel(
     else if (!loff && u < U1 - 1) out[u] = -1;
 }
 
-template <int NW>
-void launch_align(const Lattice &L, const int *Tn, const int *Un, const int *loff, float *scores, int *frames,
-                  void *scratch, int B, int T, int U1, hipStream_t s) {
-    hipLaunchKernelGGL((rnnt_align_kernel<NW>), dim3(B), dim3(NW * 64), 0, s, L.lpb, L.lpe, Tn, Un, loff, scores,
-                       frames, static_cast<unsigned long long *>(scratch), T, U1, L.Wp, L.D);
-}
-
 // d(logits) of log_softmax(scale * logits) under the RNN-T gradient WITHOUT reading the dense gradient:
 // row r of it has at most two non-zeros, kept in meta[r] by the backward call; with s = gb + ge
 //   out[r, v] = scale * ((v == blank) * gb + (v == ye) * ge - exp(lp[r, v]) * s)      (bf16, zero-padded)
@@ -842,10 +852,10 @@ __global__ __launch_bounds__(256) void rnnt_dlogits_compact_kernel(const TI *__r
                                                                    float scale, int rpw,
                                                                    float *__restrict__ colsum,
                                                                    const float *__restrict__ lse,
-                                                                   long long ld_in = 0,
-                                                                   const float *__restrict__ gathered = nullptr,
-                                                                   const int *__restrict__ g_labels = nullptr,
-                                                                   int g_blank = 0, int T = 1, int U1 = 1) {
+                                                                   long long ld_in,
+                                                                   const float *__restrict__ gathered,
+                                                                   const int *__restrict__ g_labels,
+                                                                   int g_blank, int T, int U1) {
     if (ld_in == 0) ld_in = V;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c4 = V >> 2, o4 = (int)(ld_out >> 2);
     const long long r0 = ((long long)blockIdx.x * 4 + wave) * rpw;
@@ -936,10 +946,10 @@ __global__ __launch_bounds__(256) void rnnt_dlogits_compact8_kernel(const TI *__
                                                                     float scale, int rpw,
                                                                     float *__restrict__ colsum,
                                                                     const float *__restrict__ lse,
-                                                                    long long ld_in = 0,
-                                                                    const float *__restrict__ gathered = nullptr,
-                                                                    const int *__restrict__ g_labels = nullptr,
-                                                                    int g_blank = 0, int T = 1, int U1 = 1) {
+                                                                    long long ld_in,
+                                                                    const float *__restrict__ gathered,
+                                                                    const int *__restrict__ g_labels,
+                                                                    int g_blank, int T, int U1) {
     if (ld_in == 0) ld_in = V;
     constexpr float LOG2E = 1.4426950408889634f;
     const int lane = threadIdx.x & 63;
@@ -1049,19 +1059,77 @@ __global__ __launch_bounds__(256) void rnnt_dlogits_compact8_kernel(const TI *__
     if (cs_blank != 0.f) atomicAdd(colsum + blank, cs_blank);
 }
 
-int run_alpha_beta(const Lattice &L, const int *frames_lengths, const int *labels_lengths, float *costs, int B,
+// What every forward does once its one launch has filled the lpb / lpe planes: alpha, beta and the costs.
+int finish_forward(const Lattice &L, const int *frames_lengths, const int *labels_lengths, float *costs, int B,
                    int T, int U1, hipStream_t s) {
-    switch (L.Wp / 64) {
-        case 1: launch_ab<1>(L, frames_lengths, labels_lengths, costs, B, T, U1, s); break;
-        case 2: launch_ab<2>(L, frames_lengths, labels_lengths, costs, B, T, U1, s); break;
-        case 3: launch_ab<3>(L, frames_lengths, labels_lengths, costs, B, T, U1, s); break;
-        case 4: launch_ab<4>(L, frames_lengths, labels_lengths, costs, B, T, U1, s); break;
-        case 6: launch_ab<6>(L, frames_lengths, labels_lengths, costs, B, T, U1, s); break;
-        case 8: launch_ab<8>(L, frames_lengths, labels_lengths, costs, B, T, U1, s); break;
-        case 12: launch_ab<12>(L, frames_lengths, labels_lengths, costs, B, T, U1, s); break;
-        case 16: launch_ab<16>(L, frames_lengths, labels_lengths, costs, B, T, U1, s); break;
-        default: return PIKA_ETOOBIG;
+    const bool ok = dispatch_nw(L.Wp / 64, [&](auto nw) {
+        constexpr int NW = decltype(nw)::value;
+        hipLaunchKernelGGL((rnnt_alpha_beta_kernel<NW>), dim3(2, B), dim3(NW * 64), 0, s, L.lpb, L.lpe, L.alpha, L.beta,
+                           L.off_a, L.off_b, frames_lengths, labels_lengths, L.ll, L.ll_a, costs, T, U1, L.Wp, L.D);
+    });
+    return ok ? (int)hipGetLastError() : PIKA_ETOOBIG;
+}
+
+// The arguments of a padded forward: the dimensions; then own_ok -- the entry point's own tests of its pointers, V and
+// pitches -- and the labels when some utterance can have one (PIKA_EINVAL); then, for the calls whose kernels index the
+// B*T*U1 rows as an int (`rows` given), the row count (PIKA_ETOOBIG).
+int forward_args_ok(int B, int T, int U1, int V, int blank, bool own_ok, const int *labels, long long *rows = nullptr) {
+    if (int rc = check_dims(B, T, U1, V, blank)) return rc;
+    if (!own_ok || (U1 > 1 && !labels)) return PIKA_EINVAL;
+    if (rows && (*rows = (long long)B * T * U1) > ROWS_MAX) return PIKA_ETOOBIG;
+    return PIKA_OK;
+}
+
+// fp32 logits as the one-wave-per-row kernels read them: 16-byte groups, the row in registers
+bool logits_ok(const float *logits, int V) {
+    return !(V & 3) && V <= V_MAX && !(reinterpret_cast<uintptr_t>(logits) & 15);
+}
+
+// The 8-column d(logits) kernel takes fp32 input in whole 8-column granules ...
+bool compact8_ok_f32(int V, long long ld_out, const void *out) {
+    return !(V & 7) && !(ld_out & 7) && V > 512 * 9 && !(reinterpret_cast<uintptr_t>(out) & 15);
+}
+
+// ... and fp16 input on a pitch of whole granules (V % 8 == 4 -- the shipped recipes' 6268 -- rides on it: the last
+// granule is masked)
+bool compact8_ok_f16(int V, long long ld_out, long long ld_in, const void *out, const void *logits16) {
+    return !(ld_out & 7) && !(ld_in & 7) && ld_in >= ((V + 7) & ~7) && V > 512 * 9 &&
+           !(reinterpret_cast<uintptr_t>(out) & 15) && !(reinterpret_cast<uintptr_t>(logits16) & 15);
+}
+
+// The compact d(logits) pass of both input types, after the entry point's own checks.  ld_in 0: the rows of `x` are V
+// apart; wide: the 8-column kernel may take the column-summing form (compact8_ok_*).
+template <typename TI>
+int launch_dlogits_compact(const TI *x, long long ld_in, bool wide, const float *lse, const void *workspace, int B, int T,
+                           int U1, int V, int blank, void *out, long long ld_out, float scale, float *colsum,
+                           const float *gathered, const int *g_labels, int g_blank, void *stream) {
+    const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
+    const long long rows = (long long)B * T * U1;
+    if (rows > ROWS_MAX) return PIKA_ETOOBIG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    __bf16 *o = static_cast<__bf16 *>(out);
+    if (!colsum) {
+        PIKA_CQ(ld_out, hipLaunchKernelGGL((rnnt_dlogits_compact_kernel<false, TI, CQ>), dim3((unsigned)((rows + 3) / 4)),
+                                           dim3(256), 0, s, x, L.meta, o, rows, V, ld_out, blank, scale, 1, colsum, lse, ld_in,
+                                           gathered, g_labels, g_blank, T, U1));
+        return (int)hipGetLastError();
     }
+    hipError_t e = hipMemsetAsync(colsum, 0, (size_t)V * sizeof(float), s);
+    if (e != hipSuccess) return (int)e;
+    static const int rpw_env = [] { const char *e = pika_knob("PIKA_DLOGITS_RPW"); return e ? atoi(e) : 0; }();   // A/B
+    // tools/dlogits_bench.py at the config-2 lattice: 16 rows per wave 2.43 ms, 32: 2.35, 64: 2.31, 128: 2.31, 256: 2.57;
+    // the 4- and 8-column kernels tie (2.35 ms): the pass is the mixed read / write HBM stream at 5.0-5.1 TB/s
+    const int rpw = rpw_env > 0 ? rpw_env : rows_per_wave(rows);
+    const dim3 grid((unsigned)((rows + 4LL * rpw - 1) / (4LL * rpw)));
+    static const bool wide_off = pika_knob("PIKA_DLOGITS_NARROW") != nullptr;     // A/B: the 4-column kernel
+    if (wide && !wide_off) {
+#define PIKA_C8(NIT) hipLaunchKernelGGL((rnnt_dlogits_compact8_kernel<NIT, TI>), grid, dim3(256), 0, s, x, L.meta, o, rows, V, \
+                                        ld_out, blank, scale, rpw, colsum, lse, ld_in, gathered, g_labels, g_blank, T, U1)
+        if (ld_out <= 512 * 10) PIKA_C8(10); else if (ld_out <= 512 * 13) PIKA_C8(13); else PIKA_C8(16);
+#undef PIKA_C8
+    } else
+        PIKA_CQ(ld_out, hipLaunchKernelGGL((rnnt_dlogits_compact_kernel<true, TI, CQ>), grid, dim3(256), 0, s, x, L.meta, o, rows,
+                                           V, ld_out, blank, scale, rpw, colsum, lse, ld_in, gathered, g_labels, g_blank, T, U1));
     return (int)hipGetLastError();
 }
 
@@ -1255,16 +1323,15 @@ extern "C" {
 int pika_amd_abi_version(void) { return 25; }
 
 size_t pika_rnnt_workspace_bytes(int B, int T, int U1) {
-    if (B <= 0 || T <= 0 || U1 <= 0 || U1 > 1024) return 0;
+    if (check_lattice_dims(B, T, U1)) return 0;
     return workspace_bytes(B, T, U1);
 }
 
 int pika_rnnt_loss_forward(const float *log_probs, const int *labels, const int *frames_lengths,
                            const int *labels_lengths, int B, int T, int U1, int V, int blank,
                            float *costs, void *workspace, void *stream) {
-    if (int rc = check_dims(B, T, U1, V, blank)) return rc;
-    if (!log_probs || !frames_lengths || !labels_lengths || !costs || !workspace) return PIKA_EINVAL;
-    if (U1 > 1 && !labels) return PIKA_EINVAL;
+    if (int rc = forward_args_ok(B, T, U1, V, blank, log_probs && frames_lengths && labels_lengths && costs && workspace, labels))
+        return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Lattice L = carve(workspace, B, T, U1);
     const dim3 grid((unsigned)((L.D + 4 * GATHER_ROWS - 1) / (4 * GATHER_ROWS)), (unsigned)(L.Wp / 64),
@@ -1272,7 +1339,7 @@ int pika_rnnt_loss_forward(const float *log_probs, const int *labels, const int 
     hipLaunchKernelGGL(rnnt_gather_kernel<false>, grid, dim3(256), 0, s,
                        log_probs, labels, frames_lengths, labels_lengths, B, T, U1, V, blank, L.lpb,
                        L.lpe, L.Wp, L.D);
-    return run_alpha_beta(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
+    return finish_forward(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
 }
 
 namespace {
@@ -1335,7 +1402,7 @@ int check_packed(int B, int T, int U1, long long N, int V, int blank, const int 
     if (int rc = check_dims(B, T, U1, V, blank)) return rc;
     if (!frames_lengths || !labels_lengths || !roff || N <= 0) return PIKA_EINVAL;
     if (U1 > 1 && (!labels || !loff)) return PIKA_EINVAL;
-    if (N > 0x7fffffffLL) return PIKA_ETOOBIG;
+    if (N > ROWS_MAX) return PIKA_ETOOBIG;
     if (N > (long long)B * T * U1) return PIKA_EINVAL;
     return PIKA_OK;
 }
@@ -1384,8 +1451,8 @@ int pika_rnnt_loss_fwd_bwd(const float *log_probs, const int *labels, const int 
 int pika_rnnt_export_lattice(const void *workspace, const int *frames_lengths,
                              const int *labels_lengths, int B, int T, int U1, float *alphas,
                              float *betas, void *stream) {
-    if (B <= 0 || T <= 0 || U1 <= 0 || U1 > 1024 || !workspace || !frames_lengths || !labels_lengths)
-        return PIKA_EINVAL;
+    // (U1 > 1024 is PIKA_EINVAL here, PIKA_ETOOBIG in the calls that fill the workspace: kept)
+    if (check_lattice_dims(B, T, U1) || !workspace || !frames_lengths || !labels_lengths) return PIKA_EINVAL;
     const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
     const size_t cells = (size_t)B * T * U1;
     hipLaunchKernelGGL(rnnt_export_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0,
@@ -1397,97 +1464,61 @@ int pika_rnnt_export_lattice(const void *workspace, const int *frames_lengths,
 int pika_rnnt_dlogits_compact_bf16(const float *log_probs, const float *lse, const void *workspace, int B, int T,
                                    int U1, int V, int blank, void *out, long long ld_out, float scale,
                                    float *colsum, void *stream) {
-    if (!log_probs || !workspace || !out || B <= 0 || T <= 0 || U1 <= 0 || U1 > 1024 || V <= 0 || blank < 0 ||
-        blank >= V)
-        return PIKA_EINVAL;
+    // (both compact calls: U1 > 1024 is PIKA_EINVAL, where the calls that fill the workspace answer PIKA_ETOOBIG: kept)
+    if (check_dims(B, T, U1, V, blank) || !log_probs || !workspace || !out) return PIKA_EINVAL;
     if ((V & 3) || V > V_MAX || ld_out < V || (ld_out & 3) || ld_out > V_MAX ||
         (reinterpret_cast<uintptr_t>(log_probs) & 15) || (reinterpret_cast<uintptr_t>(out) & 7))
         return PIKA_EINVAL;
-    const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
-    const long long rows = (long long)B * T * U1;
-    if (rows > 0x7fffffffLL) return PIKA_ETOOBIG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (colsum) {
-        hipError_t e = hipMemsetAsync(colsum, 0, (size_t)V * sizeof(float), s);
-        if (e != hipSuccess) return (int)e;
-        static const int rpw_env = [] { const char *e = pika_knob("PIKA_DLOGITS_RPW"); return e ? atoi(e) : 0; }();   // A/B
-        // tools/dlogits_bench.py at the config-2 lattice: 16 rows per wave 2.43 ms, 32: 2.35, 64: 2.31, 128: 2.31, 256: 2.57;
-        // the 4- and 8-column kernels tie (2.35 ms): the pass is the mixed read / write HBM stream at 5.0-5.1 TB/s
-        const int rpw = rpw_env > 0 ? rpw_env : rows_per_wave(rows);
-        const long long per_block = 4LL * rpw;
-        static const bool wide_off = pika_knob("PIKA_DLOGITS_NARROW") != nullptr;     // A/B: the 4-column kernel
-        if (!wide_off && !(V & 7) && !(ld_out & 7) && V > 512 * 9 && !(reinterpret_cast<uintptr_t>(out) & 15)) {
-#define PIKA_C8(NIT) hipLaunchKernelGGL((rnnt_dlogits_compact8_kernel<NIT, float>), dim3((unsigned)((rows + per_block - 1) / per_block)), \
-                                        dim3(256), 0, s, log_probs, L.meta, static_cast<__bf16 *>(out), rows, V, ld_out, blank, scale,  \
-                                        rpw, colsum, lse, 0LL)
-            if (ld_out <= 512 * 10) PIKA_C8(10); else if (ld_out <= 512 * 13) PIKA_C8(13); else PIKA_C8(16);
-#undef PIKA_C8
-            return (int)hipGetLastError();
-        }
-        PIKA_CQ(ld_out, hipLaunchKernelGGL((rnnt_dlogits_compact_kernel<true, float, CQ>),
-                                           dim3((unsigned)((rows + per_block - 1) / per_block)), dim3(256), 0, s, log_probs, L.meta,
-                                           static_cast<__bf16 *>(out), rows, V, ld_out, blank, scale, rpw, colsum, lse, 0LL));
-    } else {
-        PIKA_CQ(ld_out, hipLaunchKernelGGL((rnnt_dlogits_compact_kernel<false, float, CQ>), dim3((unsigned)((rows + 3) / 4)),
-                                           dim3(256), 0, s, log_probs, L.meta, static_cast<__bf16 *>(out), rows, V, ld_out, blank,
-                                           scale, 1, static_cast<float *>(nullptr), lse, 0LL));
-    }
-    return (int)hipGetLastError();
+    return launch_dlogits_compact<float>(log_probs, 0, compact8_ok_f32(V, ld_out, out), lse, workspace, B, T, U1, V, blank, out,
+                                         ld_out, scale, colsum, nullptr, nullptr, 0, stream);
 }
 
 int pika_rnnt_fused_forward(const float *logits, const int *labels, const int *frames_lengths,
                             const int *labels_lengths, int B, int T, int U1, int V, int blank, float *costs,
                             float *lse, void *workspace, void *stream) {
-    if (int rc = check_dims(B, T, U1, V, blank)) return rc;
-    if (!logits || !frames_lengths || !labels_lengths || !costs || !lse || !workspace) return PIKA_EINVAL;
-    if (U1 > 1 && !labels) return PIKA_EINVAL;
-    if ((V & 3) || V > V_MAX || (reinterpret_cast<uintptr_t>(logits) & 15)) return PIKA_EINVAL;
-    const long long rows = (long long)B * T * U1;
-    if (rows > 0x7fffffffLL) return PIKA_ETOOBIG;
+    long long rows;
+    if (int rc = forward_args_ok(B, T, U1, V, blank, logits && frames_lengths && labels_lengths && costs && lse && workspace &&
+                                 logits_ok(logits, V), labels, &rows))
+        return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Lattice L = carve(workspace, B, T, U1);
     PIKA_CQ(V, hipLaunchKernelGGL(rnnt_lse_gather_kernel<CQ>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, labels,
                                   frames_lengths, labels_lengths, rows, T, U1, V, blank, lse, L.lpb, L.lpe, L.Wp, L.D));
-    return run_alpha_beta(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
+    return finish_forward(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
 }
 
 int pika_rnnt_fused_forward_partials(const float *logits, const float *pmax, const float *psum, int n_part,
                                      const int *labels, const int *frames_lengths, const int *labels_lengths, int B,
                                      int T, int U1, int V, int blank, float *costs, float *lse, void *workspace,
                                      void *stream) {
-    if (int rc = check_dims(B, T, U1, V, blank)) return rc;
-    if (!logits || !pmax || !psum || n_part <= 0 || !frames_lengths || !labels_lengths || !costs || !lse || !workspace)
-        return PIKA_EINVAL;
-    if (U1 > 1 && !labels) return PIKA_EINVAL;
-    const long long rows = (long long)B * T * U1;
-    if (rows > 0x7fffffffLL) return PIKA_ETOOBIG;
+    long long rows;
+    if (int rc = forward_args_ok(B, T, U1, V, blank, logits && pmax && psum && n_part > 0 && frames_lengths && labels_lengths &&
+                                 costs && lse && workspace, labels, &rows))
+        return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Lattice L = carve(workspace, B, T, U1);
     hipLaunchKernelGGL(rnnt_lse_merge_gather_kernel<false>, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s, logits,
                        pmax, psum, n_part, labels, frames_lengths, labels_lengths, rows, T, U1, V, blank, lse, L.lpb, L.lpe,
                        L.Wp, L.D, static_cast<const _Float16 *>(nullptr), 0LL, static_cast<const float *>(nullptr),
                        static_cast<const int *>(nullptr), 0);
-    return run_alpha_beta(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
+    return finish_forward(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
 }
 
 int pika_rnnt_fused_forward_gathered(const void *logits16, long long ld16, const float *gathered, const int *g_labels,
                                      int g_blank, const float *pmax, const float *psum, int n_part, const int *labels,
                                      const int *frames_lengths, const int *labels_lengths, int B, int T, int U1, int V,
                                      int blank, float *costs, float *lse, void *workspace, void *stream) {
-    if (int rc = check_dims(B, T, U1, V, blank)) return rc;
-    if (!logits16 || ld16 < V || !gathered || !pmax || !psum || n_part <= 0 || !frames_lengths || !labels_lengths || !costs ||
-        !lse || !workspace)
-        return PIKA_EINVAL;
-    if (U1 > 1 && !labels) return PIKA_EINVAL;
-    const long long rows = (long long)B * T * U1;
-    if (rows > 0x7fffffffLL) return PIKA_ETOOBIG;
+    long long rows;
+    if (int rc = forward_args_ok(B, T, U1, V, blank, logits16 && ld16 >= V && gathered && pmax && psum && n_part > 0 &&
+                                 frames_lengths && labels_lengths && costs && lse && workspace, labels, &rows))
+        return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Lattice L = carve(workspace, B, T, U1);
     hipLaunchKernelGGL(rnnt_lse_merge_gather_kernel<true>, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s,
                        static_cast<const float *>(nullptr), pmax, psum, n_part, labels, frames_lengths, labels_lengths, rows,
                        T, U1, V, blank, lse, L.lpb, L.lpe, L.Wp, L.D, static_cast<const _Float16 *>(logits16), ld16, gathered,
                        g_labels, g_blank);
-    return run_alpha_beta(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
+    return finish_forward(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
 }
 
 int pika_rnnt_dlogits_compact_bf16_f16in(const void *logits16, long long ld_in, const float *lse, const void *workspace,
@@ -1495,42 +1526,13 @@ int pika_rnnt_dlogits_compact_bf16_f16in(const void *logits16, long long ld_in, 
                                          float *colsum, const float *gathered, const int *g_labels, int g_blank,
                                          void *stream) {
     if (gathered && !g_labels) return PIKA_EINVAL;
-    if (!logits16 || !lse || !workspace || !out || B <= 0 || T <= 0 || U1 <= 0 || U1 > 1024 || V <= 0 || blank < 0 ||
-        blank >= V)
-        return PIKA_EINVAL;
+    if (check_dims(B, T, U1, V, blank) || !logits16 || !lse || !workspace || !out) return PIKA_EINVAL;
     if ((V & 3) || V > V_MAX || ld_out < V || (ld_out & 3) || ld_out > V_MAX || ld_in < V || (ld_in & 3) ||
         (reinterpret_cast<uintptr_t>(logits16) & 7) || (reinterpret_cast<uintptr_t>(out) & 7))
         return PIKA_EINVAL;
-    const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
-    const long long rows = (long long)B * T * U1;
-    if (rows > 0x7fffffffLL) return PIKA_ETOOBIG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const _Float16 *x = static_cast<const _Float16 *>(logits16);
-    if (colsum) {
-        hipError_t e = hipMemsetAsync(colsum, 0, (size_t)V * sizeof(float), s);
-        if (e != hipSuccess) return (int)e;
-        const int rpw = rows_per_wave(rows);
-        const long long per_block = 4LL * rpw;
-        // (V % 8 == 4 -- the shipped recipes' 6268 -- rides on a 16-bit pitch of whole granules: the last one is masked)
-        if (!(ld_out & 7) && !(ld_in & 7) && ld_in >= ((V + 7) & ~7) && V > 512 * 9 && !(reinterpret_cast<uintptr_t>(out) & 15) &&
-            !(reinterpret_cast<uintptr_t>(logits16) & 15)) {
-#define PIKA_C8(NIT) hipLaunchKernelGGL((rnnt_dlogits_compact8_kernel<NIT, _Float16>), dim3((unsigned)((rows + per_block - 1) / per_block)), \
-                                        dim3(256), 0, s, x, L.meta, static_cast<__bf16 *>(out), rows, V, ld_out, blank, scale, rpw, colsum,  \
-                                        lse, ld_in, gathered, g_labels, g_blank, T, U1)
-            if (ld_out <= 512 * 10) PIKA_C8(10); else if (ld_out <= 512 * 13) PIKA_C8(13); else PIKA_C8(16);
-#undef PIKA_C8
-            return (int)hipGetLastError();
-        }
-        PIKA_CQ(ld_out, hipLaunchKernelGGL((rnnt_dlogits_compact_kernel<true, _Float16, CQ>),
-                                           dim3((unsigned)((rows + per_block - 1) / per_block)), dim3(256), 0, s, x, L.meta,
-                                           static_cast<__bf16 *>(out), rows, V, ld_out, blank, scale, rpw, colsum, lse, ld_in,
-                                           gathered, g_labels, g_blank, T, U1));
-    } else {
-        PIKA_CQ(ld_out, hipLaunchKernelGGL((rnnt_dlogits_compact_kernel<false, _Float16, CQ>), dim3((unsigned)((rows + 3) / 4)),
-                                           dim3(256), 0, s, x, L.meta, static_cast<__bf16 *>(out), rows, V, ld_out, blank, scale, 1,
-                                           static_cast<float *>(nullptr), lse, ld_in, gathered, g_labels, g_blank, T, U1));
-    }
-    return (int)hipGetLastError();
+    return launch_dlogits_compact<_Float16>(static_cast<const _Float16 *>(logits16), ld_in,
+                                            compact8_ok_f16(V, ld_out, ld_in, out, logits16), lse, workspace, B, T, U1, V,
+                                            blank, out, ld_out, scale, colsum, gathered, g_labels, g_blank, stream);
 }
 
 namespace {
@@ -1549,9 +1551,7 @@ int launch_dlogits_fused(const Lattice &L, const float *logits, const float *lse
 
 // the d(logits) arguments of the fused backward calls
 int check_dlogits_out(const float *logits, int V, const void *grad_logits, int out_dtype, long long ld_out) {
-    if ((V & 3) || V > V_MAX || ld_out < V || (ld_out & 3) || ld_out > V_MAX ||
-        (reinterpret_cast<uintptr_t>(logits) & 15))
-        return PIKA_EINVAL;
+    if (!logits_ok(logits, V) || ld_out < V || (ld_out & 3) || ld_out > V_MAX) return PIKA_EINVAL;
     if (out_dtype != 0 && out_dtype != 1) return PIKA_EINVAL;   // PIKA_F32 / PIKA_BF16 (pika_gemm.h)
     if (reinterpret_cast<uintptr_t>(grad_logits) & (out_dtype == 0 ? 15 : 7)) return PIKA_EINVAL;
     return PIKA_OK;
@@ -1569,7 +1569,7 @@ int pika_rnnt_fused_backward_fe(const float *logits, const float *lse, const int
     float lscale;
     if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
     const long long rows = (long long)B * T * U1;
-    if (rows > 0x7fffffffLL) return PIKA_ETOOBIG;
+    if (rows > ROWS_MAX) return PIKA_ETOOBIG;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
     launch_rowmeta(L, labels, frames_lengths, labels_lengths, B, T, U1, V, grad_costs, lscale, s);
@@ -1602,7 +1602,7 @@ int pika_rnnt_packed_forward(const float *log_probs, const int *labels, const in
                     (unsigned)B);
     hipLaunchKernelGGL(rnnt_gather_kernel<true>, grid, dim3(256), 0, s, log_probs, labels, frames_lengths,
                        labels_lengths, B, T_max, U1_max, V, blank, L.lpb, L.lpe, L.Wp, L.D, row_offsets, label_offsets);
-    return run_alpha_beta(L, frames_lengths, labels_lengths, costs, B, T_max, U1_max, s);
+    return finish_forward(L, frames_lengths, labels_lengths, costs, B, T_max, U1_max, s);
 }
 
 int pika_rnnt_packed_backward(const int *labels, const int *frames_lengths, const int *labels_lengths,
@@ -1630,14 +1630,13 @@ int pika_rnnt_packed_fused_forward(const float *logits, const int *labels, const
     if (int rc = check_packed(B, T_max, U1_max, N, V, blank, labels, frames_lengths, labels_lengths, row_offsets,
                               label_offsets))
         return rc;
-    if (!logits || !costs || !lse || !workspace) return PIKA_EINVAL;
-    if ((V & 3) || V > V_MAX || (reinterpret_cast<uintptr_t>(logits) & 15)) return PIKA_EINVAL;
+    if (!logits || !costs || !lse || !workspace || !logits_ok(logits, V)) return PIKA_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Lattice L = carve(workspace, B, T_max, U1_max);
     PIKA_CQ(V, hipLaunchKernelGGL((rnnt_lse_gather_kernel<CQ, true>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, logits,
                                   labels, frames_lengths, labels_lengths, N, T_max, U1_max, V, blank, lse, L.lpb, L.lpe, L.Wp,
                                   L.D, row_offsets, label_offsets, B));
-    return run_alpha_beta(L, frames_lengths, labels_lengths, costs, B, T_max, U1_max, s);
+    return finish_forward(L, frames_lengths, labels_lengths, costs, B, T_max, U1_max, s);
 }
 
 int pika_rnnt_packed_fused_backward(const float *logits, const float *lse, const int *labels,
@@ -1663,31 +1662,24 @@ int pika_rnnt_packed_fused_backward(const float *logits, const float *lse, const
 // forced alignment (pika_rnnt.h): Viterbi over the lpb / lpe planes any forward call left
 // ---------------------------------------------------------------------------------------------
 size_t pika_rnnt_align_scratch_bytes(int B, int T, int U1) {
-    if (B <= 0 || T <= 0 || U1 <= 0 || U1 > 1024) return 0;
+    if (check_lattice_dims(B, T, U1)) return 0;
     return (size_t)B * (size_t)(T + U1 - 1) * (size_t)(lattice_width(U1) / 64) * sizeof(unsigned long long);
 }
 
 int pika_rnnt_align(const void *workspace, const int *frames_lengths, const int *labels_lengths,
                     const int *label_offsets, int B, int T, int U1, float *scores, int *emit_frames, void *scratch,
                     void *stream) {
-    if (B <= 0 || T <= 0 || U1 <= 0) return PIKA_EINVAL;
-    if (U1 > 1024) return PIKA_ETOOBIG;
+    if (int rc = check_lattice_dims(B, T, U1)) return rc;
     if (!workspace || !frames_lengths || !labels_lengths || !scores || !scratch) return PIKA_EINVAL;
     if (U1 > 1 && !emit_frames) return PIKA_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
-    switch (L.Wp / 64) {
-        case 1: launch_align<1>(L, frames_lengths, labels_lengths, label_offsets, scores, emit_frames, scratch, B, T, U1, s); break;
-        case 2: launch_align<2>(L, frames_lengths, labels_lengths, label_offsets, scores, emit_frames, scratch, B, T, U1, s); break;
-        case 3: launch_align<3>(L, frames_lengths, labels_lengths, label_offsets, scores, emit_frames, scratch, B, T, U1, s); break;
-        case 4: launch_align<4>(L, frames_lengths, labels_lengths, label_offsets, scores, emit_frames, scratch, B, T, U1, s); break;
-        case 6: launch_align<6>(L, frames_lengths, labels_lengths, label_offsets, scores, emit_frames, scratch, B, T, U1, s); break;
-        case 8: launch_align<8>(L, frames_lengths, labels_lengths, label_offsets, scores, emit_frames, scratch, B, T, U1, s); break;
-        case 12: launch_align<12>(L, frames_lengths, labels_lengths, label_offsets, scores, emit_frames, scratch, B, T, U1, s); break;
-        case 16: launch_align<16>(L, frames_lengths, labels_lengths, label_offsets, scores, emit_frames, scratch, B, T, U1, s); break;
-        default: return PIKA_ETOOBIG;
-    }
-    return (int)hipGetLastError();
+    const bool ok = dispatch_nw(L.Wp / 64, [&](auto nw) {
+        constexpr int NW = decltype(nw)::value;
+        hipLaunchKernelGGL((rnnt_align_kernel<NW>), dim3(B), dim3(NW * 64), 0, s, L.lpb, L.lpe, frames_lengths, labels_lengths,
+                           label_offsets, scores, emit_frames, static_cast<unsigned long long *>(scratch), T, U1, L.Wp, L.D);
+    });
+    return ok ? (int)hipGetLastError() : PIKA_ETOOBIG;
 }
 
 }  // extern "C"

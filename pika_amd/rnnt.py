@@ -46,14 +46,15 @@ class _timed(object):
     def __init__(self, key):
         self.key = key
 
-    def __enter__(self):
-        if KERNEL_EVENTS is not None:
+    def __enter__(self):         # (key None: a call nobody times -- alignment)
+        self.on = KERNEL_EVENTS is not None and self.key is not None
+        if self.on:
             self.e0 = torch.cuda.Event(enable_timing=True)
             self.e1 = torch.cuda.Event(enable_timing=True)
             self.e0.record()
 
     def __exit__(self, *exc):
-        if KERNEL_EVENTS is not None:
+        if self.on:
             self.e1.record()
             KERNEL_EVENTS[self.key].append((self.e0, self.e1))
 
@@ -66,19 +67,22 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def _check_inputs(log_probs, labels, frames_lengths, labels_lengths, blank):
+def _check_tensors(x, what, labels, frames_lengths, labels_lengths, no_cpu=""):
     # same argument checks, same exception types as the reference binding's Python wrapper
-    if not log_probs.is_cuda:
-        raise RuntimeError("pika_amd RNNTLoss: log_probs must live on a HIP device "
-                           "(there is no CPU path; the CPU checker lives in oracle/ for tests only)")
-    if log_probs.dtype != torch.float32:
-        raise TypeError("log_probs must be float32, got %s" % log_probs.dtype)
-    for name, t in (("labels", labels), ("frames_lengths", frames_lengths),
-                    ("labels_lengths", labels_lengths)):
+    if not x.is_cuda:
+        raise RuntimeError("pika_amd RNNTLoss: %s must live on a HIP device%s" % (what, no_cpu))
+    if x.dtype != torch.float32:
+        raise TypeError("%s must be float32, got %s" % (what, x.dtype))
+    for name, t in (("labels", labels), ("frames_lengths", frames_lengths), ("labels_lengths", labels_lengths)):
         if t.dtype != torch.int32:
             raise TypeError("%s must be int32, got %s" % (name, t.dtype))
-        if t.device != log_probs.device:
-            raise RuntimeError("%s is on %s but log_probs is on %s" % (name, t.device, log_probs.device))
+        if t.device != x.device:
+            raise RuntimeError("%s is on %s but %s is on %s" % (name, t.device, what, x.device))
+
+
+def _check_inputs(log_probs, labels, frames_lengths, labels_lengths, blank):
+    _check_tensors(log_probs, "log_probs", labels, frames_lengths, labels_lengths,
+                   " (there is no CPU path; the CPU checker lives in oracle/ for tests only)")
     if log_probs.dim() != 4:
         raise ValueError("log_probs must be (B,T,U+1,V), got %s" % (tuple(log_probs.shape),))
     B, T, U1, V = log_probs.shape
@@ -100,8 +104,10 @@ class CompactGrad(object):
 
     __slots__ = ("ws", "dims", "ptr", "version")
 
-    def __init__(self, ws, dims, grads):
-        self.ws, self.dims, self.ptr, self.version = ws, dims, grads.data_ptr(), grads._version
+    def __init__(self, ws, dims, grads=None):
+        # (grads None: the workspace alone, for a LazyDenseGrad -- there is no dense tensor to match)
+        self.ws, self.dims = ws, dims
+        self.ptr, self.version = (grads.data_ptr(), grads._version) if grads is not None else (0, 0)
 
     def matches(self, g):
         return g.data_ptr() == self.ptr and g._version == self.version and tuple(g.shape) == tuple(self.dims[:4])
@@ -112,7 +118,24 @@ def _lazy_enabled():
     return os.environ.get("PIKA_RNNT_LAZY_GRAD", "1") != "0"
 
 
-class LazyDenseGrad(torch.Tensor):
+class _LazyTensor(torch.Tensor):
+    """A wrapper tensor whose values exist once somebody asks: every use other than the one its producer registered for
+    goes through `dense()` of the subclass first."""
+
+    def __reduce_ex__(self, proto):     # pickling / torch.save: the real values
+        return self.dense().__reduce_ex__(proto)
+
+    def __deepcopy__(self, memo):
+        return self.dense().clone()
+
+    @classmethod
+    def __torch_dispatch__(cls, func, types, args=(), kwargs=None):
+        from torch.utils._pytree import tree_map
+        un = lambda t: t.dense() if isinstance(t, _LazyTensor) else t   # noqa: E731
+        return func(*tree_map(un, args), **tree_map(un, kwargs or {}))
+
+
+class LazyDenseGrad(_LazyTensor):
     """The loss' (B,T,U1,V) gradient as a tensor that is only written when somebody looks at it.
 
     The backward of the loss always leaves the at most two non-zeros of every V-row in its workspace.  A
@@ -150,18 +173,6 @@ class LazyDenseGrad(torch.Tensor):
 
     def __repr__(self):
         return "LazyDenseGrad(shape=%s, written=%s)" % (tuple(self.shape), self._dense is not None)
-
-    def __reduce_ex__(self, proto):
-        return self.dense().__reduce_ex__(proto)
-
-    def __deepcopy__(self, memo):
-        return self.dense().clone()
-
-    @classmethod
-    def __torch_dispatch__(cls, func, types, args=(), kwargs=None):
-        from torch.utils._pytree import tree_map
-        un = lambda t: t.dense() if isinstance(t, LazyDenseGrad) else t   # noqa: E731
-        return func(*tree_map(un, args), **tree_map(un, kwargs or {}))
 
 
 class LogitsState(object):
@@ -201,7 +212,7 @@ class LogitsState(object):
         return buf
 
 
-class LazyLogProbs(torch.Tensor):
+class LazyLogProbs(_LazyTensor):
     """log_softmax(logits) over the lattice as a tensor whose log-softmax pass only runs if somebody needs the
     values.  pika_amd.model.hipops.JointOutFn returns it; this module's loss takes the row log-sum-exp and the two
     log-probs per lattice cell it needs in ONE read of the raw logits (pika_rnnt_fused_forward), and the joint's
@@ -226,24 +237,78 @@ class LazyLogProbs(torch.Tensor):
     def __repr__(self):
         return "LazyLogProbs(shape=%s, normalised=%s)" % (tuple(self.shape), not self.state.raw)
 
-    def __reduce_ex__(self, proto):     # pickling / torch.save: the real log-probabilities
-        return self.dense().__reduce_ex__(proto)
-
-    def __deepcopy__(self, memo):
-        return self.dense().clone()
-
-    @classmethod
-    def __torch_dispatch__(cls, func, types, args=(), kwargs=None):
-        from torch.utils._pytree import tree_map
-        un = lambda t: t.dense() if isinstance(t, LazyLogProbs) else t   # noqa: E731
-        return func(*tree_map(un, args), **tree_map(un, kwargs or {}))
-
 
 def _check_lambda(fastemit_lambda):
     lam = float(fastemit_lambda)
     if not (math.isfinite(lam) and lam >= 0.0):
         raise ValueError("fastemit_lambda must be finite and >= 0, got %r" % (fastemit_lambda,))
     return lam
+
+
+def _fused_v_ok(V):
+    return V % 4 == 0 and V <= MAX_FUSED_V
+
+
+def _raw_readable(lp):
+    """May this LazyLogProbs be read as the raw logits of its buffer (log-sum-exp + gather in one read)?  Not once it is
+    normalised, not when it is scaled, not outside the fused kernels' vocabularies; 16-bit logits only with the partial
+    statistics their merge kernel starts from."""
+    st = lp.state
+    return bool(st.raw and st.scale == 1.0 and _fused_v_ok(lp.buf.shape[-1])
+                and (st.gathered is None or st.partials is not None))
+
+
+def _fill_padded(x, labels, frames_lengths, labels_lengths, blank, logits=False, lazy=True, loss=False):
+    """Fill a loss workspace from a checked padded input with contiguous labels and lengths: (costs, ws, lse, V, width).
+
+    x: log-probs (B,T,U1,V); raw logits (`logits`, the *_from_logits forms); or a LazyLogProbs of this package's joint,
+    read as the raw logits of its buffer where `lazy` allows and it can be (`_raw_readable`: the plain, the partial
+    statistics or the gathered call) and normalised HERE otherwise -- `.contiguous()` on the wrapper subclass
+    short-circuits and would hand back the wrapper.  lse: the log-sum-exp of every row of RAW logits, None when
+    log-probs were read.  V: the columns the kernels saw -- the buffer's, when a joint padded its output layer; `width`
+    is then the caller's V, else None.
+    loss: the caller is the loss, not a reader of the planes: it uses the partial statistics up (one use: 250 MB at the
+    benchmark shape), writes into the buffers a replayed forward names (pika_amd/train_graph.py: the ones its captured
+    backward reads) and its call counts as KERNEL_EVENTS["fwd"]."""
+    lib = _lib.lib()
+    B, T, U1, V = x.shape
+    width = part = gath = bufs = None
+    if not isinstance(x, LazyLogProbs):
+        x = x.detach().contiguous()
+    elif lazy and _raw_readable(x):
+        state, logits = x.state, True
+        part, gath = state.partials, state.gathered
+        if loss:
+            state.partials, bufs = None, getattr(x, "_pika_loss_buffers", None)
+        x = x.buf
+        if x.shape[-1] != V:
+            width, V = V, x.shape[-1]
+    else:
+        x = x.dense().detach().contiguous()
+    with torch.cuda.device(x.device):
+        costs = torch.empty(B, dtype=torch.float32, device=x.device)
+        ws, lse = bufs or (None, None)
+        n_ws = lib.pika_rnnt_workspace_bytes(B, T, U1)
+        if ws is None or ws.numel() != n_ws or lse.numel() != B * T * U1 or ws.device != x.device:
+            ws = torch.empty(n_ws, dtype=torch.uint8, device=x.device)
+            lse = torch.empty(B * T * U1, dtype=torch.float32, device=x.device) if logits else None
+        head = (_ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank, _ptr(costs))
+        with _timed("fwd" if loss else None):
+            if gath is not None:
+                _lib.check(lib.pika_rnnt_fused_forward_gathered(
+                    _ptr(x), x.stride(-2), _ptr(gath[0]), _ptr(gath[1]), int(gath[2]), part[0].data_ptr(),
+                    part[1].data_ptr(), part.shape[2], *head, _ptr(lse), _ptr(ws), _stream()),
+                    "pika_rnnt_fused_forward_gathered")
+            elif part is not None:
+                _lib.check(lib.pika_rnnt_fused_forward_partials(
+                    _ptr(x), part[0].data_ptr(), part[1].data_ptr(), part.shape[2], *head, _ptr(lse), _ptr(ws), _stream()),
+                    "pika_rnnt_fused_forward_partials")
+            elif logits:
+                _lib.check(lib.pika_rnnt_fused_forward(_ptr(x), *head, _ptr(lse), _ptr(ws), _stream()),
+                           "pika_rnnt_fused_forward")
+            else:
+                _lib.check(lib.pika_rnnt_loss_forward(_ptr(x), *head, _ptr(ws), _stream()), "pika_rnnt_loss_forward")
+    return costs, ws, lse, V, width
 
 
 class _RNNTLossFn(torch.autograd.Function):
@@ -257,66 +322,13 @@ class _RNNTLossFn(torch.autograd.Function):
             labels = wide
         _check_inputs(log_probs, labels, frames_lengths, labels_lengths, blank)
         ctx.lazy = bool(getattr(log_probs, "_pika_lazy_grad_ok", False)) and _lazy_enabled()
-        lib = _lib.lib()
-        labels = labels.contiguous()
-        frames_lengths = frames_lengths.contiguous()
-        labels_lengths = labels_lengths.contiguous()
-        B, T, U1, V = log_probs.shape
-        lse = None
-        state = log_probs.state if isinstance(log_probs, LazyLogProbs) else None
-        ctx.width = None
-        if state is not None:
-            # (a joint that padded its output layer: the kernels see the buffer's columns, the caller `V` of them)
-            Vk = log_probs.buf.shape[-1]
-            ctx.width, V = (V, Vk) if Vk != V else (None, V)
-        if state is not None and not (state.raw and ctx.lazy and state.scale == 1.0 and V % 4 == 0 and V <= MAX_FUSED_V
-                                      and (state.gathered is None or state.partials is not None)):
-            state, V = None, log_probs.shape[-1]
-            ctx.width = None
-        if state is not None:
-            # raw logits of this package's joint: log-sum-exp + gather in one read, no log-prob tensor
-            x = log_probs.buf
-            with torch.cuda.device(x.device):
-                costs = torch.empty(B, dtype=torch.float32, device=x.device)
-                # a replayed forward (pika_amd/train_graph.py) names the buffers its captured backward reads
-                ws, lse = getattr(log_probs, "_pika_loss_buffers", None) or (None, None)
-                n_ws = lib.pika_rnnt_workspace_bytes(B, T, U1)
-                if ws is None or ws.numel() != n_ws or lse.numel() != B * T * U1 or ws.device != x.device:
-                    lse = torch.empty(B * T * U1, dtype=torch.float32, device=x.device)
-                    ws = torch.empty(n_ws, dtype=torch.uint8, device=x.device)
-                part = state.partials
-                state.partials = None          # one use: 250 MB at the benchmark shape
-                with _timed("fwd"):
-                    if state.gathered is not None:
-                        gath, g_labels, g_blank = state.gathered
-                        _lib.check(lib.pika_rnnt_fused_forward_gathered(
-                            _ptr(x), x.stride(-2), _ptr(gath), _ptr(g_labels), int(g_blank), part[0].data_ptr(),
-                            part[1].data_ptr(), part.shape[2], _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths),
-                            B, T, U1, V, blank, _ptr(costs), _ptr(lse), _ptr(ws), _stream()),
-                            "pika_rnnt_fused_forward_gathered")
-                    elif part is not None:
-                        _lib.check(lib.pika_rnnt_fused_forward_partials(
-                            _ptr(x), part[0].data_ptr(), part[1].data_ptr(), part.shape[2], _ptr(labels),
-                            _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank, _ptr(costs), _ptr(lse),
-                            _ptr(ws), _stream()), "pika_rnnt_fused_forward_partials")
-                    else:
-                        _lib.check(lib.pika_rnnt_fused_forward(
-                            _ptr(x), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank,
-                            _ptr(costs), _ptr(lse), _ptr(ws), _stream()), "pika_rnnt_fused_forward")
-        else:
-            # a LazyLogProbs the fused path cannot take (already read, scaled, V out of the fused kernel's range) is
-            # normalised HERE: `.contiguous()` on the wrapper subclass short-circuits and would hand back the wrapper
-            lp = log_probs.dense().contiguous() if isinstance(log_probs, LazyLogProbs) else log_probs.contiguous()
-            with torch.cuda.device(lp.device):
-                costs = torch.empty(B, dtype=torch.float32, device=lp.device)
-                ws = torch.empty(lib.pika_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8,
-                                 device=lp.device)
-                with _timed("fwd"):
-                    _lib.check(lib.pika_rnnt_loss_forward(
-                        _ptr(lp), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths),
-                        B, T, U1, V, blank, _ptr(costs), _ptr(ws), _stream()), "pika_rnnt_loss_forward")
-        # lse: the log-sum-exp of every row of the RAW logits (None when log-probs were read); it only means something
-        # to the joint's backward while its buffer is still raw, which that backward checks itself
+        labels, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, frames_lengths, labels_lengths))
+        B, T, U1, _ = log_probs.shape
+        # raw logits of this package's joint, when the joint takes the lazy gradient: log-sum-exp + gather in one read, no
+        # log-prob tensor.  lse only means something to the joint's backward while its buffer is still raw, which that
+        # backward checks itself
+        costs, ws, lse, V, ctx.width = _fill_padded(log_probs, labels, frames_lengths, labels_lengths, blank,
+                                                    lazy=ctx.lazy, loss=True)
         ctx.save_for_backward(labels, frames_lengths, labels_lengths, ws, lse)
         ctx.dims = (B, T, U1, V, blank)
         ctx.fastemit_lambda = fastemit_lambda
@@ -334,9 +346,7 @@ class _RNNTLossFn(torch.autograd.Function):
                 _lib.check(lib.pika_rnnt_loss_backward_fe(
                     _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank,
                     _ptr(gc), _ptr(ws), None, lam, _stream()), "pika_rnnt_loss_backward_fe")
-            compact = CompactGrad.__new__(CompactGrad)
-            compact.ws, compact.dims, compact.ptr, compact.version = ws, (B, T, U1, V, blank), 0, 0
-            lazy = LazyDenseGrad(compact, labels, frames_lengths, labels_lengths, width=ctx.width)
+            lazy = LazyDenseGrad(CompactGrad(ws, (B, T, U1, V, blank)), labels, frames_lengths, labels_lengths, width=ctx.width)
             lazy.lse = lse
             return lazy, None, None, None, None, None
         with torch.cuda.device(ws.device):
@@ -357,18 +367,10 @@ class _FusedLogitsLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0):
         _check_inputs(logits, labels, frames_lengths, labels_lengths, blank)
-        lib = _lib.lib()
         x = logits.contiguous()
         labels, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, frames_lengths, labels_lengths))
         B, T, U1, V = x.shape
-        with torch.cuda.device(x.device):
-            costs = torch.empty(B, dtype=torch.float32, device=x.device)
-            lse = torch.empty(B * T * U1, dtype=torch.float32, device=x.device)
-            ws = torch.empty(lib.pika_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8, device=x.device)
-            with _timed("fwd"):
-                _lib.check(lib.pika_rnnt_fused_forward(
-                    _ptr(x), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank,
-                    _ptr(costs), _ptr(lse), _ptr(ws), _stream()), "pika_rnnt_fused_forward")
+        costs, ws, lse, _, _ = _fill_padded(x, labels, frames_lengths, labels_lengths, blank, logits=True, loss=True)
         ctx.save_for_backward(x, labels, frames_lengths, labels_lengths, ws, lse)
         ctx.dims = (B, T, U1, V, blank)
         ctx.fastemit_lambda = fastemit_lambda
@@ -397,15 +399,7 @@ class _Packed(object):
 
 def _check_packed(x, labels, frames_lengths, labels_lengths, blank, what):
     """Validate a packed call before any launch; ONE device-to-host copy of the two length vectors."""
-    if not x.is_cuda:
-        raise RuntimeError("pika_amd RNNTLoss: %s must live on a HIP device" % what)
-    if x.dtype != torch.float32:
-        raise TypeError("%s must be float32, got %s" % (what, x.dtype))
-    for name, t in (("labels", labels), ("frames_lengths", frames_lengths), ("labels_lengths", labels_lengths)):
-        if t.dtype != torch.int32:
-            raise TypeError("%s must be int32, got %s" % (name, t.dtype))
-        if t.device != x.device:
-            raise RuntimeError("%s is on %s but %s is on %s" % (name, t.device, what, x.device))
+    _check_tensors(x, what, labels, frames_lengths, labels_lengths)
     if x.dim() != 2:
         raise ValueError("compact=True: %s must be (N, V), got %s" % (what, tuple(x.shape)))
     if labels.dim() != 1:
@@ -443,25 +437,42 @@ def _check_packed(x, labels, frames_lengths, labels_lengths, blank, what):
     return p
 
 
+def _fill_packed(x, labels, frames_lengths, labels_lengths, blank, caller=None, loss=False):
+    """`_fill_padded` for the packed layout: checks the call and fills a workspace from log-probs (N, V) or -- `caller`,
+    the name of a *_from_logits form -- raw logits.  Returns (p, (x, labels, frames_lengths, labels_lengths), costs, ws,
+    lse): the batch's description and the contiguous tensors the kernels read.  loss: the call counts as
+    KERNEL_EVENTS["fwd"]."""
+    p = _check_packed(x, labels, frames_lengths, labels_lengths, blank, "logits" if caller else "log_probs")
+    lib = _lib.lib()
+    x = x.detach().contiguous()
+    labels, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, frames_lengths, labels_lengths))
+    V = x.shape[1]
+    if caller and not _fused_v_ok(V):
+        raise ValueError("%s: V = %d must be a multiple of 4 and <= %d" % (caller, V, MAX_FUSED_V))
+    with torch.cuda.device(x.device):
+        costs = torch.empty(p.B, dtype=torch.float32, device=x.device)
+        lse = torch.empty(p.N, dtype=torch.float32, device=x.device) if caller else None
+        ws = torch.empty(lib.pika_rnnt_workspace_bytes(p.B, p.T, p.U1), dtype=torch.uint8, device=x.device)
+        head = (_ptr(x), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(p.roff), _ptr(p.loff),
+                p.B, p.T, p.U1, p.N, V, blank, _ptr(costs))
+        with _timed("fwd" if loss else None):
+            if caller:
+                _lib.check(lib.pika_rnnt_packed_fused_forward(*head, _ptr(lse), _ptr(ws), _stream()),
+                           "pika_rnnt_packed_fused_forward")
+            else:
+                _lib.check(lib.pika_rnnt_packed_forward(*head, _ptr(ws), _stream()), "pika_rnnt_packed_forward")
+    return p, (x, labels, frames_lengths, labels_lengths), costs, ws, lse
+
+
 class _PackedLossFn(torch.autograd.Function):
     """RNN-T costs of a packed batch of log-probs (N, V); gradient (N, V)."""
 
     @staticmethod
     def forward(ctx, log_probs, labels, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0):
-        p = _check_packed(log_probs, labels, frames_lengths, labels_lengths, blank, "log_probs")
-        lib = _lib.lib()
-        lp = log_probs.contiguous()
-        labels, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, frames_lengths, labels_lengths))
-        V = lp.shape[1]
-        with torch.cuda.device(lp.device):
-            costs = torch.empty(p.B, dtype=torch.float32, device=lp.device)
-            ws = torch.empty(lib.pika_rnnt_workspace_bytes(p.B, p.T, p.U1), dtype=torch.uint8, device=lp.device)
-            with _timed("fwd"):
-                _lib.check(lib.pika_rnnt_packed_forward(
-                    _ptr(lp), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(p.roff), _ptr(p.loff),
-                    p.B, p.T, p.U1, p.N, V, blank, _ptr(costs), _ptr(ws), _stream()), "pika_rnnt_packed_forward")
+        p, (lp, labels, frames_lengths, labels_lengths), costs, ws, _ = _fill_packed(
+            log_probs, labels, frames_lengths, labels_lengths, blank, loss=True)
         ctx.save_for_backward(labels, frames_lengths, labels_lengths, ws, p.roff, p.loff)
-        ctx.dims = (p.B, p.T, p.U1, p.N, V, blank)
+        ctx.dims = (p.B, p.T, p.U1, p.N, lp.shape[1], blank)
         ctx.fastemit_lambda = fastemit_lambda
         return costs
 
@@ -484,24 +495,10 @@ class _PackedLogitsLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, labels, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0):
-        p = _check_packed(logits, labels, frames_lengths, labels_lengths, blank, "logits")
-        lib = _lib.lib()
-        x = logits.contiguous()
-        labels, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, frames_lengths, labels_lengths))
-        V = x.shape[1]
-        if V % 4 or V > MAX_FUSED_V:
-            raise ValueError("rnnt_loss_from_logits: V = %d must be a multiple of 4 and <= %d" % (V, MAX_FUSED_V))
-        with torch.cuda.device(x.device):
-            costs = torch.empty(p.B, dtype=torch.float32, device=x.device)
-            lse = torch.empty(p.N, dtype=torch.float32, device=x.device)
-            ws = torch.empty(lib.pika_rnnt_workspace_bytes(p.B, p.T, p.U1), dtype=torch.uint8, device=x.device)
-            with _timed("fwd"):
-                _lib.check(lib.pika_rnnt_packed_fused_forward(
-                    _ptr(x), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(p.roff), _ptr(p.loff),
-                    p.B, p.T, p.U1, p.N, V, blank, _ptr(costs), _ptr(lse), _ptr(ws), _stream()),
-                    "pika_rnnt_packed_fused_forward")
+        p, (x, labels, frames_lengths, labels_lengths), costs, ws, lse = _fill_packed(
+            logits, labels, frames_lengths, labels_lengths, blank, caller="rnnt_loss_from_logits", loss=True)
         ctx.save_for_backward(x, labels, frames_lengths, labels_lengths, ws, lse, p.roff, p.loff)
-        ctx.dims = (p.B, p.T, p.U1, p.N, V, blank)
+        ctx.dims = (p.B, p.T, p.U1, p.N, x.shape[1], blank)
         ctx.fastemit_lambda = fastemit_lambda
         return costs
 
@@ -570,32 +567,25 @@ def _align_call(lib, ws, frames_lengths, labels_lengths, loff, B, T, U1, n_frame
     return scores, frames
 
 
-def _align_packed(x, labels, frames_lengths, labels_lengths, blank, fused):
-    p = _check_packed(x, labels, frames_lengths, labels_lengths, blank, "logits" if fused else "log_probs")
+def _align(x, labels, frames_lengths, labels_lengths, blank, compact, caller=None):
+    """Both alignment forms: fill a workspace the way the loss does (caller: the *_from_logits form's name), walk it."""
     lib = _lib.lib()
-    x = x.detach().contiguous()
+    if compact:
+        p, (x, labels, frames_lengths, labels_lengths), _, ws, _ = _fill_packed(x, labels, frames_lengths, labels_lengths,
+                                                                               blank, caller)
+        with torch.cuda.device(x.device):
+            return _align_call(lib, ws, frames_lengths, labels_lengths, p.loff, p.B, p.T, p.U1, labels.numel(), x.device)
+    _check_inputs(x, labels, frames_lengths, labels_lengths, blank)
     labels, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, frames_lengths, labels_lengths))
-    V = x.shape[1]
-    if fused and (V % 4 or V > MAX_FUSED_V):
-        raise ValueError("rnnt_align_from_logits: V = %d must be a multiple of 4 and <= %d" % (V, MAX_FUSED_V))
-    with torch.cuda.device(x.device):
-        costs = torch.empty(p.B, dtype=torch.float32, device=x.device)
-        ws = torch.empty(lib.pika_rnnt_workspace_bytes(p.B, p.T, p.U1), dtype=torch.uint8, device=x.device)
-        if fused:
-            lse = torch.empty(p.N, dtype=torch.float32, device=x.device)
-            _lib.check(lib.pika_rnnt_packed_fused_forward(
-                _ptr(x), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(p.roff), _ptr(p.loff),
-                p.B, p.T, p.U1, p.N, V, blank, _ptr(costs), _ptr(lse), _ptr(ws), _stream()),
-                "pika_rnnt_packed_fused_forward")
-        else:
-            _lib.check(lib.pika_rnnt_packed_forward(
-                _ptr(x), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(p.roff), _ptr(p.loff),
-                p.B, p.T, p.U1, p.N, V, blank, _ptr(costs), _ptr(ws), _stream()), "pika_rnnt_packed_forward")
-        return _align_call(lib, ws, frames_lengths, labels_lengths, p.loff, p.B, p.T, p.U1, labels.numel(), x.device)
-
-
-def _fused_v_ok(V):
-    return V % 4 == 0 and V <= MAX_FUSED_V
+    B, T, U1, V = x.shape
+    if caller and not _fused_v_ok(V):
+        raise ValueError("%s: V = %d must be a multiple of 4 and <= %d" % (caller, V, MAX_FUSED_V))
+    # (a LazyLogProbs: the planes come from the raw buffer as it is; the partial statistics, which the loss uses once,
+    # stay for it)
+    _, ws, _, _, _ = _fill_padded(x, labels, frames_lengths, labels_lengths, blank, logits=caller is not None)
+    with torch.cuda.device(ws.device):
+        scores, frames = _align_call(lib, ws, frames_lengths, labels_lengths, None, B, T, U1, B * (U1 - 1), ws.device)
+    return scores, frames.view(B, U1 - 1)
 
 
 def rnnt_align(log_probs, labels, frames_lengths, labels_lengths, blank=0, compact=False):
@@ -608,77 +598,13 @@ def rnnt_align(log_probs, labels, frames_lengths, labels_lengths, blank=0, compa
     of `rnnt_loss` (a LazyLogProbs of this package's joint is read the way the loss reads it); no autograd.  The
     padded form never synchronises the host and can be captured in a graph; compact=True pays the packed layout's
     one length copy and raises under stream capture."""
-    if compact:
-        return _align_packed(log_probs, labels, frames_lengths, labels_lengths, blank, False)
-    _check_inputs(log_probs, labels, frames_lengths, labels_lengths, blank)
-    lib = _lib.lib()
-    labels, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, frames_lengths, labels_lengths))
-    B, T, U1, V = log_probs.shape
-    state = log_probs.state if isinstance(log_probs, LazyLogProbs) else None
-    if state is not None:
-        V = log_probs.buf.shape[-1]
-        if not (state.raw and state.scale == 1.0 and _fused_v_ok(V)
-                and (state.gathered is None or state.partials is not None)):
-            state = None
-    if state is not None:
-        # raw logits of this package's joint: the planes come from the buffer as it is (the partial statistics, which
-        # the loss uses once, stay for it)
-        x, part = log_probs.buf, state.partials
-        with torch.cuda.device(x.device):
-            costs = torch.empty(B, dtype=torch.float32, device=x.device)
-            lse = torch.empty(B * T * U1, dtype=torch.float32, device=x.device)
-            ws = torch.empty(lib.pika_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8, device=x.device)
-            if state.gathered is not None:
-                gath, g_labels, g_blank = state.gathered
-                _lib.check(lib.pika_rnnt_fused_forward_gathered(
-                    _ptr(x), x.stride(-2), _ptr(gath), _ptr(g_labels), int(g_blank), part[0].data_ptr(),
-                    part[1].data_ptr(), part.shape[2], _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths),
-                    B, T, U1, V, blank, _ptr(costs), _ptr(lse), _ptr(ws), _stream()),
-                    "pika_rnnt_fused_forward_gathered")
-            elif part is not None:
-                _lib.check(lib.pika_rnnt_fused_forward_partials(
-                    _ptr(x), part[0].data_ptr(), part[1].data_ptr(), part.shape[2], _ptr(labels),
-                    _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank, _ptr(costs), _ptr(lse),
-                    _ptr(ws), _stream()), "pika_rnnt_fused_forward_partials")
-            else:
-                _lib.check(lib.pika_rnnt_fused_forward(
-                    _ptr(x), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank,
-                    _ptr(costs), _ptr(lse), _ptr(ws), _stream()), "pika_rnnt_fused_forward")
-            scores, frames = _align_call(lib, ws, frames_lengths, labels_lengths, None, B, T, U1, B * (U1 - 1), x.device)
-    else:
-        lp = log_probs.dense() if isinstance(log_probs, LazyLogProbs) else log_probs
-        lp = lp.detach().contiguous()
-        with torch.cuda.device(lp.device):
-            costs = torch.empty(B, dtype=torch.float32, device=lp.device)
-            ws = torch.empty(lib.pika_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8, device=lp.device)
-            _lib.check(lib.pika_rnnt_loss_forward(
-                _ptr(lp), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, lp.shape[-1], blank,
-                _ptr(costs), _ptr(ws), _stream()), "pika_rnnt_loss_forward")
-            scores, frames = _align_call(lib, ws, frames_lengths, labels_lengths, None, B, T, U1, B * (U1 - 1), lp.device)
-    return scores, frames.view(B, U1 - 1)
+    return _align(log_probs, labels, frames_lengths, labels_lengths, blank, compact)
 
 
 def rnnt_align_from_logits(logits, labels, frames_lengths, labels_lengths, blank=0, compact=False):
     """`rnnt_align` of log_softmax(logits) without materialising the log-probabilities (V % 4 == 0, V <= 8192):
     the planes come from the one read of the raw logits `rnnt_loss_from_logits` makes."""
-    if compact:
-        return _align_packed(logits, labels, frames_lengths, labels_lengths, blank, True)
-    _check_inputs(logits, labels, frames_lengths, labels_lengths, blank)
-    lib = _lib.lib()
-    x = logits.detach().contiguous()
-    labels, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, frames_lengths, labels_lengths))
-    B, T, U1, V = x.shape
-    if not _fused_v_ok(V):
-        raise ValueError("rnnt_align_from_logits: V = %d must be a multiple of 4 and <= %d" % (V, MAX_FUSED_V))
-    with torch.cuda.device(x.device):
-        costs = torch.empty(B, dtype=torch.float32, device=x.device)
-        lse = torch.empty(B * T * U1, dtype=torch.float32, device=x.device)
-        ws = torch.empty(lib.pika_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8, device=x.device)
-        _lib.check(lib.pika_rnnt_fused_forward(
-            _ptr(x), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank,
-            _ptr(costs), _ptr(lse), _ptr(ws), _stream()), "pika_rnnt_fused_forward")
-        scores, frames = _align_call(lib, ws, frames_lengths, labels_lengths, None, B, T, U1, B * (U1 - 1), x.device)
-    return scores, frames.view(B, U1 - 1)
+    return _align(logits, labels, frames_lengths, labels_lengths, blank, compact, "rnnt_align_from_logits")
 
 
 class RNNTLoss(object):

@@ -235,9 +235,7 @@ def _capture(model, st, key, x, y, x_len, t_valid=None):
         with torch.cuda.device(dev):
             e.ws = torch.empty(int(lib.pika_rnnt_workspace_bytes(B, T, U1)), dtype=torch.uint8, device=dev)
             e.lse = torch.empty(B * T * U1, dtype=torch.float32, device=dev)
-        compact = CompactGrad.__new__(CompactGrad)
-        compact.ws, compact.dims, compact.ptr, compact.version = e.ws, e.dims, 0, 0
-        gout = LazyDenseGrad(compact, None, None, None, width=None if out.shape[-1] == V else out.shape[-1])
+        gout = LazyDenseGrad(CompactGrad(e.ws, e.dims), None, None, None, width=None if out.shape[-1] == V else out.shape[-1])
         gout.lse = e.lse
     elif type(out) is torch.Tensor and out.requires_grad:
         # the general form (vocabularies the lazy joint does not take, PIKA_LAZY_LOGPROBS=0, ...): a plain output tensor

@@ -79,14 +79,26 @@ def reached(row):
 def source_instantiations():
     """Every shape-selected instantiation rnnt_loss.hip names, read from its host code."""
     src = open(SRC).read()
-    waves = tuple(int(w) for w in re.search(r"kWaves\[\]\s*=\s*\{([^}]*)\}", src).group(1).split(","))
+    lists = re.findall(r"std::integer_sequence<int, (\d[^>]*)>", src)
+    assert len(lists) == 1, lists          # THE list: lattice_width searches it, dispatch_nw folds over it
+    waves = tuple(int(w) for w in lists[0].split(","))
     assert waves == K_WAVES, waves
-    launched = {int(n) for n in re.findall(r"launch_ab<(\d+)>\(", src)}
-    assert launched == set(waves), (launched, waves)
+    assert not re.search(r"kWaves|launch_ab<\w+>\(|launch_align<\w+>\(|case \d+:", src)      # no second list, no ladder
+    for kernel in ("rnnt_alpha_beta_kernel", "rnnt_align_kernel"):    # one launch each, under dispatch_nw over that list
+        assert len(re.findall(r"dispatch_nw\(L\.Wp / 64, \[&\]\(auto nw\) \{\s*constexpr int NW = decltype\(nw\)::value;\s*"
+                              r"hipLaunchKernelGGL\(\(%s<NW>\)," % kernel, src)) == 1, kernel
+        assert len(re.findall(r"hipLaunchKernelGGL\(\(?%s<" % kernel, src)) == 1, kernel
+    assert re.search(r"return \(\(nw == NW && \(f\(std::integral_constant<int, NW>\{\}\), true\)\) \|\| \.\.\.\);", src)
     cq = {int(c) for c in re.findall(r"constexpr int CQ = (\d+);", src)}
     nits = {int(n) for n in re.findall(r"PIKA_C8\((\d+)\)", src)}
-    c8_types = set(re.findall(r"rnnt_dlogits_compact8_kernel<NIT, (\w+)>", src))
-    compact = set(re.findall(r"rnnt_dlogits_compact_kernel<(true|false), (\w+), CQ>", src))
+    # both compact d(logits) kernels are named once, in launch_dlogits_compact<TI>, for the input types it is called with
+    in_types = set(re.findall(r"return launch_dlogits_compact<(\w+)>\(", src))
+    assert in_types == {R.F32, R.F16}, in_types
+    assert len(re.findall(r"rnnt_dlogits_compact8_kernel<NIT, TI>\)", src)) == 1
+    assert not re.search(r"rnnt_dlogits_compact8_kernel<NIT, (?!TI>)", src)
+    c8_types = in_types
+    compact = {(cs, t) for cs in re.findall(r"rnnt_dlogits_compact_kernel<(true|false), TI, CQ>", src) for t in in_types}
+    assert not re.search(r"rnnt_dlogits_compact_kernel<(true|false), (?!TI,)", src)
     fused = set(re.findall(r"rnnt_dlogits_fused_kernel<(\w+), CQ>", src))
     merge = set(re.findall(r"rnnt_lse_merge_gather_kernel<(true|false)>", src))
     assert "rnnt_lse_gather_kernel<CQ>" in src
@@ -105,9 +117,18 @@ def test_selection_constants_match_the_source():
     assert re.search(r"\(extent\) <= 64 \* 4 \* 20\) \{ constexpr int CQ = 20; CALL; \} else \{ constexpr int CQ = 32;", src)
     assert re.search(r"constexpr int CQ_MAX = 32, V_MAX = 64 \* 4 \* CQ_MAX;", src)
     assert len(re.findall(r"if \(ld_out <= 512 \* 10\) PIKA_C8\(10\); else if \(ld_out <= 512 \* 13\) PIKA_C8\(13\); "
-                          r"else PIKA_C8\(16\);", src)) == 2
-    assert re.search(r"!wide_off && !\(V & 7\) && !\(ld_out & 7\) && V > 512 \* 9 &&", src)
-    assert re.search(r"!\(ld_out & 7\) && !\(ld_in & 7\) && ld_in >= \(\(V \+ 7\) & ~7\) && V > 512 \* 9 &&", src)
+                          r"else PIKA_C8\(16\);", src)) == 1
+    assert len(re.findall(r"PIKA_C8\(\d+\)", src)) == 3 and src.count("#define PIKA_C8(NIT)") == 1
+    # the two eligibility predicates of the 8-column kernel, each the whole condition of its input type
+    assert re.search(r"bool compact8_ok_f32\(int V, long long ld_out, const void \*out\) \{\s*"
+                     r"return !\(V & 7\) && !\(ld_out & 7\) && V > 512 \* 9 && !\(reinterpret_cast<uintptr_t>\(out\) & 15\);", src)
+    assert re.search(r"bool compact8_ok_f16\(int V, long long ld_out, long long ld_in, const void \*out, const void \*logits16\) \{\s*"
+                     r"return !\(ld_out & 7\) && !\(ld_in & 7\) && ld_in >= \(\(V \+ 7\) & ~7\) && V > 512 \* 9 &&\s*"
+                     r"!\(reinterpret_cast<uintptr_t>\(out\) & 15\) && !\(reinterpret_cast<uintptr_t>\(logits16\) & 15\);", src)
+    assert re.search(r"launch_dlogits_compact<float>\(log_probs, 0, compact8_ok_f32\(V, ld_out, out\),", src)
+    assert re.search(r"launch_dlogits_compact<_Float16>\(static_cast<const _Float16 \*>\(logits16\), ld_in,\s*"
+                     r"compact8_ok_f16\(V, ld_out, ld_in, out, logits16\),", src)
+    assert re.search(r"if \(wide && !wide_off\) \{", src)
     assert re.search(r"const long long r = rows / \(4 \* 2 \* 256\);\s*return \(int\)\(r < 4 \? 4 : \(r > 64 \? 64 : r\)\);", src)
     assert re.search(r"if \(nw \* 64 >= U1\) return nw \* 64;", src)
 
