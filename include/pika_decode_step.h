@@ -133,6 +133,11 @@ typedef struct {
     const int *stop;
     pika_dstep_joint_t joint;
 } pika_dstep_prep_t;
+/* PIKA_EINVAL, before any launch: a NULL pointer among prev_k / y / hyp_len / step_t / t_idx / state / anc / emb / node / pos /
+ * rowmap / count or X[l] / A[l] of a layer in use; rows, beam, H <= 0; layers outside 1..PIKA_DSTEP_MAX_LAYERS; L <= 4 (four
+ * taps + the new position); H % 4 != 0 (state rows are moved four floats at a time); C[l] <= 0 or lda[l] < 5*C[l]; and with
+ * the joint on (pj[0] != NULL): pj[1], h or e_all NULL, T <= 0, JH <= 0 or JH % 4 != 0 (rowmap32 may be NULL).
+ * pika_dstep_prep_lstm checks its joint the same way. */
 int pika_dstep_prep(const pika_dstep_prep_t *p, void *stream);
 
 /* Self-attention of the new position of every row over its cached prefix (arithmetic of
@@ -199,9 +204,9 @@ int pika_dfc2_logits(const float *h, long long ldh, const void *W, const float *
  * `first` is read from the device (*step_t == 0); the step counter is incremented by the call;
  * done[b] (u8) = eos_top[b] && fin_n[b] >= n_best; *stop = all utterances done; *max_hyp = max hyp_len.
  * sync (int32[8], zeroed once by the caller): [0..3] scratch for the cross-workgroup arrival counts of even / odd
- * steps; [4] is set once a call was skipped because *stop was already set (the gate of the FST advance that follows);
- * [5], [6] are the compact-row counters of pika_dstep_prep (count = sync + 5): the call zeroes the one the next step
- * will fill.  LDS: pika_beam_advance_logits_lds(K, L, splits) bytes (0: the shape is not taken -> PIKA_ETOOBIG). */
+ * steps; [4] is set once a call was skipped because *stop was already set (the gate of the FST advance that follows; the
+ * only thing a skipped call writes); [5], [6] are the compact-row counters of pika_dstep_prep (count = sync + 5): the call
+ * zeroes the one the next step will fill, and the call that sets *stop zeroes both (later replays run on zero rows).  LDS: pika_beam_advance_logits_lds(K, L, splits) bytes (0: the shape is not taken -> PIKA_ETOOBIG). */
 size_t pika_beam_advance_logits_lds(int K, int L, int splits);
 int pika_beam_advance_logits(const float *pmax, const float *psum, const float *logits, long long ldl, int splits,
                              float *scores, const float *lm_scores, float lm_scale, long long *y,

@@ -478,10 +478,9 @@ __global__ __launch_bounds__(1024) void beam_partials_kernel(const float *__rest
     if (*stop) {                                      // a replay after the search has ended: nothing happens, and the
         if (blockIdx.x == 0 && threadIdx.x == 0) {    // FST advance of this (skipped) step must not run either
             sync[4] = 1;
-            // both compact-row counters: the prediction-network launches of the remaining replays then run on ZERO rows
-            // (the LSTM cell kernel updates its state in place -- a stale count would advance the final states again)
-            sync[5] = 0;
-            sync[6] = 0;
+            // (nothing else is touched, include/pika_decode_step.h.  Both compact-row counters already read zero: the call
+            // that set *stop zeroed them below, and every prep since has been skipped -- the prediction-network launches of
+            // the remaining replays run on ZERO rows)
         }
         return;
     }

@@ -1267,9 +1267,22 @@ int pika_dgemm(const pika_dgemm_t *q, void *stream) {
     return check(hipGetLastError());
 }
 
+// joint_carry moves f32x4 groups of pj / e_all / h and looks a frame up in e_all: all buffers, JH % 4 == 0, T > 0
+static bool joint_ok(const pika_dstep_joint_t &j) {
+    if (!j.pj[0]) return true;      // off
+    return j.pj[1] && j.h && j.e_all && j.T > 0 && j.JH > 0 && !(j.JH & 3);
+}
+
 int pika_dstep_prep(const pika_dstep_prep_t *q, void *stream) {
-    if (!q || q->rows <= 0 || q->layers < 1 || q->layers > PIKA_DSTEP_MAX_LAYERS || q->beam <= 0 || q->H <= 0 || q->L <= 4)
+    if (!q || q->rows <= 0 || q->layers < 1 || q->layers > PIKA_DSTEP_MAX_LAYERS || q->beam <= 0 || q->H <= 0 || q->L <= 4 ||
+        (q->H & 3))                 // (the vector copy of the state rows r > 0)
         return PIKA_EINVAL;
+    if (!q->prev_k || !q->y || !q->hyp_len || !q->step_t || !q->t_idx || !q->state[0] || !q->state[1] || !q->anc[0] ||
+        !q->anc[1] || !q->emb || !q->node || !q->pos || !q->rowmap || !q->count)
+        return PIKA_EINVAL;
+    for (int l = 0; l < q->layers; ++l)
+        if (!q->X[l] || !q->A[l] || q->C[l] <= 0 || q->lda[l] < 5LL * q->C[l]) return PIKA_EINVAL;
+    if (!joint_ok(q->joint)) return PIKA_EINVAL;
     PrepDev a{*q};
     hipLaunchKernelGGL(dstep_prep_kernel, dim3(q->rows), dim3(256), 0, (hipStream_t)stream, a);
     return check(hipGetLastError());
@@ -1284,6 +1297,7 @@ int pika_dstep_prep_lstm(const pika_dstep_prep_lstm_t *q, void *stream) {
         return PIKA_EINVAL;
     for (int l = 0; l < q->layers; ++l)
         if (!q->A[l] || q->lda[l] < (l == 0 ? q->E + q->H : 2 * q->H)) return PIKA_EINVAL;
+    if (!joint_ok(q->joint)) return PIKA_EINVAL;
     hipLaunchKernelGGL(dstep_prep_lstm_kernel, dim3(q->rows), dim3(256), 0, (hipStream_t)stream, *q);
     return check(hipGetLastError());
 }
