@@ -846,21 +846,34 @@ __global__ __launch_bounds__(64) void fst_advance_kernel(FstDev F, const long lo
     if (overflow) atomicOr(err, 1);
 }
 
+// What the two advance entry points check of the state arguments they share
+bool beam_state_ok(const BeamState &a) {        // false: PIKA_EINVAL (y_raw may be NULL)
+    return a.scores && a.lm_scores && a.y && a.t_idx && a.num_frames && a.max_len && a.hyp && a.hyp_len && a.ks_hist &&
+           a.ys_hist && a.step_t && a.eos_top && a.fin_score && a.fin_step && a.fin_k && a.fin_n && a.prev_k_out &&
+           a.B > 0 && a.K > 0 && a.V > 0 && a.L > 0 && a.fin_cap >= 3;
+}
+
+// LDS of beam_partials_kernel (its fit is the caller's test) and its waves: a wave per beam row (at most 16), fewer when
+// their candidate pools would not fit the LDS budget
+size_t advance_lds(int K, int L, int *waves) {
+    auto lds_for = [&](int w) { return (size_t)K * L * 4 + (size_t)K * K * sizeof(Cand) + (size_t)w * POOL_CAP * sizeof(Cand); };
+    int w = K < 16 ? K : 16;
+    while (w > 4 && lds_for(w) > 96 * 1024) w >>= 1;
+    *waves = w < 4 ? 4 : w;
+    return lds_for(*waves);
+}
+
 }  // namespace
 
-extern "C" int pika_beam_advance(const float *logits, float sm_scale, int first, float *scores,
-                                 const float *lm_scores, float lm_scale, long long *y,
-                                 long long *t_idx, const long long *num_frames,
-                                 const long long *max_len, long long *hyp, long long *hyp_len, int L,
-                                 long long *ks_hist, long long *ys_hist, const long long *step_t,
-                                 unsigned char *eos_top, float *fin_score, long long *fin_step,
-                                 long long *fin_k, long long *fin_n, int fin_cap,
-                                 long long *prev_k_out, long long *y_raw, void *cand_ws, int B, int K,
-                                 int V, int blk, int beam_prune, void *stream) {
-    if (!logits || !scores || !lm_scores || !y || !t_idx || !num_frames || !max_len || !hyp ||
-        !hyp_len || !ks_hist || !ys_hist || !step_t || !eos_top || !fin_score || !fin_step ||
-        !fin_k || !fin_n || !prev_k_out || B <= 0 || K <= 0 || V <= 0 || L <= 0 || fin_cap < 3)
-        return PIKA_EINVAL;
+extern "C" int pika_beam_advance(const float *logits, float sm_scale, int first, float *scores, const float *lm_scores,
+                                 float lm_scale, long long *y, long long *t_idx, const long long *num_frames,
+                                 const long long *max_len, long long *hyp, long long *hyp_len, int L, long long *ks_hist,
+                                 long long *ys_hist, const long long *step_t, unsigned char *eos_top, float *fin_score,
+                                 long long *fin_step, long long *fin_k, long long *fin_n, int fin_cap, long long *prev_k_out,
+                                 long long *y_raw, void *cand_ws, int B, int K, int V, int blk, int beam_prune, void *stream) {
+    const BeamState a{scores, lm_scores, lm_scale, y, t_idx, num_frames, max_len, hyp, hyp_len, L, ks_hist, ys_hist, step_t,
+                      eos_top, fin_score, fin_step, fin_k, fin_n, fin_cap, prev_k_out, y_raw, B, K, V, blk};
+    if (!logits || !beam_state_ok(a)) return PIKA_EINVAL;
     if (K > MAXK || V > MAXV || V < K || (size_t)K * L * 4 > 64 * 1024) return PIKA_ETOOBIG;
     if (!cand_ws) return PIKA_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -878,10 +891,7 @@ extern "C" int pika_beam_advance(const float *logits, float sm_scale, int first,
     hipLaunchKernelGGL(beam_row_topk_kernel, dim3((B * K + WAVES - 1) / WAVES), dim3(WAVES * 64),
                        (size_t)WAVES * ((V + 3) & ~3) * 4, st, logits, sm_scale, first, scores, lm_scores, lm_scale,
                        y, hyp, hyp_len, L, B, K, V, beam_prune, cand);
-    BeamState a{scores, lm_scores, lm_scale, y, t_idx, num_frames, max_len, hyp, hyp_len, L, ks_hist, ys_hist, step_t,
-                eos_top, fin_score, fin_step, fin_k, fin_n, fin_cap, prev_k_out, y_raw, B, K, V, blk};
-    hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256),
-                       (size_t)K * L * 4 + (size_t)K * K * sizeof(Cand), st, cand, a);
+    hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256), (size_t)K * L * 4 + (size_t)K * K * sizeof(Cand), st, cand, a);
     return (int)hipGetLastError();
 }
 
@@ -889,34 +899,25 @@ extern "C" int pika_beam_advance(const float *logits, float sm_scale, int first,
 // asks the library instead of restating its arithmetic.  Returns the bytes, or 0 when the shape is not taken.
 extern "C" size_t pika_beam_advance_logits_lds(int K, int L, int splits) {
     if (K <= 0 || L <= 0 || splits < 1 || K > MAXK || splits > 64) return 0;
-    int waves = K < 16 ? K : 16;
-    auto lds_for = [&](int w) { return (size_t)K * L * 4 + (size_t)K * K * sizeof(Cand) + (size_t)w * POOL_CAP * sizeof(Cand); };
-    while (waves > 4 && lds_for(waves) > 96 * 1024) waves >>= 1;
-    if (waves < 4) waves = 4;
-    return lds_for(waves) > 96 * 1024 ? 0 : lds_for(waves);
+    int waves;
+    const size_t lds_bytes = advance_lds(K, L, &waves);
+    return lds_bytes > 96 * 1024 ? 0 : lds_bytes;
 }
 
-extern "C" int pika_beam_advance_logits(const float *pmax, const float *psum, const float *logits, long long ldl,
-                                        int splits,
-                                        float *scores, const float *lm_scores, float lm_scale, long long *y,
-                                        long long *t_idx, const long long *num_frames, const long long *max_len,
-                                        long long *hyp, long long *hyp_len, int L, long long *ks_hist,
-                                        long long *ys_hist, long long *step_t, unsigned char *eos_top,
-                                        float *fin_score, long long *fin_step, long long *fin_k, long long *fin_n,
-                                        int fin_cap, long long *prev_k_out, long long *y_raw, int B, int K, int V,
-                                        int blk, int beam_prune, int n_best, int *stop, long long *max_hyp,
-                                        int *sync, void *stream) {
+extern "C" int pika_beam_advance_logits(const float *pmax, const float *psum, const float *logits, long long ldl, int splits,
+                                        float *scores, const float *lm_scores, float lm_scale, long long *y, long long *t_idx,
+                                        const long long *num_frames, const long long *max_len, long long *hyp,
+                                        long long *hyp_len, int L, long long *ks_hist, long long *ys_hist, long long *step_t,
+                                        unsigned char *eos_top, float *fin_score, long long *fin_step, long long *fin_k,
+                                        long long *fin_n, int fin_cap, long long *prev_k_out, long long *y_raw, int B, int K,
+                                        int V, int blk, int beam_prune, int n_best, int *stop, long long *max_hyp, int *sync,
+                                        void *stream) {
     if (!logits || ldl < V) return PIKA_EINVAL;
-    if (!pmax || !psum || !scores || !lm_scores || !y || !t_idx || !num_frames || !max_len || !hyp ||
-        !hyp_len || !ks_hist || !ys_hist || !step_t || !eos_top || !fin_score || !fin_step || !fin_k || !fin_n ||
-        !prev_k_out || !stop || !max_hyp || !sync || B <= 0 || K <= 0 || V <= 0 || L <= 0 || fin_cap < 3 || splits < 1)
-        return PIKA_EINVAL;
-    // a wave per beam row (at most 16), fewer when their candidate pools would not fit the LDS budget
-    int waves = K < 16 ? K : 16;
-    auto lds_for = [&](int w) { return (size_t)K * L * 4 + (size_t)K * K * sizeof(Cand) + (size_t)w * POOL_CAP * sizeof(Cand); };
-    while (waves > 4 && lds_for(waves) > 96 * 1024) waves >>= 1;
-    if (waves < 4) waves = 4;
-    const size_t lds_bytes = lds_for(waves);
+    const BeamState a{scores, lm_scores, lm_scale, y, t_idx, num_frames, max_len, hyp, hyp_len, L, ks_hist, ys_hist, step_t,
+                      eos_top, fin_score, fin_step, fin_k, fin_n, fin_cap, prev_k_out, y_raw, B, K, V, blk};
+    if (!pmax || !psum || !stop || !max_hyp || !sync || splits < 1 || !beam_state_ok(a)) return PIKA_EINVAL;
+    int waves;
+    const size_t lds_bytes = advance_lds(K, L, &waves);
     if (K > MAXK || splits > 64 || lds_bytes > 96 * 1024) return PIKA_ETOOBIG;
     static bool attr_set = false;
     if (!attr_set) {
@@ -925,8 +926,6 @@ extern "C" int pika_beam_advance_logits(const float *pmax, const float *psum, co
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
-    BeamState a{scores, lm_scores, lm_scale, y, t_idx, num_frames, max_len, hyp, hyp_len, L, ks_hist, ys_hist, step_t,
-                eos_top, fin_score, fin_step, fin_k, fin_n, fin_cap, prev_k_out, y_raw, B, K, V, blk};
     hipLaunchKernelGGL(beam_partials_kernel, dim3(B), dim3(64 * waves), lds_bytes, static_cast<hipStream_t>(stream), pmax, psum,
                        splits, a, beam_prune, n_best, stop, max_hyp, sync, step_t, logits, ldl);
     return (int)hipGetLastError();

@@ -11,6 +11,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <type_traits>
+#include <utility>
 
 #include "pika_decode_step.h"
 #include "pika_rnnt.h"  // PIKA_EINVAL
@@ -21,7 +22,6 @@ namespace {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
@@ -33,6 +33,23 @@ constexpr int TERMS_F16X2 = 4;
 constexpr float LO_SCALE = 2048.f, LO_UNSCALE = 1.f / 2048.f;
 __host__ __device__ constexpr int planes_of(int terms) { return terms == TERMS_F16X2 ? 2 : terms; }
 
+int check(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
+inline bool aligned16(const void *a) { return !(reinterpret_cast<uintptr_t>(a) & 15); }
+constexpr int tiles16(int n) { return (n + 15) / 16; }      // packed column tiles
+constexpr int tiles32(int k) { return (k + 31) / 32; }      // packed k-tiles
+// columns of an A row that are read: K when K % 4 == 0, else ceil32(K) (the caller zero-pads, as the header says)
+constexpr int k_valid(int K) { return (K & 3) ? tiles32(K) * 32 : K; }
+
+// The instantiated term counts; dispatch_terms calls f(std::integral_constant<int, NS>{}) for NS == terms (checked before).
+using Terms = std::integer_sequence<int, 1, 2, 3, 4>;
+template <class F, int... NS>
+inline void dispatch_terms(int terms, F f, std::integer_sequence<int, NS...>) {
+    (void)((terms == NS && (f(std::integral_constant<int, NS>{}), true)) || ...);
+}
+template <class F>
+inline void dispatch_terms(int terms, F f) { dispatch_terms(terms, f, Terms{}); }
+template <class F>      // a run-time switch as a template argument
+inline void dispatch_bool(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
 
 // ---- weight packing: packed[term][n_tile][k_tile][lane][8], n_tile = 16 columns, k_tile = 32 ----------------
 __global__ void dpack_kernel(const float *__restrict__ W, long long ldw, int N, int K, int NT, int KT, int terms,
@@ -287,7 +304,7 @@ struct DG {   // device copy of pika_dgemm_t
     const float *e_all; const long long *t_idx; int T, beam, M, N, NT, KT, flags;
     const int *m_dev; const long long *crow;
     const int *rowlist; const int *rowoff_dev;
-    int Kvalid;   // K when K % 4 == 0 (columns beyond are never read), else ceil32(K) (the caller zero-pads, as the header says)
+    int Kvalid;   // k_valid(K)
     const float *ln_g, *ln_b; float ln_eps;     // LayerNorm of the A rows on the way in (dgemm_sk_kernel only)
 };
 
@@ -296,17 +313,7 @@ struct DG {   // device copy of pika_dgemm_t
 // XCD's L2 instead of each pulling it from the Infinity Cache at the per-CU fetch rate (a quarter of the L2 rate),
 // and an XCD works on ONE slab at a time (its 4 MiB L2 holds a slab, not all the slabs of its column groups).
 // false = idle workgroup.
-__device__ inline bool xcd_tile(int n_groups, int m_tiles, int &mg, int &ng) {
-    const int g = blockIdx.x, xcd = g & 7, i = g >> 3;
-    ng = xcd + 8 * (i / m_tiles);
-    mg = i % m_tiles;
-    return ng < n_groups;
-}
-
-// The other way round, for many rows (M = B*beam): an XCD owns a band of row tiles -- their A rows (a few hundred
-// KB) stay in its L2 -- and walks the column groups with the band's row tiles dispatched back to back, so a slab of
-// W is fetched from beyond L2 once per XCD (8x in total) instead of once per row tile.
-// ... and for a product whose WEIGHTS are the large operand (the vocabulary product of a search step: 20 MB of two-term W
+// This map is for a product whose WEIGHTS are the large operand (the vocabulary product of a search step: 20 MB of two-term W
 // against 4 MB of rows at B * beam = 1024, 128 KB at 32): an XCD owns the column groups x, x + 8, .. and takes every row tile
 // of them, the row tiles of a group dispatched back to back -- a slab of W is fetched from beyond L2 by ONE XCD (1x in
 // total; the rows 8x), and at one row tile the launch's workgroups spread over all eight XCDs instead of sitting on one.
@@ -318,6 +325,9 @@ __device__ inline bool xcd_tile_cols(int n_groups, int m_tiles, int &mg, int &ng
     return ng < n_groups;
 }
 
+// The other way round, for many rows (M = B*beam): an XCD owns a band of row tiles -- their A rows (a few hundred
+// KB) stay in its L2 -- and walks the column groups with the band's row tiles dispatched back to back, so a slab of
+// W is fetched from beyond L2 once per XCD (8x in total) instead of once per row tile.
 __device__ inline bool xcd_tile_rows(int n_groups, int m_tiles, int &mg, int &ng) {
     const int g = blockIdx.x, xcd = g & 7, i = g >> 3;
     const int band = (m_tiles + 7) >> 3;
@@ -887,7 +897,6 @@ __global__ __launch_bounds__(256) void dstep_prep_kernel(PrepDev a) {
     }
 }
 
-
 // ---- LSTM prediction network (trainer/model/transducer.py:55-61; decoder/transducer_decoder.py:139-148) --------
 // A row's state is [h_0 | c_0 | h_1 | c_1 | ...] (SP = layers * 2 * H floats), double-buffered like the transformer
 // state.  Every row follows its parent; rows that emitted a label get a slot in the compact row list and the input
@@ -1048,15 +1057,6 @@ static_assert(FC2_COLS == PIKA_DFC2_COLS, "pika_decode_step.h");
 // floats per slab row: 4 more than the columns, so that 16 rows read at the same column sit in 16 different LDS banks
 // (the row statistics of the logits mode: four lanes per row, all rows of a wave at once)
 constexpr int FC2_PITCH = FC2_COLS + 4;
-struct Cand { float v; int idx; };
-
-__device__ inline bool better(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
-
-// order-preserving map float -> unsigned (a > b <=> fkey(a) > fkey(b); -inf is the smallest non-NaN key)
-__device__ inline unsigned fkey(float f) {
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 template <int NS, int BM>
 __host__ __device__ constexpr size_t FC2_LDS_MAIN() {      // operand staging buffers, overlaid by the logits slab
@@ -1143,21 +1143,82 @@ __global__ __launch_bounds__(256, (FC2_BM == 32 && NS != 3) ? 3 : 2) void dfc2_l
     }
 }
 
-int check(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
+bool dgemm_args_ok(const pika_dgemm_t *q) {
+    if (!q || !q->A || !q->W || !q->C || q->M <= 0 || q->N <= 0 || q->K <= 0 || q->terms < 1 || q->terms > 4) return false;
+    if ((q->lda & 3) || !aligned16(q->A)) return false;
+    const bool gate = q->flags & PIKA_DG_GATE;
+    if (gate && (!q->e_all || !q->t_idx || q->T <= 0 || q->beam <= 0 || (q->N & 3))) return false;
+    if (((q->flags & PIKA_DG_ROWMASK) || (q->C2 && !gate)) && !q->node) return false;
+    if (gate && q->C2 && ((q->ldc2 & 3) || !aligned16(q->C2))) return false;
+    return !q->ln_gamma || (q->ln_beta && !(q->K & 31) && q->K <= 1024 && aligned16(q->ln_gamma) && aligned16(q->ln_beta));
+}
+
+DG make_dg(const pika_dgemm_t *q) {
+    DG p{};
+    p.A = q->A; p.lda = q->lda; p.W = reinterpret_cast<const __bf16 *>(q->W); p.bias = q->bias; p.res = q->res; p.ldr = q->ldr;
+    p.C = q->C; p.ldc = q->ldc; p.C2 = q->C2; p.ldc2 = q->ldc2; p.node = q->node; p.skip_node = q->skip_node;
+    p.e_all = q->e_all; p.t_idx = q->t_idx; p.T = q->T; p.beam = q->beam; p.M = q->M; p.N = q->N; p.flags = q->flags;
+    p.m_dev = q->m_dev; p.crow = q->crow; p.rowlist = q->rowlist; p.rowoff_dev = q->rowoff_dev;
+    p.ln_g = q->ln_gamma; p.ln_b = q->ln_beta; p.ln_eps = q->ln_eps;
+    p.NT = tiles16(q->N); p.KT = tiles32(q->K); p.Kvalid = k_valid(q->K);
+    return p;
+}
+
+// Which kernel a product runs on, and its grid (kw, wn, pipe: SK only).  sk_env: PIKA_DGEMM_SK (-1: unset), wide_on:
+// PIKA_DGEMM_WIDE -- both read once by pika_dgemm.
+struct Route { enum Kind { SK, WIDE, TILED32, TILED64 } kind; unsigned grid; int kw, wn; bool pipe; };
+Route dgemm_route(int M, int N, int KT, int flags, bool ln, int sk_env, bool wide_on) {
+    const int NT = tiles16(N), n_groups = (NT + 3) / 4;
+    // Few rows (the caller says so for a compact row list whose count lives on the device: PIKA_DG_FEW_ROWS; or M itself
+    // is small): the split-reduction kernel, one 16/32-column tile of 32 rows per workgroup.  PIKA_DGEMM_SK=0 / 1 forces the
+    // choice (A/B runs).
+    const bool sk = ln || (sk_env >= 0 ? sk_env != 0 : ((flags & PIKA_DG_FEW_ROWS) || M <= 256));
+    // 4 waves per workgroup take K <= 512 in ONE request round, 8 waves K <= 1024; beyond (K up to 4096) 8 waves in
+    // rounds of 4 k-tiles.  Wide products (N >= 1024) take 32-column tiles: all tiles of a ~170-row launch resident at once.
+    if (sk && KT <= 128) {       // (ln always fits: dgemm_args_ok took K <= 1024, KT <= 32)
+        const int kw = KT <= 16 ? 4 : 8, wn = N >= 1024 ? 2 : 1;
+        const long long tiles = (long long)((M + 31) / 32) * ((NT + wn - 1) / wn);
+        // workgroups resident at once per XCD (32 CUs): 2 per CU of 256 threads, 1 of 512
+        const long long cap8 = kw == 4 ? 64 : 32;
+        return {Route::SK, (unsigned)(8 * (tiles / 8 + 1 < cap8 ? tiles / 8 + 1 : cap8)), kw, wn, KT > 4 * kw};
+    }
+    // wide products (N >= 2048) beyond the few-rows kernel: 64 x 128 tiles (PIKA_DGEMM_WIDE=0: the 64 x 64 tiles, A/B runs)
+    if (N >= 2048 && wide_on && !(flags & PIKA_DG_GATE))
+        return {Route::WIDE, (unsigned)(8 * ((((NT + 7) / 8) + 7) / 8) * ((M + 63) / 64)), 0, 0, false};
+    // enough workgroups to cover the chip: 32-row tiles unless 64-row tiles already give > 256 of them
+    const bool big = (long long)((M + 63) / 64) * n_groups >= 512;
+    const int BM = big ? 64 : 32;
+    return {big ? Route::TILED64 : Route::TILED32, (unsigned)((((M + BM - 1) / BM + 7) / 8) * 8 * n_groups), 0, 0, false};
+}
 
 template <int BM, int NS>
 void launch_dgemm(unsigned grid, hipStream_t st, const DG &p) {
-    constexpr size_t lds = DgCfg<BM, NS>::core_t::LDS_BYTES;
-    dgemm_kernel<BM, NS><<<dim3(grid), dim3(256), lds, st>>>(p);
+    dgemm_kernel<BM, NS><<<dim3(grid), dim3(256), DgCfg<BM, NS>::core_t::LDS_BYTES, st>>>(p);
+}
+template <int NS>
+void launch_wide(unsigned grid, hipStream_t st, const DG &p) {
+    dgemm_wide_kernel<NS><<<dim3(grid), dim3(256), Core<64, 2, NS, 2>::LDS_BYTES, st>>>(p);
 }
 
+// One request round of KW waves x 4 k-tiles each, or -- pipe: KT > 4 KW, which only 8 waves meet (4 waves run KT <= 16) --
+// rounds of 2.  The pipelined form is instantiated without LN: ln implies KT <= 32, one round of 8 waves.
+template <int NS, int KW, int WN, bool LN>
+void launch_sk(const Route &r, hipStream_t st, const DG &p) {
+    const dim3 grid(r.grid), block(64 * KW);
+    if constexpr (KW == 8)
+        if (r.pipe) return dgemm_sk_kernel<NS, 8, 2, WN, 2, false, true><<<grid, block, 0, st>>>(p);
+    dgemm_sk_kernel<NS, KW, 2, WN, 4, LN, false><<<grid, block, 0, st>>>(p);
+}
+
+// The arguments of dfc2_logits_kernel, in its order, up to the launcher's own (Kvalid = k_valid(K); by_cols last).
+struct Fc2 { const float *h; long long ldh; const __bf16 *W; const float *bias; int rows, V, NT, KT; float sm_scale;
+             int splits; float *pmax, *psum; int Kvalid; float *logits; long long ldl; };
+
 template <int NS, int BM>
-void launch_fc2_bm(unsigned grid, hipStream_t st, const float *h, long long ldh, const __bf16 *w, const float *bias, int rows,
-                   int V, int NT, int KT, float sm_scale, int splits, float *pmax, float *psum, int K, float *logits,
-                   long long ldl, int by_cols) {
+void launch_fc2_bm(unsigned grid, hipStream_t st, const Fc2 &a, int by_cols) {
     constexpr size_t lds = FC2_LDS_MAIN<NS, BM>() + FC2_COLS * 4;
-    dfc2_logits_kernel<NS, BM><<<dim3(grid), dim3(256), lds, st>>>(h, ldh, w, bias, rows, V, NT, KT, sm_scale, splits, pmax, psum,
-                                                                   (K & 3) ? KT * 32 : K, logits, ldl, by_cols);
+    dfc2_logits_kernel<NS, BM><<<dim3(grid), dim3(256), lds, st>>>(a.h, a.ldh, a.W, a.bias, a.rows, a.V, a.NT, a.KT, a.sm_scale,
+                                                                   a.splits, a.pmax, a.psum, a.Kvalid, a.logits, a.ldl, by_cols);
 }
 
 int fc2_bm(int rows) {
@@ -1169,31 +1230,40 @@ int fc2_bm(int rows) {
 }
 
 template <int NS>
-void launch_fc2(hipStream_t st, const float *h, long long ldh, const __bf16 *w, const float *bias, int rows,
-                int V, int NT, int KT, float sm_scale, int splits, float *pmax, float *psum, int K, float *logits, long long ldl) {
-    const int bm = fc2_bm(rows);
-    const int m_tiles = (rows + bm - 1) / bm;
+void launch_fc2(hipStream_t st, const Fc2 &a) {
+    const int bm = fc2_bm(a.rows);
+    const int m_tiles = (a.rows + bm - 1) / bm;
     // up to 512 rows: W slabs pinned to XCDs (xcd_tile_cols: 28.6 vs 33.0 us at 32 rows, 29.0 vs 34.3 at 128, 39.7 vs 42.3 at
     // 512; 48.7 vs 46.8 at 1024 -- tools/dfc2_bench.py); beyond: row bands per XCD.  PIKA_DFC2_MAP=rows / cols in a tuning build
     static const int forced_map = [] { const char *e = pika_knob("PIKA_DFC2_MAP"); return !e ? -1 : (e[0] == 'r' ? 0 : 1); }();
-    const int by_cols = forced_map >= 0 ? forced_map : (rows <= 512 ? 1 : 0);
-    const unsigned grid = by_cols ? (unsigned)(8 * ((splits + 7) / 8) * m_tiles) : (unsigned)(((m_tiles + 7) / 8) * 8 * splits);
-    if (bm == 64) launch_fc2_bm<NS, 64>(grid, st, h, ldh, w, bias, rows, V, NT, KT, sm_scale, splits, pmax, psum, K, logits, ldl, by_cols);
-    else launch_fc2_bm<NS, 32>(grid, st, h, ldh, w, bias, rows, V, NT, KT, sm_scale, splits, pmax, psum, K, logits, ldl, by_cols);
+    const int by_cols = forced_map >= 0 ? forced_map : (a.rows <= 512 ? 1 : 0);
+    const unsigned grid = by_cols ? (unsigned)(8 * ((a.splits + 7) / 8) * m_tiles) : (unsigned)(((m_tiles + 7) / 8) * 8 * a.splits);
+    if (bm == 64) launch_fc2_bm<NS, 64>(grid, st, a, by_cols);
+    else launch_fc2_bm<NS, 32>(grid, st, a, by_cols);
+}
+
+// joint_carry moves f32x4 groups of pj / e_all / h and looks a frame up in e_all: all buffers, JH % 4 == 0, T > 0
+bool joint_ok(const pika_dstep_joint_t &j) {       // pj[0] == NULL: off
+    return !j.pj[0] || (j.pj[1] && j.h && j.e_all && j.T > 0 && j.JH > 0 && !(j.JH & 3));
+}
+
+// What both prep entry points check (H % 4: the vector copy of the state rows r > 0), ahead of their per-layer loops
+template <class P>
+bool prep_common_ok(const P *q) {
+    return q && q->rows > 0 && q->layers >= 1 && q->layers <= PIKA_DSTEP_MAX_LAYERS && q->beam > 0 && q->H > 0 && !(q->H & 3) &&
+           q->prev_k && q->y && q->step_t && q->t_idx && q->state[0] && q->state[1] && q->emb && q->rowmap && q->count &&
+           joint_ok(q->joint);
 }
 
 }  // namespace
 
 extern "C" {
 
-size_t pika_dpack_bytes(int N, int K, int terms) {
-    return (size_t)planes_of(terms) * ((N + 15) / 16 * 16) * ((K + 31) / 32 * 32) * 2;
-}
+size_t pika_dpack_bytes(int N, int K, int terms) { return (size_t)planes_of(terms) * (tiles16(N) * 16) * (tiles32(K) * 32) * 2; }
 
-int pika_dpack_weight(const float *W, long long ldw, int N, int K, int terms, int interleave2, void *packed,
-                      void *stream) {
+int pika_dpack_weight(const float *W, long long ldw, int N, int K, int terms, int interleave2, void *packed, void *stream) {
     if (!W || !packed || N <= 0 || K <= 0 || terms < 1 || terms > 4 || (interleave2 && (N & 1))) return PIKA_EINVAL;
-    const int NT = (N + 15) / 16, KT = (K + 31) / 32;
+    const int NT = tiles16(N), KT = tiles32(K);
     const long long total = (long long)NT * KT * 64;
     hipLaunchKernelGGL(dpack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W, ldw, N, K,
                        NT, KT, terms, interleave2, reinterpret_cast<__bf16 *>(packed));
@@ -1201,103 +1271,37 @@ int pika_dpack_weight(const float *W, long long ldw, int N, int K, int terms, in
 }
 
 int pika_dgemm(const pika_dgemm_t *q, void *stream) {
-    if (!q || !q->A || !q->W || !q->C || q->M <= 0 || q->N <= 0 || q->K <= 0 || q->terms < 1 || q->terms > 4)
-        return PIKA_EINVAL;
-    if ((q->lda & 3) || (reinterpret_cast<uintptr_t>(q->A) & 15)) return PIKA_EINVAL;
-    if ((q->flags & PIKA_DG_GATE) && (!q->e_all || !q->t_idx || q->T <= 0 || q->beam <= 0 || (q->N & 3))) return PIKA_EINVAL;
-    if (((q->flags & PIKA_DG_ROWMASK) || (q->C2 && !(q->flags & PIKA_DG_GATE))) && !q->node) return PIKA_EINVAL;
-    if ((q->flags & PIKA_DG_GATE) && q->C2 && ((q->ldc2 & 3) || (reinterpret_cast<uintptr_t>(q->C2) & 15))) return PIKA_EINVAL;
-    const bool ln = q->ln_gamma != nullptr;
-    if (ln && (!q->ln_beta || (q->K & 31) || q->K > 1024 || ((reinterpret_cast<uintptr_t>(q->ln_gamma) |
-                                                               reinterpret_cast<uintptr_t>(q->ln_beta)) & 15)))
-        return PIKA_EINVAL;
-    DG p{q->A, q->lda, reinterpret_cast<const __bf16 *>(q->W), q->bias, q->res, q->ldr, q->C, q->ldc, q->C2, q->ldc2,
-         q->node, q->skip_node, q->e_all, q->t_idx, q->T, q->beam, q->M, q->N, (q->N + 15) / 16, (q->K + 31) / 32, q->flags,
-         q->m_dev, q->crow, q->rowlist, q->rowoff_dev, (q->K & 3) ? ((q->K + 31) / 32) * 32 : q->K,
-         q->ln_gamma, q->ln_beta, q->ln_eps};
-    hipStream_t st = (hipStream_t)stream;
-    // Few rows (the caller says so for a compact row list whose count lives on the device: PIKA_DG_FEW_ROWS; or M itself
-    // is small): the split-reduction kernel, one 16/32-column tile of 32 rows per workgroup.  PIKA_DGEMM_SK=0 / 1 forces the
-    // choice (A/B runs).
+    if (!dgemm_args_ok(q)) return PIKA_EINVAL;
     static const int sk_env = [] { const char *e = pika_knob("PIKA_DGEMM_SK"); return e ? atoi(e) : -1; }();
-    const bool sk = ln || (sk_env >= 0 ? sk_env != 0 : ((q->flags & PIKA_DG_FEW_ROWS) || q->M <= 256));
-    // 4 waves per workgroup take K <= 512 in ONE request round, 8 waves K <= 1024; beyond (K up to 4096) 8 waves in
-    // rounds of 4 k-tiles.  Wide products (N >= 1024) take 32-column tiles: all tiles of a ~170-row launch resident at once.
-    const bool sk_fits = p.KT <= 128 && !(ln && p.KT > 32);
-    if (ln && !sk_fits) return PIKA_EINVAL;
-    if (sk && sk_fits) {
-        const int kw = p.KT <= 16 ? 4 : 8, wn = q->N >= 1024 ? 2 : 1;
-        const long long tiles = (long long)((q->M + 31) / 32) * ((p.NT + wn - 1) / wn);
-        // workgroups resident at once per XCD (32 CUs): 2 per CU of 256 threads, 1 of 512
-        const long long cap8 = kw == 4 ? 64 : 32;
-        const unsigned grid = (unsigned)(8 * (tiles / 8 + 1 < cap8 ? tiles / 8 + 1 : cap8));
-#define PIKA_SK(NS, KW, WN, LN) do { if (p.KT <= 4 * KW) dgemm_sk_kernel<NS, KW, 2, WN, 4, LN, false><<<dim3(grid), dim3(64 * KW), 0, st>>>(p); \
-                                     else dgemm_sk_kernel<NS, KW, 2, WN, 2, false, true><<<dim3(grid), dim3(64 * KW), 0, st>>>(p); } while (0)
-#define PIKA_SK_T(KW, WN, LN) do { if (q->terms == 1) PIKA_SK(1, KW, WN, LN); else if (q->terms == 2) PIKA_SK(2, KW, WN, LN); \
-                                   else if (q->terms == 3) PIKA_SK(3, KW, WN, LN); else PIKA_SK(4, KW, WN, LN); } while (0)
-#define PIKA_SK_W(KW, LN) do { if (wn == 2) PIKA_SK_T(KW, 2, LN); else PIKA_SK_T(KW, 1, LN); } while (0)
-        if (ln) { if (kw == 4) PIKA_SK_W(4, true); else PIKA_SK_W(8, true); }
-        else { if (kw == 4) PIKA_SK_W(4, false); else PIKA_SK_W(8, false); }
-#undef PIKA_SK_W
-#undef PIKA_SK_T
-#undef PIKA_SK
-        return check(hipGetLastError());
-    }
-    // wide products (N >= 2048) beyond the few-rows kernel: 64 x 128 tiles (PIKA_DGEMM_WIDE=0: the 64 x 64 tiles, A/B runs)
     static const bool wide_on = [] { const char *e = pika_knob("PIKA_DGEMM_WIDE"); return !e || atoi(e) != 0; }();
-    if (q->N >= 2048 && wide_on && !(q->flags & PIKA_DG_GATE)) {
-        const unsigned grid = (unsigned)(8 * ((((p.NT + 7) / 8) + 7) / 8) * ((q->M + 63) / 64));
-#define PIKA_WIDE(NS) dgemm_wide_kernel<NS><<<dim3(grid), dim3(256), Core<64, 2, NS, 2>::LDS_BYTES, st>>>(p)
-        if (q->terms == 1) PIKA_WIDE(1); else if (q->terms == 2) PIKA_WIDE(2); else if (q->terms == 3) PIKA_WIDE(3); else PIKA_WIDE(4);
-#undef PIKA_WIDE
-        return check(hipGetLastError());
-    }
-    const int n_groups = (p.NT + 3) / 4;
-    // enough workgroups to cover the chip: 32-row tiles unless 64-row tiles already give > 256 of them
-    const bool big = (long long)((q->M + 63) / 64) * n_groups >= 512;
-    const int BM = big ? 64 : 32;
-    const unsigned grid = (unsigned)((((q->M + BM - 1) / BM + 7) / 8) * 8 * n_groups);
-    if (big) {
-        if (q->terms == 1) launch_dgemm<64, 1>(grid, st, p); else if (q->terms == 2) launch_dgemm<64, 2>(grid, st, p);
-        else if (q->terms == 3) launch_dgemm<64, 3>(grid, st, p); else launch_dgemm<64, 4>(grid, st, p);
-    } else {
-        if (q->terms == 1) launch_dgemm<32, 1>(grid, st, p); else if (q->terms == 2) launch_dgemm<32, 2>(grid, st, p);
-        else if (q->terms == 3) launch_dgemm<32, 3>(grid, st, p); else launch_dgemm<32, 4>(grid, st, p);
-    }
+    const DG p = make_dg(q);
+    const bool ln = q->ln_gamma != nullptr;
+    const Route r = dgemm_route(q->M, q->N, p.KT, q->flags, ln, sk_env, wide_on);
+    hipStream_t st = (hipStream_t)stream;
+    dispatch_terms(q->terms, [&](auto ns) {
+        constexpr int NS = decltype(ns)::value;
+        if (r.kind == Route::WIDE) launch_wide<NS>(r.grid, st, p);
+        else if (r.kind == Route::TILED32) launch_dgemm<32, NS>(r.grid, st, p);
+        else if (r.kind == Route::TILED64) launch_dgemm<64, NS>(r.grid, st, p);
+        else dispatch_bool(r.kw == 8, [&](auto k8) { dispatch_bool(r.wn == 2, [&](auto w2) { dispatch_bool(ln, [&](auto l) {
+            launch_sk<NS, decltype(k8)::value ? 8 : 4, decltype(w2)::value ? 2 : 1, decltype(l)::value>(r, st, p);
+        }); }); });
+    });
     return check(hipGetLastError());
-}
-
-// joint_carry moves f32x4 groups of pj / e_all / h and looks a frame up in e_all: all buffers, JH % 4 == 0, T > 0
-static bool joint_ok(const pika_dstep_joint_t &j) {
-    if (!j.pj[0]) return true;      // off
-    return j.pj[1] && j.h && j.e_all && j.T > 0 && j.JH > 0 && !(j.JH & 3);
 }
 
 int pika_dstep_prep(const pika_dstep_prep_t *q, void *stream) {
-    if (!q || q->rows <= 0 || q->layers < 1 || q->layers > PIKA_DSTEP_MAX_LAYERS || q->beam <= 0 || q->H <= 0 || q->L <= 4 ||
-        (q->H & 3))                 // (the vector copy of the state rows r > 0)
-        return PIKA_EINVAL;
-    if (!q->prev_k || !q->y || !q->hyp_len || !q->step_t || !q->t_idx || !q->state[0] || !q->state[1] || !q->anc[0] ||
-        !q->anc[1] || !q->emb || !q->node || !q->pos || !q->rowmap || !q->count)
-        return PIKA_EINVAL;
+    if (!prep_common_ok(q) || q->L <= 4 || !q->hyp_len || !q->anc[0] || !q->anc[1] || !q->node || !q->pos) return PIKA_EINVAL;
     for (int l = 0; l < q->layers; ++l)
         if (!q->X[l] || !q->A[l] || q->C[l] <= 0 || q->lda[l] < 5LL * q->C[l]) return PIKA_EINVAL;
-    if (!joint_ok(q->joint)) return PIKA_EINVAL;
-    PrepDev a{*q};
-    hipLaunchKernelGGL(dstep_prep_kernel, dim3(q->rows), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(dstep_prep_kernel, dim3(q->rows), dim3(256), 0, (hipStream_t)stream, PrepDev{*q});
     return check(hipGetLastError());
 }
 
-
 int pika_dstep_prep_lstm(const pika_dstep_prep_lstm_t *q, void *stream) {
-    if (!q || q->rows <= 0 || q->layers < 1 || q->layers > PIKA_DSTEP_MAX_LAYERS || q->beam <= 0 || q->H <= 0 || q->E <= 0 ||
-        (q->H & 3))
-        return PIKA_EINVAL;
-    if (!q->prev_k || !q->y || !q->step_t || !q->t_idx || !q->state[0] || !q->state[1] || !q->emb || !q->rowmap || !q->count)
-        return PIKA_EINVAL;
+    if (!prep_common_ok(q) || q->E <= 0) return PIKA_EINVAL;
     for (int l = 0; l < q->layers; ++l)
         if (!q->A[l] || q->lda[l] < (l == 0 ? q->E + q->H : 2 * q->H)) return PIKA_EINVAL;
-    if (!joint_ok(q->joint)) return PIKA_EINVAL;
     hipLaunchKernelGGL(dstep_prep_lstm_kernel, dim3(q->rows), dim3(256), 0, (hipStream_t)stream, *q);
     return check(hipGetLastError());
 }
@@ -1336,16 +1340,11 @@ int pika_dfc2_cols_per_split(void) { return FC2_COLS; }
 int pika_dfc2_logits(const float *h, long long ldh, const void *W, const float *bias, int rows, int V, int K, int terms,
                      float sm_scale, float *pmax, float *psum, float *logits, long long ldl, void *stream) {
     if (!h || !W || !pmax || !psum || !logits || rows <= 0 || V <= 0 || K <= 0 || terms < 1 || terms > 4 || (ldh & 3) ||
-        (reinterpret_cast<uintptr_t>(h) & 15) || ldl < (long long)pika_dfc2_splits(V) * FC2_COLS || (ldl & 3) ||
-        (reinterpret_cast<uintptr_t>(logits) & 15))
+        !aligned16(h) || ldl < (long long)pika_dfc2_splits(V) * FC2_COLS || (ldl & 3) || !aligned16(logits))
         return PIKA_EINVAL;
-    const int NT = (V + 15) / 16, KT = (K + 31) / 32, splits = pika_dfc2_splits(V);
-    hipStream_t st = (hipStream_t)stream;
-    const __bf16 *w = reinterpret_cast<const __bf16 *>(W);
-    if (terms == 1) launch_fc2<1>(st, h, ldh, w, bias, rows, V, NT, KT, sm_scale, splits, pmax, psum, K, logits, ldl);
-    else if (terms == 2) launch_fc2<2>(st, h, ldh, w, bias, rows, V, NT, KT, sm_scale, splits, pmax, psum, K, logits, ldl);
-    else if (terms == 3) launch_fc2<3>(st, h, ldh, w, bias, rows, V, NT, KT, sm_scale, splits, pmax, psum, K, logits, ldl);
-    else launch_fc2<4>(st, h, ldh, w, bias, rows, V, NT, KT, sm_scale, splits, pmax, psum, K, logits, ldl);
+    const Fc2 a{h, ldh, reinterpret_cast<const __bf16 *>(W), bias, rows, V, tiles16(V), tiles32(K), sm_scale,
+                pika_dfc2_splits(V), pmax, psum, k_valid(K), logits, ldl};
+    dispatch_terms(terms, [&](auto ns) { launch_fc2<decltype(ns)::value>((hipStream_t)stream, a); });
     return check(hipGetLastError());
 }
 

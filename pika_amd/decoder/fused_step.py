@@ -57,7 +57,22 @@ class DPrepLSTM(ctypes.Structure):
 
 
 def _ptr(t):
-    return None if t is None else t.data_ptr()
+    return t.data_ptr() if hasattr(t, "data_ptr") else t        # a tensor; or a plain address, number or None as it is
+
+
+def dgemm_args(A, lda, W, bias, C, ldc, M, relu=False, gate=False, rowmask=False, few_rows=False, ln=None, **fields):
+    """The filled pika_dgemm_t of C = epilogue(A . W^T), W a PackedWeight; pointers are tensors, addresses or None.  few_rows: *m_dev
+    is a small part of M; ln = (gamma, beta, eps): LayerNorm of the A rows inside the launch; `fields`: other members by name."""
+    g = DGemm()
+    g.A, g.lda, g.W, g.bias, g.C, g.ldc = _ptr(A), lda, _ptr(W.buf), _ptr(bias), _ptr(C), ldc
+    g.M, g.N, g.K, g.terms = M, W.N, W.K, W.terms
+    g.flags = (DG_RELU if relu else 0) | (DG_GATE if gate else 0) | (DG_ROWMASK if rowmask else 0) | (DG_FEW_ROWS if few_rows else 0)
+    for name, v in fields.items():
+        getattr(DGemm, name)        # (AttributeError: no such member)
+        setattr(g, name, _ptr(v))
+    if ln is not None:
+        g.ln_gamma, g.ln_beta, g.ln_eps = _ptr(ln[0]), _ptr(ln[1]), float(ln[2])
+    return g
 
 
 def _stream():
@@ -212,20 +227,10 @@ class FusedSearch(object):
         self._init_sos()
 
     # ---- launches ------------------------------------------------------------------------------------------
-    def _gemm(self, A, lda, W, bias, C, ldc, M, relu=False, res=None, ldr=0, C2=None, ldc2=0, rowmask=False, gate=False,
-              m_dev=None, crow=None, ln=None, rowlist=None):
-        g = DGemm()
-        g.m_dev, g.crow, g.rowlist = _ptr(m_dev), _ptr(crow), _ptr(rowlist)
-        if ln is not None:      # LayerNorm of the A rows inside the launch
-            g.ln_gamma, g.ln_beta, g.ln_eps = ln.weight.data_ptr(), ln.bias.data_ptr(), float(ln.eps)
-        g.A, g.lda, g.W, g.bias = _ptr(A), lda, W.buf.data_ptr(), _ptr(bias)
-        g.res, g.ldr, g.C, g.ldc = _ptr(res), ldr, _ptr(C), ldc
-        g.C2, g.ldc2 = _ptr(C2), ldc2
-        g.node, g.skip_node = self.node.data_ptr(), self.dump_node
-        g.e_all, g.t_idx, g.T, g.beam = self.e_all.data_ptr(), self.t_idx.data_ptr(), self.T, self.K
-        g.M, g.N, g.K, g.terms = M, W.N, W.K, W.terms
-        g.flags = ((DG_RELU if relu else 0) | (DG_GATE if gate else 0) | (DG_ROWMASK if rowmask else 0) |
-                   (DG_FEW_ROWS if m_dev is not None else 0))      # compact rows: ~1/6 of the beam rows emit a label in a step
+    def _gemm(self, A, lda, W, bias, C, ldc, M, m_dev=None, ln=None, **kw):
+        g = dgemm_args(A, lda, W, bias, C, ldc, M, few_rows=m_dev is not None, m_dev=m_dev, node=self.node,  # (compact rows: ~1/6
+                       skip_node=self.dump_node, e_all=self.e_all, t_idx=self.t_idx, T=self.T, beam=self.K,  # of the beam rows)
+                       ln=None if ln is None else (ln.weight, ln.bias, ln.eps), **kw)
         _lib.check(_lib.lib().pika_dgemm(ctypes.byref(g), _stream()), "pika_dgemm(M=%d,N=%d,K=%d)" % (M, W.N, W.K))
 
     def _prednet(self, anc_dst, state_dst, count):
@@ -252,22 +257,23 @@ class FusedSearch(object):
                 self._gemm(self.hmid, self.hmid.shape[1], w["w2"], w["b2"], state_dst, d, R, res=self.o, ldr=d, m_dev=count,
                            crow=self.rowmap)
 
+    def _prep_common(self, p):
+        """The members DPrep and DPrepLSTM share."""
+        b = self.beam
+        p.prev_k, p.y, p.step_t, p.t_idx = self.prev_k.data_ptr(), b.y.data_ptr(), b.step_t.data_ptr(), self.t_idx.data_ptr()
+        p.state[0], p.state[1], p.emb = self.state[0].data_ptr(), self.state[1].data_ptr(), self.emb.data_ptr()
+        p.rowmap, p.count, p.stop = self.rowmap.data_ptr(), self.sync[5:7].data_ptr(), self.stop.data_ptr()
+        p.layers, p.rows, p.beam, p.blk = self.nl, self.rows, self.K, b.blk
+        self._fill_joint(p.joint)
+
     def _prep(self, parity):
         p = DPrep()
-        b = self.beam
-        p.prev_k, p.y, p.hyp_len, p.step_t = self.prev_k.data_ptr(), b.y.data_ptr(), b.hyp_len.data_ptr(), b.step_t.data_ptr()
-        p.t_idx = self.t_idx.data_ptr()
-        for i in range(2):
-            p.state[i], p.anc[i] = self.state[i].data_ptr(), self.anc[i].data_ptr()
-        p.emb = self.emb.data_ptr()
+        self._prep_common(p)
+        p.hyp_len, p.anc[0], p.anc[1] = self.beam.hyp_len.data_ptr(), self.anc[0].data_ptr(), self.anc[1].data_ptr()
         for l in range(self.nl):
             p.X[l], p.A[l], p.C[l], p.lda[l] = self.X[l].data_ptr(), self.A[l].data_ptr(), self.Cin[l], self.lda[l]
-        p.node, p.pos, p.rowmap = self.node.data_ptr(), self.pos.data_ptr(), self.rowmap.data_ptr()
-        p.count = self.sync[5:7].data_ptr()
-        p.dump_node, p.zero_node = self.dump_node, self.zero_node
-        p.layers, p.rows, p.beam, p.H, p.L, p.blk = self.nl, self.rows, self.K, self.d, self.L, b.blk     # (H: state width)
-        p.stop = self.stop.data_ptr()
-        self._fill_joint(p.joint)
+        p.node, p.pos, p.dump_node, p.zero_node = self.node.data_ptr(), self.pos.data_ptr(), self.dump_node, self.zero_node
+        p.H, p.L = self.d, self.L     # (H: state width)
         _lib.check(_lib.lib().pika_dstep_prep(ctypes.byref(p), _stream()), "pika_dstep_prep")
 
     def _init_sos(self):
@@ -402,19 +408,10 @@ class FusedSearchLSTM(FusedSearch):
 
     def _prep(self, parity):
         p = DPrepLSTM()
-        b = self.beam
-        p.prev_k, p.y, p.step_t = self.prev_k.data_ptr(), b.y.data_ptr(), b.step_t.data_ptr()
-        p.t_idx = self.t_idx.data_ptr()
-        for i in range(2):
-            p.state[i] = self.state[i].data_ptr()
-        p.emb = self.emb.data_ptr()
+        self._prep_common(p)
         for l in range(self.nl):
             p.A[l], p.lda[l] = self.A[l].data_ptr(), self.lda[l]
-        p.rowmap = self.rowmap.data_ptr()
-        p.count = self.sync[5:7].data_ptr()
-        p.layers, p.rows, p.beam, p.H, p.E, p.blk = self.nl, self.rows, self.K, self.H, self.E, b.blk
-        p.stop = self.stop.data_ptr()
-        self._fill_joint(p.joint)
+        p.H, p.E = self.H, self.E
         _lib.check(_lib.lib().pika_dstep_prep_lstm(ctypes.byref(p), _stream()), "pika_dstep_prep_lstm")
 
     def step_launches(self, parity):

@@ -629,7 +629,7 @@ class InputFeedRNNDecoder(nn.Module):
             # bf16 arithmetic mode; otherwise two fp16 terms (terms = 4: 22 mantissa bits per operand, an fp32 product to
             # ~2^-22 with three MFMAs -- the decoder's activations are bounded, far inside fp16's range);
             # self.fused_terms = 3: three bf16 terms, exact fp32 products, six MFMAs
-            from ..decoder.fused_step import DGemm, PackedWeight
+            from ..decoder.fused_step import PackedWeight, dgemm_args
             terms = 1 if G.PRECISION == "bf16" else int(getattr(self, "fused_terms", 4))
             # (packed once per set of weights: the pack is four kernels over ~90 MB, the weights of a scoring model do not change)
             srcs = [w for c in self.rnn.layers for w in (c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh)] + \
@@ -673,17 +673,10 @@ class InputFeedRNNDecoder(nn.Module):
             n_max = int(n_act.max())
 
             def dgemm(A, lda, W, bias, C, ldc, crow_=None, C2=None, ldc2=0):
-                g = DGemm()
-                g.A, g.lda, g.W, g.bias = A.data_ptr(), lda, W.buf.data_ptr(), bias.data_ptr()
-                g.C, g.ldc = C.data_ptr(), ldc
-                if C2 is not None:
-                    g.C2, g.ldc2, g.node = C2.data_ptr(), ldc2, iden.data_ptr()
-                g.skip_node = -1
-                g.M, g.N, g.K, g.terms, g.flags = n_max, W.N, W.K, W.terms, 0
-                g.m_dev = n_dev.data_ptr()
-                g.rowlist, g.rowoff_dev = qlist.data_ptr(), step[2:3].data_ptr()      # the step's active rows
-                if crow_ is not None:
-                    g.crow = crow_.data_ptr()
+                # the step's active rows: the gather list qlist from step[2], step[1] of them
+                g = dgemm_args(A, lda, W, bias, C, ldc, n_max, crow=crow_, C2=C2, ldc2=ldc2 if C2 is not None else 0,
+                               node=iden if C2 is not None else None, skip_node=-1, m_dev=n_dev, rowlist=qlist,
+                               rowoff_dev=step[2:3])
                 _lib.check(lib.pika_dgemm(ctypes.byref(g), torch.cuda.current_stream().cuda_stream),
                            "pika_dgemm(M=%d,N=%d,K=%d)" % (n_max, W.N, W.K))
 

@@ -505,6 +505,73 @@ def test_dgemm_as_the_search_launches_it(hip_device, form, terms):
         print("dgemm %s terms %d: worst error / |want|max %.3g (tolerance %.1g)" % (form, terms, worst, R.GEMM_TOL[terms]))
 
 
+# ---- every host route of pika_dgemm, at the smallest shape that reaches it ------------------------------------------------
+# (M, N, K); no m_dev and no PIKA_DG_FEW_ROWS: the route follows from the shape alone.  KT = ceil(K / 32).
+ROUTES = {
+    "sk_kw4": (16, 48, 512),                    # split reduction, 4 waves, one request round (KT = 16)
+    "sk_kw8": (16, 48, 544),                    # 8 waves, one round (KT = 17)
+    "sk_kw8_pipelined": (16, 48, 1056),         # 8 waves, rounds of 2 k-tiles each (KT = 33 > 32)
+    "sk_wn2": (16, 1024, 64),                   # 32-column tiles
+    "sk_ln": (16, 48, 1024),                    # LayerNorm inside the launch, at the largest K it accepts
+    "tiled32": (257, 48, 64),                   # more than 256 rows: the 32-row tiles
+    "tiled64": (1024, 2032, 32),                # 16 row tiles x 32 column groups = 512: the 64-row tiles
+    "wide": (257, 2048, 32),                    # N >= 2048: 64 x 128 tiles
+    "sk_too_long": (16, 48, 4128),              # KT = 129 > 128: few rows, but the tiled kernel
+    "k_padded": (16, 48, 30),                   # K % 4 != 0: the reduction runs over ceil32(K) zero-padded columns
+}
+ROUTE_CASES = [("sk_kw4", t) for t in (1, 2, 3, 4)] + [(r, t) for r in ROUTES if r != "sk_kw4" for t in (3, 4)]
+
+
+def run_route(dev, route, terms, K=None):
+    """One launch on the route's shape with fixed seeds -> (return code, the whole output buffer, its C view, float64 want)."""
+    from pika_amd.decoder.fused_step import PackedWeight, dgemm_args
+    M, N, K0 = ROUTES[route]
+    K = K or K0
+    ln = route == "sk_ln"
+    g = torch.Generator().manual_seed(M + N + K + terms)
+    Kp = (K + 31) // 32 * 32
+    A = torch.full((M, Kp + 32), float("nan"))                      # beyond the columns a launch may read: NaN
+    A[:, :K] = torch.randn(M, K, generator=g) * (3 if ln else 1) + (0.7 if ln else 0)
+    if K % 4:
+        A[:, K:Kp] = 0                                               # (the caller zero-pads, as the header says)
+    A = A.to(dev)
+    W = (torch.randn(N, K, generator=g) / K ** 0.5).to(dev)
+    bias = torch.randn(N, generator=g).to(dev)
+    gamma, beta = (1 + 0.2 * torch.randn(K, generator=g)).to(dev), (0.1 * torch.randn(K, generator=g)).to(dev)
+    a64 = R.layer_norm(A[:, :K], gamma, beta, 1e-6) if ln else A[:, :K].double()
+    want = a64 @ W.double().t() + bias.double()
+    pw = PackedWeight(W, terms)
+    buf = torch.full((M + 2, N + 8), R.SENT_F, device=dev)          # a sentinel row above and below, 8 pad columns
+    C = buf[1:M + 1]
+    d = dgemm_args(A, Kp + 32, pw, bias, C, N + 8, M, ln=(gamma, beta, 1e-6) if ln else None)
+    rc = _lib().lib().pika_dgemm(ctypes.byref(d), _st())
+    torch.cuda.synchronize()
+    return rc, buf, C, want
+
+
+@pytest.mark.parametrize("route,terms", ROUTE_CASES, ids=lambda v: str(v))
+def test_dgemm_host_routes(hip_device, route, terms):
+    M, N, K = ROUTES[route]
+    outs = []
+    for _ in range(2):
+        rc, buf, C, want = run_route(hip_device, route, terms)
+        assert rc == 0
+        outs.append(buf)
+    assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32))
+    scale = float(want.abs().max())
+    e = R.err(C[:, :N], want)
+    print("dgemm route %s terms %d: error / |want|max %.3g (tolerance %.1g)" % (route, terms, e / scale, R.GEMM_TOL[terms]))
+    assert e <= R.GEMM_TOL[terms] * scale, (route, terms, e / scale)
+    keep = torch.ones_like(buf, dtype=torch.bool)
+    keep[1:M + 1, :N] = False
+    assert bool((buf[keep] == R.SENT_F).all()), route
+
+
+def test_dgemm_ln_refuses_k_beyond_1024(hip_device):
+    rc, buf, _, _ = run_route(hip_device, "sk_ln", 3, K=1056)
+    assert rc == EINVAL and bool((buf == R.SENT_F).all())
+
+
 # ---- stop ------------------------------------------------------------------------------------------------------------------
 
 def test_stop_leaves_every_buffer_alone(hip_device):

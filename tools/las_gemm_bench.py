@@ -18,7 +18,7 @@ def worker():
     import torch
     sys.path.insert(0, ROOT)
     from pika_amd import _lib
-    from pika_amd.decoder.fused_step import DGemm, PackedWeight
+    from pika_amd.decoder.fused_step import PackedWeight, dgemm_args
     lib = _lib.lib()
     dev = torch.device("cuda:0")
     tag = os.environ.get("TAG", "")
@@ -47,11 +47,7 @@ def worker():
         bias = torch.randn(N, generator=g).to(dev)
         C = torch.zeros(NMAX, N, device=dev)
         pw = PackedWeight(W, 4)
-        d = DGemm()
-        d.A, d.lda, d.W, d.bias, d.C, d.ldc = A.data_ptr(), Kp, pw.buf.data_ptr(), bias.data_ptr(), C.data_ptr(), N
-        d.M, d.N, d.K, d.terms, d.flags = NMAX, N, K, 4, 0
-        d.m_dev, d.rowlist, d.rowoff_dev = md.data_ptr(), rl.data_ptr(), off.data_ptr()
-        d.skip_node = -1
+        d = dgemm_args(A, Kp, pw, bias, C, N, NMAX, m_dev=md, rowlist=rl, rowoff_dev=off, skip_node=-1)
         line = []
         for m in ROWS:
             md.fill_(m)
