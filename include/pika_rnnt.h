@@ -40,7 +40,7 @@ extern "C" {
 #define PIKA_EINVAL (-1)   /* null pointer / non-positive dimension / blank out of range */
 #define PIKA_ETOOBIG (-2)  /* U1 > 1024 (one workgroup spans the label axis) */
 
-/* Library/ABI version, bumped on any signature change. */
+/* Library/ABI version, bumped on any signature change.  Adding symbols is not one: pika_ctc.h came in under 25. */
 int pika_amd_abi_version(void);
 
 /* Bytes of device scratch `workspace` needed by the calls below for a (B,T,U1)

@@ -51,3 +51,19 @@ def _hip_graph_workaround():
 # False: the HIP runtime was initialised before this package could turn the fast path off (or the user turned it on):
 # pika_amd.train_graph then keeps the training step an eager launch sequence
 HIP_GRAPHS_SAFE_TO_ALTERNATE = _hip_graph_workaround()
+
+
+# The CTC surface (pika_amd/ctc.py), resolved on first use: importing it here would import torch before the flag above
+# is placed.
+_CTC_EXPORTS = ("ctc_loss", "ctc_loss_from_logits", "CTCLoss", "ctc_align", "ctc_align_from_logits")
+
+
+def __getattr__(name):
+    if name in _CTC_EXPORTS:
+        from . import ctc
+        return getattr(ctc, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
+def __dir__():
+    return sorted(list(globals()) + list(_CTC_EXPORTS))

@@ -37,6 +37,14 @@ SIGNATURES = {
                                               _ll, _f, _vp]),
     "pika_rnnt_align_scratch_bytes": (_sz, [_i, _i, _i]),
     "pika_rnnt_align": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    # include/pika_ctc.h
+    "pika_ctc_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pika_ctc_align_scratch_bytes": (_sz, [_i, _i, _i]),
+    "pika_ctc_loss_forward": (_i, [_vp] * 5 + [_i] * 5 + [_vp] * 3),
+    "pika_ctc_loss_backward": (_i, [_vp] * 2 + [_i] * 5 + [_vp] * 4),
+    "pika_ctc_fused_forward": (_i, [_vp] * 5 + [_i] * 5 + [_vp] * 4),
+    "pika_ctc_fused_backward": (_i, [_vp] * 4 + [_i] * 5 + [_vp] * 4),
+    "pika_ctc_align": (_i, [_vp] * 3 + [_i] * 3 + [_vp] * 4),
     # include/pika_bmuf.h
     "pika_bmuf_delta": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "pika_bmuf_nan_flag": (_i, [_vp, _sz, _vp, _vp]),

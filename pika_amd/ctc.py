@@ -1,0 +1,240 @@
+"""Host side of the CTC loss, its gradient and forced alignment (include/pika_ctc.h, csrc/ctc_loss.hip).
+
+The surface is `torch.nn.functional.ctc_loss`'s -- the loss the reference's LAS trainer builds as `nn.CTCLoss()`
+(trainer/train_las_bmuf_otfaug.py:58-81):
+
+    ctc_loss(log_probs, targets, input_lengths, target_lengths, blank=0, reduction='mean', zero_infinity=False)
+    ctc_loss_from_logits(logits, ...same...)      log-softmax + loss + log-softmax backward, no log-prob tensor
+    CTCLoss(blank=0, reduction='mean', zero_infinity=False)     nn.Module, forward(log_probs, targets, il, tl)
+    ctc_align(log_probs, targets, input_lengths, target_lengths, blank=0) -> (scores (B,), frame_labels (B, T))
+    ctc_align_from_logits(logits, ...)
+
+Differences from torch, on purpose:
+
+* THE GRADIENT IS THE TRUE DERIVATIVE.  torch's native CTC backward returns `exp(log_probs) - occ` for d/d log_probs,
+  not the derivative `-occ` of the cost with respect to its input; the two agree only after a `log_softmax` backward
+  (whose projection removes any multiple of exp(lp) whose rows sum to the same total).  `ctc_loss` here returns
+  `-occ`, as `rnnt_loss` does for its lattice; `ctc_loss_from_logits` returns d/d logits = softmax - occ, which IS what
+  torch gives through `log_softmax`.  A caller that feeds unnormalised scores straight into the loss (the reference's
+  LAS script does) gets a different gradient from the two libraries.
+* An infeasible utterance (T_n < U_n + adjacent repeats, or a label outside [0, C)) has cost +inf and an all-zero
+  gradient; torch gives NaN gradients there unless zero_infinity=True.  zero_infinity only turns the cost into 0.
+* Lengths are clamped on the device (input_lengths to [1, T], target_lengths to [0, U_max]); nothing is checked on
+  the host, so nothing synchronises.
+
+Host synchronisation: none with padded 2-D targets (U_max = targets.shape[1]) -- with targets and lengths already on
+the device the forward, backward and alignment calls can be captured in one `torch.cuda.graph`.  1-D concatenated
+targets take their offsets from a device cumsum; U_max is the largest target length, read on the host when the
+lengths live there (no sync) and by ONE device-to-host copy per call when they live on the device (the trade
+`rnnt_loss(compact=True)` makes; it raises under stream capture).
+"""
+import torch
+
+from . import _lib
+
+MAX_STATES = 1024   # 2 * U_max + 1: one workgroup spans the state axis
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _prepare(x, what, targets, input_lengths, target_lengths, blank):
+    """Checks and device copies: (x as (T,B,C), any stride; targets i32; offsets i32 or None; il i32; tl i32; U_max;
+    unbatched)."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("pika_amd ctc_loss: %s must live on a HIP device (there is no CPU path)" % what)
+    if x.dtype != torch.float32:
+        raise TypeError("%s must be float32, got %s" % (what, x.dtype))
+    unbatched = x.dim() == 2
+    if unbatched:
+        x = x.unsqueeze(1)
+    if x.dim() != 3:
+        raise ValueError("%s must be (T,B,C) or (T,C), got %s" % (what, tuple(x.shape)))
+    T, B, C = x.shape
+    if T < 1 or B < 1 or C < 1:
+        raise ValueError("%s has an empty dimension: %s" % (what, tuple(x.shape)))
+    if not 0 <= blank < C:
+        raise ValueError("blank=%d outside [0,%d)" % (blank, C))
+    dev = x.device
+    targets = torch.as_tensor(targets)
+    il_host, tl_host = torch.as_tensor(input_lengths), torch.as_tensor(target_lengths)
+    for name, t in (("targets", targets), ("input_lengths", il_host), ("target_lengths", tl_host)):
+        if t.dtype not in (torch.int32, torch.int64):
+            raise TypeError("%s must be int32 or int64, got %s" % (name, t.dtype))
+    if unbatched:
+        targets = targets.reshape(1, -1)
+    il = il_host.reshape(-1).to(dev, torch.int32).contiguous()
+    tl = tl_host.reshape(-1).to(dev, torch.int32).contiguous()
+    if il.numel() != B or tl.numel() != B:
+        raise ValueError("input_lengths / target_lengths must hold B = %d entries" % B)
+    toff = None
+    if targets.dim() == 2:
+        if targets.shape[0] != B:
+            raise ValueError("targets must be (B,S) = (%d,S), got %s" % (B, tuple(targets.shape)))
+        U = int(targets.shape[1])
+    elif targets.dim() == 1:
+        if tl_host.is_cuda:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ctc_loss with 1-D targets and device target_lengths reads U_max on the host and "
+                                   "cannot run under stream capture; capture padded (B,S) targets instead")
+            U = int(tl_host.max())        # the one device-to-host copy of this form
+        else:
+            U = int(tl_host.max())
+            if int(tl_host.clamp(min=0).sum()) > targets.numel():
+                raise ValueError("1-D targets hold %d labels, target_lengths sum to %d"
+                                 % (targets.numel(), int(tl_host.clamp(min=0).sum())))
+        U = max(0, min(U, int(targets.numel())))
+        wide = tl.to(torch.int64)
+        toff = (torch.cumsum(wide, 0) - wide).to(torch.int32)
+    else:
+        raise ValueError("targets must be (B,S) or 1-D, got %s" % (tuple(targets.shape),))
+    if 2 * U + 1 > MAX_STATES:
+        raise ValueError("2*U_max+1 = %d > %d not supported" % (2 * U + 1, MAX_STATES))
+    targets = targets.to(dev, torch.int32).contiguous()
+    return x, targets, toff, il, tl, U, unbatched
+
+
+def _fill(x, targets, toff, il, tl, U, blank, logits):
+    """Fill a workspace: (costs, ws, lse)."""
+    lib = _lib.lib()
+    T, B, C = x.shape
+    with torch.cuda.device(x.device):
+        costs = torch.empty(B, dtype=torch.float32, device=x.device)
+        ws = torch.empty(lib.pika_ctc_workspace_bytes(B, T, U), dtype=torch.uint8, device=x.device)
+        tg = _ptr(targets) if U > 0 else None
+        if logits:
+            lse = torch.empty(T * B, dtype=torch.float32, device=x.device)
+            _lib.check(lib.pika_ctc_fused_forward(_ptr(x), tg, _ptr(toff), _ptr(il), _ptr(tl), B, T, U, C, blank,
+                                                  _ptr(costs), _ptr(lse), _ptr(ws), _stream()), "pika_ctc_fused_forward")
+        else:
+            lse = None
+            _lib.check(lib.pika_ctc_loss_forward(_ptr(x), tg, _ptr(toff), _ptr(il), _ptr(tl), B, T, U, C, blank,
+                                                 _ptr(costs), _ptr(ws), _stream()), "pika_ctc_loss_forward")
+    return costs, ws, lse
+
+
+class _CTCFn(torch.autograd.Function):
+    """Per-utterance costs (B,); backward writes the dense (T,B,C) gradient once, already scaled by grad_output."""
+
+    @staticmethod
+    def forward(ctx, x, targets, toff, il, tl, U, blank, logits):
+        xc = x.detach().contiguous()
+        costs, ws, lse = _fill(xc, targets, toff, il, tl, U, blank, logits)
+        ctx.save_for_backward(*((xc, lse) if logits else ()), il, tl, ws)
+        ctx.dims = tuple(xc.shape) + (U, blank, logits)
+        return costs
+
+    @staticmethod
+    def backward(ctx, grad_costs):
+        T, B, C, U, blank, logits = ctx.dims
+        lib = _lib.lib()
+        gc = grad_costs.to(torch.float32).contiguous()
+        if logits:
+            x, lse, il, tl, ws = ctx.saved_tensors
+        else:
+            il, tl, ws = ctx.saved_tensors
+        with torch.cuda.device(ws.device):
+            grads = torch.empty((T, B, C), dtype=torch.float32, device=ws.device)
+            if logits:
+                _lib.check(lib.pika_ctc_fused_backward(_ptr(x), _ptr(lse), _ptr(il), _ptr(tl), B, T, U, C, blank,
+                                                       _ptr(gc), _ptr(ws), _ptr(grads), _stream()),
+                           "pika_ctc_fused_backward")
+            else:
+                _lib.check(lib.pika_ctc_loss_backward(_ptr(il), _ptr(tl), B, T, U, C, blank, _ptr(gc), _ptr(ws),
+                                                      _ptr(grads), _stream()), "pika_ctc_loss_backward")
+        return grads, None, None, None, None, None, None, None
+
+
+def _loss(x, what, targets, input_lengths, target_lengths, blank, reduction, zero_infinity, logits):
+    if reduction not in ("none", "mean", "sum"):
+        raise ValueError("%r is not a valid value for reduction" % (reduction,))
+    blank = int(blank)
+    x, tg, toff, il, tl, U, unbatched = _prepare(x, what, targets, input_lengths, target_lengths, blank)
+    # (any stride: the kernels read the one contiguous copy the forward makes when it is needed)
+    costs = _CTCFn.apply(x, tg, toff, il, tl, U, blank, logits)
+    if zero_infinity:
+        costs = torch.where(torch.isinf(costs), torch.zeros_like(costs), costs)
+    # the reduction acts on the (B,) costs: its factors reach the kernel folded into grad_costs, so no pass over the
+    # (T,B,C) gradient follows the one that writes it
+    if reduction == "mean":
+        return (costs / tl.clamp(min=1).to(costs.dtype)).mean()
+    if reduction == "sum":
+        return costs.sum()
+    return costs.reshape(()) if unbatched else costs
+
+
+def ctc_loss(log_probs, targets, input_lengths, target_lengths, blank=0, reduction='mean', zero_infinity=False):
+    """`torch.nn.functional.ctc_loss` on the MI355X: same arguments, defaults, shapes and reductions.
+
+    log_probs (T,B,C) or (T,C) float32 on a HIP device, any stride (one contiguous copy when needed); targets (B,S)
+    padded or 1-D concatenated; lengths (B,); targets and lengths int32 or int64, on the CPU or the device.
+    'mean' divides each cost by clamp(target_length, 1) and averages over the batch.
+
+    The gradient is the true derivative -occ with respect to log_probs -- torch's native kernel returns
+    exp(log_probs) - occ, which equals it only after a log_softmax backward (module docstring).  Infeasible utterances
+    cost +inf (0 with zero_infinity) and have an all-zero gradient.  Host synchronisation: module docstring."""
+    return _loss(log_probs, "log_probs", targets, input_lengths, target_lengths, blank, reduction, zero_infinity, False)
+
+
+def ctc_loss_from_logits(logits, targets, input_lengths, target_lengths, blank=0, reduction='mean',
+                         zero_infinity=False):
+    """`ctc_loss(log_softmax(logits, -1), ...)` without materialising the log-probabilities: the row log-sum-exp is
+    taken in the pass that gathers the state plane, and the backward writes d/d logits = grad * (softmax - occ)."""
+    return _loss(logits, "logits", targets, input_lengths, target_lengths, blank, reduction, zero_infinity, True)
+
+
+class CTCLoss(torch.nn.Module):
+    """`torch.nn.CTCLoss` on the MI355X: `CTCLoss(blank=0, reduction='mean', zero_infinity=False)` and
+    `forward(log_probs, targets, input_lengths, target_lengths)`; values and gradient as `ctc_loss`."""
+
+    def __init__(self, blank=0, reduction='mean', zero_infinity=False):
+        super().__init__()
+        self.blank, self.reduction, self.zero_infinity = int(blank), reduction, bool(zero_infinity)
+
+    def forward(self, log_probs, targets, input_lengths, target_lengths):
+        return ctc_loss(log_probs, targets, input_lengths, target_lengths, self.blank, self.reduction,
+                        self.zero_infinity)
+
+
+def align_workspace(ws, il, tl, B, T, U):
+    """pika_ctc_align on a workspace a forward call filled: (scores (B,), frame_labels (B,T)).  The workspace is only
+    read."""
+    lib = _lib.lib()
+    with torch.cuda.device(ws.device):
+        scores = torch.empty(B, dtype=torch.float32, device=ws.device)
+        labels = torch.empty((B, T), dtype=torch.int32, device=ws.device)
+        scratch = torch.empty(lib.pika_ctc_align_scratch_bytes(B, T, U), dtype=torch.uint8, device=ws.device)
+        _lib.check(lib.pika_ctc_align(_ptr(ws), _ptr(il), _ptr(tl), B, T, U, _ptr(scores), _ptr(labels), _ptr(scratch),
+                                      _stream()), "pika_ctc_align")
+    return scores, labels
+
+
+def _align(x, what, targets, input_lengths, target_lengths, blank, logits):
+    blank = int(blank)
+    x, tg, toff, il, tl, U, _ = _prepare(x, what, targets, input_lengths, target_lengths, blank)
+    xc = x.detach().contiguous()
+    _, ws, _ = _fill(xc, tg, toff, il, tl, U, blank, logits)
+    T, B, _ = xc.shape
+    return align_workspace(ws, il, tl, B, T, U)
+
+
+def ctc_align(log_probs, targets, input_lengths, target_lengths, blank=0):
+    """Forced alignment: the single best (Viterbi) path of every transcript through its CTC lattice.
+
+    Returns (scores, frame_labels), detached: scores (B,) f32, the log-probability of the best path (<= -cost);
+    frame_labels (B,T) i32, the class that path emits at every frame, blank included, -1 for t >= T_n -- merging
+    repeats and dropping blanks gives the transcript back.  Tie rule: the path ends in the final blank rather than the
+    last label, and in the back-trace staying in a state is preferred to coming from s-1, and that to s-2.  An
+    infeasible transcript scores <= -1e30 and still yields a path of valid states.  Inputs as `ctc_loss`; no autograd;
+    same host-synchronisation behaviour."""
+    return _align(log_probs, "log_probs", targets, input_lengths, target_lengths, blank, False)
+
+
+def ctc_align_from_logits(logits, targets, input_lengths, target_lengths, blank=0):
+    """`ctc_align` of log_softmax(logits, -1) without materialising the log-probabilities."""
+    return _align(logits, "logits", targets, input_lengths, target_lengths, blank, True)
