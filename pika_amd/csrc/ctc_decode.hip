@@ -1,0 +1,581 @@
+// pika_amd/csrc/ctc_decode.hip -- CTC decoding for gfx950 (MI355X), hand-written HIP: best path and exact prefix beam
+// search over the full vocabulary (include/pika_ctc_decode.h).
+//
+//   rows   : one workgroup per (t, b) row with t < T_n; the only pass that reads the (T,B,C) input, once.  Online
+//            max / sum for the log-sum-exp of the from-logits form (the grouping and the fixed tree of ctc_loss.hip's
+//            gather), the blank's value, and the K best non-blank classes ordered (value descending, class ascending).
+//            K = 1 is a workgroup arg-max.  K > 1: the K-th largest of the 256 per-thread maxima is a lower bound on the
+//            row's K-th largest value, so one more pass over the row (staged in LDS while it was read; rows wider than
+//            the stage are read again through the cache) keeps the few dozen values at or above it; the survivors are
+//            ranked by counting.  More survivors than the pool holds (rows of near-equal values): the exact K-th key by
+//            bisection with counting passes, ties at it resolved by a second bisection on the class (lowest first).
+//   greedy : one workgroup per utterance; ballot prefix scan over the "starts a new non-blank run" flags, compacted
+//            tokens and frames stored in frame order; the score is summed in fp64 by a fixed tree.
+//   search : one persistent 64-lane workgroup per utterance, lane = beam slot, the beam in LDS (double buffered).  Per
+//            frame: every slot finds its parent's slot (node identity), the position of its own last label in the
+//            frame's class list, and strikes that position from its own list (the repeat is scored with p_b, as a
+//            candidate of its own) and from its parent's (that child is in the beam: the contribution is added to it).
+//            Then `beam` rounds of "wave arg-max over every slot's best open candidate" -- the stay, the repeat child,
+//            the head of the slot's class list -- under the total order of the header.  Fresh winners get their node by
+//            insert-or-find in the utterance's open-addressing table of (parent node, token) keys: the node IS the
+//            table slot, so a prefix that left the beam and comes back is the same node and its children merge with a
+//            descendant that stayed.  Numerics as the loss: fp32 (p_b, p_nb), the best tot moved into an fp64 offset
+//            every RENORM frames.  The n-best back-trace walks the table in the same launch.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "pika_ctc_decode.h"
+
+namespace {
+
+constexpr float NEG = -1.0e30f;  // "log zero": finite, so NEG+NEG / NEG-NEG never make NaN
+constexpr float NEG_HALF = -0.5e30f;
+constexpr float LOG2E = 1.4426950408889634f;
+constexpr float LN2 = 0.6931471805599453f;
+constexpr int ROW_THREADS = 256;
+constexpr int ROW_STAGE = 8192;  // classes of a row staged in LDS for the second look
+constexpr int POOL_CAP = 1024;   // survivors ranked by counting
+constexpr int MAX_K = 128;
+constexpr int MAX_BEAM = 64;
+constexpr int RENORM = 8;
+constexpr int ROOT = 0x7ffffffe;  // node of the empty prefix
+constexpr int NONE = 0x7ffffffd;  // its parent
+constexpr int PENDING = -1;
+constexpr unsigned long long EMPTY = ~0ull;
+
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+__device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// order-preserving integer image of a finite float; 0 is below every image
+__device__ inline unsigned fkey(float v) {
+    const unsigned u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ inline float funkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+
+__device__ inline float addn(float a, float b) { return fmaxf(a + b, NEG); }
+
+// log(exp(x)+exp(y)) on the transcendental pipe; NEG when both are "log zero"
+__device__ inline float lse2(float x, float y) {
+    const float m = fmaxf(x, y);
+    if (!(m > NEG_HALF)) return NEG;
+    const float e = __builtin_amdgcn_exp2f((x - m) * LOG2E) + __builtin_amdgcn_exp2f((y - m) * LOG2E);
+    return m + LN2 * __builtin_amdgcn_logf(e);
+}
+
+// ---------------------------------------------------------------------------------------------
+// rows.  grid = (T, B), block = 256.
+// ---------------------------------------------------------------------------------------------
+template <bool TOPK>
+__global__ __launch_bounds__(ROW_THREADS) void ctc_rows_kernel(const float *__restrict__ x, long long st, long long sb,
+                                                               const int *__restrict__ Tn_, int B, int T, int C,
+                                                               int blank, int K, int logits,
+                                                               float *__restrict__ blank_lp, float *__restrict__ top_val,
+                                                               int *__restrict__ top_idx, float *__restrict__ lse_out) {
+    __shared__ float rm[ROW_THREADS], rs[ROW_THREADS];
+    __shared__ unsigned tk[ROW_THREADS];
+    __shared__ int ti[ROW_THREADS];
+    __shared__ float stage[TOPK ? ROW_STAGE : 1];
+    __shared__ unsigned pool_k[TOPK ? POOL_CAP : 1];
+    __shared__ int pool_i[TOPK ? POOL_CAP : 1];
+    __shared__ int red[ROW_THREADS / 64];
+    __shared__ int pool_n;
+    __shared__ unsigned bound;
+    const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int Tn = clampi(Tn_[b], 1, T);
+    if (t >= Tn) return;  // workgroup-uniform; rows t >= T_n are never read
+    const float *row = x + (long long)t * st + (long long)b * sb;
+    const size_t rb = (size_t)t * B + b;
+    const bool staged = TOPK && C <= ROW_STAGE;
+
+    float m = NEG, s = 0.0f;  // online max / sum of exp
+    unsigned bk = 0;          // the thread's best non-blank key (0: none) and its class
+    int bi = -1;
+    auto take = [&](float v, int c) __attribute__((always_inline)) {
+        v = fmaxf(v, NEG);
+        if (logits) {
+            const float mn = fmaxf(m, v);
+            s = s * __expf(m - mn) + __expf(v - mn);
+            m = mn;
+        }
+        if (TOPK && staged) stage[c] = v;
+        const unsigned k = fkey(v);
+        if (c != blank && k > bk) {  // a thread's classes ascend: strict > keeps the lowest class of equal values
+            bk = k;
+            bi = c;
+        }
+    };
+    // a thread takes the groups of four classes tid, tid + 256, ... whichever way they are loaded, so nothing below
+    // depends on the alignment of the row
+    const bool vec = C % 4 == 0 && (reinterpret_cast<uintptr_t>(row) & 15) == 0;  // workgroup-uniform
+    for (int i = tid; i < (C + 3) / 4; i += ROW_THREADS) {
+        if (vec) {
+            const v4f v = reinterpret_cast<const v4f *>(row)[i];
+            take(v.x, 4 * i); take(v.y, 4 * i + 1); take(v.z, 4 * i + 2); take(v.w, 4 * i + 3);
+        } else {
+            for (int k = 4 * i; k < min(4 * i + 4, C); ++k) take(row[k], k);
+        }
+    }
+    float l = 0.0f;
+    if (logits) {
+        rm[tid] = m;
+        rs[tid] = s;
+        __syncthreads();
+        for (int h = ROW_THREADS / 2; h > 0; h >>= 1) {  // fixed tree: the same value on every run
+            if (tid < h) {
+                const float m0 = rm[tid], m1 = rm[tid + h], mn = fmaxf(m0, m1);
+                rs[tid] = rs[tid] * __expf(m0 - mn) + rs[tid + h] * __expf(m1 - mn);
+                rm[tid] = mn;
+            }
+            __syncthreads();
+        }
+        l = rm[0] + logf(rs[0]);
+    }
+    if (tid == 0) {
+        blank_lp[rb] = fmaxf(fmaxf(row[blank], NEG) - l, NEG);
+        if (logits) lse_out[rb] = l;
+    }
+    tk[tid] = bk;
+    ti[tid] = bi;
+    __syncthreads();
+
+    if constexpr (!TOPK) {  // K == 1: the workgroup's arg-max, equal values to the lower class
+        for (int h = ROW_THREADS / 2; h > 0; h >>= 1) {
+            if (tid < h) {
+                const unsigned k1 = tk[tid + h];
+                const int i1 = ti[tid + h];
+                if (k1 > tk[tid] || (k1 == tk[tid] && (unsigned)i1 < (unsigned)ti[tid])) {
+                    tk[tid] = k1;
+                    ti[tid] = i1;
+                }
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            const bool any = ti[0] >= 0;
+            top_val[rb] = any ? fmaxf(funkey(tk[0]) - l, NEG) : NEG;
+            top_idx[rb] = any ? ti[0] : -1;
+        }
+    } else {
+        const int need = min(K, C - 1);
+        float *ov = top_val + rb * K;
+        int *oi = top_idx + rb * K;
+        for (int k = need + tid; k < K; k += ROW_THREADS) {  // fewer non-blank classes than K: padding
+            ov[k] = NEG;
+            oi[k] = -1;
+        }
+        if (need <= 0) return;  // workgroup-uniform
+        // the need-th largest thread maximum: at least `need` values of the row lie at or above it
+        {
+            int above = 0;
+            for (int j = 0; j < ROW_THREADS; ++j) {
+                const unsigned kj = tk[j];
+                above += (kj > bk || (kj == bk && j < tid)) ? 1 : 0;
+            }
+            if (tid == 0) pool_n = 0;
+            if (above == need - 1) bound = bk;  // exactly one thread (need <= 128 < 256 threads)
+        }
+        __syncthreads();
+        const unsigned long long lt = (1ull << lane) - 1ull;
+        // one look at every non-blank class: counts the classes pred(key, class) holds for and, with `collect`, appends
+        // them to the pool (in any order: the ranking below does not depend on it).  Returns the workgroup's count.
+        auto scan = [&](auto pred, bool collect) __attribute__((always_inline)) {
+            int cnt = 0;
+            for (int c0 = 0; c0 < C; c0 += ROW_THREADS) {  // workgroup-uniform trip count
+                const int c = c0 + tid;
+                bool sel = false;
+                unsigned k = 0;
+                if (c < C && c != blank) {
+                    k = fkey(staged ? stage[c] : fmaxf(row[c], NEG));
+                    sel = pred(k, (unsigned)c);
+                }
+                if (collect) {
+                    const unsigned long long mk = __ballot(sel);
+                    int base = 0;
+                    if (lane == 0 && mk) base = atomicAdd(&pool_n, __popcll(mk));
+                    base = __shfl(base, 0);
+                    const int p = base + __popcll(mk & lt);
+                    if (sel && p < POOL_CAP) {
+                        pool_k[p] = k;
+                        pool_i[p] = c;
+                    }
+                }
+                cnt += sel ? 1 : 0;
+            }
+            for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+            __syncthreads();  // the previous total is read
+            if (lane == 0) red[w] = cnt;
+            __syncthreads();
+            return red[0] + red[1] + red[2] + red[3];
+        };
+        const unsigned lo = bound;
+        int n = scan([&](unsigned k, unsigned) { return k >= lo; }, true);
+        if (n > POOL_CAP) {  // workgroup-uniform: the exact selection
+            unsigned kth = 0;  // the largest key with at least `need` keys at or above it
+            for (int bit = 31; bit >= 0; --bit) {
+                const unsigned mid = kth | (1u << bit);
+                if (scan([&](unsigned k, unsigned) { return k >= mid; }, false) >= need) kth = mid;
+            }
+            const int rem = need - scan([&](unsigned k, unsigned) { return k > kth; }, false);
+            const int n_eq = scan([&](unsigned k, unsigned) { return k == kth; }, false);
+            unsigned cut = 0xffffffffu;  // classes below `cut` among the ties: the `rem` lowest
+            if (n_eq > rem) {
+                cut = 0;
+                for (int bit = 31; bit >= 0; --bit) {
+                    const unsigned mid = cut | (1u << bit);
+                    if (scan([&](unsigned k, unsigned c) { return k == kth && c < mid; }, false) <= rem) cut = mid;
+                }
+            }
+            if (tid == 0) pool_n = 0;
+            __syncthreads();
+            n = scan([&](unsigned k, unsigned c) { return k > kth || (k == kth && c < cut); }, true);
+        }
+        n = min(n, POOL_CAP);
+        for (int e = tid; e < n; e += ROW_THREADS) {  // rank by counting: classes are unique, so are the ranks
+            const unsigned ke = pool_k[e];
+            const int ie = pool_i[e];
+            int rank = 0;
+            for (int j = 0; j < n; ++j) {
+                const unsigned kj = pool_k[j];
+                rank += (kj > ke || (kj == ke && pool_i[j] < ie)) ? 1 : 0;
+            }
+            if (rank < need) {
+                ov[rank] = fmaxf(funkey(ke) - l, NEG);
+                oi[rank] = ie;
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// greedy.  grid = B, block = 256.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ctc_greedy_kernel(const float *__restrict__ blank_lp,
+                                                         const float *__restrict__ top_val,
+                                                         const int *__restrict__ top_idx, const int *__restrict__ Tn_,
+                                                         int B, int T, int blank, int *__restrict__ tokens,
+                                                         int *__restrict__ lengths, float *__restrict__ scores,
+                                                         int *__restrict__ frames) {
+    __shared__ int wcnt[4];
+    __shared__ double acc_s[256];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int Tn = clampi(Tn_[b], 1, T);
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    // the frame's arg-max over all classes: the blank against the best non-blank class, equal values to the lower class
+    auto best = [&](int t, float &v) __attribute__((always_inline)) {
+        const size_t rb = (size_t)t * B + b;
+        const float bv = blank_lp[rb], tv = top_val[rb];
+        const int c = top_idx[rb];
+        const bool is_blank = c < 0 || bv > tv || (bv == tv && blank < c);
+        v = is_blank ? bv : tv;
+        return is_blank ? blank : c;
+    };
+    int base = 0;
+    double acc = 0.0;
+    for (int t0 = 0; t0 < Tn; t0 += 256) {  // workgroup-uniform
+        const int t = t0 + tid;
+        bool flag = false;
+        int c = blank;
+        if (t < Tn) {
+            float v, pv;
+            c = best(t, v);
+            acc += (double)v;
+            const int prev = t > 0 ? best(t - 1, pv) : -1;
+            flag = c != blank && c != prev;
+        }
+        const unsigned long long mk = __ballot(flag);
+        if (lane == 0) wcnt[w] = __popcll(mk);
+        __syncthreads();
+        int off = base;
+        for (int j = 0; j < w; ++j) off += wcnt[j];
+        if (flag) {
+            const int p = off + __popcll(mk & lt);  // p <= t < T
+            tokens[(size_t)b * T + p] = c;
+            frames[(size_t)b * T + p] = t;
+        }
+        base += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        __syncthreads();
+    }
+    acc_s[tid] = acc;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {  // fixed tree
+        if (tid < h) acc_s[tid] += acc_s[tid + h];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        scores[b] = (float)acc_s[0];
+        lengths[b] = base;
+    }
+    for (int p = base + tid; p < T; p += 256) {
+        tokens[(size_t)b * T + p] = -1;
+        frames[(size_t)b * T + p] = -1;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// search.  grid = B, block = 64: lane r owns beam slot r.
+// ---------------------------------------------------------------------------------------------
+struct Beam {
+    int node[MAX_BEAM];   // the prefix: slot of its (parent, token) key in the utterance's table, ROOT for the empty one
+    int last[MAX_BEAM];   // its last label, -1 for the empty prefix
+    int pnode[MAX_BEAM];  // its parent's node
+    int len[MAX_BEAM];
+    float pb[MAX_BEAM], pnb[MAX_BEAM], tot[MAX_BEAM];
+};
+
+__device__ inline unsigned long long trie_key(int parent, int token) {
+    return ((unsigned long long)(unsigned)parent << 32) | (unsigned)token;
+}
+
+// insert-or-find: every probe is an atomic, so a slot is never seen through a stale cache line; only this workgroup
+// touches the table
+__device__ inline int trie_node(unsigned long long *table, unsigned mask, int parent, int token) {
+    const unsigned long long key = trie_key(parent, token);
+    unsigned h = ((unsigned)parent * 0x9E3779B1u) ^ ((unsigned)token * 0x85EBCA6Bu);
+    h = (h ^ (h >> 15)) & mask;
+    for (unsigned probes = 0; probes <= mask; ++probes) {  // at most T * beam <= (mask + 1) / 2 keys: it ends early
+        const unsigned long long old = atomicCAS(&table[h], EMPTY, key);
+        if (old == EMPTY || old == key) break;
+        h = (h + 1) & mask;
+    }
+    return (int)h;
+}
+
+__global__ __launch_bounds__(64) void ctc_beam_kernel(const float *__restrict__ x, long long st, long long sb,
+                                                      const float *__restrict__ lse, const float *__restrict__ blank_lp,
+                                                      const float *__restrict__ top_val, const int *__restrict__ top_idx,
+                                                      const int *__restrict__ Tn_, int B, int T, int blank, int beam,
+                                                      int nbest, int *__restrict__ tokens, int *__restrict__ lengths,
+                                                      float *__restrict__ scores, unsigned long long *table_,
+                                                      unsigned mask) {
+    __shared__ Beam S[2];
+    __shared__ float cv[MAX_K];
+    __shared__ int ci[MAX_K];
+    __shared__ unsigned excl[MAX_BEAM][MAX_K / 32];
+    __shared__ int hasrep[MAX_BEAM];
+    const int b = blockIdx.x, r = threadIdx.x, K = 2 * beam;
+    const int Tn = clampi(Tn_[b], 1, T);
+    unsigned long long *table = table_ + (size_t)b * ((size_t)mask + 1);
+    const float *xb = x + (long long)b * sb;
+
+    int cur = 0, n = 1;
+    double off = 0.0;  // sum of the subtracted maxima (identical in every lane)
+    if (r == 0) {
+        Beam &A = S[0];
+        A.node[0] = ROOT; A.last[0] = -1; A.pnode[0] = NONE; A.len[0] = 0;
+        A.pb[0] = 0.0f; A.pnb[0] = NEG; A.tot[0] = 0.0f;
+    }
+    // the frame's compact row, fetched one frame ahead
+    float pv0 = NEG, pv1 = NEG, plb = NEG, pl = 0.0f;
+    int pi0 = -1, pi1 = -1;
+    auto fetch = [&](int t) __attribute__((always_inline)) {
+        const size_t rb = (size_t)t * B + b;
+        pv0 = r < K ? top_val[rb * K + r] : NEG;
+        pi0 = r < K ? top_idx[rb * K + r] : -1;
+        pv1 = r + 64 < K ? top_val[rb * K + r + 64] : NEG;
+        pi1 = r + 64 < K ? top_idx[rb * K + r + 64] : -1;
+        plb = blank_lp[rb];
+        pl = lse ? lse[rb] : 0.0f;
+    };
+    fetch(0);
+    for (int t = 0; t < Tn; ++t) {  // workgroup-uniform
+        __syncthreads();            // the previous frame's beam is complete; cv / ci / excl are free
+        const Beam &A = S[cur];
+        Beam &N = S[cur ^ 1];
+        cv[r] = pv0; ci[r] = pi0; cv[r + 64] = pv1; ci[r + 64] = pi1;
+        const float lpb = plb, l = pl;
+        if (t + 1 < Tn) fetch(t + 1);
+        const bool act = r < n;
+        const int node_r = act ? A.node[r] : NONE, last_r = act ? A.last[r] : -1, pn_r = act ? A.pnode[r] : NONE;
+        const int len_r = act ? A.len[r] : 0;
+        const float pb_r = act ? A.pb[r] : NEG, pnb_r = act ? A.pnb[r] : NEG, tot_r = act ? A.tot[r] : NEG;
+        float g = NEG;  // the value of the slot's own last label: the one gather from the full row
+        if (last_r >= 0) g = fmaxf(fmaxf(xb[(long long)t * st + last_r], NEG) - l, NEG);
+        for (int q = 0; q < MAX_K / 32; ++q) excl[r][q] = 0;
+        hasrep[r] = 0;
+        __syncthreads();
+        int ps = -1;  // the parent's slot, if the parent is in the beam
+        if (act && pn_r != NONE)
+            for (int q = 0; q < n; ++q)
+                if (A.node[q] == pn_r) ps = q;
+        int pos = -1;  // where the slot's last label stands in the frame's class list
+        if (last_r >= 0)
+            for (int j = 0; j < K; ++j)
+                if (ci[j] == last_r) pos = j;
+        if (pos >= 0) {
+            atomicOr(&excl[r][pos >> 5], 1u << (pos & 31));               // the repeat: scored with p_b, below
+            if (ps >= 0) atomicOr(&excl[ps][pos >> 5], 1u << (pos & 31));  // the parent's child that is in the beam
+        }
+        const bool rep_child = ps >= 0 && A.last[ps] == last_r;
+        if (rep_child) hasrep[ps] = 1;
+        float npb = NEG, npnb = NEG, s_stay = NEG;
+        if (act) {
+            npb = addn(lpb, tot_r);
+            if (last_r >= 0) npnb = addn(g, pnb_r);
+            if (ps >= 0) npnb = lse2(npnb, addn(g, rep_child ? A.pb[ps] : A.tot[ps]));
+            s_stay = lse2(npb, npnb);
+        }
+        __syncthreads();  // excl and hasrep are complete
+        const float s_rep = (last_r >= 0 && !hasrep[r]) ? addn(g, pb_r) : NEG;
+        bool stay_open = s_stay > NEG_HALF, rep_open = s_rep > NEG_HALF;
+        int j = -1;  // head of the slot's class list
+        auto advance = [&]() __attribute__((always_inline)) {
+            do ++j; while (j < K && ci[j] >= 0 && ((excl[r][j >> 5] >> (j & 31)) & 1u));
+        };
+        advance();
+        int k = 0;
+        for (; k < beam; ++k) {  // workgroup-uniform
+            // the slot's best open candidate.  order key: (0, rank, 0) for the stay, (1, parent rank, class) for fresh
+            float bs = NEG;
+            unsigned bhi = 0xffffffffu, blo = 0xffffffffu;
+            int kind = -1;
+            if (stay_open) { bs = s_stay; bhi = (unsigned)r; blo = 0; kind = 0; }
+            float fs = NEG;
+            unsigned fc = 0xffffffffu;
+            int fk = -1;
+            if (rep_open) { fs = s_rep; fc = (unsigned)last_r; fk = 1; }
+            if (act && j < K && ci[j] >= 0) {
+                const float hs = addn(cv[j], tot_r);
+                if (hs > NEG_HALF && (fk < 0 || hs > fs || (hs == fs && (unsigned)ci[j] < fc))) {
+                    fs = hs; fc = (unsigned)ci[j]; fk = 2;
+                }
+            }
+            if (fk >= 0 && fs > bs) { bs = fs; bhi = 64u + (unsigned)r; blo = fc; kind = fk; }
+            float ws = bs;
+            unsigned whi = bhi, wlo = blo;
+            for (int o = 32; o > 0; o >>= 1) {
+                const float os = __shfl_xor(ws, o);
+                const unsigned ohi = __shfl_xor(whi, o), olo = __shfl_xor(wlo, o);
+                if (os > ws || (os == ws && (ohi < whi || (ohi == whi && olo < wlo)))) { ws = os; whi = ohi; wlo = olo; }
+            }
+            if (!(ws > NEG_HALF)) break;  // nothing left: fewer prefixes exist than the beam holds
+            if (whi == bhi && wlo == blo && kind >= 0) {  // this slot's candidate won (keys are unique)
+                if (kind == 0) {
+                    N.node[k] = node_r; N.last[k] = last_r; N.pnode[k] = pn_r; N.len[k] = len_r;
+                    N.pb[k] = npb; N.pnb[k] = npnb;
+                    stay_open = false;
+                } else {
+                    N.node[k] = PENDING; N.last[k] = (int)blo; N.pnode[k] = node_r; N.len[k] = len_r + 1;
+                    N.pb[k] = NEG; N.pnb[k] = bs;
+                    if (kind == 1) rep_open = false;
+                    else advance();
+                }
+                N.tot[k] = bs;
+            }
+        }
+        __syncthreads();  // the new beam's k slots are written
+        if (r < k && N.node[r] == PENDING) N.node[r] = trie_node(table, mask, N.pnode[r], N.last[r]);
+        if (t % RENORM == RENORM - 1 && k > 0) {  // workgroup-uniform
+            const float m = N.tot[0];             // slot 0 is the best: finite
+            __syncthreads();
+            if (r < k) {
+                N.pb[r] = N.pb[r] > NEG_HALF ? N.pb[r] - m : NEG;
+                N.pnb[r] = N.pnb[r] > NEG_HALF ? N.pnb[r] - m : NEG;
+                N.tot[r] = N.tot[r] - m;
+            }
+            off += (double)m;
+        }
+        cur ^= 1;
+        n = k;
+    }
+    __syncthreads();
+    const Beam &A = S[cur];
+    // n-best: lengths, scores, -1 beyond each length, then the back-trace through the table
+    if (r < nbest) {
+        const bool have = r < n;
+        lengths[(size_t)b * nbest + r] = have ? A.len[r] : -1;
+        scores[(size_t)b * nbest + r] = have ? (float)(off + (double)A.tot[r]) : -__builtin_inff();
+    }
+    for (int e = r; e < nbest * T; e += 64) {
+        const int kk = e / T, p = e - kk * T;
+        if (kk >= n || p >= A.len[kk]) tokens[((size_t)b * nbest + kk) * T + p] = -1;
+    }
+    if (r < nbest && r < n) {
+        int node = A.node[r];
+        int *out = tokens + ((size_t)b * nbest + r) * T;
+        for (int p = A.len[r] - 1; p >= 0 && node != ROOT; --p) {  // len <= T_n <= T: one label per frame at most
+            const unsigned long long key =
+                __hip_atomic_load(&table[(unsigned)node & mask], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            out[p] = (int)(unsigned)(key & 0xffffffffull);
+            node = (int)(unsigned)(key >> 32);
+        }
+    }
+}
+
+int check_rows(int B, int T, int C, int blank) {
+    if (B <= 0 || T <= 0 || C <= 0 || blank < 0 || blank >= C) return PIKA_EINVAL;
+    if (B > 65535) return PIKA_ETOOBIG;  // B is a grid's y extent
+    return PIKA_OK;
+}
+
+int check_beam(int B, int T, int beam) {
+    if (B <= 0 || T <= 0 || beam <= 0) return PIKA_EINVAL;
+    if (beam > MAX_BEAM || B > 65535 || 2ll * T * beam > (1ll << 28)) return PIKA_ETOOBIG;
+    return PIKA_OK;
+}
+
+size_t table_slots(int T, int beam) {
+    size_t n = 64;
+    while (n < 2 * (size_t)T * beam) n <<= 1;
+    return n;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pika_ctc_decode_rows(const float *x, long long stride_t, long long stride_b, const int *input_lengths, int B, int T,
+                         int C, int blank, int K, int logits, float *blank_lp, float *top_val, int *top_idx, float *lse,
+                         void *stream) {
+    if (int rc = check_rows(B, T, C, blank)) return rc;
+    if (K <= 0) return PIKA_EINVAL;
+    if (K > MAX_K) return PIKA_ETOOBIG;
+    if (!x || !input_lengths || !blank_lp || !top_val || !top_idx || (logits && !lse)) return PIKA_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)T, (unsigned)B);
+    if (K == 1)
+        hipLaunchKernelGGL(ctc_rows_kernel<false>, grid, dim3(ROW_THREADS), 0, s, x, stride_t, stride_b, input_lengths,
+                           B, T, C, blank, K, logits, blank_lp, top_val, top_idx, lse);
+    else
+        hipLaunchKernelGGL(ctc_rows_kernel<true>, grid, dim3(ROW_THREADS), 0, s, x, stride_t, stride_b, input_lengths,
+                           B, T, C, blank, K, logits, blank_lp, top_val, top_idx, lse);
+    return (int)hipGetLastError();
+}
+
+int pika_ctc_greedy(const float *blank_lp, const float *top_val, const int *top_idx, const int *input_lengths, int B,
+                    int T, int C, int blank, int *tokens, int *lengths, float *scores, int *frames, void *stream) {
+    if (int rc = check_rows(B, T, C, blank)) return rc;
+    if (!blank_lp || !top_val || !top_idx || !input_lengths || !tokens || !lengths || !scores || !frames)
+        return PIKA_EINVAL;
+    hipLaunchKernelGGL(ctc_greedy_kernel, dim3((unsigned)B), dim3(256), 0, static_cast<hipStream_t>(stream), blank_lp,
+                       top_val, top_idx, input_lengths, B, T, blank, tokens, lengths, scores, frames);
+    return (int)hipGetLastError();
+}
+
+size_t pika_ctc_beam_scratch_bytes(int B, int T, int beam) {
+    if (check_beam(B, T, beam)) return 0;
+    return 8 * (size_t)B * table_slots(T, beam);
+}
+
+int pika_ctc_beam_search(const float *x, long long stride_t, long long stride_b, const float *lse,
+                         const float *blank_lp, const float *top_val, const int *top_idx, const int *input_lengths,
+                         int B, int T, int C, int blank, int beam, int nbest, int *tokens, int *lengths, float *scores,
+                         void *scratch, void *stream) {
+    if (int rc = check_rows(B, T, C, blank)) return rc;
+    if (nbest <= 0) return PIKA_EINVAL;
+    if (int rc = check_beam(B, T, beam)) return rc;
+    if (nbest > beam) return PIKA_ETOOBIG;
+    if (!x || !blank_lp || !top_val || !top_idx || !input_lengths || !tokens || !lengths || !scores || !scratch)
+        return PIKA_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t slots = table_slots(T, beam);
+    if (hipError_t e = hipMemsetAsync(scratch, 0xff, 8 * (size_t)B * slots, s)) return (int)e;  // every key EMPTY
+    hipLaunchKernelGGL(ctc_beam_kernel, dim3((unsigned)B), dim3(64), 0, s, x, stride_t, stride_b, lse, blank_lp, top_val,
+                       top_idx, input_lengths, B, T, blank, beam, nbest, tokens, lengths, scores,
+                       static_cast<unsigned long long *>(scratch), (unsigned)(slots - 1));
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

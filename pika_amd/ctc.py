@@ -9,6 +9,13 @@ The surface is `torch.nn.functional.ctc_loss`'s -- the loss the reference's LAS 
     ctc_align(log_probs, targets, input_lengths, target_lengths, blank=0) -> (scores (B,), frame_labels (B, T))
     ctc_align_from_logits(logits, ...)
 
+and the decoders (include/pika_ctc_decode.h, csrc/ctc_decode.hip), which need no transcript:
+
+    ctc_greedy_decode(log_probs, input_lengths, blank=0) -> (tokens (B,T), lengths (B,), scores (B,), frames (B,T))
+    ctc_beam_search(log_probs, input_lengths, beam=16, nbest=1, blank=0)
+        -> (tokens (B,nbest,T), lengths (B,nbest), scores (B,nbest))
+    ctc_greedy_decode_from_logits(logits, ...), ctc_beam_search_from_logits(logits, ...)
+
 Differences from torch, on purpose:
 
 * THE GRADIENT IS THE TRUE DERIVATIVE.  torch's native CTC backward returns `exp(log_probs) - occ` for d/d log_probs,
@@ -33,6 +40,7 @@ import torch
 from . import _lib
 
 MAX_STATES = 1024   # 2 * U_max + 1: one workgroup spans the state axis
+MAX_BEAM = 64       # one lane per beam slot
 
 
 def _ptr(t):
@@ -238,3 +246,123 @@ def ctc_align(log_probs, targets, input_lengths, target_lengths, blank=0):
 def ctc_align_from_logits(logits, targets, input_lengths, target_lengths, blank=0):
     """`ctc_align` of log_softmax(logits, -1) without materialising the log-probabilities."""
     return _align(logits, "logits", targets, input_lengths, target_lengths, blank, True)
+
+
+def _decode_rows(x, what, input_lengths, blank, K, logits):
+    """Checks + the row pass: (x as (T,B,C) with unit class stride, il i32, blank_lp, top_val, top_idx, lse or None,
+    unbatched)."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("pika_amd ctc decode: %s must live on a HIP device (there is no CPU path)" % what)
+    if x.dtype != torch.float32:
+        raise TypeError("%s must be float32, got %s" % (what, x.dtype))
+    x = x.detach()
+    unbatched = x.dim() == 2
+    if unbatched:
+        x = x.unsqueeze(1)
+    if x.dim() != 3:
+        raise ValueError("%s must be (T,B,C) or (T,C), got %s" % (what, tuple(x.shape)))
+    T, B, C = x.shape
+    if T < 1 or B < 1 or C < 1:
+        raise ValueError("%s has an empty dimension: %s" % (what, tuple(x.shape)))
+    if not 0 <= blank < C:
+        raise ValueError("blank=%d outside [0,%d)" % (blank, C))
+    il = torch.as_tensor(input_lengths)
+    if il.dtype not in (torch.int32, torch.int64):
+        raise TypeError("input_lengths must be int32 or int64, got %s" % il.dtype)
+    il = il.reshape(-1).to(x.device, torch.int32).contiguous()
+    if il.numel() != B:
+        raise ValueError("input_lengths must hold B = %d entries" % B)
+    # the kernels take the two outer strides: only the class axis has to be dense (one copy when it is not)
+    if C > 1 and x.stride(2) != 1:
+        x = x.contiguous()
+    lib = _lib.lib()
+    with torch.cuda.device(x.device):
+        blank_lp = torch.empty((T, B), dtype=torch.float32, device=x.device)
+        top_val = torch.empty((T, B, K), dtype=torch.float32, device=x.device)
+        top_idx = torch.empty((T, B, K), dtype=torch.int32, device=x.device)
+        lse = torch.empty((T, B), dtype=torch.float32, device=x.device) if logits else None
+        _lib.check(lib.pika_ctc_decode_rows(_ptr(x), x.stride(0), x.stride(1), _ptr(il), B, T, C, blank, K, int(logits),
+                                            _ptr(blank_lp), _ptr(top_val), _ptr(top_idx), _ptr(lse), _stream()),
+                   "pika_ctc_decode_rows")
+    return x, il, blank_lp, top_val, top_idx, lse, unbatched
+
+
+def _greedy(x, what, input_lengths, blank, logits):
+    blank = int(blank)
+    x, il, blank_lp, top_val, top_idx, _, unbatched = _decode_rows(x, what, input_lengths, blank, 1, logits)
+    T, B, C = x.shape
+    lib = _lib.lib()
+    with torch.cuda.device(x.device):
+        tokens = torch.empty((B, T), dtype=torch.int32, device=x.device)
+        frames = torch.empty((B, T), dtype=torch.int32, device=x.device)
+        lengths = torch.empty(B, dtype=torch.int32, device=x.device)
+        scores = torch.empty(B, dtype=torch.float32, device=x.device)
+        _lib.check(lib.pika_ctc_greedy(_ptr(blank_lp), _ptr(top_val), _ptr(top_idx), _ptr(il), B, T, C, blank,
+                                       _ptr(tokens), _ptr(lengths), _ptr(scores), _ptr(frames), _stream()),
+                   "pika_ctc_greedy")
+    out = (tokens, lengths, scores, frames)
+    return tuple(o[0] for o in out) if unbatched else out
+
+
+def _beam(x, what, input_lengths, beam, nbest, blank, logits):
+    blank, beam, nbest = int(blank), int(beam), int(nbest)
+    if not 1 <= nbest <= beam <= MAX_BEAM:
+        raise ValueError("need 1 <= nbest <= beam <= %d, got beam=%d nbest=%d" % (MAX_BEAM, beam, nbest))
+    x, il, blank_lp, top_val, top_idx, lse, unbatched = _decode_rows(x, what, input_lengths, blank, 2 * beam, logits)
+    T, B, C = x.shape
+    lib = _lib.lib()
+    nbytes = lib.pika_ctc_beam_scratch_bytes(B, T, beam)
+    if nbytes == 0:
+        raise ValueError("(B,T,beam) = (%d,%d,%d) not supported" % (B, T, beam))
+    with torch.cuda.device(x.device):
+        tokens = torch.empty((B, nbest, T), dtype=torch.int32, device=x.device)
+        lengths = torch.empty((B, nbest), dtype=torch.int32, device=x.device)
+        scores = torch.empty((B, nbest), dtype=torch.float32, device=x.device)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        _lib.check(lib.pika_ctc_beam_search(_ptr(x), x.stride(0), x.stride(1), _ptr(lse), _ptr(blank_lp), _ptr(top_val),
+                                            _ptr(top_idx), _ptr(il), B, T, C, blank, beam, nbest, _ptr(tokens),
+                                            _ptr(lengths), _ptr(scores), _ptr(scratch), _stream()),
+                   "pika_ctc_beam_search")
+    out = (tokens, lengths, scores)
+    return tuple(o[0] for o in out) if unbatched else out
+
+
+def ctc_greedy_decode(log_probs, input_lengths, blank=0):
+    """Best path: the per-frame arg-max (equal values: the lowest class), repeats merged, blanks dropped.
+
+    log_probs (T,B,C) or (T,C) float32 on a HIP device, any stride; input_lengths (B,) int32 or int64, on the CPU or the
+    device, clamped on the device to [1,T].  Returns (tokens (B,T) i32, lengths (B,) i32, scores (B,) f32,
+    frames (B,T) i32): scores is the sum of the chosen values over t < T_n, frames[n,k] the first frame of the run
+    that emits tokens[n,k]; both tokens and frames are -1 beyond lengths[n].  (T,C) input: no batch axis in the
+    outputs.  No autograd, no host synchronisation; capturable in a `torch.cuda.graph` with the lengths on the device."""
+    return _greedy(log_probs, "log_probs", input_lengths, blank, False)
+
+
+def ctc_greedy_decode_from_logits(logits, input_lengths, blank=0):
+    """`ctc_greedy_decode` of log_softmax(logits, -1): the row's log-sum-exp is taken in the pass that picks the
+    arg-max, and the scores are sums of logit - lse."""
+    return _greedy(logits, "logits", input_lengths, blank, True)
+
+
+def ctc_beam_search(log_probs, input_lengths, beam=16, nbest=1, blank=0):
+    """Prefix beam search over the full vocabulary, 1 <= nbest <= beam <= 64 (ValueError beyond).
+
+    Every prefix l of the beam carries (p_b, p_nb), tot = p_b (+) p_nb.  At each frame blank adds lp[blank] + tot to
+    p_b(l); c == last(l) adds lp[c] + p_nb to p_nb(l) and lp[c] + p_b to p_nb(l+c); any other class adds lp[c] + tot to
+    p_nb(l+c); contributions to one label sequence are summed whichever parent they come from; the `beam` best by tot
+    survive.  No class is pruned.  Ties: higher tot (the fp32 value the search carries), then prefixes already in the
+    beam by their previous rank, then fresh ones by parent rank; fresh children of one parent keep the row pass's order
+    -- higher value, then lower class -- and the child that repeats the parent's last label stands among children of
+    equal tot by its class.  So "class ascending" holds wherever equal tot comes from equal values; two children of one
+    parent whose different values round to the same fp32 tot keep the order of their values
+    (include/pika_ctc_decode.h).
+
+    Returns (tokens (B,nbest,T) i32, lengths (B,nbest) i32, scores (B,nbest) f32), best first; an entry that does not
+    exist (fewer distinct prefixes than nbest) has length -1, score -inf and tokens -1.  Inputs, synchronisation and
+    graph capture as `ctc_greedy_decode`."""
+    return _beam(log_probs, "log_probs", input_lengths, beam, nbest, blank, False)
+
+
+def ctc_beam_search_from_logits(logits, input_lengths, beam=16, nbest=1, blank=0):
+    """`ctc_beam_search` of log_softmax(logits, -1) without materialising the log-probabilities."""
+    return _beam(logits, "logits", input_lengths, beam, nbest, blank, True)
