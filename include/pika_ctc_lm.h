@@ -1,0 +1,74 @@
+/*
+ * include/pika_ctc_lm.h -- C ABI of the MI355X-native CTC prefix beam search with n-gram LM shallow fusion
+ * (libpika_amd.so).  Conventions, the tensor contract of x / input_lengths / blank_lp / top_val / top_idx / lse and
+ * the acoustic recursion (p_b, p_nb) are those of pika_ctc_decode.h; the row pass pika_ctc_decode_rows is used as it
+ * is, with K = candidates.
+ *
+ * The LM is an ilabel-sorted CSR back-off FST in DEVICE memory, the layout of pika_decode.h:
+ *   fst_offsets   i64 (S+1)  arcs of state s: [offsets[s], offsets[s+1])
+ *   fst_ilabel    i32 (A)    ascending inside a state; class c is label c + label_offset; back-off arcs carry backoff_id
+ *   fst_weight    f32 (A)    costs (-log, natural)
+ *   fst_nextstate i32 (A)
+ *   fst_final     f32 (S)    final cost, +inf = not final
+ * step(s, c): look for the arc c + label_offset out of s (lower bound over the state's arcs); found: the increment is
+ * -(back-off cost so far + weight), the new state its nextstate.  Otherwise take s's back-off arc, add its weight, move
+ * to its nextstate and repeat; a state with neither arc, or more than 8 back-off hops: the child does not exist (LM
+ * probability zero; it is excluded whatever lm_weight is).  The first match along the chain wins; no disambiguation
+ * labels, no state sets.  final(s): the same walk to the first state with a finite final cost.
+ * The device code ends on ANY table: the hop count, every bisection and every probe loop have fixed trip limits, arc
+ * ranges are clamped to [0, A] and a state outside [0, S) ends the walk ("does not exist").
+ *
+ * Fused score of a prefix l: F(l) = tot(l) + bonus(l), bonus(l) = lm_weight * LM(l) + length_bonus * |l|, LM(l) the sum
+ * of the step increments along l from `start` -- a function of the label sequence alone.  Only the ranking uses F;
+ * contributions to one label sequence are summed whichever parent they come from, as in pika_ctc_decode.h.
+ * Candidates of a parent l at frame t: the `candidates` best non-blank classes of the row (the row pass's order), plus
+ * last(l), plus every class whose child is in the beam (these two take their value from the full row).  This is a
+ * pruning: it is exact only when candidates >= C - 1.  (An LM term makes a fresh child's score non-monotone in lp[c],
+ * so the K = 2 beam argument of the plain search does not apply.)
+ * Tie order (total): higher F (the fp32 value carried); then prefixes already in the beam, by previous rank; then
+ * fresh ones by parent rank; then class ascending.
+ * End: with use_final every surviving prefix adds lm_weight * final(state); those whose walk finds no final state drop
+ * out; the beam is re-sorted by the resulting fp32 score, ties by the rank before.
+ * Numerics: fp32 (p_b, p_nb) with the head's tot moved into an fp64 offset every 8 frames; bonus in fp64 per slot (each
+ * increment rounded to fp32 once), renormalised the same way; F = fp32(tot + bonus) of the renormalised values.
+ * Limits: 1 <= nbest <= beam <= 64, 1 <= candidates <= 128, B <= 65535, 2 T beam <= 2^28, S >= 1, A >= 0,
+ * start in [0,S) (PIKA_EINVAL / PIKA_ETOOBIG as in pika_ctc_decode.h, before any launch).
+ */
+#ifndef PIKA_CTC_LM_H
+#define PIKA_CTC_LM_H
+
+#include <stddef.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#ifndef PIKA_OK
+#define PIKA_OK 0
+#define PIKA_EINVAL (-1)   /* null pointer / non-positive dimension / blank out of range */
+#define PIKA_ETOOBIG (-2)  /* beyond a stated limit */
+#endif
+
+/* Bytes of device scratch of pika_ctc_lm_beam_search; 0 for dimensions the call refuses (B, T, beam, candidates < 1,
+ * beam > 64, candidates > 128, B > 65535, 2 T beam > 2^28).  With N = the smallest power of two >= max(64, 2 T beam):
+ * one open-addressing table of N 8-byte (parent node, token) keys per utterance, 8 B N bytes (the trie of
+ * pika_ctc_beam_search; the LM state and bonus of a prefix are recomputed from its parent, so a node has no payload). */
+size_t pika_ctc_lm_scratch_bytes(int B, int T, int beam, int candidates);
+
+/* Fused search on the K = candidates arrays of the row pass (same x / strides / lse / B, T, C, blank, lengths).
+ *   tokens    i32 (B,nbest,T)  best first; -1 beyond the length
+ *   lengths   i32 (B,nbest)    -1 for a missing entry
+ *   scores    f32 (B,nbest)    the fused score F the ranking used (+ the final term with use_final); -inf when missing
+ *   am_scores f32 (B,nbest)    tot alone: log of the summed probability of the paths the beam kept; -inf when missing */
+int pika_ctc_lm_beam_search(const float *x, long long stride_t, long long stride_b, const float *lse,
+                            const float *blank_lp, const float *top_val, const int *top_idx, const int *input_lengths,
+                            int B, int T, int C, int blank, int beam, int nbest, const long long *fst_offsets,
+                            const int *fst_ilabel, const float *fst_weight, const int *fst_nextstate,
+                            const float *fst_final, int num_states, int num_arcs, int start, int backoff_id,
+                            int label_offset, int candidates, float lm_weight, float length_bonus, int use_final,
+                            int *tokens, int *lengths, float *scores, float *am_scores, void *scratch, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* PIKA_CTC_LM_H */

@@ -16,6 +16,14 @@ and the decoders (include/pika_ctc_decode.h, csrc/ctc_decode.hip), which need no
         -> (tokens (B,nbest,T), lengths (B,nbest), scores (B,nbest))
     ctc_greedy_decode_from_logits(logits, ...), ctc_beam_search_from_logits(logits, ...)
 
+and the search with an n-gram LM fused in (include/pika_ctc_lm.h, csrc/ctc_lm.hip):
+
+    CtcNgramLm(fst, backoff_id, label_offset=1, device=None)
+    ctc_beam_search_lm(log_probs, input_lengths, lm, beam=16, nbest=1, blank=0, lm_weight=0.5, length_bonus=0.0,
+                       candidates=None, use_final=True)
+        -> (tokens (B,nbest,T), lengths (B,nbest), scores (B,nbest), am_scores (B,nbest))
+    ctc_beam_search_lm_from_logits(logits, ...same...)
+
 Differences from torch, on purpose:
 
 * THE GRADIENT IS THE TRUE DERIVATIVE.  torch's native CTC backward returns `exp(log_probs) - occ` for d/d log_probs,
@@ -35,12 +43,15 @@ targets take their offsets from a device cumsum; U_max is the largest target len
 lengths live there (no sync) and by ONE device-to-host copy per call when they live on the device (the trade
 `rnnt_loss(compact=True)` makes; it raises under stream capture).
 """
+import numpy as np
 import torch
 
 from . import _lib
 
 MAX_STATES = 1024   # 2 * U_max + 1: one workgroup spans the state axis
 MAX_BEAM = 64       # one lane per beam slot
+MAX_CANDIDATES = 128
+MAX_BACKOFF_HOPS = 8
 
 
 def _ptr(t):
@@ -366,3 +377,131 @@ def ctc_beam_search(log_probs, input_lengths, beam=16, nbest=1, blank=0):
 def ctc_beam_search_from_logits(logits, input_lengths, beam=16, nbest=1, blank=0):
     """`ctc_beam_search` of log_softmax(logits, -1) without materialising the log-probabilities."""
     return _beam(logits, "logits", input_lengths, beam, nbest, blank, True)
+
+
+class CtcNgramLm(object):
+    """An n-gram back-off LM for `ctc_beam_search_lm`: the arrays of an `NgramFst` (pika_amd/decoder/ngram_fst.py: it
+    reads OpenFST binary and text files), checked on the host, uploaded once and kept.
+
+    Class c of the acoustic model is FST label c + label_offset (default 1: label 0 is epsilon); back-off arcs carry
+    `backoff_id`.  ValueError when: a `nextstate` or `start` is out of range; a state has more than one back-off arc; the
+    back-off graph has a cycle or a chain of more than 8 hops; `backoff_id` collides with a class label (it lies in
+    [label_offset, the largest other label of the table]; `ctc_beam_search_lm` checks it against C as well); the
+    offsets do not describe the arc arrays.  The device code ends on any table all the same."""
+
+    def __init__(self, fst, backoff_id, label_offset=1, device=None):
+        offsets = np.ascontiguousarray(fst.offsets, dtype=np.int64)
+        ilabel = np.ascontiguousarray(fst.ilabel, dtype=np.int32)
+        weight = np.ascontiguousarray(fst.weight, dtype=np.float32)
+        nextstate = np.ascontiguousarray(fst.nextstate, dtype=np.int32)
+        final = np.ascontiguousarray(fst.final, dtype=np.float32)
+        S, A = len(offsets) - 1, len(ilabel)
+        backoff_id, label_offset, start = int(backoff_id), int(label_offset), int(fst.start)
+        if S < 1 or len(final) != S or len(weight) != A or len(nextstate) != A or A >= 2 ** 31 or S >= 2 ** 31:
+            raise ValueError("CtcNgramLm: inconsistent FST arrays (%d states, %d arcs)" % (S, A))
+        if offsets[0] != 0 or offsets[-1] != A or np.any(np.diff(offsets) < 0):
+            raise ValueError("CtcNgramLm: offsets do not describe the arc arrays")
+        if not 0 <= start < S:
+            raise ValueError("CtcNgramLm: start state %d outside [0,%d)" % (start, S))
+        if A and (nextstate.min() < 0 or nextstate.max() >= S):
+            raise ValueError("CtcNgramLm: a nextstate lies outside [0,%d)" % S)
+        src = np.repeat(np.arange(S, dtype=np.int64), np.diff(offsets))
+        is_bo = ilabel == backoff_id
+        if np.any(np.bincount(src[is_bo], minlength=S) > 1):
+            raise ValueError("CtcNgramLm: a state has more than one back-off arc")
+        other = ilabel[~is_bo]
+        if other.size and label_offset <= backoff_id <= int(other.max()):
+            raise ValueError("CtcNgramLm: backoff_id %d collides with a class label (labels %d..%d)"
+                             % (backoff_id, label_offset, int(other.max())))
+        bo = np.full(S, -1, dtype=np.int64)       # the state a back-off arc leads to
+        bo[src[is_bo]] = nextstate[is_bo]
+        cur = np.arange(S, dtype=np.int64)
+        for _ in range(MAX_BACKOFF_HOPS):
+            cur = np.where(cur >= 0, bo[np.maximum(cur, 0)], -1)
+        if np.any((cur >= 0) & (bo[np.maximum(cur, 0)] >= 0)):
+            raise ValueError("CtcNgramLm: a back-off chain is longer than %d hops (or the back-off graph has a cycle)"
+                             % MAX_BACKOFF_HOPS)
+        if not torch.cuda.is_available():
+            raise RuntimeError("pika_amd CtcNgramLm: needs a HIP device (there is no CPU path)")
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise RuntimeError("pika_amd CtcNgramLm: device %s is not a HIP device (there is no CPU path)" % dev)
+        # always an indexed device: "cuda" and "cuda:0" must compare equal to a tensor's device
+        self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+        self.num_states, self.num_arcs, self.start = S, A, start
+        self.backoff_id, self.label_offset = backoff_id, label_offset
+        self.offsets, self.ilabel, self.weight, self.nextstate, self.final = (
+            torch.from_numpy(v).to(self.device) for v in (offsets, ilabel, weight, nextstate, final))
+
+
+def _beam_lm(x, what, input_lengths, lm, beam, nbest, blank, lm_weight, length_bonus, candidates, use_final, logits):
+    blank, beam, nbest = int(blank), int(beam), int(nbest)
+    if not isinstance(lm, CtcNgramLm):
+        raise TypeError("lm must be a CtcNgramLm, got %s" % type(lm).__name__)
+    if not 1 <= nbest <= beam <= MAX_BEAM:
+        raise ValueError("need 1 <= nbest <= beam <= %d, got beam=%d nbest=%d" % (MAX_BEAM, beam, nbest))
+    candidates = min(2 * beam, MAX_CANDIDATES) if candidates is None else int(candidates)
+    if not 1 <= candidates <= MAX_CANDIDATES:
+        raise ValueError("need 1 <= candidates <= %d, got %d" % (MAX_CANDIDATES, candidates))
+    x, il, blank_lp, top_val, top_idx, lse, unbatched = _decode_rows(x, what, input_lengths, blank, candidates, logits)
+    T, B, C = x.shape
+    if 0 <= lm.backoff_id - lm.label_offset < C:
+        raise ValueError("the LM's backoff_id %d is the label of class %d" % (lm.backoff_id,
+                                                                             lm.backoff_id - lm.label_offset))
+    if lm.device != x.device:
+        raise ValueError("the LM lives on %s, %s on %s" % (lm.device, what, x.device))
+    lib = _lib.lib()
+    nbytes = lib.pika_ctc_lm_scratch_bytes(B, T, beam, candidates)
+    if nbytes == 0:
+        raise ValueError("(B,T,beam,candidates) = (%d,%d,%d,%d) not supported" % (B, T, beam, candidates))
+    with torch.cuda.device(x.device):
+        tokens = torch.empty((B, nbest, T), dtype=torch.int32, device=x.device)
+        lengths = torch.empty((B, nbest), dtype=torch.int32, device=x.device)
+        scores = torch.empty((B, nbest), dtype=torch.float32, device=x.device)
+        am_scores = torch.empty((B, nbest), dtype=torch.float32, device=x.device)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        _lib.check(lib.pika_ctc_lm_beam_search(
+            _ptr(x), x.stride(0), x.stride(1), _ptr(lse), _ptr(blank_lp), _ptr(top_val), _ptr(top_idx), _ptr(il), B, T,
+            C, blank, beam, nbest, _ptr(lm.offsets), _ptr(lm.ilabel), _ptr(lm.weight), _ptr(lm.nextstate),
+            _ptr(lm.final), lm.num_states, lm.num_arcs, lm.start, lm.backoff_id, lm.label_offset, candidates,
+            float(lm_weight), float(length_bonus), int(bool(use_final)), _ptr(tokens), _ptr(lengths), _ptr(scores),
+            _ptr(am_scores), _ptr(scratch), _stream()), "pika_ctc_lm_beam_search")
+    out = (tokens, lengths, scores, am_scores)
+    return tuple(o[0] for o in out) if unbatched else out
+
+
+def ctc_beam_search_lm(log_probs, input_lengths, lm, beam=16, nbest=1, blank=0, lm_weight=0.5, length_bonus=0.0,
+                       candidates=None, use_final=True):
+    """Prefix beam search with an n-gram LM fused into the ranking (shallow fusion), 1 <= nbest <= beam <= 64,
+    1 <= candidates <= 128 (ValueError beyond); `candidates=None` means min(2 * beam, 128).
+
+    A prefix l is ranked by F(l) = tot(l) + lm_weight * LM(l) + length_bonus * |l|.  tot and its (p_b, p_nb) recursion
+    are `ctc_beam_search`'s: contributions to one label sequence are summed whichever parent they come from, and only
+    the ranking uses F.  LM(l) is the sum of the LM's log-probabilities along l from its start state, each step the
+    first match along the back-off chain of `lm` (a `CtcNgramLm`): the wanted arc if the state has it, otherwise the
+    back-off arc's cost and its target state, at most 8 hops.  A class the LM cannot reach has probability zero: that
+    child is excluded whatever `lm_weight` is, 0 included.
+
+    THE CANDIDATES ARE A PRUNING.  A parent offers, per frame, the `candidates` best non-blank classes of the row (higher
+    value, then lower class), its own last label, and every class whose child is already in the beam.  This is exact
+    only when candidates >= C - 1: with an LM term a child's score is not monotone in the frame's log-prob, so the
+    argument that makes `ctc_beam_search` exact with 2 * beam classes does not hold here.
+
+    Ties: higher F (the fp32 value the search carries), then prefixes already in the beam by their previous rank, then
+    fresh ones by parent rank, then class ascending.  With `use_final` every surviving prefix adds lm_weight times the
+    log of the LM's final probability (through back-off if need be), prefixes with none drop out, and the beam is
+    sorted again by that score (ties: the rank before).
+
+    Returns (tokens (B,nbest,T) i32, lengths (B,nbest) i32, scores (B,nbest) f32, am_scores (B,nbest) f32), best first:
+    `scores` is the fused score the ranking used (with the final term when asked), `am_scores` is tot alone.  A missing
+    entry has length -1, scores -inf and tokens -1.  Inputs, strides, length clamping, no autograd, no host
+    synchronisation and graph capture as `ctc_beam_search`."""
+    return _beam_lm(log_probs, "log_probs", input_lengths, lm, beam, nbest, blank, lm_weight, length_bonus, candidates,
+                    use_final, False)
+
+
+def ctc_beam_search_lm_from_logits(logits, input_lengths, lm, beam=16, nbest=1, blank=0, lm_weight=0.5,
+                                   length_bonus=0.0, candidates=None, use_final=True):
+    """`ctc_beam_search_lm` of log_softmax(logits, -1) without materialising the log-probabilities."""
+    return _beam_lm(logits, "logits", input_lengths, lm, beam, nbest, blank, lm_weight, length_bonus, candidates,
+                    use_final, True)
