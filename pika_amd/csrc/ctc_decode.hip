@@ -20,33 +20,20 @@
 //            insert-or-find in the utterance's open-addressing table of (parent node, token) keys: the node IS the
 //            table slot, so a prefix that left the beam and comes back is the same node and its children merge with a
 //            descendant that stayed.  Numerics as the loss: fp32 (p_b, p_nb), the best tot moved into an fp64 offset
-//            every RENORM frames.  The n-best back-trace walks the table in the same launch.
+//            every RENORM frames.  The n-best back-trace walks the table in the same launch.  What ctc_lm.hip's fused
+//            search does the same way (beam, trie, slot work, order, renormalisation, tail) is in ctc_search_core.h.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ctc_search_core.h"
 #include "pika_ctc_decode.h"
 
 namespace {
 
-constexpr float NEG = -1.0e30f;  // "log zero": finite, so NEG+NEG / NEG-NEG never make NaN
-constexpr float NEG_HALF = -0.5e30f;
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float LN2 = 0.6931471805599453f;
 constexpr int ROW_THREADS = 256;
 constexpr int ROW_STAGE = 8192;  // classes of a row staged in LDS for the second look
 constexpr int POOL_CAP = 1024;   // survivors ranked by counting
-constexpr int MAX_K = 128;
-constexpr int MAX_BEAM = 64;
-constexpr int RENORM = 8;
-constexpr int ROOT = 0x7ffffffe;  // node of the empty prefix
-constexpr int NONE = 0x7ffffffd;  // its parent
-constexpr int PENDING = -1;
-constexpr unsigned long long EMPTY = ~0ull;
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-__device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // order-preserving integer image of a finite float; 0 is below every image
 __device__ inline unsigned fkey(float v) {
@@ -54,16 +41,6 @@ __device__ inline unsigned fkey(float v) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ inline float funkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-
-__device__ inline float addn(float a, float b) { return fmaxf(a + b, NEG); }
-
-// log(exp(x)+exp(y)) on the transcendental pipe; NEG when both are "log zero"
-__device__ inline float lse2(float x, float y) {
-    const float m = fmaxf(x, y);
-    if (!(m > NEG_HALF)) return NEG;
-    const float e = __builtin_amdgcn_exp2f((x - m) * LOG2E) + __builtin_amdgcn_exp2f((y - m) * LOG2E);
-    return m + LN2 * __builtin_amdgcn_logf(e);
-}
 
 // ---------------------------------------------------------------------------------------------
 // rows.  grid = (T, B), block = 256.
@@ -317,32 +294,6 @@ __global__ __launch_bounds__(256) void ctc_greedy_kernel(const float *__restrict
 // ---------------------------------------------------------------------------------------------
 // search.  grid = B, block = 64: lane r owns beam slot r.
 // ---------------------------------------------------------------------------------------------
-struct Beam {
-    int node[MAX_BEAM];   // the prefix: slot of its (parent, token) key in the utterance's table, ROOT for the empty one
-    int last[MAX_BEAM];   // its last label, -1 for the empty prefix
-    int pnode[MAX_BEAM];  // its parent's node
-    int len[MAX_BEAM];
-    float pb[MAX_BEAM], pnb[MAX_BEAM], tot[MAX_BEAM];
-};
-
-__device__ inline unsigned long long trie_key(int parent, int token) {
-    return ((unsigned long long)(unsigned)parent << 32) | (unsigned)token;
-}
-
-// insert-or-find: every probe is an atomic, so a slot is never seen through a stale cache line; only this workgroup
-// touches the table
-__device__ inline int trie_node(unsigned long long *table, unsigned mask, int parent, int token) {
-    const unsigned long long key = trie_key(parent, token);
-    unsigned h = ((unsigned)parent * 0x9E3779B1u) ^ ((unsigned)token * 0x85EBCA6Bu);
-    h = (h ^ (h >> 15)) & mask;
-    for (unsigned probes = 0; probes <= mask; ++probes) {  // at most T * beam <= (mask + 1) / 2 keys: it ends early
-        const unsigned long long old = atomicCAS(&table[h], EMPTY, key);
-        if (old == EMPTY || old == key) break;
-        h = (h + 1) & mask;
-    }
-    return (int)h;
-}
-
 __global__ __launch_bounds__(64) void ctc_beam_kernel(const float *__restrict__ x, long long st, long long sb,
                                                       const float *__restrict__ lse, const float *__restrict__ blank_lp,
                                                       const float *__restrict__ top_val, const int *__restrict__ top_idx,
@@ -351,9 +302,9 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float *__restrict__ 
                                                       float *__restrict__ scores, unsigned long long *table_,
                                                       unsigned mask) {
     __shared__ Beam S[2];
-    __shared__ float cv[MAX_K];
-    __shared__ int ci[MAX_K];
-    __shared__ unsigned excl[MAX_BEAM][MAX_K / 32];
+    __shared__ float cv[MAX_CLASSES];
+    __shared__ int ci[MAX_CLASSES];
+    __shared__ unsigned excl[MAX_BEAM][MAX_CLASSES / 32];
     __shared__ int hasrep[MAX_BEAM];
     const int b = blockIdx.x, r = threadIdx.x, K = 2 * beam;
     const int Tn = clampi(Tn_[b], 1, T);
@@ -388,36 +339,13 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float *__restrict__ 
         const float lpb = plb, l = pl;
         if (t + 1 < Tn) fetch(t + 1);
         const bool act = r < n;
-        const int node_r = act ? A.node[r] : NONE, last_r = act ? A.last[r] : -1, pn_r = act ? A.pnode[r] : NONE;
-        const int len_r = act ? A.len[r] : 0;
-        const float pb_r = act ? A.pb[r] : NEG, pnb_r = act ? A.pnb[r] : NEG, tot_r = act ? A.tot[r] : NEG;
+        const Slot me = load_slot(A, r, act);
+        const int node_r = me.node, last_r = me.last, pn_r = me.pnode, len_r = me.len;
+        const float pb_r = me.pb, tot_r = me.tot;
         float g = NEG;  // the value of the slot's own last label: the one gather from the full row
         if (last_r >= 0) g = fmaxf(fmaxf(xb[(long long)t * st + last_r], NEG) - l, NEG);
-        for (int q = 0; q < MAX_K / 32; ++q) excl[r][q] = 0;
-        hasrep[r] = 0;
-        __syncthreads();
-        int ps = -1;  // the parent's slot, if the parent is in the beam
-        if (act && pn_r != NONE)
-            for (int q = 0; q < n; ++q)
-                if (A.node[q] == pn_r) ps = q;
-        int pos = -1;  // where the slot's last label stands in the frame's class list
-        if (last_r >= 0)
-            for (int j = 0; j < K; ++j)
-                if (ci[j] == last_r) pos = j;
-        if (pos >= 0) {
-            atomicOr(&excl[r][pos >> 5], 1u << (pos & 31));               // the repeat: scored with p_b, below
-            if (ps >= 0) atomicOr(&excl[ps][pos >> 5], 1u << (pos & 31));  // the parent's child that is in the beam
-        }
-        const bool rep_child = ps >= 0 && A.last[ps] == last_r;
-        if (rep_child) hasrep[ps] = 1;
-        float npb = NEG, npnb = NEG, s_stay = NEG;
-        if (act) {
-            npb = addn(lpb, tot_r);
-            if (last_r >= 0) npnb = addn(g, pnb_r);
-            if (ps >= 0) npnb = lse2(npnb, addn(g, rep_child ? A.pb[ps] : A.tot[ps]));
-            s_stay = lse2(npb, npnb);
-        }
-        __syncthreads();  // excl and hasrep are complete
+        float npb, npnb, s_stay;
+        slot_work(A, n, r, true, me, ci, K, lpb, g, excl, hasrep, npb, npnb, s_stay);
         const float s_rep = (last_r >= 0 && !hasrep[r]) ? addn(g, pb_r) : NEG;
         bool stay_open = s_stay > NEG_HALF, rep_open = s_rep > NEG_HALF;
         int j = -1;  // head of the slot's class list
@@ -448,7 +376,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float *__restrict__ 
             for (int o = 32; o > 0; o >>= 1) {
                 const float os = __shfl_xor(ws, o);
                 const unsigned ohi = __shfl_xor(whi, o), olo = __shfl_xor(wlo, o);
-                if (os > ws || (os == ws && (ohi < whi || (ohi == whi && olo < wlo)))) { ws = os; whi = ohi; wlo = olo; }
+                if (before(os, ohi, olo, ws, whi, wlo)) { ws = os; whi = ohi; wlo = olo; }
             }
             if (!(ws > NEG_HALF)) break;  // nothing left: fewer prefixes exist than the beam holds
             if (whi == bhi && wlo == blo && kind >= 0) {  // this slot's candidate won (keys are unique)
@@ -466,60 +394,22 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float *__restrict__ 
             }
         }
         __syncthreads();  // the new beam's k slots are written
-        if (r < k && N.node[r] == PENDING) N.node[r] = trie_node(table, mask, N.pnode[r], N.last[r]);
-        if (t % RENORM == RENORM - 1 && k > 0) {  // workgroup-uniform
-            const float m = N.tot[0];             // slot 0 is the best: finite
-            __syncthreads();
-            if (r < k) {
-                N.pb[r] = N.pb[r] > NEG_HALF ? N.pb[r] - m : NEG;
-                N.pnb[r] = N.pnb[r] > NEG_HALF ? N.pnb[r] - m : NEG;
-                N.tot[r] = N.tot[r] - m;
-            }
-            off += (double)m;
-        }
+        assign_node(N, r, r < k, table, mask);
+        if (renorm_due(t, k)) off += (double)renorm(N, r, r < k);
         cur ^= 1;
         n = k;
     }
     __syncthreads();
     const Beam &A = S[cur];
-    // n-best: lengths, scores, -1 beyond each length, then the back-trace through the table
-    if (r < nbest) {
-        const bool have = r < n;
-        lengths[(size_t)b * nbest + r] = have ? A.len[r] : -1;
-        scores[(size_t)b * nbest + r] = have ? (float)(off + (double)A.tot[r]) : -__builtin_inff();
-    }
-    for (int e = r; e < nbest * T; e += 64) {
-        const int kk = e / T, p = e - kk * T;
-        if (kk >= n || p >= A.len[kk]) tokens[((size_t)b * nbest + kk) * T + p] = -1;
-    }
-    if (r < nbest && r < n) {
-        int node = A.node[r];
-        int *out = tokens + ((size_t)b * nbest + r) * T;
-        for (int p = A.len[r] - 1; p >= 0 && node != ROOT; --p) {  // len <= T_n <= T: one label per frame at most
-            const unsigned long long key =
-                __hip_atomic_load(&table[(unsigned)node & mask], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            out[p] = (int)(unsigned)(key & 0xffffffffull);
-            node = (int)(unsigned)(key >> 32);
-        }
-    }
+    // n-best: scores here; lengths, tokens and the back-trace by the shared tail, slots in beam order
+    if (r < nbest) scores[(size_t)b * nbest + r] = r < n ? (float)(off + (double)A.tot[r]) : -__builtin_inff();
+    write_nbest<64>(A, n, [](int q) { return q; }, r, b, T, nbest, tokens, lengths, table, mask);
 }
 
 int check_rows(int B, int T, int C, int blank) {
     if (B <= 0 || T <= 0 || C <= 0 || blank < 0 || blank >= C) return PIKA_EINVAL;
     if (B > 65535) return PIKA_ETOOBIG;  // B is a grid's y extent
     return PIKA_OK;
-}
-
-int check_beam(int B, int T, int beam) {
-    if (B <= 0 || T <= 0 || beam <= 0) return PIKA_EINVAL;
-    if (beam > MAX_BEAM || B > 65535 || 2ll * T * beam > (1ll << 28)) return PIKA_ETOOBIG;
-    return PIKA_OK;
-}
-
-size_t table_slots(int T, int beam) {
-    size_t n = 64;
-    while (n < 2 * (size_t)T * beam) n <<= 1;
-    return n;
 }
 
 }  // namespace
@@ -531,7 +421,7 @@ int pika_ctc_decode_rows(const float *x, long long stride_t, long long stride_b,
                          void *stream) {
     if (int rc = check_rows(B, T, C, blank)) return rc;
     if (K <= 0) return PIKA_EINVAL;
-    if (K > MAX_K) return PIKA_ETOOBIG;
+    if (K > MAX_CLASSES) return PIKA_ETOOBIG;
     if (!x || !input_lengths || !blank_lp || !top_val || !top_idx || (logits && !lse)) return PIKA_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)T, (unsigned)B);
@@ -555,8 +445,8 @@ int pika_ctc_greedy(const float *blank_lp, const float *top_val, const int *top_
 }
 
 size_t pika_ctc_beam_scratch_bytes(int B, int T, int beam) {
-    if (check_beam(B, T, beam)) return 0;
-    return 8 * (size_t)B * table_slots(T, beam);
+    if (check_search_dims(B, T, beam, 1)) return 0;
+    return table_bytes(B, T, beam);
 }
 
 int pika_ctc_beam_search(const float *x, long long stride_t, long long stride_b, const float *lse,
@@ -565,16 +455,15 @@ int pika_ctc_beam_search(const float *x, long long stride_t, long long stride_b,
                          void *scratch, void *stream) {
     if (int rc = check_rows(B, T, C, blank)) return rc;
     if (nbest <= 0) return PIKA_EINVAL;
-    if (int rc = check_beam(B, T, beam)) return rc;
+    if (int rc = check_search_dims(B, T, beam, 1)) return rc;
     if (nbest > beam) return PIKA_ETOOBIG;
     if (!x || !blank_lp || !top_val || !top_idx || !input_lengths || !tokens || !lengths || !scores || !scratch)
         return PIKA_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t slots = table_slots(T, beam);
-    if (hipError_t e = hipMemsetAsync(scratch, 0xff, 8 * (size_t)B * slots, s)) return (int)e;  // every key EMPTY
+    if (hipError_t e = clear_tables(scratch, B, T, beam, s)) return (int)e;
     hipLaunchKernelGGL(ctc_beam_kernel, dim3((unsigned)B), dim3(64), 0, s, x, stride_t, stride_b, lse, blank_lp, top_val,
                        top_idx, input_lengths, B, T, blank, beam, nbest, tokens, lengths, scores,
-                       static_cast<unsigned long long *>(scratch), (unsigned)(slots - 1));
+                       static_cast<unsigned long long *>(scratch), (unsigned)(table_slots(T, beam) - 1));
     return (int)hipGetLastError();
 }
 

@@ -10,8 +10,8 @@
 //            lp[c], so there is no "head of the class list": `beam` rounds of a workgroup arg-max over every open cell
 //            and every stay follow, under the total order of the header; each thread keeps the best of its own cells
 //            in registers and only the round's winner looks at its cells again.  Nodes, the trie table, the fp32
-//            (p_b, p_nb) and the renormalisation are those of ctc_beam_kernel (helpers copied, that file is not
-//            touched); the bonus is renormalised with tot.  The end applies the final cost, re-sorts by counting and
+//            (p_b, p_nb) and the renormalisation are those of ctc_beam_kernel, shared through ctc_search_core.h;
+//            the bonus is renormalised with tot.  The end applies the final cost, re-sorts by counting and
 //            walks the table for the n-best.
 //   Every loop over the FST has a fixed trip limit (header): a malformed table cannot spin the workgroup.
 
@@ -19,61 +19,16 @@
 #include <stdint.h>
 
 #include "pika_ctc_lm.h"
+#include "ctc_search_core.h"
 
 namespace {
 
-constexpr float NEG = -1.0e30f;  // "log zero": finite, so NEG+NEG / NEG-NEG never make NaN
-constexpr float NEG_HALF = -0.5e30f;
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float LN2 = 0.6931471805599453f;
 constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / 64;
-constexpr int MAX_CAND = 128;
-constexpr int MAX_BEAM = 64;
 constexpr int MAX_HOPS = 8;
-constexpr int RENORM = 8;
-constexpr int CELLS_SMALL = 1024;                 // beam * candidates up to here: 12 KB of cells
-constexpr int CELLS_LARGE = MAX_BEAM * MAX_CAND;  // 96 KB
-constexpr int ROOT = 0x7ffffffe;                  // node of the empty prefix
-constexpr int NONE = 0x7ffffffd;                  // its parent
-constexpr int PENDING = -1;
+constexpr int CELLS_SMALL = 1024;                    // beam * candidates up to here: 12 KB of cells
+constexpr int CELLS_LARGE = MAX_BEAM * MAX_CLASSES;  // 96 KB
 constexpr unsigned NOKEY = 0xffffffffu;
-constexpr unsigned long long EMPTY = ~0ull;
-
-__device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ inline float addn(float a, float b) { return fmaxf(a + b, NEG); }
-
-// log(exp(x)+exp(y)) on the transcendental pipe; NEG when both are "log zero"
-__device__ inline float lse2(float x, float y) {
-    const float m = fmaxf(x, y);
-    if (!(m > NEG_HALF)) return NEG;
-    const float e = __builtin_amdgcn_exp2f((x - m) * LOG2E) + __builtin_amdgcn_exp2f((y - m) * LOG2E);
-    return m + LN2 * __builtin_amdgcn_logf(e);
-}
-
-__device__ inline unsigned long long trie_key(int parent, int token) {
-    return ((unsigned long long)(unsigned)parent << 32) | (unsigned)token;
-}
-
-// insert-or-find: every probe is an atomic, so a slot is never seen through a stale cache line; only this workgroup
-// touches the table
-__device__ inline int trie_node(unsigned long long *table, unsigned mask, int parent, int token) {
-    const unsigned long long key = trie_key(parent, token);
-    unsigned h = ((unsigned)parent * 0x9E3779B1u) ^ ((unsigned)token * 0x85EBCA6Bu);
-    h = (h ^ (h >> 15)) & mask;
-    for (unsigned probes = 0; probes <= mask; ++probes) {  // at most T * beam <= (mask + 1) / 2 keys: it ends early
-        const unsigned long long old = atomicCAS(&table[h], EMPTY, key);
-        if (old == EMPTY || old == key) break;
-        h = (h + 1) & mask;
-    }
-    return (int)h;
-}
-
-// (F, hi, lo) before (G, ghi, glo) in the total order: higher score, then the lower key
-__device__ inline bool before(float F, unsigned hi, unsigned lo, float G, unsigned ghi, unsigned glo) {
-    return F > G || (F == G && (hi < ghi || (hi == ghi && lo < glo)));
-}
 
 // ---------------------------------------------------------------------------------------------
 // the LM: per-lane walks through the CSR table, vector loads (every lane its own state and label)
@@ -152,14 +107,10 @@ __device__ inline bool lm_final(const Fst &f, int s, float &inc) {
 // ---------------------------------------------------------------------------------------------
 // search.  grid = B, block = 256: wave 0's lane r owns beam slot r, every thread owns cells tid, tid + 256, ...
 // ---------------------------------------------------------------------------------------------
-struct Beam {
-    int node[MAX_BEAM];   // the prefix: slot of its (parent, token) key in the utterance's table, ROOT for the empty one
-    int last[MAX_BEAM];   // its last label, -1 for the empty prefix
-    int pnode[MAX_BEAM];  // its parent's node
-    int len[MAX_BEAM];
-    int lmst[MAX_BEAM];   // its LM state
-    float pb[MAX_BEAM], pnb[MAX_BEAM], tot[MAX_BEAM];
+struct LmBeam : Beam {
+    // (bonus before lmst: measured 2% faster than the other order, profiles/ctc_search_refactor.txt)
     double bonus[MAX_BEAM];  // lm_weight * LM + length_bonus * len, less the offset moved out
+    int lmst[MAX_BEAM];      // its LM state
 };
 
 struct Args {
@@ -177,10 +128,10 @@ struct Args {
 
 template <int CELLS>
 __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst f) {
-    __shared__ Beam S[2];
-    __shared__ float cv[MAX_CAND];
-    __shared__ int ci[MAX_CAND];
-    __shared__ unsigned excl[MAX_BEAM][MAX_CAND / 32];
+    __shared__ LmBeam S[2];
+    __shared__ float cv[MAX_CLASSES];
+    __shared__ int ci[MAX_CLASSES];
+    __shared__ unsigned excl[MAX_BEAM][MAX_CLASSES / 32];
     __shared__ int hasrep[MAX_BEAM];
     __shared__ float gs[MAX_BEAM];  // the value of the slot's own last label
     // fresh children: cell r * ncand + j is class ci[j] under slot r, cell n * ncand + r the repeat of slot r's last label
@@ -205,7 +156,7 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
     int cur = 0, n = 1;
     double off = 0.0, boff = 0.0;  // what was moved out of tot and of bonus (identical in every thread)
     if (tid == 0) {
-        Beam &A = S[0];
+        LmBeam &A = S[0];
         A.node[0] = ROOT; A.last[0] = -1; A.pnode[0] = NONE; A.len[0] = 0; A.lmst[0] = a.start;
         A.pb[0] = 0.0f; A.pnb[0] = NEG; A.tot[0] = 0.0f; A.bonus[0] = 0.0;
     }
@@ -222,45 +173,20 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
     fetch(0);
     for (int t = 0; t < Tn; ++t) {  // workgroup-uniform
         __syncthreads();            // the previous frame's beam is complete; cv / ci / excl / the cells are free
-        const Beam &A = S[cur];
-        Beam &N = S[cur ^ 1];
-        if (tid < MAX_CAND) { cv[tid] = pv; ci[tid] = pi; }
+        const LmBeam &A = S[cur];
+        LmBeam &N = S[cur ^ 1];
+        if (tid < MAX_CLASSES) { cv[tid] = pv; ci[tid] = pi; }
         const float lpb = plb, l = pl;
         if (t + 1 < Tn) fetch(t + 1);
-        // ---- slot work (wave 0; the other waves only meet the barriers)
+        // ---- slot work (wave 0; the other waves only meet its barriers)
         const bool act = slots && r < n;
-        const int node_r = act ? A.node[r] : NONE, last_r = act ? A.last[r] : -1, pn_r = act ? A.pnode[r] : NONE;
-        const float pb_r = act ? A.pb[r] : NEG, pnb_r = act ? A.pnb[r] : NEG, tot_r = act ? A.tot[r] : NEG;
+        const Slot me = load_slot(A, r, act);
+        const int node_r = me.node, last_r = me.last, pn_r = me.pnode;
         float g = NEG;  // the value of the slot's own last label: the one gather from the full row
         if (last_r >= 0) g = fmaxf(fmaxf(xb[(long long)t * a.st + last_r], NEG) - l, NEG);
-        if (slots) {
-            for (int q = 0; q < MAX_CAND / 32; ++q) excl[r][q] = 0;
-            hasrep[r] = 0;
-            gs[r] = g;
-        }
-        __syncthreads();
-        float npb = NEG, npnb = NEG, s_stay = NEG;
-        if (act) {
-            int ps = -1;  // the parent's slot, if the parent is in the beam
-            if (pn_r != NONE)
-                for (int q = 0; q < n; ++q)
-                    if (A.node[q] == pn_r) ps = q;
-            int pos = -1;  // where the slot's last label stands in the frame's class list
-            if (last_r >= 0)
-                for (int j = 0; j < ncand; ++j)
-                    if (ci[j] == last_r) pos = j;
-            if (pos >= 0) {
-                atomicOr(&excl[r][pos >> 5], 1u << (pos & 31));               // the repeat: its own cell, scored with p_b
-                if (ps >= 0) atomicOr(&excl[ps][pos >> 5], 1u << (pos & 31));  // the parent's child that is in the beam
-            }
-            const bool rep_child = ps >= 0 && A.last[ps] == last_r;
-            if (rep_child) hasrep[ps] = 1;
-            npb = addn(lpb, tot_r);
-            if (last_r >= 0) npnb = addn(g, pnb_r);
-            if (ps >= 0) npnb = lse2(npnb, addn(g, rep_child ? A.pb[ps] : A.tot[ps]));
-            s_stay = lse2(npb, npnb);
-        }
-        __syncthreads();  // excl, hasrep and gs are complete
+        if (slots) gs[r] = g;
+        float npb, npnb, s_stay;
+        slot_work(A, n, r, slots, me, ci, ncand, lpb, g, excl, hasrep, npb, npnb, s_stay);  // gs is complete too
         // ---- the fresh children: one FST lookup per open cell
         const int nl = n * ncand, ne = nl + n;
         float bF = NEG;  // the best of this thread's open candidates: (score, key); bE: its cell, -1 for the stay
@@ -346,25 +272,18 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
             }
         }
         __syncthreads();  // the new beam's k slots are written
-        if (slots && r < k && N.node[r] == PENDING) N.node[r] = trie_node(table, mask, N.pnode[r], N.last[r]);
-        if (t % RENORM == RENORM - 1 && k > 0) {  // workgroup-uniform
-            const float m = N.tot[0];             // slot 0 has the best fused score: its tot is finite
-            const double mb = N.bonus[0];
-            __syncthreads();
-            if (slots && r < k) {
-                N.pb[r] = N.pb[r] > NEG_HALF ? N.pb[r] - m : NEG;
-                N.pnb[r] = N.pnb[r] > NEG_HALF ? N.pnb[r] - m : NEG;
-                N.tot[r] = N.tot[r] - m;
-                N.bonus[r] = N.bonus[r] - mb;
-            }
-            off += (double)m;
+        assign_node(N, r, slots && r < k, table, mask);
+        if (renorm_due(t, k)) {
+            const double mb = N.bonus[0];  // slot 0 has the best fused score; read before renorm()'s barrier
+            off += (double)renorm(N, r, slots && r < k);
+            if (slots && r < k) N.bonus[r] = N.bonus[r] - mb;
             boff += mb;
         }
         cur ^= 1;
         n = k;
     }
     __syncthreads();
-    const Beam &A = S[cur];
+    const LmBeam &A = S[cur];
     // ---- the end: the final cost, the order of the fp32 scores (ties: the rank before), the n-best
     float sc = -__builtin_inff();
     if (slots && r < n) {
@@ -391,37 +310,10 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
     if (slots && r < nbest) {
         const bool have = r < nlive;
         const int src = have ? perm[r] : 0;
-        a.lengths[(size_t)b * nbest + r] = have ? A.len[src] : -1;
         a.scores[(size_t)b * nbest + r] = have ? fsc[src] : -__builtin_inff();
         a.am_scores[(size_t)b * nbest + r] = have ? (float)(off + (double)A.tot[src]) : -__builtin_inff();
     }
-    for (int e = tid; e < nbest * T; e += THREADS) {
-        const int kk = e / T, p = e - kk * T;
-        if (kk >= nlive || p >= A.len[perm[kk]]) a.tokens[((size_t)b * nbest + kk) * T + p] = -1;
-    }
-    if (slots && r < nbest && r < nlive) {
-        const int src = perm[r];
-        int node = A.node[src];
-        int *out = a.tokens + ((size_t)b * nbest + r) * T;
-        for (int p = A.len[src] - 1; p >= 0 && node != ROOT; --p) {  // len <= T_n <= T: one label per frame at most
-            const unsigned long long key =
-                __hip_atomic_load(&table[(unsigned)node & mask], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            out[p] = (int)(unsigned)(key & 0xffffffffull);
-            node = (int)(unsigned)(key >> 32);
-        }
-    }
-}
-
-int check_dims(int B, int T, int beam, int candidates) {
-    if (B <= 0 || T <= 0 || beam <= 0 || candidates <= 0) return PIKA_EINVAL;
-    if (beam > MAX_BEAM || candidates > MAX_CAND || B > 65535 || 2ll * T * beam > (1ll << 28)) return PIKA_ETOOBIG;
-    return PIKA_OK;
-}
-
-size_t table_slots(int T, int beam) {
-    size_t n = 64;
-    while (n < 2 * (size_t)T * beam) n <<= 1;
-    return n;
+    write_nbest<THREADS>(A, nlive, [&](int q) { return perm[q]; }, tid, b, T, nbest, a.tokens, a.lengths, table, mask);
 }
 
 }  // namespace
@@ -429,8 +321,8 @@ size_t table_slots(int T, int beam) {
 extern "C" {
 
 size_t pika_ctc_lm_scratch_bytes(int B, int T, int beam, int candidates) {
-    if (check_dims(B, T, beam, candidates)) return 0;
-    return 8 * (size_t)B * table_slots(T, beam);
+    if (check_search_dims(B, T, beam, candidates)) return 0;
+    return table_bytes(B, T, beam);
 }
 
 int pika_ctc_lm_beam_search(const float *x, long long stride_t, long long stride_b, const float *lse,
@@ -442,17 +334,16 @@ int pika_ctc_lm_beam_search(const float *x, long long stride_t, long long stride
                             int *tokens, int *lengths, float *scores, float *am_scores, void *scratch, void *stream) {
     if (B <= 0 || T <= 0 || C <= 0 || blank < 0 || blank >= C || nbest <= 0) return PIKA_EINVAL;
     if (num_states <= 0 || num_arcs < 0 || start < 0 || start >= num_states) return PIKA_EINVAL;
-    if (int rc = check_dims(B, T, beam, candidates)) return rc;
+    if (int rc = check_search_dims(B, T, beam, candidates)) return rc;
     if (nbest > beam) return PIKA_ETOOBIG;
     if (!x || !blank_lp || !top_val || !top_idx || !input_lengths || !tokens || !lengths || !scores || !am_scores ||
         !scratch || !fst_offsets || !fst_final || (num_arcs > 0 && (!fst_ilabel || !fst_weight || !fst_nextstate)))
         return PIKA_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t slots = table_slots(T, beam);
-    if (hipError_t e = hipMemsetAsync(scratch, 0xff, 8 * (size_t)B * slots, s)) return (int)e;  // every key EMPTY
+    if (hipError_t e = clear_tables(scratch, B, T, beam, s)) return (int)e;
     const Args a = {x, stride_t, stride_b, lse, blank_lp, top_val, top_idx, input_lengths, B, T, beam, nbest,
                     candidates, start, use_final, lm_weight, length_bonus, tokens, lengths, scores, am_scores,
-                    static_cast<unsigned long long *>(scratch), (unsigned)(slots - 1)};
+                    static_cast<unsigned long long *>(scratch), (unsigned)(table_slots(T, beam) - 1)};
     const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
                    label_offset};
     if (beam * candidates <= CELLS_SMALL)

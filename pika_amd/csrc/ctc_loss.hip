@@ -25,19 +25,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ctc_numerics.h"
 #include "pika_ctc.h"
 
 namespace {
 
-constexpr float NEG = -1.0e30f;  // "log zero": finite, so NEG+NEG / NEG-NEG never make NaN
-constexpr float NEG_HALF = -0.5e30f;
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float LN2 = 0.6931471805599453f;
 constexpr int UNR = 8;     // frames prefetched per register batch
 constexpr int RENORM = 8;  // frames between renormalisations (== UNR: the last frame of a batch)
 constexpr int MAX_WAVES = 16;
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 struct Ctc {
     float *lp;      // [B][T][Wp] log-prob of state s's class at frame t, NEG where invalid
@@ -87,8 +82,6 @@ int check_dims(int B, int T, int U, int C, int blank) {
     if (C <= 0 || blank < 0 || blank >= C) return PIKA_EINVAL;
     return check_lattice_dims(B, T, U);
 }
-
-__device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // log(exp(x)+exp(y)+exp(z)) on the transcendental pipe (v_exp_f32 / v_log_f32); one term is exp2(0) = 1
 __device__ inline float lse3(float x, float y, float z) {

@@ -1,0 +1,180 @@
+// pika_amd/csrc/ctc_search_core.h -- what the CTC prefix beam searches share (ctc_decode.hip: ctc_beam_kernel,
+// ctc_lm.hip: ctc_lm_kernel; not part of the C ABI): the beam, the trie of prefixes in an open-addressing table, the
+// per-frame slot work, the total order of the arg-max, node assignment, the renormalisation, the n-best tail and the
+// host-side limits.  What differs -- which candidates a slot offers and how they are scored -- stays with each kernel.
+#ifndef PIKA_CTC_SEARCH_CORE_H
+#define PIKA_CTC_SEARCH_CORE_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "ctc_numerics.h"
+#include "pika_ctc_decode.h"  // PIKA_OK / PIKA_EINVAL / PIKA_ETOOBIG
+
+namespace {
+
+constexpr int MAX_BEAM = 64;
+constexpr int MAX_CLASSES = 128;  // the frame's class list: the row pass's K
+constexpr int RENORM = 8;         // frames between renormalisations
+constexpr int ROOT = 0x7ffffffe;  // node of the empty prefix
+constexpr int NONE = 0x7ffffffd;  // its parent
+constexpr int PENDING = -1;
+constexpr unsigned long long EMPTY = ~0ull;
+
+struct Beam {
+    int node[MAX_BEAM];   // the prefix: slot of its (parent, token) key in the utterance's table, ROOT for the empty one
+    int last[MAX_BEAM];   // its last label, -1 for the empty prefix
+    int pnode[MAX_BEAM];  // its parent's node
+    int len[MAX_BEAM];
+    float pb[MAX_BEAM], pnb[MAX_BEAM], tot[MAX_BEAM];
+};
+
+__device__ inline unsigned long long trie_key(int parent, int token) {
+    return ((unsigned long long)(unsigned)parent << 32) | (unsigned)token;
+}
+
+// insert-or-find: every probe is an atomic, so a slot is never seen through a stale cache line; only this workgroup
+// touches the table
+__device__ inline int trie_node(unsigned long long *table, unsigned mask, int parent, int token) {
+    const unsigned long long key = trie_key(parent, token);
+    unsigned h = ((unsigned)parent * 0x9E3779B1u) ^ ((unsigned)token * 0x85EBCA6Bu);
+    h = (h ^ (h >> 15)) & mask;
+    for (unsigned probes = 0; probes <= mask; ++probes) {  // at most T * beam <= (mask + 1) / 2 keys: it ends early
+        const unsigned long long old = atomicCAS(&table[h], EMPTY, key);
+        if (old == EMPTY || old == key) break;
+        h = (h + 1) & mask;
+    }
+    return (int)h;
+}
+
+// the key of a node, read as it was inserted
+__device__ inline unsigned long long trie_load(const unsigned long long *table, unsigned mask, int node) {
+    return __hip_atomic_load(&table[(unsigned)node & mask], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// a beam slot in its owner's registers
+struct Slot {
+    int node, last, pnode, len;
+    float pb, pnb, tot;
+};
+
+// slot r of A if `act`, otherwise the values that stand for "no such slot".  A kernel reads its slot once per frame,
+// before the gather of the slot's last label from the full row, so the LDS reads overlap that load.
+__device__ __forceinline__ Slot load_slot(const Beam &A, int r, bool act) {
+    return {act ? A.node[r] : NONE, act ? A.last[r] : -1, act ? A.pnode[r] : NONE, act ? A.len[r] : 0,
+            act ? A.pb[r] : NEG, act ? A.pnb[r] : NEG, act ? A.tot[r] : NEG};
+}
+
+// (F, hi, lo) before (G, ghi, glo) in the total order: higher score, then the lower key
+__device__ inline bool before(float F, unsigned hi, unsigned lo, float G, unsigned ghi, unsigned glo) {
+    return F > G || (F == G && (hi < ghi || (hi == ghi && lo < glo)));
+}
+
+// The slot work of one frame, between two barriers that EVERY thread of the workgroup reaches.  A `slot` thread owns
+// beam slot r; `me` is load_slot(A, r, slot && r < n), g the frame's value of the slot's last label.  Slot r < n finds
+// its parent's slot (node identity) and the position of its own last label in the frame's class list ci[0..K), and
+// strikes that position from its own list (the repeat is a candidate of its own, scored with p_b) and from its
+// parent's (that child is in the beam: the contribution is added to it).  Out: the slot's (p_b, p_nb) and tot after
+// the frame if it stays, and excl / hasrep complete.
+__device__ __forceinline__ void slot_work(const Beam &A, int n, int r, bool slot, const Slot &me, const int *ci, int K,
+                                          float lpb, float g, unsigned (*excl)[MAX_CLASSES / 32], int *hasrep,
+                                          float &npb, float &npnb, float &s_stay) {
+    if (slot) {
+        for (int q = 0; q < MAX_CLASSES / 32; ++q) excl[r][q] = 0;
+        hasrep[r] = 0;
+    }
+    __syncthreads();
+    npb = NEG; npnb = NEG; s_stay = NEG;
+    if (slot && r < n) {
+        int ps = -1;  // the parent's slot, if the parent is in the beam
+        if (me.pnode != NONE)
+            for (int q = 0; q < n; ++q)
+                if (A.node[q] == me.pnode) ps = q;
+        int pos = -1;  // where the slot's last label stands in the frame's class list
+        if (me.last >= 0)
+            for (int j = 0; j < K; ++j)
+                if (ci[j] == me.last) pos = j;
+        if (pos >= 0) {
+            atomicOr(&excl[r][pos >> 5], 1u << (pos & 31));               // the repeat
+            if (ps >= 0) atomicOr(&excl[ps][pos >> 5], 1u << (pos & 31));  // the parent's child that is in the beam
+        }
+        const bool rep_child = ps >= 0 && A.last[ps] == me.last;
+        if (rep_child) hasrep[ps] = 1;
+        npb = addn(lpb, me.tot);
+        if (me.last >= 0) npnb = addn(g, me.pnb);
+        if (ps >= 0) npnb = lse2(npnb, addn(g, rep_child ? A.pb[ps] : A.tot[ps]));
+        s_stay = lse2(npb, npnb);
+    }
+    __syncthreads();  // excl and hasrep are complete
+}
+
+// a fresh winner gets its node: the table slot of its (parent node, token) key
+__device__ __forceinline__ void assign_node(Beam &N, int r, bool mine, unsigned long long *table, unsigned mask) {
+    if (mine && N.node[r] == PENDING) N.node[r] = trie_node(table, mask, N.pnode[r], N.last[r]);
+}
+
+// frame t ends with k > 0 slots and is the last of RENORM (workgroup-uniform)
+__device__ inline bool renorm_due(int t, int k) { return t % RENORM == RENORM - 1 && k > 0; }
+
+// subtracts the best tot from the slots (`mine`: this thread owns slot r < k) and returns it for the caller's fp64
+// offset.  Every thread of the workgroup reaches the barrier.
+__device__ __forceinline__ float renorm(Beam &N, int r, bool mine) {
+    const float m = N.tot[0];  // slot 0 is the best: finite
+    __syncthreads();
+    if (mine) {
+        N.pb[r] = N.pb[r] > NEG_HALF ? N.pb[r] - m : NEG;
+        N.pnb[r] = N.pnb[r] > NEG_HALF ? N.pnb[r] - m : NEG;
+        N.tot[r] = N.tot[r] - m;
+    }
+    return m;
+}
+
+// the n-best of utterance b by THREADS threads: entry k is slot perm(k) for k < n; lengths, -1 beyond each length (and
+// for entries that do not exist), then the back-trace through the table.  Scores stay with the caller.
+template <int THREADS, class Perm>
+__device__ __forceinline__ void write_nbest(const Beam &A, int n, Perm perm, int tid, int b, int T, int nbest,
+                                            int *tokens, int *lengths, const unsigned long long *table,
+                                            unsigned mask) {
+    if (tid < nbest) lengths[(size_t)b * nbest + tid] = tid < n ? A.len[perm(tid)] : -1;
+    for (int e = tid; e < nbest * T; e += THREADS) {
+        const int kk = e / T, p = e - kk * T;
+        if (kk >= n || p >= A.len[perm(kk)]) tokens[((size_t)b * nbest + kk) * T + p] = -1;
+    }
+    if (tid < nbest && tid < n) {
+        const int src = perm(tid);
+        int node = A.node[src];
+        int *out = tokens + ((size_t)b * nbest + tid) * T;
+        for (int p = A.len[src] - 1; p >= 0 && node != ROOT; --p) {  // len <= T_n <= T: one label per frame at most
+            const unsigned long long key = trie_load(table, mask, node);
+            out[p] = (int)(unsigned)(key & 0xffffffffull);
+            node = (int)(unsigned)(key >> 32);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// host
+// ---------------------------------------------------------------------------------------------
+static inline size_t table_slots(int T, int beam) {
+    size_t n = 64;
+    while (n < 2 * (size_t)T * beam) n <<= 1;
+    return n;
+}
+
+// `classes`: the length of the frame's class list
+static inline int check_search_dims(int B, int T, int beam, int classes) {
+    if (B <= 0 || T <= 0 || beam <= 0 || classes <= 0) return PIKA_EINVAL;
+    if (beam > MAX_BEAM || classes > MAX_CLASSES || B > 65535 || 2ll * T * beam > (1ll << 28)) return PIKA_ETOOBIG;
+    return PIKA_OK;
+}
+
+static inline size_t table_bytes(int B, int T, int beam) { return 8 * (size_t)B * table_slots(T, beam); }
+
+// every key of the B tables EMPTY
+static inline hipError_t clear_tables(void *scratch, int B, int T, int beam, hipStream_t s) {
+    return hipMemsetAsync(scratch, 0xff, table_bytes(B, T, beam), s);
+}
+
+}  // namespace
+
+#endif

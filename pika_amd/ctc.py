@@ -62,11 +62,10 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def _prepare(x, what, targets, input_lengths, target_lengths, blank):
-    """Checks and device copies: (x as (T,B,C), any stride; targets i32; offsets i32 or None; il i32; tl i32; U_max;
-    unbatched)."""
+def _check_input(x, what, who, blank):
+    """The checks on the input that the loss and the decoders share (`who`: the caller): (x as (T,B,C), unbatched)."""
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise RuntimeError("pika_amd ctc_loss: %s must live on a HIP device (there is no CPU path)" % what)
+        raise RuntimeError("pika_amd %s: %s must live on a HIP device (there is no CPU path)" % (who, what))
     if x.dtype != torch.float32:
         raise TypeError("%s must be float32, got %s" % (what, x.dtype))
     unbatched = x.dim() == 2
@@ -79,7 +78,14 @@ def _prepare(x, what, targets, input_lengths, target_lengths, blank):
         raise ValueError("%s has an empty dimension: %s" % (what, tuple(x.shape)))
     if not 0 <= blank < C:
         raise ValueError("blank=%d outside [0,%d)" % (blank, C))
-    dev = x.device
+    return x, unbatched
+
+
+def _prepare(x, what, targets, input_lengths, target_lengths, blank):
+    """Checks and device copies: (x as (T,B,C), any stride; targets i32; offsets i32 or None; il i32; tl i32; U_max;
+    unbatched)."""
+    x, unbatched = _check_input(x, what, "ctc_loss", blank)
+    B, dev = x.shape[1], x.device
     targets = torch.as_tensor(targets)
     il_host, tl_host = torch.as_tensor(input_lengths), torch.as_tensor(target_lengths)
     for name, t in (("targets", targets), ("input_lengths", il_host), ("target_lengths", tl_host)):
@@ -262,21 +268,9 @@ def ctc_align_from_logits(logits, targets, input_lengths, target_lengths, blank=
 def _decode_rows(x, what, input_lengths, blank, K, logits):
     """Checks + the row pass: (x as (T,B,C) with unit class stride, il i32, blank_lp, top_val, top_idx, lse or None,
     unbatched)."""
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise RuntimeError("pika_amd ctc decode: %s must live on a HIP device (there is no CPU path)" % what)
-    if x.dtype != torch.float32:
-        raise TypeError("%s must be float32, got %s" % (what, x.dtype))
+    x, unbatched = _check_input(x, what, "ctc decode", blank)
     x = x.detach()
-    unbatched = x.dim() == 2
-    if unbatched:
-        x = x.unsqueeze(1)
-    if x.dim() != 3:
-        raise ValueError("%s must be (T,B,C) or (T,C), got %s" % (what, tuple(x.shape)))
     T, B, C = x.shape
-    if T < 1 or B < 1 or C < 1:
-        raise ValueError("%s has an empty dimension: %s" % (what, tuple(x.shape)))
-    if not 0 <= blank < C:
-        raise ValueError("blank=%d outside [0,%d)" % (blank, C))
     il = torch.as_tensor(input_lengths)
     if il.dtype not in (torch.int32, torch.int64):
         raise TypeError("input_lengths must be int32 or int64, got %s" % il.dtype)
@@ -315,10 +309,22 @@ def _greedy(x, what, input_lengths, blank, logits):
     return tuple(o[0] for o in out) if unbatched else out
 
 
-def _beam(x, what, input_lengths, beam, nbest, blank, logits):
-    blank, beam, nbest = int(blank), int(beam), int(nbest)
+def _nbest_outputs(beam, nbest):
+    """Checks beam / nbest; returns the function that allocates (tokens, lengths, scores) for the (T,B,C) input x."""
     if not 1 <= nbest <= beam <= MAX_BEAM:
         raise ValueError("need 1 <= nbest <= beam <= %d, got beam=%d nbest=%d" % (MAX_BEAM, beam, nbest))
+
+    def alloc(x):
+        T, B, _ = x.shape
+        return (torch.empty((B, nbest, T), dtype=torch.int32, device=x.device),
+                torch.empty((B, nbest), dtype=torch.int32, device=x.device),
+                torch.empty((B, nbest), dtype=torch.float32, device=x.device))
+    return alloc
+
+
+def _beam(x, what, input_lengths, beam, nbest, blank, logits):
+    blank, beam, nbest = int(blank), int(beam), int(nbest)
+    alloc = _nbest_outputs(beam, nbest)
     x, il, blank_lp, top_val, top_idx, lse, unbatched = _decode_rows(x, what, input_lengths, blank, 2 * beam, logits)
     T, B, C = x.shape
     lib = _lib.lib()
@@ -326,15 +332,12 @@ def _beam(x, what, input_lengths, beam, nbest, blank, logits):
     if nbytes == 0:
         raise ValueError("(B,T,beam) = (%d,%d,%d) not supported" % (B, T, beam))
     with torch.cuda.device(x.device):
-        tokens = torch.empty((B, nbest, T), dtype=torch.int32, device=x.device)
-        lengths = torch.empty((B, nbest), dtype=torch.int32, device=x.device)
-        scores = torch.empty((B, nbest), dtype=torch.float32, device=x.device)
+        out = tokens, lengths, scores = alloc(x)
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         _lib.check(lib.pika_ctc_beam_search(_ptr(x), x.stride(0), x.stride(1), _ptr(lse), _ptr(blank_lp), _ptr(top_val),
                                             _ptr(top_idx), _ptr(il), B, T, C, blank, beam, nbest, _ptr(tokens),
                                             _ptr(lengths), _ptr(scores), _ptr(scratch), _stream()),
                    "pika_ctc_beam_search")
-    out = (tokens, lengths, scores)
     return tuple(o[0] for o in out) if unbatched else out
 
 
@@ -438,8 +441,7 @@ def _beam_lm(x, what, input_lengths, lm, beam, nbest, blank, lm_weight, length_b
     blank, beam, nbest = int(blank), int(beam), int(nbest)
     if not isinstance(lm, CtcNgramLm):
         raise TypeError("lm must be a CtcNgramLm, got %s" % type(lm).__name__)
-    if not 1 <= nbest <= beam <= MAX_BEAM:
-        raise ValueError("need 1 <= nbest <= beam <= %d, got beam=%d nbest=%d" % (MAX_BEAM, beam, nbest))
+    alloc = _nbest_outputs(beam, nbest)
     candidates = min(2 * beam, MAX_CANDIDATES) if candidates is None else int(candidates)
     if not 1 <= candidates <= MAX_CANDIDATES:
         raise ValueError("need 1 <= candidates <= %d, got %d" % (MAX_CANDIDATES, candidates))
@@ -455,9 +457,7 @@ def _beam_lm(x, what, input_lengths, lm, beam, nbest, blank, lm_weight, length_b
     if nbytes == 0:
         raise ValueError("(B,T,beam,candidates) = (%d,%d,%d,%d) not supported" % (B, T, beam, candidates))
     with torch.cuda.device(x.device):
-        tokens = torch.empty((B, nbest, T), dtype=torch.int32, device=x.device)
-        lengths = torch.empty((B, nbest), dtype=torch.int32, device=x.device)
-        scores = torch.empty((B, nbest), dtype=torch.float32, device=x.device)
+        tokens, lengths, scores = alloc(x)
         am_scores = torch.empty((B, nbest), dtype=torch.float32, device=x.device)
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         _lib.check(lib.pika_ctc_lm_beam_search(
