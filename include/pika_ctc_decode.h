@@ -81,6 +81,45 @@ int pika_ctc_beam_search(const float *x, long long stride_t, long long stride_b,
                          int B, int T, int C, int blank, int beam, int nbest, int *tokens, int *lengths, float *scores,
                          void *scratch, void *stream);
 
+/* ---- Streaming: the beam search with its state carried across calls -------------------------------------------------
+ * The search is a function of (state, frame), so the state can rest in device memory between launches: feed the frames
+ * of an utterance in chunks of any sizes and the n-best is BIT FOR BIT what pika_ctc_beam_search gives on the whole
+ * tensor.  One opaque blob serves a batch of B independent streams with room for max_frames frames each; the limits are
+ * the one-shot's with T := max_frames.  Layout, with N = the smallest power of two >= max(64, 2 max_frames beam):
+ *   [0, 8 B N)                 the B tables of pika_ctc_beam_scratch_bytes(B, max_frames, beam)
+ *   then B records of PIKA_CTC_STREAM_RECORD_BYTES, record b of stream b:
+ *     i32 n (slots in the beam) | i32 frames (consumed so far) | i32 overflow | i32 pad | f64 off | f64 (unused here) |
+ *     the beam, seven arrays of 64 (slots [0,n) hold values): i32 node, last, parent node, len; f32 p_b, p_nb, tot
+ * `frames` and `overflow` of stream b may be read at PIKA_CTC_STREAM_FRAMES_OFFSET / _OVERFLOW_OFFSET of its record;
+ * everything else is the library's.  A blob must be reset before its first advance. */
+#define PIKA_CTC_STREAM_RECORD_BYTES 1824
+#define PIKA_CTC_STREAM_FRAMES_OFFSET 4
+#define PIKA_CTC_STREAM_OVERFLOW_OFFSET 8
+
+/* Bytes of the blob: pika_ctc_beam_scratch_bytes(B, max_frames, beam) + B * PIKA_CTC_STREAM_RECORD_BYTES; 0 for
+ * dimensions the calls refuse. */
+size_t pika_ctc_stream_state_bytes(int B, int max_frames, int beam);
+
+/* The empty-prefix beam, frames = 0, offsets 0, overflow 0 and an empty table -- for every stream (which NULL), or for
+ * the streams b with which[b] != 0 (i32 (B,), device): the others' records and tables are not touched. */
+int pika_ctc_stream_reset(void *state, int B, int max_frames, int beam, const int *which, void *stream);
+
+/* The frames t < L_b of a chunk (Tc,B,C) through the search.  x / strides / lse / blank_lp / top_val / top_idx as in
+ * pika_ctc_beam_search, from pika_ctc_decode_rows on the chunk with K = 2 * beam and the same chunk_lengths.
+ *   chunk_lengths  i32 (B,)  L_b, clamped on the device to [0,Tc]; 0: the stream is left exactly as it was.  (The row
+ *                  pass clamps to [1,Tc] and may look at row 0 of such a stream; the advance does not use it.)
+ * A stream never takes more than max_frames frames: L_b is cut there, the extra frames are ignored and `overflow` is
+ * set (until the next reset), so a table is never more than half full. */
+int pika_ctc_stream_advance(const float *x, long long stride_t, long long stride_b, const float *lse,
+                            const float *blank_lp, const float *top_val, const int *top_idx, const int *chunk_lengths,
+                            int B, int Tc, int C, int blank, int beam, void *state, int max_frames, void *stream);
+
+/* The n-best of the current beams, as pika_ctc_beam_search writes them; the state is only read, so partial hypotheses
+ * can be taken after any chunk.  tokens i32 (B,nbest,L): L >= 1 is the width the caller allocated -- an entry longer
+ * than L (possible only for L < frames) keeps its length and its first L labels.  lengths, scores (B,nbest). */
+int pika_ctc_stream_results(const void *state, int B, int max_frames, int beam, int nbest, int L, int *tokens,
+                            int *lengths, float *scores, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

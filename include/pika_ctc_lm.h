@@ -68,6 +68,48 @@ int pika_ctc_lm_beam_search(const float *x, long long stride_t, long long stride
                             int label_offset, int candidates, float lm_weight, float length_bonus, int use_final,
                             int *tokens, int *lengths, float *scores, float *am_scores, void *scratch, void *stream);
 
+/* ---- Streaming: the fused search with its state carried across calls (pika_ctc_decode.h, "Streaming") ----------------
+ * Any chunking of the frames gives BIT FOR BIT what pika_ctc_lm_beam_search gives on the whole tensor.  The blob of a
+ * batch of B streams with room for max_frames frames each: the B tables of pika_ctc_lm_scratch_bytes(B, max_frames,
+ * beam, candidates), then B records of PIKA_CTC_LM_STREAM_RECORD_BYTES:
+ *   i32 n | i32 frames | i32 overflow | i32 pad | f64 off (moved out of tot) | f64 boff (moved out of bonus) |
+ *   the beam, arrays of 64 (slots [0,n) hold values): i32 node, last, parent node, len; f32 p_b, p_nb, tot; f64 bonus;
+ *   i32 LM state
+ * `frames` and `overflow` of stream b lie at PIKA_CTC_STREAM_FRAMES_OFFSET / _OVERFLOW_OFFSET of its record, as in
+ * pika_ctc_decode.h.  The FST arrays, lm_weight, length_bonus, beam and candidates must be the same in every call on a
+ * blob between two resets; nothing checks that. */
+#define PIKA_CTC_LM_STREAM_RECORD_BYTES 2592
+#ifndef PIKA_CTC_STREAM_FRAMES_OFFSET
+#define PIKA_CTC_STREAM_FRAMES_OFFSET 4
+#define PIKA_CTC_STREAM_OVERFLOW_OFFSET 8
+#endif
+
+/* pika_ctc_lm_scratch_bytes(B, max_frames, beam, candidates) + B * PIKA_CTC_LM_STREAM_RECORD_BYTES; 0 for dimensions the
+ * calls refuse. */
+size_t pika_ctc_lm_stream_state_bytes(int B, int max_frames, int beam, int candidates);
+
+/* As pika_ctc_stream_reset; the empty prefix starts in LM state `start` in [0, num_states) with bonus 0. */
+int pika_ctc_lm_stream_reset(void *state, int B, int max_frames, int beam, int candidates, int num_states, int start,
+                             const int *which, void *stream);
+
+/* As pika_ctc_stream_advance, on the K = candidates arrays of the row pass on the chunk. */
+int pika_ctc_lm_stream_advance(const float *x, long long stride_t, long long stride_b, const float *lse,
+                               const float *blank_lp, const float *top_val, const int *top_idx,
+                               const int *chunk_lengths, int B, int Tc, int C, int blank, int beam,
+                               const long long *fst_offsets, const int *fst_ilabel, const float *fst_weight,
+                               const int *fst_nextstate, const float *fst_final, int num_states, int num_arcs,
+                               int backoff_id, int label_offset, int candidates, float lm_weight, float length_bonus,
+                               void *state, int max_frames, void *stream);
+
+/* The n-best of the current beams with the outputs of pika_ctc_lm_beam_search and the token width L of
+ * pika_ctc_stream_results.  use_final: the final term and the re-sort happen on the side; the state is only read, so
+ * decoding can go on after it and a later call with the other setting gives that setting's answer. */
+int pika_ctc_lm_stream_results(const void *state, int B, int max_frames, int beam, int candidates,
+                               const long long *fst_offsets, const int *fst_ilabel, const float *fst_weight,
+                               const int *fst_nextstate, const float *fst_final, int num_states, int num_arcs,
+                               int backoff_id, int label_offset, float lm_weight, int use_final, int nbest, int L,
+                               int *tokens, int *lengths, float *scores, float *am_scores, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,8 +22,12 @@
 //            descendant that stayed.  Numerics as the loss: fp32 (p_b, p_nb), the best tot moved into an fp64 offset
 //            every RENORM frames.  The n-best back-trace walks the table in the same launch.  What ctc_lm.hip's fused
 //            search does the same way (beam, trie, slot work, order, renormalisation, tail) is in ctc_search_core.h.
+//   stream : the search with its state in device memory between launches: reset writes the first beam and clears the
+//            table, advance runs a chunk's frames through the frame body of the one-shot kernel (load, frames, store),
+//            results is the one-shot tail on the stored beam and modifies nothing.
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "ctc_search_core.h"
@@ -292,31 +296,79 @@ __global__ __launch_bounds__(256) void ctc_greedy_kernel(const float *__restrict
 }
 
 // ---------------------------------------------------------------------------------------------
+// the state of a stream (pika_ctc_decode.h): reset writes it, the advance loads and stores it, the results only read it
+// ---------------------------------------------------------------------------------------------
+using Rec = StreamRec<Beam>;
+static_assert(sizeof(Rec) == PIKA_CTC_STREAM_RECORD_BYTES && offsetof(StreamHdr, frames) == PIKA_CTC_STREAM_FRAMES_OFFSET &&
+                  offsetof(StreamHdr, overflow) == PIKA_CTC_STREAM_OVERFLOW_OFFSET,
+              "the record the header documents");
+
+__global__ __launch_bounds__(256) void ctc_stream_reset_kernel(unsigned long long *tables, size_t slots, Rec *recs,
+                                                               const int *__restrict__ which) {
+    stream_reset(tables, slots, recs, which, [](Beam &A) { root_slot(A); });
+}
+
+// the beam of a record into LDS; a label outside the classes (a record that was never reset) is no label
+__device__ __forceinline__ void load_beam(Beam &A, const Rec &R, const StreamHdr &h, int r, int C) {
+    if (r < h.n) {
+        copy_slot(A, R.beam, r);
+        A.len[r] = clampi(A.len[r], 0, h.frames);
+        if (A.last[r] < -1 || A.last[r] >= C) A.last[r] = -1;
+    }
+}
+
+// the n-best of a beam with n slots: scores here; lengths, tokens and the back-trace by the shared tail, slots in beam
+// order
+template <bool CLIP>
+__device__ __forceinline__ void beam_tail(const Beam &A, int n, double off, int r, int b, int T, int nbest, int *tokens,
+                                          int *lengths, float *scores, const unsigned long long *table, unsigned mask) {
+    if (r < nbest) scores[(size_t)b * nbest + r] = r < n ? (float)(off + (double)A.tot[r]) : -__builtin_inff();
+    write_nbest<64, CLIP>(A, n, [](int q) { return q; }, r, b, T, nbest, tokens, lengths, table, mask);
+}
+
+// ---------------------------------------------------------------------------------------------
 // search.  grid = B, block = 64: lane r owns beam slot r.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void ctc_beam_kernel(const float *__restrict__ x, long long st, long long sb,
-                                                      const float *__restrict__ lse, const float *__restrict__ blank_lp,
-                                                      const float *__restrict__ top_val, const int *__restrict__ top_idx,
-                                                      const int *__restrict__ Tn_, int B, int T, int blank, int beam,
-                                                      int nbest, int *__restrict__ tokens, int *__restrict__ lengths,
-                                                      float *__restrict__ scores, unsigned long long *table_,
-                                                      unsigned mask) {
+// The search of utterance b = blockIdx.x, as the one-shot kernel (STREAM false: the first beam, the frames t < T_n, the
+// n-best) and as the streaming advance (STREAM true: the beam of the stream's record, the frames of the chunk -- Tn_ its
+// lengths, T its Tc; the outputs are not used -- and the beam back into the record).  One body, so the two cannot drift
+// apart.
+template <bool STREAM>
+__device__ __forceinline__ void beam_search(const float *__restrict__ x, long long st, long long sb,
+                                            const float *__restrict__ lse, const float *__restrict__ blank_lp,
+                                            const float *__restrict__ top_val, const int *__restrict__ top_idx,
+                                            const int *__restrict__ Tn_, int B, int T, int blank, int beam, int nbest,
+                                            int *__restrict__ tokens, int *__restrict__ lengths,
+                                            float *__restrict__ scores, unsigned long long *table_, unsigned mask,
+                                            Rec *recs, int C, int max_frames) {
     __shared__ Beam S[2];
     __shared__ float cv[MAX_CLASSES];
     __shared__ int ci[MAX_CLASSES];
     __shared__ unsigned excl[MAX_BEAM][MAX_CLASSES / 32];
     __shared__ int hasrep[MAX_BEAM];
     const int b = blockIdx.x, r = threadIdx.x, K = 2 * beam;
-    const int Tn = clampi(Tn_[b], 1, T);
+    StreamHdr h = {};
+    int Tn;
+    if constexpr (STREAM) {
+        h = load_hdr(recs[b].h, beam, max_frames);
+        bool cut;
+        Tn = stream_frames(Tn_, b, T, h.frames, max_frames, cut);
+        // (not ordered against the other threads' load of the header above: nothing reads h.overflow)
+        if (cut && r == 0) recs[b].h.overflow = 1;
+        if (Tn <= 0) return;  // workgroup-uniform: nothing of this chunk is the stream's, the state stays as it is
+    } else {
+        Tn = clampi(Tn_[b], 1, T);
+    }
     unsigned long long *table = table_ + (size_t)b * ((size_t)mask + 1);
     const float *xb = x + (long long)b * sb;
 
     int cur = 0, n = 1;
     double off = 0.0;  // sum of the subtracted maxima (identical in every lane)
-    if (r == 0) {
-        Beam &A = S[0];
-        A.node[0] = ROOT; A.last[0] = -1; A.pnode[0] = NONE; A.len[0] = 0;
-        A.pb[0] = 0.0f; A.pnb[0] = NEG; A.tot[0] = 0.0f;
+    if constexpr (STREAM) {
+        n = h.n; off = h.off;
+        load_beam(S[0], recs[b], h, r, C);
+    } else {
+        if (r == 0) root_slot(S[0]);
     }
     // the frame's compact row, fetched one frame ahead
     float pv0 = NEG, pv1 = NEG, plb = NEG, pl = 0.0f;
@@ -395,15 +447,59 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float *__restrict__ 
         }
         __syncthreads();  // the new beam's k slots are written
         assign_node(N, r, r < k, table, mask);
-        if (renorm_due(t, k)) off += (double)renorm(N, r, r < k);
+        if (renorm_due(h.frames + t, k)) off += (double)renorm(N, r, r < k);
         cur ^= 1;
         n = k;
     }
     __syncthreads();
     const Beam &A = S[cur];
-    // n-best: scores here; lengths, tokens and the back-trace by the shared tail, slots in beam order
-    if (r < nbest) scores[(size_t)b * nbest + r] = r < n ? (float)(off + (double)A.tot[r]) : -__builtin_inff();
-    write_nbest<64>(A, n, [](int q) { return q; }, r, b, T, nbest, tokens, lengths, table, mask);
+    if constexpr (STREAM) {  // the beam and what was moved out of it, back into the record
+        Rec &R = recs[b];
+        if (r < n) copy_slot(R.beam, A, r);
+        if (r == 0) {
+            R.h.n = n; R.h.frames = h.frames + Tn;
+            R.h.off = off;
+        }
+    } else {
+        beam_tail<false>(A, n, off, r, b, T, nbest, tokens, lengths, scores, table, mask);
+    }
+}
+
+__global__ __launch_bounds__(64) void ctc_beam_kernel(const float *__restrict__ x, long long st, long long sb,
+                                                      const float *__restrict__ lse, const float *__restrict__ blank_lp,
+                                                      const float *__restrict__ top_val, const int *__restrict__ top_idx,
+                                                      const int *__restrict__ Tn_, int B, int T, int blank, int beam,
+                                                      int nbest, int *__restrict__ tokens, int *__restrict__ lengths,
+                                                      float *__restrict__ scores, unsigned long long *table_,
+                                                      unsigned mask) {
+    beam_search<false>(x, st, sb, lse, blank_lp, top_val, top_idx, Tn_, B, T, blank, beam, nbest, tokens, lengths, scores,
+                       table_, mask, nullptr, 0, 0);
+}
+
+// grid = B, block = 64, as the one-shot search
+__global__ __launch_bounds__(64) void ctc_stream_advance_kernel(
+    const float *__restrict__ x, long long st, long long sb, const float *__restrict__ lse,
+    const float *__restrict__ blank_lp, const float *__restrict__ top_val, const int *__restrict__ top_idx,
+    const int *__restrict__ len_, int B, int Tc, int C, int beam, unsigned long long *table_, unsigned mask, Rec *recs,
+    int max_frames) {
+    beam_search<true>(x, st, sb, lse, blank_lp, top_val, top_idx, len_, B, Tc, 0, beam, 0, nullptr, nullptr, nullptr,
+                      table_, mask, recs, C, max_frames);
+}
+
+// grid = B, block = 64; reads the state only
+__global__ __launch_bounds__(64) void ctc_stream_results_kernel(const Rec *__restrict__ recs,
+                                                                const unsigned long long *table_, unsigned mask,
+                                                                int beam, int max_frames, int nbest, int L,
+                                                                int *__restrict__ tokens, int *__restrict__ lengths,
+                                                                float *__restrict__ scores) {
+    __shared__ Beam A;
+    const int b = blockIdx.x, r = threadIdx.x;
+    const Rec &R = recs[b];
+    const StreamHdr h = load_hdr(R.h, beam, max_frames);
+    load_beam(A, R, h, r, 0x7fffffff);
+    __syncthreads();
+    beam_tail<true>(A, h.n, h.off, r, b, L, nbest, tokens, lengths, scores, table_ + (size_t)b * ((size_t)mask + 1),
+                    mask);
 }
 
 int check_rows(int B, int T, int C, int blank) {
@@ -464,6 +560,45 @@ int pika_ctc_beam_search(const float *x, long long stride_t, long long stride_b,
     hipLaunchKernelGGL(ctc_beam_kernel, dim3((unsigned)B), dim3(64), 0, s, x, stride_t, stride_b, lse, blank_lp, top_val,
                        top_idx, input_lengths, B, T, blank, beam, nbest, tokens, lengths, scores,
                        static_cast<unsigned long long *>(scratch), (unsigned)(table_slots(T, beam) - 1));
+    return (int)hipGetLastError();
+}
+
+size_t pika_ctc_stream_state_bytes(int B, int max_frames, int beam) {
+    if (check_search_dims(B, max_frames, beam, 1)) return 0;
+    return table_bytes(B, max_frames, beam) + (size_t)B * sizeof(Rec);
+}
+
+int pika_ctc_stream_reset(void *state, int B, int max_frames, int beam, const int *which, void *stream) {
+    if (int rc = check_search_dims(B, max_frames, beam, 1)) return rc;
+    if (!state) return PIKA_EINVAL;
+    hipLaunchKernelGGL(ctc_stream_reset_kernel, reset_grid(B, max_frames, beam), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), static_cast<unsigned long long *>(state),
+                       table_slots(max_frames, beam), stream_recs<Rec>(state, B, max_frames, beam), which);
+    return (int)hipGetLastError();
+}
+
+int pika_ctc_stream_advance(const float *x, long long stride_t, long long stride_b, const float *lse,
+                            const float *blank_lp, const float *top_val, const int *top_idx, const int *chunk_lengths,
+                            int B, int Tc, int C, int blank, int beam, void *state, int max_frames, void *stream) {
+    if (int rc = check_rows(B, Tc, C, blank)) return rc;
+    if (int rc = check_search_dims(B, max_frames, beam, 1)) return rc;
+    if (2ll * Tc * beam > (1ll << 28)) return PIKA_ETOOBIG;  // the row arrays' index range, as in the one-shot search
+    if (!x || !blank_lp || !top_val || !top_idx || !chunk_lengths || !state) return PIKA_EINVAL;
+    hipLaunchKernelGGL(ctc_stream_advance_kernel, dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream), x,
+                       stride_t, stride_b, lse, blank_lp, top_val, top_idx, chunk_lengths, B, Tc, C, beam,
+                       static_cast<unsigned long long *>(state), (unsigned)(table_slots(max_frames, beam) - 1),
+                       stream_recs<Rec>(state, B, max_frames, beam), max_frames);
+    return (int)hipGetLastError();
+}
+
+int pika_ctc_stream_results(const void *state, int B, int max_frames, int beam, int nbest, int L, int *tokens,
+                            int *lengths, float *scores, void *stream) {
+    if (int rc = check_results_dims(B, max_frames, beam, 1, nbest, L)) return rc;
+    if (!state || !tokens || !lengths || !scores) return PIKA_EINVAL;
+    hipLaunchKernelGGL(ctc_stream_results_kernel, dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       stream_recs<Rec>(state, B, max_frames, beam), static_cast<const unsigned long long *>(state),
+                       (unsigned)(table_slots(max_frames, beam) - 1), beam, max_frames, nbest, L, tokens, lengths,
+                       scores);
     return (int)hipGetLastError();
 }
 

@@ -13,9 +13,14 @@
 //            (p_b, p_nb) and the renormalisation are those of ctc_beam_kernel, shared through ctc_search_core.h;
 //            the bonus is renormalised with tot.  The end applies the final cost, re-sorts by counting and
 //            walks the table for the n-best.
+//   stream : the search with its state in device memory between launches: reset writes the first beam and clears the
+//            table, advance runs a chunk's frames through the frame body of the one-shot kernel (load, frames, store),
+//            results is the one-shot end -- final cost and new order on the side -- on the stored beam, which it only
+//            reads.
 //   Every loop over the FST has a fixed trip limit (header): a malformed table cannot spin the workgroup.
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "pika_ctc_lm.h"
@@ -113,6 +118,18 @@ struct LmBeam : Beam {
     int lmst[MAX_BEAM];      // its LM state
 };
 
+// the beam a search starts from: the empty prefix in slot 0, in the LM's start state
+__device__ __forceinline__ void root_slot(LmBeam &A, int start) {
+    A.node[0] = ROOT; A.last[0] = -1; A.pnode[0] = NONE; A.len[0] = 0; A.lmst[0] = start;
+    A.pb[0] = 0.0f; A.pnb[0] = NEG; A.tot[0] = 0.0f; A.bonus[0] = 0.0;
+}
+
+__device__ __forceinline__ void copy_slot(LmBeam &D, const LmBeam &G, int r) {
+    copy_slot(static_cast<Beam &>(D), static_cast<const Beam &>(G), r);
+    D.lmst[r] = G.lmst[r];
+    D.bonus[r] = G.bonus[r];
+}
+
 struct Args {
     const float *x;
     long long st, sb;
@@ -126,8 +143,39 @@ struct Args {
     unsigned mask;
 };
 
-template <int CELLS>
-__global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst f) {
+// ---------------------------------------------------------------------------------------------
+// the state of a stream (pika_ctc_lm.h): reset writes it, the advance loads and stores it, the results only read it
+// ---------------------------------------------------------------------------------------------
+using Rec = StreamRec<LmBeam>;
+static_assert(sizeof(Rec) == PIKA_CTC_LM_STREAM_RECORD_BYTES && offsetof(StreamHdr, frames) == PIKA_CTC_STREAM_FRAMES_OFFSET &&
+                  offsetof(StreamHdr, overflow) == PIKA_CTC_STREAM_OVERFLOW_OFFSET,
+              "the record the header documents");
+
+__global__ __launch_bounds__(256) void ctc_lm_stream_reset_kernel(unsigned long long *tables, size_t slots, Rec *recs,
+                                                                  const int *__restrict__ which, int start) {
+    stream_reset(tables, slots, recs, which, [start](LmBeam &A) { root_slot(A, start); });
+}
+
+// the beam of a record into LDS (wave 0: lane r loads slot r); a label outside the classes (a record that was never
+// reset) is no label
+__device__ __forceinline__ void load_beam(LmBeam &A, const Rec &R, const StreamHdr &h, int tid, int C) {
+    if (tid < h.n) {
+        copy_slot(A, R.beam, tid);
+        A.len[tid] = clampi(A.len[tid], 0, h.frames);
+        if (A.last[tid] < -1 || A.last[tid] >= C) A.last[tid] = -1;
+    }
+}
+
+// The search of utterance b = blockIdx.x in its three forms, one kernel template.  ONE_SHOT: the first beam, the frames t < T_n, the end.
+// ADVANCE: the beam of the stream's record, the frames of the chunk (a.Tn its lengths, a.T its Tc; the outputs of `a`
+// are not used), the beam back into the record.  RESULTS: the beam of the record, no frame, the end with a.T the token
+// width; the record is only read -- the final term and the new order live in fsc / perm.  One body, so the forms cannot
+// drift apart, and the one-shot kernel is the code it was before the other two existed.
+enum Mode { ONE_SHOT, ADVANCE, RESULTS };
+
+// grid = B, block = 256.  recs, C and max_frames serve the two streaming forms only.
+template <int CELLS, Mode MODE>
+__global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst f, Rec *recs, int C, int max_frames) {
     __shared__ LmBeam S[2];
     __shared__ float cv[MAX_CLASSES];
     __shared__ int ci[MAX_CLASSES];
@@ -147,7 +195,17 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
     const bool slots = w == 0;  // wave 0 does the slot work: its lane r owns beam slot r
     const int r = lane;
     const int B = a.B, T = a.T, beam = a.beam, ncand = a.ncand;
-    const int Tn = clampi(a.Tn[b], 1, T);
+    StreamHdr h = {};
+    int Tn = 0;
+    if constexpr (MODE != ONE_SHOT) h = load_hdr(recs[b].h, beam, max_frames);
+    if constexpr (MODE == ADVANCE) {
+        bool cut;
+        Tn = stream_frames(a.Tn, b, T, h.frames, max_frames, cut);
+        // (not ordered against the other threads' load of the header above: nothing reads h.overflow)
+        if (cut && tid == 0) recs[b].h.overflow = 1;
+        if (Tn <= 0) return;  // workgroup-uniform: nothing of this chunk is the stream's, the state stays as it is
+    }
+    if constexpr (MODE == ONE_SHOT) Tn = clampi(a.Tn[b], 1, T);
     const double lmw = (double)a.lmw, lb = (double)a.lb;
     unsigned long long *table = a.table + (size_t)b * ((size_t)a.mask + 1);
     const unsigned mask = a.mask;
@@ -155,10 +213,11 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
 
     int cur = 0, n = 1;
     double off = 0.0, boff = 0.0;  // what was moved out of tot and of bonus (identical in every thread)
-    if (tid == 0) {
-        LmBeam &A = S[0];
-        A.node[0] = ROOT; A.last[0] = -1; A.pnode[0] = NONE; A.len[0] = 0; A.lmst[0] = a.start;
-        A.pb[0] = 0.0f; A.pnb[0] = NEG; A.tot[0] = 0.0f; A.bonus[0] = 0.0;
+    if constexpr (MODE != ONE_SHOT) {
+        n = h.n; off = h.off; boff = h.boff;
+        load_beam(S[0], recs[b], h, tid, C);
+    } else {
+        if (tid == 0) root_slot(S[0], a.start);
     }
     // the frame's compact row, fetched one frame ahead
     float pv = NEG, plb = NEG, pl = 0.0f;
@@ -170,8 +229,8 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
         plb = a.blank_lp[rb];
         pl = a.lse ? a.lse[rb] : 0.0f;
     };
-    fetch(0);
-    for (int t = 0; t < Tn; ++t) {  // workgroup-uniform
+    if constexpr (MODE != RESULTS) fetch(0);
+    for (int t = 0; t < Tn; ++t) {  // workgroup-uniform (RESULTS: no frame)
         __syncthreads();            // the previous frame's beam is complete; cv / ci / excl / the cells are free
         const LmBeam &A = S[cur];
         LmBeam &N = S[cur ^ 1];
@@ -273,7 +332,7 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
         }
         __syncthreads();  // the new beam's k slots are written
         assign_node(N, r, slots && r < k, table, mask);
-        if (renorm_due(t, k)) {
+        if (renorm_due(h.frames + t, k)) {  // (one-shot: h.frames is the constant 0)
             const double mb = N.bonus[0];  // slot 0 has the best fused score; read before renorm()'s barrier
             off += (double)renorm(N, r, slots && r < k);
             if (slots && r < k) N.bonus[r] = N.bonus[r] - mb;
@@ -284,6 +343,15 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
     }
     __syncthreads();
     const LmBeam &A = S[cur];
+    if constexpr (MODE == ADVANCE) {  // the beam and what was moved out of it, back into the record
+        Rec &R = recs[b];
+        if (tid < n) copy_slot(R.beam, A, tid);
+        if (tid == 0) {
+            R.h.n = n; R.h.frames = h.frames + Tn;
+            R.h.off = off; R.h.boff = boff;
+        }
+        return;
+    }
     // ---- the end: the final cost, the order of the fp32 scores (ties: the rank before), the n-best
     float sc = -__builtin_inff();
     if (slots && r < n) {
@@ -313,7 +381,7 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
         a.scores[(size_t)b * nbest + r] = have ? fsc[src] : -__builtin_inff();
         a.am_scores[(size_t)b * nbest + r] = have ? (float)(off + (double)A.tot[src]) : -__builtin_inff();
     }
-    write_nbest<THREADS>(A, nlive, [&](int q) { return perm[q]; }, tid, b, T, nbest, a.tokens, a.lengths, table, mask);
+    write_nbest<THREADS, MODE == RESULTS>(A, nlive, [&](int q) { return perm[q]; }, tid, b, T, nbest, a.tokens, a.lengths, table, mask);
 }
 
 }  // namespace
@@ -347,9 +415,79 @@ int pika_ctc_lm_beam_search(const float *x, long long stride_t, long long stride
     const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
                    label_offset};
     if (beam * candidates <= CELLS_SMALL)
-        hipLaunchKernelGGL(ctc_lm_kernel<CELLS_SMALL>, dim3((unsigned)B), dim3(THREADS), 0, s, a, f);
+        hipLaunchKernelGGL((ctc_lm_kernel<CELLS_SMALL, ONE_SHOT>), dim3((unsigned)B), dim3(THREADS), 0, s, a, f,
+                           static_cast<Rec *>(nullptr), 0, 0);
     else
-        hipLaunchKernelGGL(ctc_lm_kernel<CELLS_LARGE>, dim3((unsigned)B), dim3(THREADS), 0, s, a, f);
+        hipLaunchKernelGGL((ctc_lm_kernel<CELLS_LARGE, ONE_SHOT>), dim3((unsigned)B), dim3(THREADS), 0, s, a, f,
+                           static_cast<Rec *>(nullptr), 0, 0);
+    return (int)hipGetLastError();
+}
+
+size_t pika_ctc_lm_stream_state_bytes(int B, int max_frames, int beam, int candidates) {
+    if (check_search_dims(B, max_frames, beam, candidates)) return 0;
+    return table_bytes(B, max_frames, beam) + (size_t)B * sizeof(Rec);
+}
+
+int pika_ctc_lm_stream_reset(void *state, int B, int max_frames, int beam, int candidates, int num_states, int start,
+                             const int *which, void *stream) {
+    if (num_states <= 0 || start < 0 || start >= num_states) return PIKA_EINVAL;
+    if (int rc = check_search_dims(B, max_frames, beam, candidates)) return rc;
+    if (!state) return PIKA_EINVAL;
+    hipLaunchKernelGGL(ctc_lm_stream_reset_kernel, reset_grid(B, max_frames, beam), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), static_cast<unsigned long long *>(state),
+                       table_slots(max_frames, beam), stream_recs<Rec>(state, B, max_frames, beam), which, start);
+    return (int)hipGetLastError();
+}
+
+int pika_ctc_lm_stream_advance(const float *x, long long stride_t, long long stride_b, const float *lse,
+                               const float *blank_lp, const float *top_val, const int *top_idx,
+                               const int *chunk_lengths, int B, int Tc, int C, int blank, int beam,
+                               const long long *fst_offsets, const int *fst_ilabel, const float *fst_weight,
+                               const int *fst_nextstate, const float *fst_final, int num_states, int num_arcs,
+                               int backoff_id, int label_offset, int candidates, float lm_weight, float length_bonus,
+                               void *state, int max_frames, void *stream) {
+    if (B <= 0 || Tc <= 0 || C <= 0 || blank < 0 || blank >= C) return PIKA_EINVAL;
+    if (num_states <= 0 || num_arcs < 0) return PIKA_EINVAL;
+    if (int rc = check_search_dims(B, max_frames, beam, candidates)) return rc;
+    if (2ll * Tc * beam > (1ll << 28)) return PIKA_ETOOBIG;  // the row arrays' index range, as in the one-shot search
+    if (!x || !blank_lp || !top_val || !top_idx || !chunk_lengths || !state || !fst_offsets || !fst_final ||
+        (num_arcs > 0 && (!fst_ilabel || !fst_weight || !fst_nextstate)))
+        return PIKA_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Args a = {x, stride_t, stride_b, lse, blank_lp, top_val, top_idx, chunk_lengths, B, Tc, beam, 0, candidates,
+                    0, 0, lm_weight, length_bonus, nullptr, nullptr, nullptr, nullptr,
+                    static_cast<unsigned long long *>(state), (unsigned)(table_slots(max_frames, beam) - 1)};
+    const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
+                   label_offset};
+    Rec *recs = stream_recs<Rec>(state, B, max_frames, beam);
+    if (beam * candidates <= CELLS_SMALL)
+        hipLaunchKernelGGL((ctc_lm_kernel<CELLS_SMALL, ADVANCE>), dim3((unsigned)B), dim3(THREADS), 0, s, a, f, recs, C,
+                           max_frames);
+    else
+        hipLaunchKernelGGL((ctc_lm_kernel<CELLS_LARGE, ADVANCE>), dim3((unsigned)B), dim3(THREADS), 0, s, a, f, recs, C,
+                           max_frames);
+    return (int)hipGetLastError();
+}
+
+int pika_ctc_lm_stream_results(const void *state, int B, int max_frames, int beam, int candidates,
+                               const long long *fst_offsets, const int *fst_ilabel, const float *fst_weight,
+                               const int *fst_nextstate, const float *fst_final, int num_states, int num_arcs,
+                               int backoff_id, int label_offset, float lm_weight, int use_final, int nbest, int L,
+                               int *tokens, int *lengths, float *scores, float *am_scores, void *stream) {
+    if (num_states <= 0 || num_arcs < 0) return PIKA_EINVAL;
+    if (int rc = check_results_dims(B, max_frames, beam, candidates, nbest, L)) return rc;
+    if (!state || !tokens || !lengths || !scores || !am_scores || !fst_offsets || !fst_final ||
+        (num_arcs > 0 && (!fst_ilabel || !fst_weight || !fst_nextstate)))
+        return PIKA_EINVAL;
+    const Args a = {nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, B, L, beam, nbest, candidates, 0, use_final,
+                    lm_weight, 0.0f, tokens, lengths, scores, am_scores,
+                    static_cast<unsigned long long *>(const_cast<void *>(state)),
+                    (unsigned)(table_slots(max_frames, beam) - 1)};
+    const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
+                   label_offset};
+    hipLaunchKernelGGL((ctc_lm_kernel<CELLS_SMALL, RESULTS>), dim3((unsigned)B), dim3(THREADS), 0,
+                       static_cast<hipStream_t>(stream), a, f, stream_recs<Rec>(state, B, max_frames, beam), 0x7fffffff,
+                       max_frames);
     return (int)hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // pika_amd/csrc/ctc_search_core.h -- what the CTC prefix beam searches share (ctc_decode.hip: ctc_beam_kernel,
-// ctc_lm.hip: ctc_lm_kernel; not part of the C ABI): the beam, the trie of prefixes in an open-addressing table, the
-// per-frame slot work, the total order of the arg-max, node assignment, the renormalisation, the n-best tail and the
-// host-side limits.  What differs -- which candidates a slot offers and how they are scored -- stays with each kernel.
+// ctc_lm.hip: ctc_lm_kernel, and the streaming kernels of both; not part of the C ABI): the beam, the trie of prefixes in
+// an open-addressing table, the per-frame slot work, the total order of the arg-max, node assignment, the
+// renormalisation, the n-best tail, the state a stream carries between launches and the host-side limits.  What differs
+// -- which candidates a slot offers and how they are scored -- stays with each kernel.
 #ifndef PIKA_CTC_SEARCH_CORE_H
 #define PIKA_CTC_SEARCH_CORE_H
 
@@ -28,6 +29,18 @@ struct Beam {
     int len[MAX_BEAM];
     float pb[MAX_BEAM], pnb[MAX_BEAM], tot[MAX_BEAM];
 };
+
+// the beam a search starts from: the empty prefix in slot 0
+__device__ __forceinline__ void root_slot(Beam &A) {
+    A.node[0] = ROOT; A.last[0] = -1; A.pnode[0] = NONE; A.len[0] = 0;
+    A.pb[0] = 0.0f; A.pnb[0] = NEG; A.tot[0] = 0.0f;
+}
+
+// slot r from one beam to another (LDS <-> a stream's record)
+__device__ __forceinline__ void copy_slot(Beam &D, const Beam &G, int r) {
+    D.node[r] = G.node[r]; D.last[r] = G.last[r]; D.pnode[r] = G.pnode[r]; D.len[r] = G.len[r];
+    D.pb[r] = G.pb[r]; D.pnb[r] = G.pnb[r]; D.tot[r] = G.tot[r];
+}
 
 __device__ inline unsigned long long trie_key(int parent, int token) {
     return ((unsigned long long)(unsigned)parent << 32) | (unsigned)token;
@@ -113,7 +126,8 @@ __device__ __forceinline__ void assign_node(Beam &N, int r, bool mine, unsigned 
     if (mine && N.node[r] == PENDING) N.node[r] = trie_node(table, mask, N.pnode[r], N.last[r]);
 }
 
-// frame t ends with k > 0 slots and is the last of RENORM (workgroup-uniform)
+// frame t (counted from the utterance's first frame) ends with k > 0 slots and is the last of RENORM
+// (workgroup-uniform)
 __device__ inline bool renorm_due(int t, int k) { return t % RENORM == RENORM - 1 && k > 0; }
 
 // subtracts the best tot from the slots (`mine`: this thread owns slot r < k) and returns it for the caller's fp64
@@ -130,8 +144,9 @@ __device__ __forceinline__ float renorm(Beam &N, int r, bool mine) {
 }
 
 // the n-best of utterance b by THREADS threads: entry k is slot perm(k) for k < n; lengths, -1 beyond each length (and
-// for entries that do not exist), then the back-trace through the table.  Scores stay with the caller.
-template <int THREADS, class Perm>
+// for entries that do not exist), then the back-trace through the table.  Scores stay with the caller.  CLIP: a prefix
+// may be longer than the T tokens the caller allocated (the streaming results); its labels beyond T are not written.
+template <int THREADS, bool CLIP = false, class Perm>
 __device__ __forceinline__ void write_nbest(const Beam &A, int n, Perm perm, int tid, int b, int T, int nbest,
                                             int *tokens, int *lengths, const unsigned long long *table,
                                             unsigned mask) {
@@ -146,10 +161,62 @@ __device__ __forceinline__ void write_nbest(const Beam &A, int n, Perm perm, int
         int *out = tokens + ((size_t)b * nbest + tid) * T;
         for (int p = A.len[src] - 1; p >= 0 && node != ROOT; --p) {  // len <= T_n <= T: one label per frame at most
             const unsigned long long key = trie_load(table, mask, node);
-            out[p] = (int)(unsigned)(key & 0xffffffffull);
+            if (!CLIP || p < T) out[p] = (int)(unsigned)(key & 0xffffffffull);
             node = (int)(unsigned)(key >> 32);
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// streaming: the search is a function of (state, frame), so the state can rest in device memory between launches.
+// A batch's blob is its B tables (sized for max_frames frames) followed by one record per stream.
+// ---------------------------------------------------------------------------------------------
+struct StreamHdr {
+    int n;         // slots of the beam
+    int frames;    // frames consumed: the phase of the renormalisation, and the table's fill
+    int overflow;  // frames were dropped because max_frames was reached
+    int pad;
+    double off, boff;  // what was moved out of tot (and, with an LM, out of bonus)
+};
+
+template <class BeamT>
+struct StreamRec {
+    StreamHdr h;
+    BeamT beam;  // slots [0, n)
+};
+
+// what a launch may take from a record, read as it stands: a blob that was never reset holds anything, and n, frames and
+// every len bound loops and stores
+__device__ __forceinline__ StreamHdr load_hdr(const StreamHdr &G, int beam, int max_frames) {
+    StreamHdr h = G;
+    h.n = clampi(h.n, 0, beam);
+    h.frames = clampi(h.frames, 0, max_frames);
+    return h;
+}
+
+// Reset.  grid = (B, y), block = 256: the workgroups (b, *) clear stream b's table, (b, 0) writes its record; streams with
+// which[b] == 0 are not touched.  `root(beam)` writes the search's first beam.
+template <class BeamT, class Root>
+__device__ __forceinline__ void stream_reset(unsigned long long *tables, size_t slots, StreamRec<BeamT> *recs,
+                                             const int *which, Root root) {
+    const int b = blockIdx.x;
+    if (which && which[b] == 0) return;  // workgroup-uniform
+    unsigned long long *table = tables + (size_t)b * slots;
+    for (size_t i = (size_t)blockIdx.y * 256 + threadIdx.x; i < slots; i += (size_t)gridDim.y * 256) table[i] = EMPTY;
+    if (blockIdx.y == 0 && threadIdx.x == 0) {
+        StreamRec<BeamT> &R = recs[b];
+        R.h.n = 1; R.h.frames = 0; R.h.overflow = 0; R.h.pad = 0;
+        R.h.off = 0.0; R.h.boff = 0.0;
+        root(R.beam);
+    }
+}
+
+// the frames of a chunk that stream b takes: its length clamped to [0, Tc], cut where max_frames would be passed
+// (`cut`: frames were dropped)
+__device__ __forceinline__ int stream_frames(const int *len, int b, int Tc, int frames, int max_frames, bool &cut) {
+    const int L = clampi(len[b], 0, Tc);
+    cut = L > max_frames - frames;
+    return cut ? max_frames - frames : L;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -173,6 +240,25 @@ static inline size_t table_bytes(int B, int T, int beam) { return 8 * (size_t)B 
 // every key of the B tables EMPTY
 static inline hipError_t clear_tables(void *scratch, int B, int T, int beam, hipStream_t s) {
     return hipMemsetAsync(scratch, 0xff, table_bytes(B, T, beam), s);
+}
+
+// the streaming calls: where the blob's parts lie, and the reset's grid
+template <class Rec>
+static inline Rec *stream_recs(const void *state, int B, int max_frames, int beam) {
+    return reinterpret_cast<Rec *>(static_cast<char *>(const_cast<void *>(state)) + table_bytes(B, max_frames, beam));
+}
+
+static inline dim3 reset_grid(int B, int max_frames, int beam) {
+    const size_t y = table_slots(max_frames, beam) / 4096;  // 16 keys per thread
+    return dim3((unsigned)B, (unsigned)(y < 1 ? 1 : (y > 256 ? 256 : y)));
+}
+
+// the n-best outputs of a results call: nbest entries of L tokens
+static inline int check_results_dims(int B, int max_frames, int beam, int classes, int nbest, int L) {
+    if (nbest <= 0 || L <= 0) return PIKA_EINVAL;
+    if (int rc = check_search_dims(B, max_frames, beam, classes)) return rc;
+    if (nbest > beam || (long long)nbest * L > 0x7fffffffll) return PIKA_ETOOBIG;
+    return PIKA_OK;
 }
 
 }  // namespace

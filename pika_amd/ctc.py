@@ -24,6 +24,13 @@ and the search with an n-gram LM fused in (include/pika_ctc_lm.h, csrc/ctc_lm.hi
         -> (tokens (B,nbest,T), lengths (B,nbest), scores (B,nbest), am_scores (B,nbest))
     ctc_beam_search_lm_from_logits(logits, ...same...)
 
+and both searches with their state carried across calls, for audio that arrives in chunks:
+
+    CtcBeamStream(batch, max_frames, beam=16, blank=0, lm=None, lm_weight=0.5, length_bonus=0.0, candidates=None,
+                  device=None)
+        .reset(which=None)  .advance(log_probs, lengths=None)  .advance_from_logits(logits, lengths=None)
+        .results(nbest=1, use_final=True)  .frames  .overflowed
+
 Differences from torch, on purpose:
 
 * THE GRADIENT IS THE TRUE DERIVATIVE.  torch's native CTC backward returns `exp(log_probs) - occ` for d/d log_probs,
@@ -52,6 +59,9 @@ MAX_STATES = 1024   # 2 * U_max + 1: one workgroup spans the state axis
 MAX_BEAM = 64       # one lane per beam slot
 MAX_CANDIDATES = 128
 MAX_BACKOFF_HOPS = 8
+# a stream's record behind the tables of its blob (include/pika_ctc_decode.h): i32 words n, frames, overflow, ...
+STREAM_FRAMES_WORD = 1      # PIKA_CTC_STREAM_FRAMES_OFFSET / 4
+STREAM_OVERFLOW_WORD = 2    # PIKA_CTC_STREAM_OVERFLOW_OFFSET / 4
 
 
 def _ptr(t):
@@ -505,3 +515,171 @@ def ctc_beam_search_lm_from_logits(logits, input_lengths, lm, beam=16, nbest=1, 
     """`ctc_beam_search_lm` of log_softmax(logits, -1) without materialising the log-probabilities."""
     return _beam_lm(logits, "logits", input_lengths, lm, beam, nbest, blank, lm_weight, length_bonus, candidates,
                     use_final, True)
+
+
+class CtcBeamStream(object):
+    """`ctc_beam_search` (lm=None) or `ctc_beam_search_lm` (lm a `CtcNgramLm`) for `batch` independent streams whose
+    frames arrive in chunks.  The beam, the fp64 offsets, the frame count and the trie of every stream rest in one blob
+    of device memory between calls (include/pika_ctc_decode.h, "Streaming"), and the frames go through the per-frame
+    code of the one-shot kernels, so ANY chunking gives bit for bit what the one-shot call gives on the whole tensor.
+
+    advance(log_probs, lengths=None)   log_probs (Tc,B,C) float32 on the device, any stride, B == batch; C is fixed by
+        the first call.  lengths (B,) int32 / int64, host or device, clamped on the device to [0,Tc], None = Tc: stream b
+        takes the frames t < lengths[b] of the chunk; with 0 it is left exactly as it was.
+    advance_from_logits(logits, lengths=None)   the same on log_softmax(logits, -1), which never exists.
+    results(nbest=1, use_final=True)   the n-best of the beams as they stand, in the shapes of the one-shot call with
+        T = max_frames: (tokens (B,nbest,max_frames), lengths, scores), and am_scores with an LM.  It only reads the
+        state: partial hypotheses can be taken after every chunk and decoding goes on; with an LM the final term and
+        the re-sort of `use_final` happen on the side, so either setting can be asked at any time (ignored without LM).
+    reset(which=None)   every stream back to the empty prefix, or those selected by `which` ((B,) bool / int tensor or
+        sequence, host or device); the others' state, tables included, is not touched, so one stream of a serving
+        batch can start a new utterance while its neighbours continue.
+    frames       (B,) int32 device tensor: frames consumed per stream (a view of the state: it follows the stream)
+    overflowed   (B,) bool device tensor: frames were dropped because the stream was full
+
+    A stream holds at most max_frames frames.  On the host the object sums the chunk widths Tc fed since the last FULL
+    reset() and raises ValueError before launching anything once the sum would exceed max_frames; this bound is
+    conservative (it ignores `lengths`) and needs no synchronisation.  A partial reset does not lower it: the streams
+    that continue still hold their frames.  What the host cannot see -- replays of a captured graph -- the device
+    handles: a stream takes frames up to max_frames, ignores the rest of the chunk and sets `overflowed`.
+
+    Argument checks as the one-shot functions (1 <= nbest <= beam <= 64, 1 <= candidates <= 128 with None meaning
+    min(2 * beam, 128), the LM's device, its backoff_id against C).  No autograd; no host synchronisation in `advance`
+    or `results`: both can be captured in a `torch.cuda.graph` when the lengths are on the device."""
+
+    def __init__(self, batch, max_frames, beam=16, blank=0, lm=None, lm_weight=0.5, length_bonus=0.0, candidates=None,
+                 device=None):
+        batch, max_frames, beam, blank = int(batch), int(max_frames), int(beam), int(blank)
+        if not 1 <= beam <= MAX_BEAM:
+            raise ValueError("need 1 <= beam <= %d, got beam=%d" % (MAX_BEAM, beam))
+        if lm is not None and not isinstance(lm, CtcNgramLm):
+            raise TypeError("lm must be a CtcNgramLm or None, got %s" % type(lm).__name__)
+        if lm is None:
+            candidates = 2 * beam                       # the row pass's K of the plain search: exact
+        else:
+            candidates = min(2 * beam, MAX_CANDIDATES) if candidates is None else int(candidates)
+            if not 1 <= candidates <= MAX_CANDIDATES:
+                raise ValueError("need 1 <= candidates <= %d, got %d" % (MAX_CANDIDATES, candidates))
+        if batch < 1 or max_frames < 1 or blank < 0:
+            raise ValueError("need batch >= 1, max_frames >= 1 and blank >= 0, got %d, %d, %d" % (batch, max_frames, blank))
+        if not torch.cuda.is_available():
+            raise RuntimeError("pika_amd CtcBeamStream: needs a HIP device (there is no CPU path)")
+        dev = torch.device(("cuda" if lm is None else lm.device) if device is None else device)
+        if dev.type != "cuda":
+            raise RuntimeError("pika_amd CtcBeamStream: device %s is not a HIP device (there is no CPU path)" % dev)
+        self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+        if lm is not None and lm.device != self.device:
+            raise ValueError("the LM lives on %s, the stream on %s" % (lm.device, self.device))
+        self.batch, self.max_frames, self.beam, self.blank, self.candidates = batch, max_frames, beam, blank, candidates
+        self.lm, self.lm_weight, self.length_bonus = lm, float(lm_weight), float(length_bonus)
+        lib = _lib.lib()
+        if lm is None:
+            nbytes = lib.pika_ctc_stream_state_bytes(batch, max_frames, beam)
+            tables = lib.pika_ctc_beam_scratch_bytes(batch, max_frames, beam)
+        else:
+            nbytes = lib.pika_ctc_lm_stream_state_bytes(batch, max_frames, beam, candidates)
+            tables = lib.pika_ctc_lm_scratch_bytes(batch, max_frames, beam, candidates)
+        if nbytes == 0:
+            raise ValueError("(batch,max_frames,beam) = (%d,%d,%d) not supported" % (batch, max_frames, beam))
+        rec = (nbytes - tables) // batch                # the record's size is the library's: the blob is tables + records
+        self.classes = None                             # C, fixed by the first advance
+        self._fed = 0                                   # chunk widths since the last full reset
+        with torch.cuda.device(self.device):
+            self._state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._hdr = self._state[tables:].view(torch.int32).view(batch, rec // 4)
+        self.reset()
+
+    def _fst(self):
+        lm = self.lm
+        return (_ptr(lm.offsets), _ptr(lm.ilabel), _ptr(lm.weight), _ptr(lm.nextstate), _ptr(lm.final), lm.num_states,
+                lm.num_arcs)
+
+    @property
+    def frames(self):
+        return self._hdr[:, STREAM_FRAMES_WORD]
+
+    @property
+    def overflowed(self):
+        return self._hdr[:, STREAM_OVERFLOW_WORD] != 0
+
+    def reset(self, which=None):
+        if which is not None:
+            which = torch.as_tensor(which)
+            if which.dtype not in (torch.bool, torch.int32, torch.int64):
+                raise TypeError("which must be bool, int32 or int64, got %s" % which.dtype)
+            which = which.reshape(-1).to(self.device, torch.int32).contiguous()
+            if which.numel() != self.batch:
+                raise ValueError("which must hold batch = %d entries" % self.batch)
+        lib = _lib.lib()
+        with torch.cuda.device(self.device):
+            if self.lm is None:
+                _lib.check(lib.pika_ctc_stream_reset(_ptr(self._state), self.batch, self.max_frames, self.beam,
+                                                     _ptr(which), _stream()), "pika_ctc_stream_reset")
+            else:
+                _lib.check(lib.pika_ctc_lm_stream_reset(_ptr(self._state), self.batch, self.max_frames, self.beam,
+                                                        self.candidates, self.lm.num_states, self.lm.start, _ptr(which),
+                                                        _stream()), "pika_ctc_lm_stream_reset")
+        if which is None:
+            self._fed = 0
+
+    def _advance(self, x, what, lengths, logits):
+        x, _ = _check_input(x, what, "CtcBeamStream", self.blank)
+        Tc, B, C = x.shape
+        if B != self.batch:
+            raise ValueError("%s holds %d streams, the object %d" % (what, B, self.batch))
+        if self.classes is not None and C != self.classes:
+            raise ValueError("%s has %d classes, the chunks before had %d" % (what, C, self.classes))
+        if x.device != self.device:
+            raise ValueError("the stream lives on %s, %s on %s" % (self.device, what, x.device))
+        lm = self.lm
+        if lm is not None and 0 <= lm.backoff_id - lm.label_offset < C:
+            raise ValueError("the LM's backoff_id %d is the label of class %d" % (lm.backoff_id,
+                                                                                 lm.backoff_id - lm.label_offset))
+        if self._fed + Tc > self.max_frames:
+            raise ValueError("%d frames were fed since the last full reset: %d more exceed max_frames = %d"
+                             % (self._fed, Tc, self.max_frames))
+        if lengths is None:
+            with torch.cuda.device(self.device):
+                lengths = torch.full((B,), Tc, dtype=torch.int32, device=self.device)
+        x, il, blank_lp, top_val, top_idx, lse, _ = _decode_rows(x, what, lengths, self.blank, self.candidates, logits)
+        lib = _lib.lib()
+        with torch.cuda.device(self.device):
+            head = (_ptr(x), x.stride(0), x.stride(1), _ptr(lse), _ptr(blank_lp), _ptr(top_val), _ptr(top_idx), _ptr(il),
+                    B, Tc, C, self.blank, self.beam)
+            if lm is None:
+                _lib.check(lib.pika_ctc_stream_advance(*(head + (_ptr(self._state), self.max_frames, _stream()))),
+                           "pika_ctc_stream_advance")
+            else:
+                _lib.check(lib.pika_ctc_lm_stream_advance(*(head + self._fst() + (
+                    lm.backoff_id, lm.label_offset, self.candidates, self.lm_weight, self.length_bonus,
+                    _ptr(self._state), self.max_frames, _stream()))), "pika_ctc_lm_stream_advance")
+        self.classes = C
+        self._fed += Tc
+
+    def advance(self, log_probs, lengths=None):
+        self._advance(log_probs, "log_probs", lengths, False)
+
+    def advance_from_logits(self, logits, lengths=None):
+        self._advance(logits, "logits", lengths, True)
+
+    def results(self, nbest=1, use_final=True):
+        nbest = int(nbest)
+        _nbest_outputs(self.beam, nbest)
+        B, L, lm, dev = self.batch, self.max_frames, self.lm, self.device
+        lib = _lib.lib()
+        with torch.cuda.device(dev):
+            tokens = torch.empty((B, nbest, L), dtype=torch.int32, device=dev)
+            lengths = torch.empty((B, nbest), dtype=torch.int32, device=dev)
+            scores = torch.empty((B, nbest), dtype=torch.float32, device=dev)
+            if lm is None:
+                _lib.check(lib.pika_ctc_stream_results(_ptr(self._state), B, L, self.beam, nbest, L, _ptr(tokens),
+                                                       _ptr(lengths), _ptr(scores), _stream()),
+                           "pika_ctc_stream_results")
+                return tokens, lengths, scores
+            am_scores = torch.empty((B, nbest), dtype=torch.float32, device=dev)
+            _lib.check(lib.pika_ctc_lm_stream_results(*((_ptr(self._state), B, L, self.beam, self.candidates)
+                                                        + self._fst() + (lm.backoff_id, lm.label_offset, self.lm_weight,
+                                                                         int(bool(use_final)), nbest, L, _ptr(tokens),
+                                                                         _ptr(lengths), _ptr(scores), _ptr(am_scores),
+                                                                         _stream()))), "pika_ctc_lm_stream_results")
+        return tokens, lengths, scores, am_scores
