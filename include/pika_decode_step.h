@@ -202,7 +202,10 @@ int pika_dfc2_logits(const float *h, long long ldh, const void *W, const float *
  * best (ties: lowest column first).  Rows whose survivors outnumber the 256-entry pool (many near-equal values; splits < K)
  * have the bound raised by bisection with counting passes.  Results identical to pika_beam_advance.  Plus:
  * `first` is read from the device (*step_t == 0); the step counter is incremented by the call;
- * done[b] (u8) = eos_top[b] && fin_n[b] >= n_best; *stop = all utterances done; *max_hyp = max hyp_len.
+ * *stop = 1 once every utterance is done (eos_top[b] && fin_n[b] >= n_best; the per-utterance flag itself is not an
+ * output); *max_hyp = max(*max_hyp, the longest hyp_len after the step).
+ * Refused before any launch: K > 64, V < K (as pika_beam_advance: a row must hold K candidates), splits > 64 or a shape
+ * whose LDS does not fit -> PIKA_ETOOBIG; a NULL pointer (y_raw excepted), splits < 1 or ldl < V -> PIKA_EINVAL.
  * sync (int32[8], zeroed once by the caller): [0..3] scratch for the cross-workgroup arrival counts of even / odd
  * steps; [4] is set once a call was skipped because *stop was already set (the gate of the FST advance that follows; the
  * only thing a skipped call writes); [5], [6] are the compact-row counters of pika_dstep_prep (count = sync + 5): the call

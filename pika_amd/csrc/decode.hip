@@ -918,7 +918,8 @@ extern "C" int pika_beam_advance_logits(const float *pmax, const float *psum, co
     if (!pmax || !psum || !stop || !max_hyp || !sync || splits < 1 || !beam_state_ok(a)) return PIKA_EINVAL;
     int waves;
     const size_t lds_bytes = advance_lds(K, L, &waves);
-    if (K > MAXK || splits > 64 || lds_bytes > 96 * 1024) return PIKA_ETOOBIG;
+    // (V < K: a row has fewer than K candidates, and the merge would rank entries of `cand` that no wave wrote)
+    if (K > MAXK || V < K || splits > 64 || lds_bytes > 96 * 1024) return PIKA_ETOOBIG;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(beam_partials_kernel),
