@@ -18,13 +18,16 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 //   sigmoid = (e + 1) r,   1 - tanh = 2 (1 + f) r =: q,   1 - sigmoid = f (e + 1) r =: ns
 // q and ns carry no cancellation, so the backward factors (1 - tanh^2) = q (2 - q) and sigmoid (1 - sigmoid) keep their
 // relative accuracy in the saturated tails.  The clamps keep the product below FLT_MAX; tanh(+-15) is +-1 in fp32
-// and sigmoid(-50) = 2e-22.
+// and sigmoid(-50) = 2e-22.  fminf / fmaxf return the OTHER operand when one is NaN, so on their own the clamps would
+// turn a NaN pre-activation into tanh(-15) or sigmoid(-50): one unordered compare of z1 with zg (true when either is NaN)
+// and one select put the NaN back into r, from which all four values derive.  +-inf are clamped like any large value.
 struct GateVals { float th, sg, q, ns; };
 __device__ inline GateVals gate_vals(float z1, float zg) {
+    const bool nan = __builtin_isunordered(z1, zg);
     z1 = fminf(fmaxf(z1, -15.f), 15.f);
     zg = fmaxf(zg, -50.f);
     const float e1 = __expf(2.0f * z1) + 1.0f, f = __expf(-zg), f1 = 1.0f + f;
-    const float r = __builtin_amdgcn_rcpf(e1 * f1);
+    const float r = nan ? __builtin_nanf("") : __builtin_amdgcn_rcpf(e1 * f1);
     GateVals v;
     v.sg = e1 * r;
     v.q = 2.0f * f1 * r;
@@ -113,9 +116,9 @@ __global__ void gate_bwd_kernel(const TD *__restrict__ dh, const float *__restri
     }
 }
 
-// ---- row kernels: one 256-thread workgroup per row, row held in registers (cols <= 8192) ----
+// ---- row kernels: one 256-thread workgroup per row, strided scalar passes over the row; taken for every call the
+// wave-per-row kernels below do not take (wave_row_ok(): cols, pitch or base not a multiple of four floats, cols > 8192) ----
 constexpr int ROW_THREADS = 256;
-constexpr int MAXQ = 8;  // float4 per thread
 
 __device__ inline float block_reduce(float v, bool is_max, float *lds) {
 #pragma unroll
@@ -137,43 +140,14 @@ __global__ __launch_bounds__(ROW_THREADS) void log_softmax_kernel(float *__restr
                                                                   long long ld, float scale) {
     __shared__ float lds[ROW_THREADS / 64];
     float *row = x + (long long)blockIdx.x * ld;
-    const bool vec = ((cols & 3) == 0) && ((ld & 3) == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-    if (vec && cols <= ROW_THREADS * 4 * MAXQ) {
-        const int c4 = cols >> 2;
-        f32x4 v[MAXQ];
-        float m = -INFINITY;
-#pragma unroll
-        for (int q = 0; q < MAXQ; ++q) {
-            const int i = threadIdx.x + q * ROW_THREADS;
-            if (i < c4) {
-                v[q] = reinterpret_cast<const f32x4 *>(row)[i] * scale;
-                m = fmaxf(m, fmaxf(fmaxf(v[q].x, v[q].y), fmaxf(v[q].z, v[q].w)));
-            }
-        }
-        m = block_reduce(m, true, lds);
-        float s = 0.f;
-#pragma unroll
-        for (int q = 0; q < MAXQ; ++q) {
-            const int i = threadIdx.x + q * ROW_THREADS;
-            if (i < c4) s += __expf(v[q].x - m) + __expf(v[q].y - m) + __expf(v[q].z - m) + __expf(v[q].w - m);
-        }
-        s = block_reduce(s, false, lds);
-        const float lse = m + __logf(s);
-#pragma unroll
-        for (int q = 0; q < MAXQ; ++q) {
-            const int i = threadIdx.x + q * ROW_THREADS;
-            if (i < c4) reinterpret_cast<f32x4 *>(row)[i] = v[q] - lse;
-        }
-    } else {
-        float m = -INFINITY;
-        for (int i = threadIdx.x; i < cols; i += ROW_THREADS) m = fmaxf(m, row[i] * scale);
-        m = block_reduce(m, true, lds);
-        float s = 0.f;
-        for (int i = threadIdx.x; i < cols; i += ROW_THREADS) s += __expf(row[i] * scale - m);
-        s = block_reduce(s, false, lds);
-        const float lse = m + __logf(s);
-        for (int i = threadIdx.x; i < cols; i += ROW_THREADS) row[i] = row[i] * scale - lse;
-    }
+    float m = -INFINITY;
+    for (int i = threadIdx.x; i < cols; i += ROW_THREADS) m = fmaxf(m, row[i] * scale);
+    m = block_reduce(m, true, lds);
+    float s = 0.f;
+    for (int i = threadIdx.x; i < cols; i += ROW_THREADS) s += __expf(row[i] * scale - m);
+    s = block_reduce(s, false, lds);
+    const float lse = m + __logf(s);
+    for (int i = threadIdx.x; i < cols; i += ROW_THREADS) row[i] = row[i] * scale - lse;
 }
 
 __global__ __launch_bounds__(ROW_THREADS) void log_softmax_bwd_kernel(const float *__restrict__ lp,
@@ -182,41 +156,11 @@ __global__ __launch_bounds__(ROW_THREADS) void log_softmax_bwd_kernel(const floa
     __shared__ float lds[ROW_THREADS / 64];
     const float *lrow = lp + (long long)blockIdx.x * ld;
     float *grow = g + (long long)blockIdx.x * ld;
-    const bool vec = ((cols & 3) == 0) && ((ld & 3) == 0) && ((reinterpret_cast<uintptr_t>(g) & 15) == 0) &&
-                     ((reinterpret_cast<uintptr_t>(lp) & 15) == 0);
-    if (vec && cols <= ROW_THREADS * 4 * MAXQ) {
-        const int c4 = cols >> 2;
-        f32x4 v[MAXQ];
-        float s = 0.f;
-#pragma unroll
-        for (int q = 0; q < MAXQ; ++q) {
-            const int i = threadIdx.x + q * ROW_THREADS;
-            if (i < c4) {
-                v[q] = reinterpret_cast<const f32x4 *>(grow)[i];
-                s += (v[q].x + v[q].y) + (v[q].z + v[q].w);
-            }
-        }
-        s = block_reduce(s, false, lds);
-#pragma unroll
-        for (int q = 0; q < MAXQ; ++q) {
-            const int i = threadIdx.x + q * ROW_THREADS;
-            if (i < c4) {
-                const f32x4 l = reinterpret_cast<const f32x4 *>(lrow)[i];
-                f32x4 r;
-                r.x = scale * (v[q].x - __expf(l.x) * s);
-                r.y = scale * (v[q].y - __expf(l.y) * s);
-                r.z = scale * (v[q].z - __expf(l.z) * s);
-                r.w = scale * (v[q].w - __expf(l.w) * s);
-                reinterpret_cast<f32x4 *>(grow)[i] = r;
-            }
-        }
-    } else {
-        float s = 0.f;
-        for (int i = threadIdx.x; i < cols; i += ROW_THREADS) s += grow[i];
-        s = block_reduce(s, false, lds);
-        for (int i = threadIdx.x; i < cols; i += ROW_THREADS)
-            grow[i] = scale * (grow[i] - __expf(lrow[i]) * s);
-    }
+    float s = 0.f;
+    for (int i = threadIdx.x; i < cols; i += ROW_THREADS) s += grow[i];
+    s = block_reduce(s, false, lds);
+    for (int i = threadIdx.x; i < cols; i += ROW_THREADS)
+        grow[i] = scale * (grow[i] - __expf(lrow[i]) * s);
 }
 
 

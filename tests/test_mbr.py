@@ -376,6 +376,39 @@ def test_edit_distances_library_call_equals_the_python_dp():
     assert mbr.edit_distances([]) == []
 
 
+def _edit_distances_abi(seqs, a_off, a_len, b_off, b_len, n_pairs=None):
+    """pika_edit_distances itself (pika_amd.mbr.edit_distances returns early on an empty list): (rc, out)."""
+    from pika_amd import _lib
+    n = len(a_len) if n_pairs is None else n_pairs
+    seqs = np.asarray(list(seqs) + [-99], dtype=np.int32)               # never empty, and a guard nobody may compare
+    ao, bo = np.asarray(list(a_off) + [0], dtype=np.int64), np.asarray(list(b_off) + [0], dtype=np.int64)
+    al, bl = np.asarray(list(a_len) + [0], dtype=np.int32), np.asarray(list(b_len) + [0], dtype=np.int32)
+    out = np.full(len(a_len) + 1, -7, dtype=np.int32)
+    rc = _lib.lib().pika_edit_distances(seqs.ctypes.data, ao.ctypes.data, al.ctypes.data, bo.ctypes.data, bl.ctypes.data,
+                                        n, out.ctypes.data)
+    return rc, out.tolist()
+
+
+def test_edit_distances_edge_cases_at_the_abi():
+    """n_pairs == 0 writes nothing; two empty sequences are 0 apart; an empty one against n symbols is n (either side);
+    identical sequences are 0 apart (also one sequence against itself at the same offset); a negative length in ANY pair is
+    PIKA_EINVAL and nothing is written."""
+    assert _edit_distances_abi([], [], [], [], []) == (0, [-7])
+    assert _edit_distances_abi([1, 2, 3], [0], [3], [0], [3], n_pairs=0) == (0, [-7, -7])
+    assert _edit_distances_abi([], [0], [0], [0], [0]) == (0, [0, -7])
+    assert _edit_distances_abi([5, 6, 7], [0], [0], [0], [3]) == (0, [3, -7])
+    assert _edit_distances_abi([5, 6, 7], [0], [3], [3], [0]) == (0, [3, -7])
+    assert _edit_distances_abi([4, 4, 9, 4, 4, 9], [0], [3], [3], [3]) == (0, [0, -7])
+    assert _edit_distances_abi([4, 4, 9], [0], [3], [0], [3]) == (0, [0, -7])
+    # several pairs in one call, an empty one between two others: the rolling rows are sized by the longest b
+    assert _edit_distances_abi([1, 2, 3, 1, 9, 3, 8], [0, 0, 3], [3, 0, 3], [3, 0, 6], [3, 0, 1]) == (0, [1, 0, 3, -7])
+    for a_len, b_len in (([-1], [2]), ([2], [-1]), ([2, -3], [2, 2]), ([2, 2], [2, -1])):
+        off = [0] * len(a_len)
+        rc, out = _edit_distances_abi([1, 2, 3, 4], off, a_len, off, b_len)
+        assert rc == -1 and out == [-7] * (len(a_len) + 1), (a_len, b_len)
+    assert _edit_distances_abi([1, 2], [0], [1], [1], [1], n_pairs=-1)[0] == -1
+
+
 @pytest.mark.gpu
 def test_gpu_graphed_mbr_step_replays_on_other_nbest_lists_and_buckets(hip_device):
     """GraphedMbrStep beyond the fixed batch of the golden: ONE captured graph must serve other N-best lists of its (S, U)
