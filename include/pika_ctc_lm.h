@@ -110,6 +110,67 @@ int pika_ctc_lm_stream_results(const void *state, int B, int max_frames, int bea
                                int backoff_id, int label_offset, float lm_weight, int use_final, int nbest, int L,
                                int *tokens, int *lengths, float *scores, float *am_scores, void *stream);
 
+/* ---- A second automaton beside the LM: contextual biasing (hotwords), or a second, domain LM ---------------------------
+ * The pika_ctc_lm2_* calls are their pika_ctc_lm_* counterparts with a second FST of the same layout (fst2_*, its own
+ * backoff_id2 / label_offset2) and its weight:
+ *   F(l) = tot(l) + lm_weight * LM(l) + bias_weight * BIAS(l) + length_bonus * |l|
+ * LM(l) and BIAS(l) each the sum of step increments of its own automaton from its own start state (start / start2), by
+ * the step() above.  A child that EITHER automaton cannot reach does not exist.  With use_final a prefix adds
+ * lm_weight * final(state) + bias_weight * final2(state2) and drops out when either walk finds no final state.
+ * Candidates, the acoustic recursion, the tie order, am_scores, the limits and the renormalisation are unchanged.
+ * Numerics: each automaton's increment is rounded to fp32 once; the products with the weights and the sums into the
+ * slot's bonus are fp64; a slot carries ONE bonus for both terms and the length bonus; F = fp32(tot + bonus).
+ * The second FST's arguments follow the first's (after label_offset), bias_weight follows lm_weight; a call without
+ * `start` has no `start2`.  PIKA_EINVAL for num_states2 <= 0, num_arcs2 < 0, start2 outside [0, num_states2) or a
+ * missing array of the second FST (the arc arrays may be NULL when num_arcs2 == 0), before any launch.  The device code
+ * ends on any pair of tables, as it does for one.
+ * A stream's record is the LM record followed by the second states, i32 x 64: PIKA_CTC_LM2_STREAM_RECORD_BYTES;
+ * `frames` and `overflow` lie at the same offsets.  Both FSTs and both weights must be the same in every call on a
+ * blob between two resets. */
+#define PIKA_CTC_LM2_STREAM_RECORD_BYTES (PIKA_CTC_LM_STREAM_RECORD_BYTES + 256)
+
+/* == pika_ctc_lm_scratch_bytes: the second automaton needs no scratch. */
+size_t pika_ctc_lm2_scratch_bytes(int B, int T, int beam, int candidates);
+
+int pika_ctc_lm2_beam_search(const float *x, long long stride_t, long long stride_b, const float *lse,
+                             const float *blank_lp, const float *top_val, const int *top_idx, const int *input_lengths,
+                             int B, int T, int C, int blank, int beam, int nbest, const long long *fst_offsets,
+                             const int *fst_ilabel, const float *fst_weight, const int *fst_nextstate,
+                             const float *fst_final, int num_states, int num_arcs, int start, int backoff_id,
+                             int label_offset, const long long *fst2_offsets, const int *fst2_ilabel,
+                             const float *fst2_weight, const int *fst2_nextstate, const float *fst2_final,
+                             int num_states2, int num_arcs2, int start2, int backoff_id2, int label_offset2,
+                             int candidates, float lm_weight, float bias_weight, float length_bonus, int use_final,
+                             int *tokens, int *lengths, float *scores, float *am_scores, void *scratch, void *stream);
+
+/* pika_ctc_lm2_scratch_bytes(B, max_frames, beam, candidates) + B * PIKA_CTC_LM2_STREAM_RECORD_BYTES; 0 for dimensions
+ * the calls refuse. */
+size_t pika_ctc_lm2_stream_state_bytes(int B, int max_frames, int beam, int candidates);
+
+/* The empty prefix starts in state `start` of the first and `start2` of the second automaton with bonus 0. */
+int pika_ctc_lm2_stream_reset(void *state, int B, int max_frames, int beam, int candidates, int num_states, int start,
+                              int num_states2, int start2, const int *which, void *stream);
+
+int pika_ctc_lm2_stream_advance(const float *x, long long stride_t, long long stride_b, const float *lse,
+                                const float *blank_lp, const float *top_val, const int *top_idx,
+                                const int *chunk_lengths, int B, int Tc, int C, int blank, int beam,
+                                const long long *fst_offsets, const int *fst_ilabel, const float *fst_weight,
+                                const int *fst_nextstate, const float *fst_final, int num_states, int num_arcs,
+                                int backoff_id, int label_offset, const long long *fst2_offsets, const int *fst2_ilabel,
+                                const float *fst2_weight, const int *fst2_nextstate, const float *fst2_final,
+                                int num_states2, int num_arcs2, int backoff_id2, int label_offset2, int candidates,
+                                float lm_weight, float bias_weight, float length_bonus, void *state, int max_frames,
+                                void *stream);
+
+int pika_ctc_lm2_stream_results(const void *state, int B, int max_frames, int beam, int candidates,
+                                const long long *fst_offsets, const int *fst_ilabel, const float *fst_weight,
+                                const int *fst_nextstate, const float *fst_final, int num_states, int num_arcs,
+                                int backoff_id, int label_offset, const long long *fst2_offsets, const int *fst2_ilabel,
+                                const float *fst2_weight, const int *fst2_nextstate, const float *fst2_final,
+                                int num_states2, int num_arcs2, int backoff_id2, int label_offset2, float lm_weight,
+                                float bias_weight, int use_final, int nbest, int L, int *tokens, int *lengths,
+                                float *scores, float *am_scores, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,15 @@ SIGNATURES = {
     "pika_ctc_lm_stream_advance": (_i, [_vp, _ll, _ll] + [_vp] * 5 + [_i] * 5 + [_vp] * 5 + [_i] * 5 + [_f, _f]
                                    + [_vp, _i, _vp]),
     "pika_ctc_lm_stream_results": (_i, [_vp] + [_i] * 4 + [_vp] * 5 + [_i] * 4 + [_f] + [_i] * 3 + [_vp] * 5),
+    "pika_ctc_lm2_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "pika_ctc_lm2_beam_search": (_i, [_vp, _ll, _ll] + [_vp] * 5 + [_i] * 6 + [_vp] * 5 + [_i] * 5 + [_vp] * 5
+                                 + [_i] * 6 + [_f, _f, _f, _i] + [_vp] * 6),
+    "pika_ctc_lm2_stream_state_bytes": (_sz, [_i, _i, _i, _i]),
+    "pika_ctc_lm2_stream_reset": (_i, [_vp] + [_i] * 8 + [_vp, _vp]),
+    "pika_ctc_lm2_stream_advance": (_i, [_vp, _ll, _ll] + [_vp] * 5 + [_i] * 5 + [_vp] * 5 + [_i] * 4 + [_vp] * 5
+                                    + [_i] * 5 + [_f, _f, _f] + [_vp, _i, _vp]),
+    "pika_ctc_lm2_stream_results": (_i, [_vp] + [_i] * 4 + [_vp] * 5 + [_i] * 4 + [_vp] * 5 + [_i] * 4 + [_f, _f]
+                                    + [_i] * 3 + [_vp] * 5),
     # include/pika_bmuf.h
     "pika_bmuf_delta": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "pika_bmuf_nan_flag": (_i, [_vp, _sz, _vp, _vp]),

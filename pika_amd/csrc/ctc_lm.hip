@@ -17,11 +17,17 @@
 //            table, advance runs a chunk's frames through the frame body of the one-shot kernel (load, frames, store),
 //            results is the one-shot end -- final cost and new order on the side -- on the stored beam, which it only
 //            reads.
+//   bias   : the same kernel template with a second automaton (pika_ctc_lm2_*): a slot carries a second state, a fresh
+//            child walks both FSTs and exists only when both reach it; the cells stay as they are -- the winners of a
+//            frame (at most `beam`) walk the second FST again at node assignment, lane = slot, to get the state and to
+//            complete the bonus.  The one-FST instantiations have no trace of it (if constexpr).
 //   Every loop over the FST has a fixed trip limit (header): a malformed table cannot spin the workgroup.
 
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "pika_ctc_lm.h"
 #include "ctc_search_core.h"
@@ -130,6 +136,28 @@ __device__ __forceinline__ void copy_slot(LmBeam &D, const LmBeam &G, int r) {
     D.bonus[r] = G.bonus[r];
 }
 
+// the beam of the search with a second automaton; bonus holds both terms
+struct Lm2Beam : LmBeam {
+    int st2[MAX_BEAM];  // its state in the second FST
+};
+
+__device__ __forceinline__ void root_slot(Lm2Beam &A, int start, int start2) {
+    root_slot(static_cast<LmBeam &>(A), start);
+    A.st2[0] = start2;
+}
+
+__device__ __forceinline__ void copy_slot(Lm2Beam &D, const Lm2Beam &G, int r) {
+    copy_slot(static_cast<LmBeam &>(D), static_cast<const LmBeam &>(G), r);
+    D.st2[r] = G.st2[r];
+}
+
+// the second automaton of a launch: a kernel takes none or one as its last argument
+struct Bias {
+    Fst f;
+    int start;
+    float w;
+};
+
 struct Args {
     const float *x;
     long long st, sb;
@@ -147,18 +175,28 @@ struct Args {
 // the state of a stream (pika_ctc_lm.h): reset writes it, the advance loads and stores it, the results only read it
 // ---------------------------------------------------------------------------------------------
 using Rec = StreamRec<LmBeam>;
+using Rec2 = StreamRec<Lm2Beam>;
 static_assert(sizeof(Rec) == PIKA_CTC_LM_STREAM_RECORD_BYTES && offsetof(StreamHdr, frames) == PIKA_CTC_STREAM_FRAMES_OFFSET &&
                   offsetof(StreamHdr, overflow) == PIKA_CTC_STREAM_OVERFLOW_OFFSET,
               "the record the header documents");
+static_assert(sizeof(Rec2) == PIKA_CTC_LM2_STREAM_RECORD_BYTES && sizeof(Rec2) == sizeof(Rec) + MAX_BEAM * sizeof(int) &&
+                  sizeof(Rec2) % 8 == 0,
+              "the LM record, then the second states");
 
 __global__ __launch_bounds__(256) void ctc_lm_stream_reset_kernel(unsigned long long *tables, size_t slots, Rec *recs,
                                                                   const int *__restrict__ which, int start) {
     stream_reset(tables, slots, recs, which, [start](LmBeam &A) { root_slot(A, start); });
 }
 
+__global__ __launch_bounds__(256) void ctc_lm2_stream_reset_kernel(unsigned long long *tables, size_t slots, Rec2 *recs,
+                                                                   const int *__restrict__ which, int start, int start2) {
+    stream_reset(tables, slots, recs, which, [start, start2](Lm2Beam &A) { root_slot(A, start, start2); });
+}
+
 // the beam of a record into LDS (wave 0: lane r loads slot r); a label outside the classes (a record that was never
 // reset) is no label
-__device__ __forceinline__ void load_beam(LmBeam &A, const Rec &R, const StreamHdr &h, int tid, int C) {
+template <class BeamT>
+__device__ __forceinline__ void load_beam(BeamT &A, const StreamRec<BeamT> &R, const StreamHdr &h, int tid, int C) {
     if (tid < h.n) {
         copy_slot(A, R.beam, tid);
         A.len[tid] = clampi(A.len[tid], 0, h.frames);
@@ -173,10 +211,22 @@ __device__ __forceinline__ void load_beam(LmBeam &A, const Rec &R, const StreamH
 // drift apart, and the one-shot kernel is the code it was before the other two existed.
 enum Mode { ONE_SHOT, ADVANCE, RESULTS };
 
+// BIAS: nothing, or one `Bias` -- the second automaton (TWO).
+template <class... BIAS>
+using BeamOf = std::conditional_t<sizeof...(BIAS) == 1, Lm2Beam, LmBeam>;
+
+__device__ __forceinline__ const Bias *bias_of() { return nullptr; }
+__device__ __forceinline__ const Bias *bias_of(const Bias &g) { return &g; }
+
 // grid = B, block = 256.  recs, C and max_frames serve the two streaming forms only.
-template <int CELLS, Mode MODE>
-__global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst f, Rec *recs, int C, int max_frames) {
-    __shared__ LmBeam S[2];
+template <int CELLS, Mode MODE, class... BIAS>
+__global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst f, StreamRec<BeamOf<BIAS...>> *recs, int C,
+                                                         int max_frames, const BIAS... bias) {
+    static_assert(sizeof...(BIAS) <= 1, "none or one second automaton");
+    constexpr bool TWO = sizeof...(BIAS) == 1;
+    using BeamT = BeamOf<BIAS...>;
+    const Bias *const second = bias_of(bias...);  // TWO: the kernel's own argument
+    __shared__ BeamT S[2];
     __shared__ float cv[MAX_CLASSES];
     __shared__ int ci[MAX_CLASSES];
     __shared__ unsigned excl[MAX_BEAM][MAX_CLASSES / 32];
@@ -207,6 +257,8 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
     }
     if constexpr (MODE == ONE_SHOT) Tn = clampi(a.Tn[b], 1, T);
     const double lmw = (double)a.lmw, lb = (double)a.lb;
+    double bw = 0.0;
+    if constexpr (TWO) bw = (double)second->w;
     unsigned long long *table = a.table + (size_t)b * ((size_t)a.mask + 1);
     const unsigned mask = a.mask;
     const float *xb = a.x + (long long)b * a.sb;
@@ -217,7 +269,11 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
         n = h.n; off = h.off; boff = h.boff;
         load_beam(S[0], recs[b], h, tid, C);
     } else {
-        if (tid == 0) root_slot(S[0], a.start);
+        if constexpr (TWO) {
+            if (tid == 0) root_slot(S[0], a.start, second->start);
+        } else {
+            if (tid == 0) root_slot(S[0], a.start);
+        }
     }
     // the frame's compact row, fetched one frame ahead
     float pv = NEG, plb = NEG, pl = 0.0f;
@@ -232,8 +288,8 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
     if constexpr (MODE != RESULTS) fetch(0);
     for (int t = 0; t < Tn; ++t) {  // workgroup-uniform (RESULTS: no frame)
         __syncthreads();            // the previous frame's beam is complete; cv / ci / excl / the cells are free
-        const LmBeam &A = S[cur];
-        LmBeam &N = S[cur ^ 1];
+        const BeamT &A = S[cur];
+        BeamT &N = S[cur ^ 1];
         if (tid < MAX_CLASSES) { cv[tid] = pv; ci[tid] = pi; }
         const float lpb = plb, l = pl;
         if (t + 1 < Tn) fetch(t + 1);
@@ -275,7 +331,14 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
             int pr, cls, next = -1;
             float am, inc = 0.0f, F = NEG;
             if (cell(e, pr, cls, am) && lm_step(f, A.lmst[pr], cls, inc, next)) {
-                F = (float)((double)am + (A.bonus[pr] + lmw * (double)inc + lb));
+                if constexpr (TWO) {  // the child exists when both automata reach it; the cell keeps the first's walk
+                    float inc2;
+                    int next2;
+                    if (lm_step(second->f, A.st2[pr], cls, inc2, next2))
+                        F = (float)((double)am + (A.bonus[pr] + lmw * (double)inc + bw * (double)inc2 + lb));
+                } else {
+                    F = (float)((double)am + (A.bonus[pr] + lmw * (double)inc + lb));
+                }
                 if (!(F > NEG_HALF)) F = NEG;  // also a NaN from a table that holds one
             }
             cF[e] = F;
@@ -307,6 +370,7 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
                 if (bH < 64u) {
                     N.node[k] = node_r; N.last[k] = last_r; N.pnode[k] = pn_r; N.len[k] = A.len[r];
                     N.lmst[k] = A.lmst[r]; N.pb[k] = npb; N.pnb[k] = npnb; N.tot[k] = s_stay; N.bonus[k] = A.bonus[r];
+                    if constexpr (TWO) N.st2[k] = A.st2[r];
                     stay_open = false;
                 } else {
                     int pr, cls;
@@ -314,7 +378,12 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
                     cell(bE, pr, cls, am);
                     N.node[k] = PENDING; N.last[k] = cls; N.pnode[k] = A.node[pr]; N.len[k] = A.len[pr] + 1;
                     N.lmst[k] = cN[bE]; N.pb[k] = NEG; N.pnb[k] = am; N.tot[k] = am;
-                    N.bonus[k] = A.bonus[pr] + lmw * (double)cI[bE] + lb;
+                    if constexpr (TWO) {  // the parent's values: the slot's owner finishes both below
+                        N.bonus[k] = A.bonus[pr] + lmw * (double)cI[bE];
+                        N.st2[k] = A.st2[pr];
+                    } else {
+                        N.bonus[k] = A.bonus[pr] + lmw * (double)cI[bE] + lb;
+                    }
                     cF[bE] = NEG;
                 }
                 bF = NEG; bH = NOKEY; bL = NOKEY; bE = -1;  // the best of what this thread still has open
@@ -331,8 +400,20 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
             }
         }
         __syncthreads();  // the new beam's k slots are written
+        if constexpr (TWO) {
+            // a fresh winner walks the second FST once more -- the walk its cell made, from the same state -- for the
+            // state and the rest of its bonus: at most `beam` lookups side by side, next to the trie's atomics
+            if (slots && r < k && N.node[r] == PENDING) {
+                float inc2 = 0.0f;
+                int next2 = -1;
+                if (!lm_step(second->f, N.st2[r], N.last[r], inc2, next2)) next2 = -1;  // (it reached the child before)
+                N.st2[r] = next2;
+                N.bonus[r] = N.bonus[r] + bw * (double)inc2 + lb;
+            }
+        }
         assign_node(N, r, slots && r < k, table, mask);
         if (renorm_due(h.frames + t, k)) {  // (one-shot: h.frames is the constant 0)
+            if constexpr (TWO) __syncthreads();  // slot 0's bonus is complete
             const double mb = N.bonus[0];  // slot 0 has the best fused score; read before renorm()'s barrier
             off += (double)renorm(N, r, slots && r < k);
             if (slots && r < k) N.bonus[r] = N.bonus[r] - mb;
@@ -342,9 +423,9 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
         n = k;
     }
     __syncthreads();
-    const LmBeam &A = S[cur];
+    const BeamT &A = S[cur];
     if constexpr (MODE == ADVANCE) {  // the beam and what was moved out of it, back into the record
-        Rec &R = recs[b];
+        StreamRec<BeamT> &R = recs[b];
         if (tid < n) copy_slot(R.beam, A, tid);
         if (tid == 0) {
             R.h.n = n; R.h.frames = h.frames + Tn;
@@ -361,6 +442,12 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
             float inc;
             live = lm_final(f, A.lmst[r], inc);
             if (live) s += lmw * (double)inc;
+            if constexpr (TWO) {
+                if (live) {
+                    live = lm_final(second->f, A.st2[r], inc);
+                    if (live) s += bw * (double)inc;
+                }
+            }
         }
         if (live && (float)s > -__builtin_inff()) sc = (float)s;  // (a NaN is not alive)
     }
@@ -384,6 +471,87 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
     write_nbest<THREADS, MODE == RESULTS>(A, nlive, [&](int q) { return perm[q]; }, tid, b, T, nbest, a.tokens, a.lengths, table, mask);
 }
 
+// ---------------------------------------------------------------------------------------------
+// host: every entry point is its checks and one launch; the pika_ctc_lm2_* forms pass a Bias along
+// ---------------------------------------------------------------------------------------------
+static inline bool fst_missing(const long long *off, const int *il, const float *w, const int *ns, const float *fin, int A) {
+    return !off || !fin || (A > 0 && (!il || !w || !ns));
+}
+
+// the second FST of a pika_ctc_lm2_* call; `start` is checked where the call has one
+static inline int check_bias(const Bias &g, bool with_start) {
+    if (g.f.S <= 0 || g.f.A < 0 || (with_start && (g.start < 0 || g.start >= g.f.S))) return PIKA_EINVAL;
+    return fst_missing(g.f.off, g.f.il, g.f.w, g.f.ns, g.f.fin, g.f.A) ? PIKA_EINVAL : PIKA_OK;
+}
+
+template <Mode MODE, class... BIAS>
+static int launch(bool small, int B, hipStream_t s, const Args &a, const Fst &f, StreamRec<BeamOf<BIAS...>> *recs, int C,
+                  int max_frames, const BIAS &...g) {
+    if (MODE == RESULTS || small)  // (the results have no cells)
+        hipLaunchKernelGGL((ctc_lm_kernel<CELLS_SMALL, MODE, BIAS...>), dim3((unsigned)B), dim3(THREADS), 0, s, a, f, recs,
+                           C, max_frames, g...);
+    else if constexpr (MODE != RESULTS)
+        hipLaunchKernelGGL((ctc_lm_kernel<CELLS_LARGE, MODE, BIAS...>), dim3((unsigned)B), dim3(THREADS), 0, s, a, f, recs,
+                           C, max_frames, g...);
+    return (int)hipGetLastError();
+}
+
+template <class... BIAS>
+static int beam_search(const float *x, long long stride_t, long long stride_b, const float *lse, const float *blank_lp,
+                       const float *top_val, const int *top_idx, const int *input_lengths, int B, int T, int C, int blank,
+                       int beam, int nbest, const Fst &f, int start, int candidates, float lm_weight, float length_bonus,
+                       int use_final, int *tokens, int *lengths, float *scores, float *am_scores, void *scratch,
+                       void *stream, const BIAS &...g) {
+    if (B <= 0 || T <= 0 || C <= 0 || blank < 0 || blank >= C || nbest <= 0) return PIKA_EINVAL;
+    if (f.S <= 0 || f.A < 0 || start < 0 || start >= f.S) return PIKA_EINVAL;
+    if (int rc = check_search_dims(B, T, beam, candidates)) return rc;
+    if (nbest > beam) return PIKA_ETOOBIG;
+    if (!x || !blank_lp || !top_val || !top_idx || !input_lengths || !tokens || !lengths || !scores || !am_scores ||
+        !scratch || fst_missing(f.off, f.il, f.w, f.ns, f.fin, f.A))
+        return PIKA_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (hipError_t e = clear_tables(scratch, B, T, beam, s)) return (int)e;
+    const Args a = {x, stride_t, stride_b, lse, blank_lp, top_val, top_idx, input_lengths, B, T, beam, nbest,
+                    candidates, start, use_final, lm_weight, length_bonus, tokens, lengths, scores, am_scores,
+                    static_cast<unsigned long long *>(scratch), (unsigned)(table_slots(T, beam) - 1)};
+    return launch<ONE_SHOT, BIAS...>(beam * candidates <= CELLS_SMALL, B, s, a, f, nullptr, 0, 0, g...);
+}
+
+template <class... BIAS>
+static int stream_advance(const float *x, long long stride_t, long long stride_b, const float *lse, const float *blank_lp,
+                          const float *top_val, const int *top_idx, const int *chunk_lengths, int B, int Tc, int C,
+                          int blank, int beam, const Fst &f, int candidates, float lm_weight, float length_bonus,
+                          void *state, int max_frames, void *stream, const BIAS &...g) {
+    if (B <= 0 || Tc <= 0 || C <= 0 || blank < 0 || blank >= C) return PIKA_EINVAL;
+    if (f.S <= 0 || f.A < 0) return PIKA_EINVAL;
+    if (int rc = check_search_dims(B, max_frames, beam, candidates)) return rc;
+    if (2ll * Tc * beam > (1ll << 28)) return PIKA_ETOOBIG;  // the row arrays' index range, as in the one-shot search
+    if (!x || !blank_lp || !top_val || !top_idx || !chunk_lengths || !state || fst_missing(f.off, f.il, f.w, f.ns, f.fin, f.A))
+        return PIKA_EINVAL;
+    const Args a = {x, stride_t, stride_b, lse, blank_lp, top_val, top_idx, chunk_lengths, B, Tc, beam, 0, candidates,
+                    0, 0, lm_weight, length_bonus, nullptr, nullptr, nullptr, nullptr,
+                    static_cast<unsigned long long *>(state), (unsigned)(table_slots(max_frames, beam) - 1)};
+    return launch<ADVANCE, BIAS...>(beam * candidates <= CELLS_SMALL, B, static_cast<hipStream_t>(stream), a, f,
+                                    stream_recs<StreamRec<BeamOf<BIAS...>>>(state, B, max_frames, beam), C, max_frames, g...);
+}
+
+template <class... BIAS>
+static int stream_results(const void *state, int B, int max_frames, int beam, int candidates, const Fst &f,
+                          float lm_weight, int use_final, int nbest, int L, int *tokens, int *lengths, float *scores,
+                          float *am_scores, void *stream, const BIAS &...g) {
+    if (f.S <= 0 || f.A < 0) return PIKA_EINVAL;
+    if (int rc = check_results_dims(B, max_frames, beam, candidates, nbest, L)) return rc;
+    if (!state || !tokens || !lengths || !scores || !am_scores || fst_missing(f.off, f.il, f.w, f.ns, f.fin, f.A))
+        return PIKA_EINVAL;
+    const Args a = {nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, B, L, beam, nbest, candidates, 0, use_final,
+                    lm_weight, 0.0f, tokens, lengths, scores, am_scores,
+                    static_cast<unsigned long long *>(const_cast<void *>(state)),
+                    (unsigned)(table_slots(max_frames, beam) - 1)};
+    return launch<RESULTS, BIAS...>(true, B, static_cast<hipStream_t>(stream), a, f,
+                                    stream_recs<StreamRec<BeamOf<BIAS...>>>(state, B, max_frames, beam), 0x7fffffff,
+                                    max_frames, g...);
+}
+
 }  // namespace
 
 extern "C" {
@@ -400,27 +568,11 @@ int pika_ctc_lm_beam_search(const float *x, long long stride_t, long long stride
                             const float *fst_final, int num_states, int num_arcs, int start, int backoff_id,
                             int label_offset, int candidates, float lm_weight, float length_bonus, int use_final,
                             int *tokens, int *lengths, float *scores, float *am_scores, void *scratch, void *stream) {
-    if (B <= 0 || T <= 0 || C <= 0 || blank < 0 || blank >= C || nbest <= 0) return PIKA_EINVAL;
-    if (num_states <= 0 || num_arcs < 0 || start < 0 || start >= num_states) return PIKA_EINVAL;
-    if (int rc = check_search_dims(B, T, beam, candidates)) return rc;
-    if (nbest > beam) return PIKA_ETOOBIG;
-    if (!x || !blank_lp || !top_val || !top_idx || !input_lengths || !tokens || !lengths || !scores || !am_scores ||
-        !scratch || !fst_offsets || !fst_final || (num_arcs > 0 && (!fst_ilabel || !fst_weight || !fst_nextstate)))
-        return PIKA_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (hipError_t e = clear_tables(scratch, B, T, beam, s)) return (int)e;
-    const Args a = {x, stride_t, stride_b, lse, blank_lp, top_val, top_idx, input_lengths, B, T, beam, nbest,
-                    candidates, start, use_final, lm_weight, length_bonus, tokens, lengths, scores, am_scores,
-                    static_cast<unsigned long long *>(scratch), (unsigned)(table_slots(T, beam) - 1)};
     const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
                    label_offset};
-    if (beam * candidates <= CELLS_SMALL)
-        hipLaunchKernelGGL((ctc_lm_kernel<CELLS_SMALL, ONE_SHOT>), dim3((unsigned)B), dim3(THREADS), 0, s, a, f,
-                           static_cast<Rec *>(nullptr), 0, 0);
-    else
-        hipLaunchKernelGGL((ctc_lm_kernel<CELLS_LARGE, ONE_SHOT>), dim3((unsigned)B), dim3(THREADS), 0, s, a, f,
-                           static_cast<Rec *>(nullptr), 0, 0);
-    return (int)hipGetLastError();
+    return beam_search(x, stride_t, stride_b, lse, blank_lp, top_val, top_idx, input_lengths, B, T, C, blank, beam, nbest,
+                       f, start, candidates, lm_weight, length_bonus, use_final, tokens, lengths, scores, am_scores,
+                       scratch, stream);
 }
 
 size_t pika_ctc_lm_stream_state_bytes(int B, int max_frames, int beam, int candidates) {
@@ -446,27 +598,10 @@ int pika_ctc_lm_stream_advance(const float *x, long long stride_t, long long str
                                const int *fst_nextstate, const float *fst_final, int num_states, int num_arcs,
                                int backoff_id, int label_offset, int candidates, float lm_weight, float length_bonus,
                                void *state, int max_frames, void *stream) {
-    if (B <= 0 || Tc <= 0 || C <= 0 || blank < 0 || blank >= C) return PIKA_EINVAL;
-    if (num_states <= 0 || num_arcs < 0) return PIKA_EINVAL;
-    if (int rc = check_search_dims(B, max_frames, beam, candidates)) return rc;
-    if (2ll * Tc * beam > (1ll << 28)) return PIKA_ETOOBIG;  // the row arrays' index range, as in the one-shot search
-    if (!x || !blank_lp || !top_val || !top_idx || !chunk_lengths || !state || !fst_offsets || !fst_final ||
-        (num_arcs > 0 && (!fst_ilabel || !fst_weight || !fst_nextstate)))
-        return PIKA_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Args a = {x, stride_t, stride_b, lse, blank_lp, top_val, top_idx, chunk_lengths, B, Tc, beam, 0, candidates,
-                    0, 0, lm_weight, length_bonus, nullptr, nullptr, nullptr, nullptr,
-                    static_cast<unsigned long long *>(state), (unsigned)(table_slots(max_frames, beam) - 1)};
     const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
                    label_offset};
-    Rec *recs = stream_recs<Rec>(state, B, max_frames, beam);
-    if (beam * candidates <= CELLS_SMALL)
-        hipLaunchKernelGGL((ctc_lm_kernel<CELLS_SMALL, ADVANCE>), dim3((unsigned)B), dim3(THREADS), 0, s, a, f, recs, C,
-                           max_frames);
-    else
-        hipLaunchKernelGGL((ctc_lm_kernel<CELLS_LARGE, ADVANCE>), dim3((unsigned)B), dim3(THREADS), 0, s, a, f, recs, C,
-                           max_frames);
-    return (int)hipGetLastError();
+    return stream_advance(x, stride_t, stride_b, lse, blank_lp, top_val, top_idx, chunk_lengths, B, Tc, C, blank, beam, f,
+                          candidates, lm_weight, length_bonus, state, max_frames, stream);
 }
 
 int pika_ctc_lm_stream_results(const void *state, int B, int max_frames, int beam, int candidates,
@@ -474,21 +609,89 @@ int pika_ctc_lm_stream_results(const void *state, int B, int max_frames, int bea
                                const int *fst_nextstate, const float *fst_final, int num_states, int num_arcs,
                                int backoff_id, int label_offset, float lm_weight, int use_final, int nbest, int L,
                                int *tokens, int *lengths, float *scores, float *am_scores, void *stream) {
-    if (num_states <= 0 || num_arcs < 0) return PIKA_EINVAL;
-    if (int rc = check_results_dims(B, max_frames, beam, candidates, nbest, L)) return rc;
-    if (!state || !tokens || !lengths || !scores || !am_scores || !fst_offsets || !fst_final ||
-        (num_arcs > 0 && (!fst_ilabel || !fst_weight || !fst_nextstate)))
-        return PIKA_EINVAL;
-    const Args a = {nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, B, L, beam, nbest, candidates, 0, use_final,
-                    lm_weight, 0.0f, tokens, lengths, scores, am_scores,
-                    static_cast<unsigned long long *>(const_cast<void *>(state)),
-                    (unsigned)(table_slots(max_frames, beam) - 1)};
     const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
                    label_offset};
-    hipLaunchKernelGGL((ctc_lm_kernel<CELLS_SMALL, RESULTS>), dim3((unsigned)B), dim3(THREADS), 0,
-                       static_cast<hipStream_t>(stream), a, f, stream_recs<Rec>(state, B, max_frames, beam), 0x7fffffff,
-                       max_frames);
+    return stream_results(state, B, max_frames, beam, candidates, f, lm_weight, use_final, nbest, L, tokens, lengths,
+                          scores, am_scores, stream);
+}
+
+// ---- the same with a second automaton ----------------------------------------------------------------------------
+
+size_t pika_ctc_lm2_scratch_bytes(int B, int T, int beam, int candidates) {
+    return pika_ctc_lm_scratch_bytes(B, T, beam, candidates);
+}
+
+int pika_ctc_lm2_beam_search(const float *x, long long stride_t, long long stride_b, const float *lse,
+                             const float *blank_lp, const float *top_val, const int *top_idx, const int *input_lengths,
+                             int B, int T, int C, int blank, int beam, int nbest, const long long *fst_offsets,
+                             const int *fst_ilabel, const float *fst_weight, const int *fst_nextstate,
+                             const float *fst_final, int num_states, int num_arcs, int start, int backoff_id,
+                             int label_offset, const long long *fst2_offsets, const int *fst2_ilabel,
+                             const float *fst2_weight, const int *fst2_nextstate, const float *fst2_final,
+                             int num_states2, int num_arcs2, int start2, int backoff_id2, int label_offset2,
+                             int candidates, float lm_weight, float bias_weight, float length_bonus, int use_final,
+                             int *tokens, int *lengths, float *scores, float *am_scores, void *scratch, void *stream) {
+    const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
+                   label_offset};
+    const Bias g = {{fst2_offsets, fst2_ilabel, fst2_weight, fst2_nextstate, fst2_final, num_states2, num_arcs2,
+                     backoff_id2, label_offset2}, start2, bias_weight};
+    if (int rc = check_bias(g, true)) return rc;
+    return beam_search(x, stride_t, stride_b, lse, blank_lp, top_val, top_idx, input_lengths, B, T, C, blank, beam, nbest,
+                       f, start, candidates, lm_weight, length_bonus, use_final, tokens, lengths, scores, am_scores,
+                       scratch, stream, g);
+}
+
+size_t pika_ctc_lm2_stream_state_bytes(int B, int max_frames, int beam, int candidates) {
+    if (check_search_dims(B, max_frames, beam, candidates)) return 0;
+    return table_bytes(B, max_frames, beam) + (size_t)B * sizeof(Rec2);
+}
+
+int pika_ctc_lm2_stream_reset(void *state, int B, int max_frames, int beam, int candidates, int num_states, int start,
+                              int num_states2, int start2, const int *which, void *stream) {
+    if (num_states <= 0 || start < 0 || start >= num_states) return PIKA_EINVAL;
+    if (num_states2 <= 0 || start2 < 0 || start2 >= num_states2) return PIKA_EINVAL;
+    if (int rc = check_search_dims(B, max_frames, beam, candidates)) return rc;
+    if (!state) return PIKA_EINVAL;
+    hipLaunchKernelGGL(ctc_lm2_stream_reset_kernel, reset_grid(B, max_frames, beam), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), static_cast<unsigned long long *>(state),
+                       table_slots(max_frames, beam), stream_recs<Rec2>(state, B, max_frames, beam), which, start, start2);
     return (int)hipGetLastError();
+}
+
+int pika_ctc_lm2_stream_advance(const float *x, long long stride_t, long long stride_b, const float *lse,
+                                const float *blank_lp, const float *top_val, const int *top_idx,
+                                const int *chunk_lengths, int B, int Tc, int C, int blank, int beam,
+                                const long long *fst_offsets, const int *fst_ilabel, const float *fst_weight,
+                                const int *fst_nextstate, const float *fst_final, int num_states, int num_arcs,
+                                int backoff_id, int label_offset, const long long *fst2_offsets, const int *fst2_ilabel,
+                                const float *fst2_weight, const int *fst2_nextstate, const float *fst2_final,
+                                int num_states2, int num_arcs2, int backoff_id2, int label_offset2, int candidates,
+                                float lm_weight, float bias_weight, float length_bonus, void *state, int max_frames,
+                                void *stream) {
+    const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
+                   label_offset};
+    const Bias g = {{fst2_offsets, fst2_ilabel, fst2_weight, fst2_nextstate, fst2_final, num_states2, num_arcs2,
+                     backoff_id2, label_offset2}, 0, bias_weight};
+    if (int rc = check_bias(g, false)) return rc;
+    return stream_advance(x, stride_t, stride_b, lse, blank_lp, top_val, top_idx, chunk_lengths, B, Tc, C, blank, beam, f,
+                          candidates, lm_weight, length_bonus, state, max_frames, stream, g);
+}
+
+int pika_ctc_lm2_stream_results(const void *state, int B, int max_frames, int beam, int candidates,
+                                const long long *fst_offsets, const int *fst_ilabel, const float *fst_weight,
+                                const int *fst_nextstate, const float *fst_final, int num_states, int num_arcs,
+                                int backoff_id, int label_offset, const long long *fst2_offsets, const int *fst2_ilabel,
+                                const float *fst2_weight, const int *fst2_nextstate, const float *fst2_final,
+                                int num_states2, int num_arcs2, int backoff_id2, int label_offset2, float lm_weight,
+                                float bias_weight, int use_final, int nbest, int L, int *tokens, int *lengths,
+                                float *scores, float *am_scores, void *stream) {
+    const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
+                   label_offset};
+    const Bias g = {{fst2_offsets, fst2_ilabel, fst2_weight, fst2_nextstate, fst2_final, num_states2, num_arcs2,
+                     backoff_id2, label_offset2}, 0, bias_weight};
+    if (int rc = check_bias(g, false)) return rc;
+    return stream_results(state, B, max_frames, beam, candidates, f, lm_weight, use_final, nbest, L, tokens, lengths,
+                          scores, am_scores, stream, g);
 }
 
 }  // extern "C"

@@ -24,6 +24,11 @@ and the search with an n-gram LM fused in (include/pika_ctc_lm.h, csrc/ctc_lm.hi
         -> (tokens (B,nbest,T), lengths (B,nbest), scores (B,nbest), am_scores (B,nbest))
     ctc_beam_search_lm_from_logits(logits, ...same...)
 
+with contextual biasing as a second automaton beside the LM -- wherever an `lm` is taken, a `CtcBiasedLm` is too:
+
+    CtcHotwords(phrases, num_classes, boost=1.0, blank=0, device=None)      a phrase list compiled to the LM's FST layout
+    CtcBiasedLm(lm, bias, bias_weight=1.0)                                  an LM and a second automaton beside it
+
 and both searches with their state carried across calls, for audio that arrives in chunks:
 
     CtcBeamStream(batch, max_frames, beam=16, blank=0, lm=None, lm_weight=0.5, length_bonus=0.0, candidates=None,
@@ -447,8 +452,122 @@ class CtcNgramLm(object):
             torch.from_numpy(v).to(self.device) for v in (offsets, ilabel, weight, nextstate, final))
 
 
+class CtcHotwords(CtcNgramLm):
+    """A phrase list for contextual biasing, compiled on the host into the back-off FST layout of `CtcNgramLm`: every
+    token that extends a match of a phrase earns `boost`, and a match that is abandoned gives its credit back.
+
+    `phrases` is a list of sequences of class ids in [0, num_classes), `blank` excluded.  For a label sequence l the
+    automaton's score is BIAS(l) = boost * (tokens inside completed matches + depth of the match in progress); with
+    `use_final` the match in progress at the end of the utterance is refunded too.  Beside an LM:
+    `ctc_beam_search_lm(lp, il, CtcBiasedLm(LM, hotwords, bias_weight=w))` ranks by tot + lm_weight * LM + w * BIAS +
+    length_bonus * |l|.
+
+    Being a `CtcNgramLm`, it also works alone: `ctc_beam_search_lm(lp, il, lm=hotwords, lm_weight=1.0)` is biasing
+    without an LM, and so is `CtcBeamStream(..., lm=hotwords, lm_weight=1.0)`.
+
+    The compiled graph (`CtcHotwords.compile`, host only):
+      states   the root (state 0, the start state) and one state per distinct non-empty proper prefix of a phrase; a
+               complete phrase is no state -- the arc that completes it leads back to the root
+      credit(s) = boost * depth(s); fail(s) = the state of the longest proper suffix of s's tokens that is a state,
+               the root if there is none
+      labels   class c is label c + 1; backoff_id = num_classes + 1
+      s != root: for every token c that continues a phrase an arc of weight -boost to the child (to the root when c
+               completes a phrase); one back-off arc of weight credit(s) - credit(fail(s)) to fail(s): the refund
+      root     for every non-blank class c an arc: weight -boost to the child (to the root for a one-token phrase) when c
+               starts a phrase, weight 0 to the root otherwise; no back-off arc -- it reaches every non-blank class
+      final(s) = credit(s), 0 at the root
+    ValueError when a phrase is empty, holds `blank` or a class outside [0, num_classes), or has another phrase as a
+    proper prefix (the shorter one would complete and return to the root every time: the longer could never match);
+    when `boost` is not a finite number > 0; and, by `CtcNgramLm`'s own check, when a fail chain is longer than 8 hops
+    -- the device walks at most 8 back-off arcs per step (a phrase that starts with ten times the same token has such
+    a chain).  Duplicate phrases are merged."""
+
+    def __init__(self, phrases, num_classes, boost=1.0, blank=0, device=None):
+        fst = self.compile(phrases, num_classes, boost, blank)
+        self.num_classes, self.boost, self.blank = int(num_classes), float(boost), int(blank)
+        CtcNgramLm.__init__(self, fst, int(num_classes) + 1, 1, device)
+
+    @staticmethod
+    def compile(phrases, num_classes, boost=1.0, blank=0):
+        """The phrase list as an `NgramFst` (numpy, no device): labels class + 1, back-off label num_classes + 1."""
+        from .decoder.ngram_fst import NgramFst
+        C, blank, boost = int(num_classes), int(blank), float(np.float32(boost))    # the fp32 value the device reads
+        if not (boost > 0.0 and np.isfinite(boost)):
+            raise ValueError("CtcHotwords: boost must be a finite number > 0, got %r" % (boost,))
+        if C < 1 or not 0 <= blank < C:
+            raise ValueError("CtcHotwords: need num_classes >= 1 and blank in [0,%d), got blank=%d" % (C, blank))
+        words = set()
+        for ph in phrases:
+            ph = tuple(int(c) for c in ph)
+            if not ph:
+                raise ValueError("CtcHotwords: an empty phrase")
+            if any(c == blank or not 0 <= c < C for c in ph):
+                raise ValueError("CtcHotwords: phrase %s holds blank or a class outside [0,%d)" % (list(ph), C))
+            words.add(ph)
+        for ph in words:
+            for k in range(1, len(ph)):
+                if ph[:k] in words:
+                    raise ValueError("CtcHotwords: phrase %s is a proper prefix of phrase %s" % (list(ph[:k]), list(ph)))
+        state = {(): 0}                                     # token string -> state
+        for ph in sorted(words, key=lambda p: (len(p), p)):
+            for k in range(1, len(ph)):
+                state.setdefault(ph[:k], len(state))
+        cont = {}                                           # state -> {token: next state}
+        for ph in words:
+            for k in range(len(ph)):
+                cont.setdefault(state[ph[:k]], {})[ph[k]] = state[ph[:k + 1]] if k + 1 < len(ph) else 0
+        arcs, finals = [], {}
+        for c in range(C):
+            if c != blank:
+                nxt = cont.get(0, {}).get(c)
+                arcs.append((0, c + 1, 0.0 if nxt is None else -boost, 0 if nxt is None else nxt))
+        for tokens, s in state.items():
+            finals[s] = boost * len(tokens)
+            if s == 0:
+                continue
+            for c, nxt in cont[s].items():
+                arcs.append((s, c + 1, -boost, nxt))
+            fail = next(tokens[k:] for k in range(1, len(tokens) + 1) if tokens[k:] in state)
+            arcs.append((s, C + 1, boost * (len(tokens) - len(fail)), state[fail]))
+        return NgramFst.from_arcs(len(state), arcs, finals, start=0)
+
+
+def _check_second(lm, what, C, device, where):
+    """The checks an LM argument (`what`: its name) gets against the input: its backoff_id against C, its device."""
+    if 0 <= lm.backoff_id - lm.label_offset < C:
+        raise ValueError("the backoff_id %d of %s is the label of class %d" % (lm.backoff_id, what,
+                                                                              lm.backoff_id - lm.label_offset))
+    if lm.device != device:
+        raise ValueError("%s lives on %s, %s on %s" % (what, lm.device, where, device))
+
+
+def _fst_args(lm, start):
+    """An FST as the C ABI takes it, with or without its start state."""
+    return (_ptr(lm.offsets), _ptr(lm.ilabel), _ptr(lm.weight), _ptr(lm.nextstate), _ptr(lm.final), lm.num_states,
+            lm.num_arcs) + ((lm.start,) if start else ()) + (lm.backoff_id, lm.label_offset)
+
+
+class CtcBiasedLm(object):
+    """An LM with a second automaton beside it, for every place that takes an `lm`: `ctc_beam_search_lm`,
+    `ctc_beam_search_lm_from_logits` and `CtcBeamStream`.  `lm` and `bias` are `CtcNgramLm`s on one device (TypeError /
+    ValueError otherwise); `bias` is typically a `CtcHotwords` phrase list, but a second, domain LM works as well.  The
+    search ranks by tot + lm_weight * LM(l) + bias_weight * BIAS(l) + length_bonus * |l| (`ctc_beam_search_lm`); the
+    object holds references only, so one LM serves any number of per-request phrase lists."""
+
+    def __init__(self, lm, bias, bias_weight=1.0):
+        for name, v in (("lm", lm), ("bias", bias)):
+            if not isinstance(v, CtcNgramLm):
+                raise TypeError("%s must be a CtcNgramLm, got %s" % (name, type(v).__name__))
+        if lm.device != bias.device:
+            raise ValueError("the LM lives on %s, bias on %s" % (lm.device, bias.device))
+        self.lm, self.bias, self.bias_weight, self.device = lm, bias, float(bias_weight), lm.device
+
+
 def _beam_lm(x, what, input_lengths, lm, beam, nbest, blank, lm_weight, length_bonus, candidates, use_final, logits):
     blank, beam, nbest = int(blank), int(beam), int(nbest)
+    bias, bias_weight = None, 1.0
+    if isinstance(lm, CtcBiasedLm):
+        lm, bias, bias_weight = lm.lm, lm.bias, lm.bias_weight
     if not isinstance(lm, CtcNgramLm):
         raise TypeError("lm must be a CtcNgramLm, got %s" % type(lm).__name__)
     alloc = _nbest_outputs(beam, nbest)
@@ -462,6 +581,8 @@ def _beam_lm(x, what, input_lengths, lm, beam, nbest, blank, lm_weight, length_b
                                                                              lm.backoff_id - lm.label_offset))
     if lm.device != x.device:
         raise ValueError("the LM lives on %s, %s on %s" % (lm.device, what, x.device))
+    if bias is not None:
+        _check_second(bias, "bias", C, x.device, what)
     lib = _lib.lib()
     nbytes = lib.pika_ctc_lm_scratch_bytes(B, T, beam, candidates)
     if nbytes == 0:
@@ -470,12 +591,20 @@ def _beam_lm(x, what, input_lengths, lm, beam, nbest, blank, lm_weight, length_b
         tokens, lengths, scores = alloc(x)
         am_scores = torch.empty((B, nbest), dtype=torch.float32, device=x.device)
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        _lib.check(lib.pika_ctc_lm_beam_search(
-            _ptr(x), x.stride(0), x.stride(1), _ptr(lse), _ptr(blank_lp), _ptr(top_val), _ptr(top_idx), _ptr(il), B, T,
-            C, blank, beam, nbest, _ptr(lm.offsets), _ptr(lm.ilabel), _ptr(lm.weight), _ptr(lm.nextstate),
-            _ptr(lm.final), lm.num_states, lm.num_arcs, lm.start, lm.backoff_id, lm.label_offset, candidates,
-            float(lm_weight), float(length_bonus), int(bool(use_final)), _ptr(tokens), _ptr(lengths), _ptr(scores),
-            _ptr(am_scores), _ptr(scratch), _stream()), "pika_ctc_lm_beam_search")
+        if bias is None:
+            _lib.check(lib.pika_ctc_lm_beam_search(
+                _ptr(x), x.stride(0), x.stride(1), _ptr(lse), _ptr(blank_lp), _ptr(top_val), _ptr(top_idx), _ptr(il), B,
+                T, C, blank, beam, nbest, _ptr(lm.offsets), _ptr(lm.ilabel), _ptr(lm.weight), _ptr(lm.nextstate),
+                _ptr(lm.final), lm.num_states, lm.num_arcs, lm.start, lm.backoff_id, lm.label_offset, candidates,
+                float(lm_weight), float(length_bonus), int(bool(use_final)), _ptr(tokens), _ptr(lengths), _ptr(scores),
+                _ptr(am_scores), _ptr(scratch), _stream()), "pika_ctc_lm_beam_search")
+        else:
+            _lib.check(lib.pika_ctc_lm2_beam_search(*((
+                _ptr(x), x.stride(0), x.stride(1), _ptr(lse), _ptr(blank_lp), _ptr(top_val), _ptr(top_idx), _ptr(il), B,
+                T, C, blank, beam, nbest) + _fst_args(lm, True) + _fst_args(bias, True) + (
+                candidates, float(lm_weight), float(bias_weight), float(length_bonus), int(bool(use_final)),
+                _ptr(tokens), _ptr(lengths), _ptr(scores), _ptr(am_scores), _ptr(scratch), _stream()))),
+                "pika_ctc_lm2_beam_search")
     out = (tokens, lengths, scores, am_scores)
     return tuple(o[0] for o in out) if unbatched else out
 
@@ -505,7 +634,14 @@ def ctc_beam_search_lm(log_probs, input_lengths, lm, beam=16, nbest=1, blank=0, 
     Returns (tokens (B,nbest,T) i32, lengths (B,nbest) i32, scores (B,nbest) f32, am_scores (B,nbest) f32), best first:
     `scores` is the fused score the ranking used (with the final term when asked), `am_scores` is tot alone.  A missing
     entry has length -1, scores -inf and tokens -1.  Inputs, strides, length clamping, no autograd, no host
-    synchronisation and graph capture as `ctc_beam_search`."""
+    synchronisation and graph capture as `ctc_beam_search`.
+
+    BIASING BESIDE THE LM.  `lm` may be a `CtcBiasedLm(lm, bias, bias_weight)`: `bias` is a second automaton -- a
+    `CtcHotwords` phrase list, or any `CtcNgramLm` such as a domain LM -- walked from its own start state next to the LM:
+    F(l) = tot + lm_weight * LM(l) + bias_weight * BIAS(l) + length_bonus * |l|.  A child that either automaton cannot
+    reach does not exist (a `CtcHotwords` graph reaches every non-blank class); with `use_final` a prefix adds both
+    final terms and drops out if either automaton has none.  Everything else -- candidates, ties, am_scores -- is as
+    above.  ValueError for the second automaton's device or its backoff_id, as for the LM's."""
     return _beam_lm(log_probs, "log_probs", input_lengths, lm, beam, nbest, blank, lm_weight, length_bonus, candidates,
                     use_final, False)
 
@@ -537,6 +673,10 @@ class CtcBeamStream(object):
     frames       (B,) int32 device tensor: frames consumed per stream (a view of the state: it follows the stream)
     overflowed   (B,) bool device tensor: frames were dropped because the stream was full
 
+    lm may be a `CtcBiasedLm` -- an LM with a second automaton (hotwords) beside it, as in `ctc_beam_search_lm`: the
+        stream then carries a second state per slot, reset() restarts the selected streams in both start states, and any
+        chunking still gives the one-shot call's bits.  Hotwords without an LM: lm=CtcHotwords(...), lm_weight=1.0.
+
     A stream holds at most max_frames frames.  On the host the object sums the chunk widths Tc fed since the last FULL
     reset() and raises ValueError before launching anything once the sum would exceed max_frames; this bound is
     conservative (it ignores `lengths`) and needs no synchronisation.  A partial reset does not lower it: the streams
@@ -550,6 +690,9 @@ class CtcBeamStream(object):
     def __init__(self, batch, max_frames, beam=16, blank=0, lm=None, lm_weight=0.5, length_bonus=0.0, candidates=None,
                  device=None):
         batch, max_frames, beam, blank = int(batch), int(max_frames), int(beam), int(blank)
+        bias, bias_weight = None, 1.0
+        if isinstance(lm, CtcBiasedLm):
+            lm, bias, bias_weight = lm.lm, lm.bias, lm.bias_weight
         if not 1 <= beam <= MAX_BEAM:
             raise ValueError("need 1 <= beam <= %d, got beam=%d" % (MAX_BEAM, beam))
         if lm is not None and not isinstance(lm, CtcNgramLm):
@@ -570,15 +713,19 @@ class CtcBeamStream(object):
         self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
         if lm is not None and lm.device != self.device:
             raise ValueError("the LM lives on %s, the stream on %s" % (lm.device, self.device))
+        self.bias, self.bias_weight = bias, float(bias_weight)
         self.batch, self.max_frames, self.beam, self.blank, self.candidates = batch, max_frames, beam, blank, candidates
         self.lm, self.lm_weight, self.length_bonus = lm, float(lm_weight), float(length_bonus)
         lib = _lib.lib()
         if lm is None:
             nbytes = lib.pika_ctc_stream_state_bytes(batch, max_frames, beam)
             tables = lib.pika_ctc_beam_scratch_bytes(batch, max_frames, beam)
-        else:
+        elif bias is None:
             nbytes = lib.pika_ctc_lm_stream_state_bytes(batch, max_frames, beam, candidates)
             tables = lib.pika_ctc_lm_scratch_bytes(batch, max_frames, beam, candidates)
+        else:
+            nbytes = lib.pika_ctc_lm2_stream_state_bytes(batch, max_frames, beam, candidates)
+            tables = lib.pika_ctc_lm2_scratch_bytes(batch, max_frames, beam, candidates)
         if nbytes == 0:
             raise ValueError("(batch,max_frames,beam) = (%d,%d,%d) not supported" % (batch, max_frames, beam))
         rec = (nbytes - tables) // batch                # the record's size is the library's: the blob is tables + records
@@ -615,10 +762,15 @@ class CtcBeamStream(object):
             if self.lm is None:
                 _lib.check(lib.pika_ctc_stream_reset(_ptr(self._state), self.batch, self.max_frames, self.beam,
                                                      _ptr(which), _stream()), "pika_ctc_stream_reset")
-            else:
+            elif self.bias is None:
                 _lib.check(lib.pika_ctc_lm_stream_reset(_ptr(self._state), self.batch, self.max_frames, self.beam,
                                                         self.candidates, self.lm.num_states, self.lm.start, _ptr(which),
                                                         _stream()), "pika_ctc_lm_stream_reset")
+            else:
+                _lib.check(lib.pika_ctc_lm2_stream_reset(_ptr(self._state), self.batch, self.max_frames, self.beam,
+                                                         self.candidates, self.lm.num_states, self.lm.start,
+                                                         self.bias.num_states, self.bias.start, _ptr(which), _stream()),
+                           "pika_ctc_lm2_stream_reset")
         if which is None:
             self._fed = 0
 
@@ -635,6 +787,9 @@ class CtcBeamStream(object):
         if lm is not None and 0 <= lm.backoff_id - lm.label_offset < C:
             raise ValueError("the LM's backoff_id %d is the label of class %d" % (lm.backoff_id,
                                                                                  lm.backoff_id - lm.label_offset))
+        bias = self.bias
+        if bias is not None:
+            _check_second(bias, "bias", C, self.device, "the stream")
         if self._fed + Tc > self.max_frames:
             raise ValueError("%d frames were fed since the last full reset: %d more exceed max_frames = %d"
                              % (self._fed, Tc, self.max_frames))
@@ -649,10 +804,14 @@ class CtcBeamStream(object):
             if lm is None:
                 _lib.check(lib.pika_ctc_stream_advance(*(head + (_ptr(self._state), self.max_frames, _stream()))),
                            "pika_ctc_stream_advance")
-            else:
+            elif bias is None:
                 _lib.check(lib.pika_ctc_lm_stream_advance(*(head + self._fst() + (
                     lm.backoff_id, lm.label_offset, self.candidates, self.lm_weight, self.length_bonus,
                     _ptr(self._state), self.max_frames, _stream()))), "pika_ctc_lm_stream_advance")
+            else:
+                _lib.check(lib.pika_ctc_lm2_stream_advance(*(head + _fst_args(lm, False) + _fst_args(bias, False) + (
+                    self.candidates, self.lm_weight, self.bias_weight, self.length_bonus, _ptr(self._state),
+                    self.max_frames, _stream()))), "pika_ctc_lm2_stream_advance")
         self.classes = C
         self._fed += Tc
 
@@ -677,6 +836,13 @@ class CtcBeamStream(object):
                            "pika_ctc_stream_results")
                 return tokens, lengths, scores
             am_scores = torch.empty((B, nbest), dtype=torch.float32, device=dev)
+            if self.bias is not None:
+                _lib.check(lib.pika_ctc_lm2_stream_results(*(
+                    (_ptr(self._state), B, L, self.beam, self.candidates) + _fst_args(lm, False)
+                    + _fst_args(self.bias, False) + (self.lm_weight, self.bias_weight, int(bool(use_final)), nbest, L,
+                                                     _ptr(tokens), _ptr(lengths), _ptr(scores), _ptr(am_scores),
+                                                     _stream()))), "pika_ctc_lm2_stream_results")
+                return tokens, lengths, scores, am_scores
             _lib.check(lib.pika_ctc_lm_stream_results(*((_ptr(self._state), B, L, self.beam, self.candidates)
                                                         + self._fst() + (lm.backoff_id, lm.label_offset, self.lm_weight,
                                                                          int(bool(use_final)), nbest, L, _ptr(tokens),
