@@ -22,9 +22,10 @@
 //            descendant that stayed.  Numerics as the loss: fp32 (p_b, p_nb), the best tot moved into an fp64 offset
 //            every RENORM frames.  The n-best back-trace walks the table in the same launch.  What ctc_lm.hip's fused
 //            search does the same way (beam, trie, slot work, order, renormalisation, tail) is in ctc_search_core.h.
-//   stream : the search with its state in device memory between launches: reset writes the first beam and clears the
-//            table, advance runs a chunk's frames through the frame body of the one-shot kernel (load, frames, store),
-//            results is the one-shot tail on the stored beam and modifies nothing.
+//   stream : the search with its state in device memory between launches: reset (ctc_search_core.h: one kernel for
+//            this search's records and ctc_lm.hip's) writes the first beam and clears the table, advance runs a chunk's
+//            frames through the frame body of the one-shot kernel (load, frames, store), results is the one-shot tail on
+//            the stored beam and modifies nothing.
 
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -303,11 +304,6 @@ static_assert(sizeof(Rec) == PIKA_CTC_STREAM_RECORD_BYTES && offsetof(StreamHdr,
                   offsetof(StreamHdr, overflow) == PIKA_CTC_STREAM_OVERFLOW_OFFSET,
               "the record the header documents");
 
-__global__ __launch_bounds__(256) void ctc_stream_reset_kernel(unsigned long long *tables, size_t slots, Rec *recs,
-                                                               const int *__restrict__ which) {
-    stream_reset(tables, slots, recs, which, [](Beam &A) { root_slot(A); });
-}
-
 // the beam of a record into LDS; a label outside the classes (a record that was never reset) is no label
 __device__ __forceinline__ void load_beam(Beam &A, const Rec &R, const StreamHdr &h, int r, int C) {
     if (r < h.n) {
@@ -569,12 +565,7 @@ size_t pika_ctc_stream_state_bytes(int B, int max_frames, int beam) {
 }
 
 int pika_ctc_stream_reset(void *state, int B, int max_frames, int beam, const int *which, void *stream) {
-    if (int rc = check_search_dims(B, max_frames, beam, 1)) return rc;
-    if (!state) return PIKA_EINVAL;
-    hipLaunchKernelGGL(ctc_stream_reset_kernel, reset_grid(B, max_frames, beam), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), static_cast<unsigned long long *>(state),
-                       table_slots(max_frames, beam), stream_recs<Rec>(state, B, max_frames, beam), which);
-    return (int)hipGetLastError();
+    return reset_streams<Beam>(state, B, max_frames, beam, 1, which, stream);
 }
 
 int pika_ctc_stream_advance(const float *x, long long stride_t, long long stride_b, const float *lse,

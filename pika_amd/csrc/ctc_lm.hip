@@ -13,14 +13,17 @@
 //            (p_b, p_nb) and the renormalisation are those of ctc_beam_kernel, shared through ctc_search_core.h;
 //            the bonus is renormalised with tot.  The end applies the final cost, re-sorts by counting and
 //            walks the table for the n-best.
-//   stream : the search with its state in device memory between launches: reset writes the first beam and clears the
-//            table, advance runs a chunk's frames through the frame body of the one-shot kernel (load, frames, store),
-//            results is the one-shot end -- final cost and new order on the side -- on the stored beam, which it only
-//            reads.
+//   stream : the search with its state in device memory between launches: reset (the one kernel of ctc_search_core.h,
+//            here on the LM's records) writes the first beam and clears the table, advance runs a chunk's frames
+//            through the frame body of the one-shot kernel (load, frames, store), results is the one-shot end -- final
+//            cost and new order on the side -- on the stored beam, which it only reads.
 //   bias   : the same kernel template with a second automaton (pika_ctc_lm2_*): a slot carries a second state, a fresh
 //            child walks both FSTs and exists only when both reach it; the cells stay as they are -- the winners of a
 //            frame (at most `beam`) walk the second FST again at node assignment, lane = slot, to get the state and to
 //            complete the bonus.  The one-FST instantiations have no trace of it (if constexpr).
+//   host   : the nine arguments of an automaton are packed once (make_fst, make_bias) and checked by one set of helpers
+//            (check_fst and its halves); the one-shot search, the advance and the results are one template each over
+//            "a Bias or none", so a pika_ctc_lm_* and a pika_ctc_lm2_* entry point differ in what they pack.
 //   Every loop over the FST has a fixed trip limit (header): a malformed table cannot spin the workgroup.
 
 #include <hip/hip_runtime.h>
@@ -182,16 +185,6 @@ static_assert(sizeof(Rec) == PIKA_CTC_LM_STREAM_RECORD_BYTES && offsetof(StreamH
 static_assert(sizeof(Rec2) == PIKA_CTC_LM2_STREAM_RECORD_BYTES && sizeof(Rec2) == sizeof(Rec) + MAX_BEAM * sizeof(int) &&
                   sizeof(Rec2) % 8 == 0,
               "the LM record, then the second states");
-
-__global__ __launch_bounds__(256) void ctc_lm_stream_reset_kernel(unsigned long long *tables, size_t slots, Rec *recs,
-                                                                  const int *__restrict__ which, int start) {
-    stream_reset(tables, slots, recs, which, [start](LmBeam &A) { root_slot(A, start); });
-}
-
-__global__ __launch_bounds__(256) void ctc_lm2_stream_reset_kernel(unsigned long long *tables, size_t slots, Rec2 *recs,
-                                                                   const int *__restrict__ which, int start, int start2) {
-    stream_reset(tables, slots, recs, which, [start, start2](Lm2Beam &A) { root_slot(A, start, start2); });
-}
 
 // the beam of a record into LDS (wave 0: lane r loads slot r); a label outside the classes (a record that was never
 // reset) is no label
@@ -472,16 +465,29 @@ __global__ __launch_bounds__(THREADS) void ctc_lm_kernel(const Args a, const Fst
 }
 
 // ---------------------------------------------------------------------------------------------
-// host: every entry point is its checks and one launch; the pika_ctc_lm2_* forms pass a Bias along
+// host: an entry point packs its automata (make_fst, make_bias) and is checks and one launch -- the three forms of the
+// search as templates over "a Bias or none", the reset through reset_streams of ctc_search_core.h.  The checks of an
+// automaton exist once: bad_start / fst_dims_bad for its sizes, fst_missing for its arrays, check_fst for both.
 // ---------------------------------------------------------------------------------------------
-static inline bool fst_missing(const long long *off, const int *il, const float *w, const int *ns, const float *fin, int A) {
-    return !off || !fin || (A > 0 && (!il || !w || !ns));
+static inline Fst make_fst(const long long *off, const int *il, const float *w, const int *ns, const float *fin, int S,
+                           int A, int backoff, int label_offset) {
+    return {off, il, w, ns, fin, S, A, backoff, label_offset};
 }
 
-// the second FST of a pika_ctc_lm2_* call; `start` is checked where the call has one
-static inline int check_bias(const Bias &g, bool with_start) {
-    if (g.f.S <= 0 || g.f.A < 0 || (with_start && (g.start < 0 || g.start >= g.f.S))) return PIKA_EINVAL;
-    return fst_missing(g.f.off, g.f.il, g.f.w, g.f.ns, g.f.fin, g.f.A) ? PIKA_EINVAL : PIKA_OK;
+// the second automaton of a pika_ctc_lm2_* call; a call without a start state passes 0
+static inline Bias make_bias(const Fst &f, int start, float w) { return {f, start, w}; }
+
+// S states and a start state among them.  A call that has no start state passes 0, which every table holds.
+static inline bool bad_start(int S, int start) { return S <= 0 || start < 0 || start >= S; }
+
+static inline bool fst_dims_bad(const Fst &f, int start) { return f.A < 0 || bad_start(f.S, start); }
+
+static inline bool fst_missing(const Fst &f) { return !f.off || !f.fin || (f.A > 0 && (!f.il || !f.w || !f.ns)); }
+
+// Sizes and arrays in one: the second automaton's check, ahead of everything else.  The first automaton's two halves
+// stand apart in the forms below, the limits (PIKA_ETOOBIG) between them, as the entry points always answered.
+static inline int check_fst(const Fst &f, int start) {
+    return fst_dims_bad(f, start) || fst_missing(f) ? PIKA_EINVAL : PIKA_OK;
 }
 
 template <Mode MODE, class... BIAS>
@@ -503,11 +509,11 @@ static int beam_search(const float *x, long long stride_t, long long stride_b, c
                        int use_final, int *tokens, int *lengths, float *scores, float *am_scores, void *scratch,
                        void *stream, const BIAS &...g) {
     if (B <= 0 || T <= 0 || C <= 0 || blank < 0 || blank >= C || nbest <= 0) return PIKA_EINVAL;
-    if (f.S <= 0 || f.A < 0 || start < 0 || start >= f.S) return PIKA_EINVAL;
+    if (fst_dims_bad(f, start)) return PIKA_EINVAL;
     if (int rc = check_search_dims(B, T, beam, candidates)) return rc;
     if (nbest > beam) return PIKA_ETOOBIG;
     if (!x || !blank_lp || !top_val || !top_idx || !input_lengths || !tokens || !lengths || !scores || !am_scores ||
-        !scratch || fst_missing(f.off, f.il, f.w, f.ns, f.fin, f.A))
+        !scratch || fst_missing(f))
         return PIKA_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (hipError_t e = clear_tables(scratch, B, T, beam, s)) return (int)e;
@@ -523,10 +529,10 @@ static int stream_advance(const float *x, long long stride_t, long long stride_b
                           int blank, int beam, const Fst &f, int candidates, float lm_weight, float length_bonus,
                           void *state, int max_frames, void *stream, const BIAS &...g) {
     if (B <= 0 || Tc <= 0 || C <= 0 || blank < 0 || blank >= C) return PIKA_EINVAL;
-    if (f.S <= 0 || f.A < 0) return PIKA_EINVAL;
+    if (fst_dims_bad(f, 0)) return PIKA_EINVAL;
     if (int rc = check_search_dims(B, max_frames, beam, candidates)) return rc;
     if (2ll * Tc * beam > (1ll << 28)) return PIKA_ETOOBIG;  // the row arrays' index range, as in the one-shot search
-    if (!x || !blank_lp || !top_val || !top_idx || !chunk_lengths || !state || fst_missing(f.off, f.il, f.w, f.ns, f.fin, f.A))
+    if (!x || !blank_lp || !top_val || !top_idx || !chunk_lengths || !state || fst_missing(f))
         return PIKA_EINVAL;
     const Args a = {x, stride_t, stride_b, lse, blank_lp, top_val, top_idx, chunk_lengths, B, Tc, beam, 0, candidates,
                     0, 0, lm_weight, length_bonus, nullptr, nullptr, nullptr, nullptr,
@@ -539,9 +545,9 @@ template <class... BIAS>
 static int stream_results(const void *state, int B, int max_frames, int beam, int candidates, const Fst &f,
                           float lm_weight, int use_final, int nbest, int L, int *tokens, int *lengths, float *scores,
                           float *am_scores, void *stream, const BIAS &...g) {
-    if (f.S <= 0 || f.A < 0) return PIKA_EINVAL;
+    if (fst_dims_bad(f, 0)) return PIKA_EINVAL;
     if (int rc = check_results_dims(B, max_frames, beam, candidates, nbest, L)) return rc;
-    if (!state || !tokens || !lengths || !scores || !am_scores || fst_missing(f.off, f.il, f.w, f.ns, f.fin, f.A))
+    if (!state || !tokens || !lengths || !scores || !am_scores || fst_missing(f))
         return PIKA_EINVAL;
     const Args a = {nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, B, L, beam, nbest, candidates, 0, use_final,
                     lm_weight, 0.0f, tokens, lengths, scores, am_scores,
@@ -568,8 +574,8 @@ int pika_ctc_lm_beam_search(const float *x, long long stride_t, long long stride
                             const float *fst_final, int num_states, int num_arcs, int start, int backoff_id,
                             int label_offset, int candidates, float lm_weight, float length_bonus, int use_final,
                             int *tokens, int *lengths, float *scores, float *am_scores, void *scratch, void *stream) {
-    const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
-                   label_offset};
+    const Fst f = make_fst(fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
+                           label_offset);
     return beam_search(x, stride_t, stride_b, lse, blank_lp, top_val, top_idx, input_lengths, B, T, C, blank, beam, nbest,
                        f, start, candidates, lm_weight, length_bonus, use_final, tokens, lengths, scores, am_scores,
                        scratch, stream);
@@ -582,13 +588,8 @@ size_t pika_ctc_lm_stream_state_bytes(int B, int max_frames, int beam, int candi
 
 int pika_ctc_lm_stream_reset(void *state, int B, int max_frames, int beam, int candidates, int num_states, int start,
                              const int *which, void *stream) {
-    if (num_states <= 0 || start < 0 || start >= num_states) return PIKA_EINVAL;
-    if (int rc = check_search_dims(B, max_frames, beam, candidates)) return rc;
-    if (!state) return PIKA_EINVAL;
-    hipLaunchKernelGGL(ctc_lm_stream_reset_kernel, reset_grid(B, max_frames, beam), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), static_cast<unsigned long long *>(state),
-                       table_slots(max_frames, beam), stream_recs<Rec>(state, B, max_frames, beam), which, start);
-    return (int)hipGetLastError();
+    if (bad_start(num_states, start)) return PIKA_EINVAL;
+    return reset_streams<LmBeam>(state, B, max_frames, beam, candidates, which, stream, start);
 }
 
 int pika_ctc_lm_stream_advance(const float *x, long long stride_t, long long stride_b, const float *lse,
@@ -598,8 +599,8 @@ int pika_ctc_lm_stream_advance(const float *x, long long stride_t, long long str
                                const int *fst_nextstate, const float *fst_final, int num_states, int num_arcs,
                                int backoff_id, int label_offset, int candidates, float lm_weight, float length_bonus,
                                void *state, int max_frames, void *stream) {
-    const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
-                   label_offset};
+    const Fst f = make_fst(fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
+                           label_offset);
     return stream_advance(x, stride_t, stride_b, lse, blank_lp, top_val, top_idx, chunk_lengths, B, Tc, C, blank, beam, f,
                           candidates, lm_weight, length_bonus, state, max_frames, stream);
 }
@@ -609,8 +610,8 @@ int pika_ctc_lm_stream_results(const void *state, int B, int max_frames, int bea
                                const int *fst_nextstate, const float *fst_final, int num_states, int num_arcs,
                                int backoff_id, int label_offset, float lm_weight, int use_final, int nbest, int L,
                                int *tokens, int *lengths, float *scores, float *am_scores, void *stream) {
-    const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
-                   label_offset};
+    const Fst f = make_fst(fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
+                           label_offset);
     return stream_results(state, B, max_frames, beam, candidates, f, lm_weight, use_final, nbest, L, tokens, lengths,
                           scores, am_scores, stream);
 }
@@ -631,11 +632,11 @@ int pika_ctc_lm2_beam_search(const float *x, long long stride_t, long long strid
                              int num_states2, int num_arcs2, int start2, int backoff_id2, int label_offset2,
                              int candidates, float lm_weight, float bias_weight, float length_bonus, int use_final,
                              int *tokens, int *lengths, float *scores, float *am_scores, void *scratch, void *stream) {
-    const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
-                   label_offset};
-    const Bias g = {{fst2_offsets, fst2_ilabel, fst2_weight, fst2_nextstate, fst2_final, num_states2, num_arcs2,
-                     backoff_id2, label_offset2}, start2, bias_weight};
-    if (int rc = check_bias(g, true)) return rc;
+    const Fst f = make_fst(fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
+                           label_offset);
+    const Bias g = make_bias(make_fst(fst2_offsets, fst2_ilabel, fst2_weight, fst2_nextstate, fst2_final, num_states2,
+                                      num_arcs2, backoff_id2, label_offset2), start2, bias_weight);
+    if (int rc = check_fst(g.f, g.start)) return rc;
     return beam_search(x, stride_t, stride_b, lse, blank_lp, top_val, top_idx, input_lengths, B, T, C, blank, beam, nbest,
                        f, start, candidates, lm_weight, length_bonus, use_final, tokens, lengths, scores, am_scores,
                        scratch, stream, g);
@@ -648,14 +649,8 @@ size_t pika_ctc_lm2_stream_state_bytes(int B, int max_frames, int beam, int cand
 
 int pika_ctc_lm2_stream_reset(void *state, int B, int max_frames, int beam, int candidates, int num_states, int start,
                               int num_states2, int start2, const int *which, void *stream) {
-    if (num_states <= 0 || start < 0 || start >= num_states) return PIKA_EINVAL;
-    if (num_states2 <= 0 || start2 < 0 || start2 >= num_states2) return PIKA_EINVAL;
-    if (int rc = check_search_dims(B, max_frames, beam, candidates)) return rc;
-    if (!state) return PIKA_EINVAL;
-    hipLaunchKernelGGL(ctc_lm2_stream_reset_kernel, reset_grid(B, max_frames, beam), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), static_cast<unsigned long long *>(state),
-                       table_slots(max_frames, beam), stream_recs<Rec2>(state, B, max_frames, beam), which, start, start2);
-    return (int)hipGetLastError();
+    if (bad_start(num_states, start) || bad_start(num_states2, start2)) return PIKA_EINVAL;
+    return reset_streams<Lm2Beam>(state, B, max_frames, beam, candidates, which, stream, start, start2);
 }
 
 int pika_ctc_lm2_stream_advance(const float *x, long long stride_t, long long stride_b, const float *lse,
@@ -668,11 +663,11 @@ int pika_ctc_lm2_stream_advance(const float *x, long long stride_t, long long st
                                 int num_states2, int num_arcs2, int backoff_id2, int label_offset2, int candidates,
                                 float lm_weight, float bias_weight, float length_bonus, void *state, int max_frames,
                                 void *stream) {
-    const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
-                   label_offset};
-    const Bias g = {{fst2_offsets, fst2_ilabel, fst2_weight, fst2_nextstate, fst2_final, num_states2, num_arcs2,
-                     backoff_id2, label_offset2}, 0, bias_weight};
-    if (int rc = check_bias(g, false)) return rc;
+    const Fst f = make_fst(fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
+                           label_offset);
+    const Bias g = make_bias(make_fst(fst2_offsets, fst2_ilabel, fst2_weight, fst2_nextstate, fst2_final, num_states2,
+                                      num_arcs2, backoff_id2, label_offset2), 0, bias_weight);
+    if (int rc = check_fst(g.f, g.start)) return rc;
     return stream_advance(x, stride_t, stride_b, lse, blank_lp, top_val, top_idx, chunk_lengths, B, Tc, C, blank, beam, f,
                           candidates, lm_weight, length_bonus, state, max_frames, stream, g);
 }
@@ -685,11 +680,11 @@ int pika_ctc_lm2_stream_results(const void *state, int B, int max_frames, int be
                                 int num_states2, int num_arcs2, int backoff_id2, int label_offset2, float lm_weight,
                                 float bias_weight, int use_final, int nbest, int L, int *tokens, int *lengths,
                                 float *scores, float *am_scores, void *stream) {
-    const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
-                   label_offset};
-    const Bias g = {{fst2_offsets, fst2_ilabel, fst2_weight, fst2_nextstate, fst2_final, num_states2, num_arcs2,
-                     backoff_id2, label_offset2}, 0, bias_weight};
-    if (int rc = check_bias(g, false)) return rc;
+    const Fst f = make_fst(fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
+                           label_offset);
+    const Bias g = make_bias(make_fst(fst2_offsets, fst2_ilabel, fst2_weight, fst2_nextstate, fst2_final, num_states2,
+                                      num_arcs2, backoff_id2, label_offset2), 0, bias_weight);
+    if (int rc = check_fst(g.f, g.start)) return rc;
     return stream_results(state, B, max_frames, beam, candidates, f, lm_weight, use_final, nbest, L, tokens, lengths,
                           scores, am_scores, stream, g);
 }

@@ -194,11 +194,13 @@ __device__ __forceinline__ StreamHdr load_hdr(const StreamHdr &G, int beam, int 
     return h;
 }
 
-// Reset.  grid = (B, y), block = 256: the workgroups (b, *) clear stream b's table, (b, 0) writes its record; streams with
-// which[b] == 0 are not touched.  `root(beam)` writes the search's first beam.
-template <class BeamT, class Root>
-__device__ __forceinline__ void stream_reset(unsigned long long *tables, size_t slots, StreamRec<BeamT> *recs,
-                                             const int *which, Root root) {
+// Reset, one kernel for every record type.  grid = (B, y), block = 256: the workgroups (b, *) clear stream b's table,
+// (b, 0) writes its record; streams with which[b] == 0 are not touched.  `start...` is what the search's root_slot takes
+// after the beam: nothing, the LM's start state, or that and the second automaton's.
+template <class BeamT, class... START>
+__global__ __launch_bounds__(256) void ctc_stream_reset_kernel(unsigned long long *tables, size_t slots,
+                                                               StreamRec<BeamT> *recs, const int *__restrict__ which,
+                                                               START... start) {
     const int b = blockIdx.x;
     if (which && which[b] == 0) return;  // workgroup-uniform
     unsigned long long *table = tables + (size_t)b * slots;
@@ -207,7 +209,7 @@ __device__ __forceinline__ void stream_reset(unsigned long long *tables, size_t 
         StreamRec<BeamT> &R = recs[b];
         R.h.n = 1; R.h.frames = 0; R.h.overflow = 0; R.h.pad = 0;
         R.h.off = 0.0; R.h.boff = 0.0;
-        root(R.beam);
+        root_slot(R.beam, start...);
     }
 }
 
@@ -242,15 +244,24 @@ static inline hipError_t clear_tables(void *scratch, int B, int T, int beam, hip
     return hipMemsetAsync(scratch, 0xff, table_bytes(B, T, beam), s);
 }
 
-// the streaming calls: where the blob's parts lie, and the reset's grid
+// the streaming calls: where the blob's parts lie
 template <class Rec>
 static inline Rec *stream_recs(const void *state, int B, int max_frames, int beam) {
     return reinterpret_cast<Rec *>(static_cast<char *>(const_cast<void *>(state)) + table_bytes(B, max_frames, beam));
 }
 
-static inline dim3 reset_grid(int B, int max_frames, int beam) {
-    const size_t y = table_slots(max_frames, beam) / 4096;  // 16 keys per thread
-    return dim3((unsigned)B, (unsigned)(y < 1 ? 1 : (y > 256 ? 256 : y)));
+// the whole of a reset entry point behind its own arguments' checks (`classes` as check_search_dims)
+template <class BeamT, class... START>
+static int reset_streams(void *state, int B, int max_frames, int beam, int classes, const int *which, void *stream,
+                         START... start) {
+    if (int rc = check_search_dims(B, max_frames, beam, classes)) return rc;
+    if (!state) return PIKA_EINVAL;
+    const size_t slots = table_slots(max_frames, beam), y = slots / 4096;  // 16 keys per thread
+    hipLaunchKernelGGL((ctc_stream_reset_kernel<BeamT, START...>),
+                       dim3((unsigned)B, (unsigned)(y < 1 ? 1 : (y > 256 ? 256 : y))), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), static_cast<unsigned long long *>(state), slots,
+                       stream_recs<StreamRec<BeamT>>(state, B, max_frames, beam), which, start...);
+    return (int)hipGetLastError();
 }
 
 // the n-best outputs of a results call: nbest entries of L tokens

@@ -397,6 +397,17 @@ def ctc_beam_search_from_logits(logits, input_lengths, beam=16, nbest=1, blank=0
     return _beam(logits, "logits", input_lengths, beam, nbest, blank, True)
 
 
+def _hip_device(device, default, who):
+    """`device`, or `default` when it is None, as an indexed HIP device (`who`: the class that asks)."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("pika_amd %s: needs a HIP device (there is no CPU path)" % who)
+    dev = torch.device(default if device is None else device)
+    if dev.type != "cuda":
+        raise RuntimeError("pika_amd %s: device %s is not a HIP device (there is no CPU path)" % (who, dev))
+    # always an indexed device: "cuda" and "cuda:0" must compare equal to a tensor's device
+    return torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+
+
 class CtcNgramLm(object):
     """An n-gram back-off LM for `ctc_beam_search_lm`: the arrays of an `NgramFst` (pika_amd/decoder/ngram_fst.py: it
     reads OpenFST binary and text files), checked on the host, uploaded once and kept.
@@ -439,13 +450,7 @@ class CtcNgramLm(object):
         if np.any((cur >= 0) & (bo[np.maximum(cur, 0)] >= 0)):
             raise ValueError("CtcNgramLm: a back-off chain is longer than %d hops (or the back-off graph has a cycle)"
                              % MAX_BACKOFF_HOPS)
-        if not torch.cuda.is_available():
-            raise RuntimeError("pika_amd CtcNgramLm: needs a HIP device (there is no CPU path)")
-        dev = torch.device("cuda" if device is None else device)
-        if dev.type != "cuda":
-            raise RuntimeError("pika_amd CtcNgramLm: device %s is not a HIP device (there is no CPU path)" % dev)
-        # always an indexed device: "cuda" and "cuda:0" must compare equal to a tensor's device
-        self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+        self.device = _hip_device(device, "cuda", "CtcNgramLm")
         self.num_states, self.num_arcs, self.start = S, A, start
         self.backoff_id, self.label_offset = backoff_id, label_offset
         self.offsets, self.ilabel, self.weight, self.nextstate, self.final = (
@@ -532,21 +537,6 @@ class CtcHotwords(CtcNgramLm):
         return NgramFst.from_arcs(len(state), arcs, finals, start=0)
 
 
-def _check_second(lm, what, C, device, where):
-    """The checks an LM argument (`what`: its name) gets against the input: its backoff_id against C, its device."""
-    if 0 <= lm.backoff_id - lm.label_offset < C:
-        raise ValueError("the backoff_id %d of %s is the label of class %d" % (lm.backoff_id, what,
-                                                                              lm.backoff_id - lm.label_offset))
-    if lm.device != device:
-        raise ValueError("%s lives on %s, %s on %s" % (what, lm.device, where, device))
-
-
-def _fst_args(lm, start):
-    """An FST as the C ABI takes it, with or without its start state."""
-    return (_ptr(lm.offsets), _ptr(lm.ilabel), _ptr(lm.weight), _ptr(lm.nextstate), _ptr(lm.final), lm.num_states,
-            lm.num_arcs) + ((lm.start,) if start else ()) + (lm.backoff_id, lm.label_offset)
-
-
 class CtcBiasedLm(object):
     """An LM with a second automaton beside it, for every place that takes an `lm`: `ctc_beam_search_lm`,
     `ctc_beam_search_lm_from_logits` and `CtcBeamStream`.  `lm` and `bias` are `CtcNgramLm`s on one device (TypeError /
@@ -563,48 +553,109 @@ class CtcBiasedLm(object):
         self.lm, self.bias, self.bias_weight, self.device = lm, bias, float(bias_weight), lm.device
 
 
+def _fst_args(lm, start):
+    """An FST as the C ABI takes it, with or without its start state."""
+    return (_ptr(lm.offsets), _ptr(lm.ilabel), _ptr(lm.weight), _ptr(lm.nextstate), _ptr(lm.final), lm.num_states,
+            lm.num_arcs) + ((lm.start,) if start else ()) + (lm.backoff_id, lm.label_offset)
+
+
+class _Search(object):
+    """Which search a call runs -- plain, with an LM, with an LM and a second automaton -- decided once, from what the
+    caller gave as `lm` (None, a `CtcNgramLm`, a `CtcBiasedLm`).  The only place that knows the variants: a call site
+    checks through `check_against` and makes one C call through `call`, with the argument groups below spliced in.
+
+        prefix           of the entry points: pika_ctc_, pika_ctc_lm_ or pika_ctc_lm2_
+        scratch_bytes    the name, behind the prefix, of the entry point that sizes the tables
+        candidates       the row pass's K: 2 * beam for the plain search (exact), else as asked, None = min(2 * beam, 128)
+        dims             what follows (B, T, beam) in the sizes, the reset and the results: () or (candidates,)
+        fsts(start)      the automata as the C ABI takes them, without or with their start states
+        starts()         (num_states, start) of every automaton: the reset's
+        weights          after the automata in a search call: (), (candidates, lm_weight, length_bonus) or
+                         (candidates, lm_weight, bias_weight, length_bonus)
+        results_weights  the same in a results call: (), (lm_weight,) or (lm_weight, bias_weight)
+        fused            there is an LM: the calls take `use_final` and return am_scores
+
+    Built in two steps, `_Search(lm, lm_weight, length_bonus, need_lm).sized(beam, candidates)`: the one-shot call,
+    which needs an LM, checks beam / nbest between the type of `lm` and `candidates`; a stream may have no LM."""
+
+    def __init__(self, lm, lm_weight, length_bonus, need_lm):
+        bias, bias_weight = None, 1.0
+        if isinstance(lm, CtcBiasedLm):
+            lm, bias, bias_weight = lm.lm, lm.bias, lm.bias_weight
+        if not isinstance(lm, CtcNgramLm) and (need_lm or lm is not None):
+            raise TypeError("lm must be a CtcNgramLm%s, got %s" % ("" if need_lm else " or None", type(lm).__name__))
+        self.lm, self.bias, self.bias_weight = lm, bias, float(bias_weight)
+        self.lm_weight, self.length_bonus = float(lm_weight), float(length_bonus)
+        # the variants: the automata (each with its name and its backoff_id as the messages put them), and per number of
+        # automata the entry points' prefix, the name of the one that sizes the tables, the weights of a results call
+        n = 0 if lm is None else 1 if bias is None else 2
+        self.automata = ((lm, "the LM", "the LM's backoff_id %d"), (bias, "bias", "the backoff_id %d of bias"))[:n]
+        self.prefix, self.scratch_bytes = (("pika_ctc_", "beam_scratch_bytes"), ("pika_ctc_lm_", "scratch_bytes"),
+                                           ("pika_ctc_lm2_", "scratch_bytes"))[n]
+        self.results_weights = (self.lm_weight, self.bias_weight)[:n]
+        self.fused = n > 0
+
+    def sized(self, beam, candidates):
+        if not self.fused:
+            candidates = 2 * beam                       # the row pass's K of the plain search: exact
+        else:
+            candidates = min(2 * beam, MAX_CANDIDATES) if candidates is None else int(candidates)
+            if not 1 <= candidates <= MAX_CANDIDATES:
+                raise ValueError("need 1 <= candidates <= %d, got %d" % (MAX_CANDIDATES, candidates))
+        self.candidates = candidates
+        self.dims = (candidates,) if self.fused else ()
+        self.weights = (self.dims + self.results_weights + (self.length_bonus,)) if self.fused else ()
+        return self
+
+    # (the automata's fields are read when a call is put together: behind the checks of the input, as they always were)
+    def fsts(self, start):
+        args = ()
+        for a in self.automata:
+            args += _fst_args(a[0], start)
+        return args
+
+    def starts(self):
+        args = ()
+        for a in self.automata:
+            args += (a[0].num_states, a[0].start)
+        return args
+
+    def check_against(self, C, device, where):
+        """Every automaton against the C classes of an input and the device of `where` (its name in the message)."""
+        for m, name, its_backoff_id in self.automata:
+            if 0 <= m.backoff_id - m.label_offset < C:
+                raise ValueError((its_backoff_id + " is the label of class %d") % (m.backoff_id,
+                                                                                  m.backoff_id - m.label_offset))
+            if m.device != device:
+                raise ValueError("%s lives on %s, %s on %s" % (name, m.device, where, device))
+
+    def size(self, name, *dims):
+        """A size in bytes by the variant's entry point `name`."""
+        return getattr(_lib.lib(), self.prefix + name)(*(dims + self.dims))
+
+    def call(self, name, *args):
+        _lib.check(getattr(_lib.lib(), self.prefix + name)(*args), self.prefix + name)
+
+
 def _beam_lm(x, what, input_lengths, lm, beam, nbest, blank, lm_weight, length_bonus, candidates, use_final, logits):
     blank, beam, nbest = int(blank), int(beam), int(nbest)
-    bias, bias_weight = None, 1.0
-    if isinstance(lm, CtcBiasedLm):
-        lm, bias, bias_weight = lm.lm, lm.bias, lm.bias_weight
-    if not isinstance(lm, CtcNgramLm):
-        raise TypeError("lm must be a CtcNgramLm, got %s" % type(lm).__name__)
+    v = _Search(lm, lm_weight, length_bonus, True)
     alloc = _nbest_outputs(beam, nbest)
-    candidates = min(2 * beam, MAX_CANDIDATES) if candidates is None else int(candidates)
-    if not 1 <= candidates <= MAX_CANDIDATES:
-        raise ValueError("need 1 <= candidates <= %d, got %d" % (MAX_CANDIDATES, candidates))
-    x, il, blank_lp, top_val, top_idx, lse, unbatched = _decode_rows(x, what, input_lengths, blank, candidates, logits)
+    v.sized(beam, candidates)
+    x, il, blank_lp, top_val, top_idx, lse, unbatched = _decode_rows(x, what, input_lengths, blank, v.candidates, logits)
     T, B, C = x.shape
-    if 0 <= lm.backoff_id - lm.label_offset < C:
-        raise ValueError("the LM's backoff_id %d is the label of class %d" % (lm.backoff_id,
-                                                                             lm.backoff_id - lm.label_offset))
-    if lm.device != x.device:
-        raise ValueError("the LM lives on %s, %s on %s" % (lm.device, what, x.device))
-    if bias is not None:
-        _check_second(bias, "bias", C, x.device, what)
-    lib = _lib.lib()
-    nbytes = lib.pika_ctc_lm_scratch_bytes(B, T, beam, candidates)
+    v.check_against(C, x.device, what)
+    nbytes = v.size(v.scratch_bytes, B, T, beam)
     if nbytes == 0:
-        raise ValueError("(B,T,beam,candidates) = (%d,%d,%d,%d) not supported" % (B, T, beam, candidates))
+        raise ValueError("(B,T,beam,candidates) = (%d,%d,%d,%d) not supported" % (B, T, beam, v.candidates))
     with torch.cuda.device(x.device):
         tokens, lengths, scores = alloc(x)
         am_scores = torch.empty((B, nbest), dtype=torch.float32, device=x.device)
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        if bias is None:
-            _lib.check(lib.pika_ctc_lm_beam_search(
-                _ptr(x), x.stride(0), x.stride(1), _ptr(lse), _ptr(blank_lp), _ptr(top_val), _ptr(top_idx), _ptr(il), B,
-                T, C, blank, beam, nbest, _ptr(lm.offsets), _ptr(lm.ilabel), _ptr(lm.weight), _ptr(lm.nextstate),
-                _ptr(lm.final), lm.num_states, lm.num_arcs, lm.start, lm.backoff_id, lm.label_offset, candidates,
-                float(lm_weight), float(length_bonus), int(bool(use_final)), _ptr(tokens), _ptr(lengths), _ptr(scores),
-                _ptr(am_scores), _ptr(scratch), _stream()), "pika_ctc_lm_beam_search")
-        else:
-            _lib.check(lib.pika_ctc_lm2_beam_search(*((
-                _ptr(x), x.stride(0), x.stride(1), _ptr(lse), _ptr(blank_lp), _ptr(top_val), _ptr(top_idx), _ptr(il), B,
-                T, C, blank, beam, nbest) + _fst_args(lm, True) + _fst_args(bias, True) + (
-                candidates, float(lm_weight), float(bias_weight), float(length_bonus), int(bool(use_final)),
-                _ptr(tokens), _ptr(lengths), _ptr(scores), _ptr(am_scores), _ptr(scratch), _stream()))),
-                "pika_ctc_lm2_beam_search")
+        v.call("beam_search", *((_ptr(x), x.stride(0), x.stride(1), _ptr(lse), _ptr(blank_lp), _ptr(top_val),
+                                 _ptr(top_idx), _ptr(il), B, T, C, blank, beam, nbest) + v.fsts(True) + v.weights + (
+                                     int(bool(use_final)), _ptr(tokens), _ptr(lengths), _ptr(scores), _ptr(am_scores),
+                                     _ptr(scratch), _stream())))
     out = (tokens, lengths, scores, am_scores)
     return tuple(o[0] for o in out) if unbatched else out
 
@@ -690,56 +741,29 @@ class CtcBeamStream(object):
     def __init__(self, batch, max_frames, beam=16, blank=0, lm=None, lm_weight=0.5, length_bonus=0.0, candidates=None,
                  device=None):
         batch, max_frames, beam, blank = int(batch), int(max_frames), int(beam), int(blank)
-        bias, bias_weight = None, 1.0
-        if isinstance(lm, CtcBiasedLm):
-            lm, bias, bias_weight = lm.lm, lm.bias, lm.bias_weight
         if not 1 <= beam <= MAX_BEAM:
             raise ValueError("need 1 <= beam <= %d, got beam=%d" % (MAX_BEAM, beam))
-        if lm is not None and not isinstance(lm, CtcNgramLm):
-            raise TypeError("lm must be a CtcNgramLm or None, got %s" % type(lm).__name__)
-        if lm is None:
-            candidates = 2 * beam                       # the row pass's K of the plain search: exact
-        else:
-            candidates = min(2 * beam, MAX_CANDIDATES) if candidates is None else int(candidates)
-            if not 1 <= candidates <= MAX_CANDIDATES:
-                raise ValueError("need 1 <= candidates <= %d, got %d" % (MAX_CANDIDATES, candidates))
+        v = self._search = _Search(lm, lm_weight, length_bonus, False).sized(beam, candidates)
         if batch < 1 or max_frames < 1 or blank < 0:
             raise ValueError("need batch >= 1, max_frames >= 1 and blank >= 0, got %d, %d, %d" % (batch, max_frames, blank))
-        if not torch.cuda.is_available():
-            raise RuntimeError("pika_amd CtcBeamStream: needs a HIP device (there is no CPU path)")
-        dev = torch.device(("cuda" if lm is None else lm.device) if device is None else device)
-        if dev.type != "cuda":
-            raise RuntimeError("pika_amd CtcBeamStream: device %s is not a HIP device (there is no CPU path)" % dev)
-        self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
-        if lm is not None and lm.device != self.device:
-            raise ValueError("the LM lives on %s, the stream on %s" % (lm.device, self.device))
-        self.bias, self.bias_weight = bias, float(bias_weight)
-        self.batch, self.max_frames, self.beam, self.blank, self.candidates = batch, max_frames, beam, blank, candidates
-        self.lm, self.lm_weight, self.length_bonus = lm, float(lm_weight), float(length_bonus)
-        lib = _lib.lib()
-        if lm is None:
-            nbytes = lib.pika_ctc_stream_state_bytes(batch, max_frames, beam)
-            tables = lib.pika_ctc_beam_scratch_bytes(batch, max_frames, beam)
-        elif bias is None:
-            nbytes = lib.pika_ctc_lm_stream_state_bytes(batch, max_frames, beam, candidates)
-            tables = lib.pika_ctc_lm_scratch_bytes(batch, max_frames, beam, candidates)
-        else:
-            nbytes = lib.pika_ctc_lm2_stream_state_bytes(batch, max_frames, beam, candidates)
-            tables = lib.pika_ctc_lm2_scratch_bytes(batch, max_frames, beam, candidates)
+        self.device = _hip_device(device, "cuda" if v.lm is None else v.lm.device, "CtcBeamStream")
+        v.check_against(0, self.device, "the stream")   # (no class yet: the devices alone)
+        self.lm, self.bias, self.bias_weight = v.lm, v.bias, v.bias_weight
+        self.lm_weight, self.length_bonus, self.candidates = v.lm_weight, v.length_bonus, v.candidates
+        self.batch, self.max_frames, self.beam, self.blank = batch, max_frames, beam, blank
+        nbytes = v.size("stream_state_bytes", batch, max_frames, beam)
         if nbytes == 0:
             raise ValueError("(batch,max_frames,beam) = (%d,%d,%d) not supported" % (batch, max_frames, beam))
+        tables = v.size(v.scratch_bytes, batch, max_frames, beam)
         rec = (nbytes - tables) // batch                # the record's size is the library's: the blob is tables + records
         self.classes = None                             # C, fixed by the first advance
         self._fed = 0                                   # chunk widths since the last full reset
         with torch.cuda.device(self.device):
             self._state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self._hdr = self._state[tables:].view(torch.int32).view(batch, rec // 4)
+        self._dims = (batch, max_frames, beam) + v.dims         # behind the state in reset and results
+        self._fsts, self._starts = v.fsts(False), v.starts()    # flattened once: the automata do not change
         self.reset()
-
-    def _fst(self):
-        lm = self.lm
-        return (_ptr(lm.offsets), _ptr(lm.ilabel), _ptr(lm.weight), _ptr(lm.nextstate), _ptr(lm.final), lm.num_states,
-                lm.num_arcs)
 
     @property
     def frames(self):
@@ -757,20 +781,9 @@ class CtcBeamStream(object):
             which = which.reshape(-1).to(self.device, torch.int32).contiguous()
             if which.numel() != self.batch:
                 raise ValueError("which must hold batch = %d entries" % self.batch)
-        lib = _lib.lib()
+        v = self._search
         with torch.cuda.device(self.device):
-            if self.lm is None:
-                _lib.check(lib.pika_ctc_stream_reset(_ptr(self._state), self.batch, self.max_frames, self.beam,
-                                                     _ptr(which), _stream()), "pika_ctc_stream_reset")
-            elif self.bias is None:
-                _lib.check(lib.pika_ctc_lm_stream_reset(_ptr(self._state), self.batch, self.max_frames, self.beam,
-                                                        self.candidates, self.lm.num_states, self.lm.start, _ptr(which),
-                                                        _stream()), "pika_ctc_lm_stream_reset")
-            else:
-                _lib.check(lib.pika_ctc_lm2_stream_reset(_ptr(self._state), self.batch, self.max_frames, self.beam,
-                                                         self.candidates, self.lm.num_states, self.lm.start,
-                                                         self.bias.num_states, self.bias.start, _ptr(which), _stream()),
-                           "pika_ctc_lm2_stream_reset")
+            v.call("stream_reset", *((_ptr(self._state),) + self._dims + self._starts + (_ptr(which), _stream())))
         if which is None:
             self._fed = 0
 
@@ -783,13 +796,8 @@ class CtcBeamStream(object):
             raise ValueError("%s has %d classes, the chunks before had %d" % (what, C, self.classes))
         if x.device != self.device:
             raise ValueError("the stream lives on %s, %s on %s" % (self.device, what, x.device))
-        lm = self.lm
-        if lm is not None and 0 <= lm.backoff_id - lm.label_offset < C:
-            raise ValueError("the LM's backoff_id %d is the label of class %d" % (lm.backoff_id,
-                                                                                 lm.backoff_id - lm.label_offset))
-        bias = self.bias
-        if bias is not None:
-            _check_second(bias, "bias", C, self.device, "the stream")
+        v = self._search
+        v.check_against(C, self.device, "the stream")
         if self._fed + Tc > self.max_frames:
             raise ValueError("%d frames were fed since the last full reset: %d more exceed max_frames = %d"
                              % (self._fed, Tc, self.max_frames))
@@ -797,21 +805,10 @@ class CtcBeamStream(object):
             with torch.cuda.device(self.device):
                 lengths = torch.full((B,), Tc, dtype=torch.int32, device=self.device)
         x, il, blank_lp, top_val, top_idx, lse, _ = _decode_rows(x, what, lengths, self.blank, self.candidates, logits)
-        lib = _lib.lib()
         with torch.cuda.device(self.device):
-            head = (_ptr(x), x.stride(0), x.stride(1), _ptr(lse), _ptr(blank_lp), _ptr(top_val), _ptr(top_idx), _ptr(il),
-                    B, Tc, C, self.blank, self.beam)
-            if lm is None:
-                _lib.check(lib.pika_ctc_stream_advance(*(head + (_ptr(self._state), self.max_frames, _stream()))),
-                           "pika_ctc_stream_advance")
-            elif bias is None:
-                _lib.check(lib.pika_ctc_lm_stream_advance(*(head + self._fst() + (
-                    lm.backoff_id, lm.label_offset, self.candidates, self.lm_weight, self.length_bonus,
-                    _ptr(self._state), self.max_frames, _stream()))), "pika_ctc_lm_stream_advance")
-            else:
-                _lib.check(lib.pika_ctc_lm2_stream_advance(*(head + _fst_args(lm, False) + _fst_args(bias, False) + (
-                    self.candidates, self.lm_weight, self.bias_weight, self.length_bonus, _ptr(self._state),
-                    self.max_frames, _stream()))), "pika_ctc_lm2_stream_advance")
+            v.call("stream_advance", *((_ptr(x), x.stride(0), x.stride(1), _ptr(lse), _ptr(blank_lp), _ptr(top_val),
+                                        _ptr(top_idx), _ptr(il), B, Tc, C, self.blank, self.beam) + self._fsts + v.weights + (
+                                            _ptr(self._state), self.max_frames, _stream())))
         self.classes = C
         self._fed += Tc
 
@@ -824,28 +821,13 @@ class CtcBeamStream(object):
     def results(self, nbest=1, use_final=True):
         nbest = int(nbest)
         _nbest_outputs(self.beam, nbest)
-        B, L, lm, dev = self.batch, self.max_frames, self.lm, self.device
-        lib = _lib.lib()
+        B, L, dev, v = self.batch, self.max_frames, self.device, self._search
         with torch.cuda.device(dev):
-            tokens = torch.empty((B, nbest, L), dtype=torch.int32, device=dev)
-            lengths = torch.empty((B, nbest), dtype=torch.int32, device=dev)
-            scores = torch.empty((B, nbest), dtype=torch.float32, device=dev)
-            if lm is None:
-                _lib.check(lib.pika_ctc_stream_results(_ptr(self._state), B, L, self.beam, nbest, L, _ptr(tokens),
-                                                       _ptr(lengths), _ptr(scores), _stream()),
-                           "pika_ctc_stream_results")
-                return tokens, lengths, scores
-            am_scores = torch.empty((B, nbest), dtype=torch.float32, device=dev)
-            if self.bias is not None:
-                _lib.check(lib.pika_ctc_lm2_stream_results(*(
-                    (_ptr(self._state), B, L, self.beam, self.candidates) + _fst_args(lm, False)
-                    + _fst_args(self.bias, False) + (self.lm_weight, self.bias_weight, int(bool(use_final)), nbest, L,
-                                                     _ptr(tokens), _ptr(lengths), _ptr(scores), _ptr(am_scores),
-                                                     _stream()))), "pika_ctc_lm2_stream_results")
-                return tokens, lengths, scores, am_scores
-            _lib.check(lib.pika_ctc_lm_stream_results(*((_ptr(self._state), B, L, self.beam, self.candidates)
-                                                        + self._fst() + (lm.backoff_id, lm.label_offset, self.lm_weight,
-                                                                         int(bool(use_final)), nbest, L, _ptr(tokens),
-                                                                         _ptr(lengths), _ptr(scores), _ptr(am_scores),
-                                                                         _stream()))), "pika_ctc_lm_stream_results")
-        return tokens, lengths, scores, am_scores
+            out = (torch.empty((B, nbest, L), dtype=torch.int32, device=dev),
+                   torch.empty((B, nbest), dtype=torch.int32, device=dev),
+                   torch.empty((B, nbest), dtype=torch.float32, device=dev))
+            if v.fused:
+                out += (torch.empty((B, nbest), dtype=torch.float32, device=dev),)
+            v.call("stream_results", *((_ptr(self._state),) + self._dims + self._fsts + v.results_weights + (
+                (int(bool(use_final)),) if v.fused else ()) + (nbest, L) + tuple(_ptr(o) for o in out) + (_stream(),)))
+        return out

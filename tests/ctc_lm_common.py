@@ -134,6 +134,14 @@ def make_lm(C, blank, seed, order=2, unreachable=(), arcs_per_state=4):
     return RefLm(NgramFst.from_arcs(n, arcs, finals, start=1), backoff_id, 1)
 
 
+def fst_args(lm, start=True):
+    """A device LM (the attributes of a `CtcNgramLm`) in the order the headers give an automaton's arguments: the five
+    arrays, num_states, num_arcs, start where the call has one, backoff_id, label_offset.  Written out here, not taken
+    from the package, so that the tests that call the C ABI check this order from outside."""
+    arrays = [getattr(lm, name).data_ptr() for name in ("offsets", "ilabel", "weight", "nextstate", "final")]
+    return tuple(arrays + [lm.num_states, lm.num_arcs] + ([lm.start] if start else []) + [lm.backoff_id, lm.label_offset])
+
+
 def search(lp, lm, beam, candidates, blank=0, lm_weight=0.5, length_bonus=0.0, use_final=True, dtype=np.float64):
     """-> (hyps, margin, reentries); hyps = [(label tuple, fused score, tot)] of the whole final beam, best first."""
     lp = np.asarray(lp).astype(dtype)

@@ -20,6 +20,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ctc_common as R  # noqa: E402
 import ctc_bias_common as Bc  # noqa: E402
+import ctc_lm_common as L  # noqa: E402
 from test_ctc_lm_gpu import unpack  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -180,10 +181,9 @@ def direct_one_fst(case, x, lm, nbest):
     scratch = torch.empty(lib.pika_ctc_lm_scratch_bytes(B, T, case.beam, K), dtype=torch.uint8, device=dev)
     assert lib.pika_ctc_lm_beam_search(
         x.data_ptr(), x.stride(0), x.stride(1), None, blank_lp.data_ptr(), top_val.data_ptr(), top_idx.data_ptr(),
-        il.data_ptr(), B, T, C, case.blank, case.beam, nbest, lm.offsets.data_ptr(), lm.ilabel.data_ptr(),
-        lm.weight.data_ptr(), lm.nextstate.data_ptr(), lm.final.data_ptr(), lm.num_states, lm.num_arcs, lm.start,
-        lm.backoff_id, lm.label_offset, K, case.lm_weight, case.length_bonus, int(case.use_final), tokens.data_ptr(),
-        lengths.data_ptr(), scores.data_ptr(), am.data_ptr(), scratch.data_ptr(), stream) == 0
+        il.data_ptr(), B, T, C, case.blank, case.beam, nbest, *L.fst_args(lm), K, case.lm_weight, case.length_bonus,
+        int(case.use_final), tokens.data_ptr(), lengths.data_ptr(), scores.data_ptr(), am.data_ptr(), scratch.data_ptr(),
+        stream) == 0
     return tokens, lengths, scores, am
 
 

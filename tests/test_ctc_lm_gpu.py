@@ -273,9 +273,7 @@ def test_adjacent_buffers_keep_their_guards(hip_device):
                                     p["top_idx"], None, stream) == 0
     assert lib.pika_ctc_lm_beam_search(
         x.data_ptr(), st, sb, None, p["blank_lp"], p["top_val"], p["top_idx"], il.data_ptr(), B, T, C, 0, beam, nbest,
-        lm.offsets.data_ptr(), lm.ilabel.data_ptr(), lm.weight.data_ptr(), lm.nextstate.data_ptr(), lm.final.data_ptr(),
-        lm.num_states, lm.num_arcs, lm.start, lm.backoff_id, lm.label_offset, K, 0.5, 0.25, 1, p["tokens"], p["lengths"],
-        p["scores"], p["am"], p["scratch"], stream) == 0
+        *L.fst_args(lm), K, 0.5, 0.25, 1, p["tokens"], p["lengths"], p["scores"], p["am"], p["scratch"], stream) == 0
     torch.cuda.synchronize()
     host = arena.cpu().numpy()
     keep = np.ones(total, dtype=bool)

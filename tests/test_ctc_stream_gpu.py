@@ -429,6 +429,57 @@ def test_overflow(hip_device):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# 9b. the bytes reset writes, for the three record types
+# ---------------------------------------------------------------------------------------------------------------
+def test_reset_writes_the_documented_bytes_and_nothing_else(hip_device):
+    """One reset kernel serves the plain, the LM and the two-FST record.  A blob filled with 0xA5, reset(which=[1, 0, 1]):
+    stream 1 keeps every byte; streams 0 and 2 have an empty table (all 0xFF), the header (1, 0, 0, 0, 0.0, 0.0) and
+    the empty prefix in slot 0, in the start state of each automaton.  Offsets from the record layouts of
+    include/pika_ctc_decode.h and include/pika_ctc_lm.h: the header in 32 bytes, then arrays of 64 -- i32 node, last,
+    parent node, len, f32 p_b, p_nb, tot (1824 bytes); f64 bonus, i32 LM state (2592); i32 second state (2848).  The
+    root's values are root_slot()'s of csrc/ctc_search_core.h and csrc/ctc_lm.hip."""
+    from pika_amd import ctc
+    from pika_amd.decoder.ngram_fst import NgramFst
+    dev = hip_device
+    B, max_frames, beam, K, slots = 3, 4, 2, 2, 64          # C = 3; 64 = max(64, 2 * max_frames * beam) table slots
+    arcs = [(0, 2, 1.0, 0), (1, 2, 1.0, 0), (1, 9, 0.5, 0)]
+    lm = ctc.CtcNgramLm(NgramFst.from_arcs(2, arcs, {0: 0.0}, start=1), 9, device=dev)
+    bias = ctc.CtcNgramLm(NgramFst.from_arcs(2, arcs, {0: 0.5}, start=1), 9, device=dev)
+    assert (lm.num_states, lm.start, bias.num_states, bias.start) == (2, 1, 2, 1)
+    i32, f32, f64 = np.dtype("<i4"), np.dtype("<f4"), np.dtype("<f8")
+    header = [(0, i32, 1), (4, i32, 0), (8, i32, 0), (12, i32, 0), (16, f64, 0.0), (24, f64, 0.0)]
+    root = [(32, i32, 0x7ffffffe), (288, i32, -1), (544, i32, 0x7ffffffd), (800, i32, 0), (1056, f32, 0.0),
+            (1312, f32, np.float32(-1.0e30)), (1568, f32, 0.0)]
+    lm_root = root + [(1824, f64, 0.0), (2336, i32, lm.start)]
+    for name, given, rec, fields in (("plain", None, 1824, header + root), ("LM", lm, 2592, header + lm_root),
+                                     ("LM + bias", ctc.CtcBiasedLm(lm, bias), 2848,
+                                      header + lm_root + [(2592, i32, bias.start)])):
+        stream = ctc.CtcBeamStream(B, max_frames, beam=beam, lm=given, candidates=K, device=dev)
+        assert stream._state.numel() == B * (8 * slots + rec), name
+        stream._state.fill_(0xA5)
+        stream.reset(which=[1, 0, 1])
+        blob = stream._state.cpu().numpy()
+        tables = blob[:B * 8 * slots].reshape(B, 8 * slots)
+        recs = blob[B * 8 * slots:].reshape(B, rec)
+        assert (tables[1] == 0xA5).all() and (recs[1] == 0xA5).all(), (name, "a stream that was not selected changed")
+        written = np.zeros(rec, dtype=bool)
+        for b in (0, 2):
+            assert (tables[b] == 0xFF).all(), (name, b)
+            for off, dtype, want in fields:
+                got = recs[b, off:off + dtype.itemsize].copy().view(dtype)[0]
+                assert got == want and type(got) is dtype.type, (name, b, off, got, want)
+                written[off:off + dtype.itemsize] = True
+            assert (recs[b][~written] == 0xA5).all(), (name, b, "reset wrote beyond the header and slot 0")
+        assert stream.frames.tolist()[::2] == [0, 0] and stream.overflowed.tolist()[::2] == [False, False]
+        stream.reset()
+        blob = stream._state.cpu().numpy()
+        tables = blob[:B * 8 * slots].reshape(B, 8 * slots)
+        recs = blob[B * 8 * slots:].reshape(B, rec)
+        assert (tables[1] == tables[0]).all() and (recs[1][written] == recs[0][written]).all(), name
+        assert (recs[1][~written] == 0xA5).all(), name
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # 10. two runs are bit-identical
 # ---------------------------------------------------------------------------------------------------------------
 def test_two_runs_are_bit_identical(hip_device):
@@ -470,8 +521,7 @@ def test_adjacent_buffers_keep_their_guards(hip_device):
     arena = torch.full((total,), 0xA5, dtype=torch.uint8, device=dev)
     p = {name: arena.data_ptr() + o for name, o in offs.items()}
     stream = torch.cuda.current_stream().cuda_stream
-    fst = (lm.offsets.data_ptr(), lm.ilabel.data_ptr(), lm.weight.data_ptr(), lm.nextstate.data_ptr(),
-           lm.final.data_ptr(), lm.num_states, lm.num_arcs)
+    fst = L.fst_args(lm, start=False)
     assert lib.pika_ctc_stream_reset(p["state"], B, T, beam, which.data_ptr(), stream) == 0
     assert lib.pika_ctc_lm_stream_reset(p["lm_state"], B, T, beam, K, lm.num_states, lm.start, None, stream) == 0
     for i in range(2):
@@ -484,13 +534,12 @@ def test_adjacent_buffers_keep_their_guards(hip_device):
         assert lib.pika_ctc_decode_rows(xc.data_ptr(), st, sb, lens[i].data_ptr(), B, Tc, C, 0, K, 0, p["blank_lp"],
                                         p["lm_val"], p["lm_idx"], None, stream) == 0
         assert lib.pika_ctc_lm_stream_advance(xc.data_ptr(), st, sb, None, p["blank_lp"], p["lm_val"], p["lm_idx"],
-                                              lens[i].data_ptr(), B, Tc, C, 0, beam, *fst, lm.backoff_id,
-                                              lm.label_offset, K, 0.5, 0.25, p["lm_state"], T, stream) == 0
+                                              lens[i].data_ptr(), B, Tc, C, 0, beam, *fst, K, 0.5, 0.25,
+                                              p["lm_state"], T, stream) == 0
     assert lib.pika_ctc_stream_results(p["state"], B, T, beam, nbest, T, p["tokens"], p["lengths"], p["scores"],
                                        stream) == 0
-    assert lib.pika_ctc_lm_stream_results(p["lm_state"], B, T, beam, K, *fst, lm.backoff_id, lm.label_offset, 0.5, 1,
-                                          nbest, T, p["lm_tokens"], p["lm_lengths"], p["lm_scores"], p["lm_am"],
-                                          stream) == 0
+    assert lib.pika_ctc_lm_stream_results(p["lm_state"], B, T, beam, K, *fst, 0.5, 1, nbest, T, p["lm_tokens"],
+                                          p["lm_lengths"], p["lm_scores"], p["lm_am"], stream) == 0
     torch.cuda.synchronize()
     host = arena.cpu().numpy()
     keep = np.ones(total, dtype=bool)

@@ -3,7 +3,7 @@
     python tools/ctc_bias_time.py [--runs 30] [--warmup 5] [--parent-lib PATH] > profiles/ctc_bias_time.txt
 
 Shapes: (T,B,C) = (240,32,5000) and (1000,32,5000), beam 16, candidates 32.  The LM is the seeded bigram LM of
-tools/ctc_lm_time.py (about 110 000 arcs); the hotword list holds 100 seeded phrases of 2-6 tokens, boost 1.5.  Timed
+tools/ctc_timing.py (about 110 000 arcs); the hotword list holds 100 seeded phrases of 2-6 tokens, boost 1.5.  Timed
 alone through the C ABI on the output of the row pass (buffers allocated once): the one-FST search, the two-FST search,
 and the two-FST stream in chunks of 8 frames (row pass of each chunk included: a stream cannot have it done ahead).
 `--parent-lib` names a libpika_amd.so built from the parent commit: its one-FST search then runs in the same loop, on
@@ -13,19 +13,14 @@ current stream; median, minimum and maximum are printed.  The one-FST and two-FS
 is timed: with bias_weight 0 they must be bit-equal.  Nothing here is asserted anywhere else.  Needs a GPU.
 """
 import argparse
-import ctypes
-import os
 import statistics
 import sys
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import pika_amd  # noqa: F401,E402  (first: places the HIP runtime flag before torch initialises it)
-from pika_amd import _lib, ctc  # noqa: E402
-from ctc_lm_time import bigram_lm  # noqa: E402
+from ctc_timing import bigram_lm, fst_args as fst, load_parent, measure  # (first: it puts the repository on sys.path)
+from pika_amd import _lib, ctc
 
 
 def hotword_list(C, blank, n, seed):
@@ -51,11 +46,7 @@ def main():
         sys.exit("ctc_bias_time.py: at least 20 runs")
     dev = torch.device("cuda")
     lib = _lib.lib()
-    parent = None
-    if args.parent_lib:
-        parent = ctypes.CDLL(args.parent_lib)
-        parent.pika_ctc_lm_beam_search.restype, parent.pika_ctc_lm_beam_search.argtypes = \
-            _lib.SIGNATURES["pika_ctc_lm_beam_search"]
+    parent = load_parent(args.parent_lib) if args.parent_lib else None
     print("device: %s   runs %d, warm-up %d; times in ms: median [min, max]" % (
         torch.cuda.get_device_name(0), args.runs, args.warmup))
     beam, C, K = 16, 5000, 32
@@ -63,11 +54,6 @@ def main():
     hot = ctc.CtcHotwords(hotword_list(C, 0, 100, 13), C, boost=1.5, device=dev)
     print("LM: %d states, %d arcs; hotwords: 100 phrases of 2-6 tokens, %d states, %d arcs" % (
         lm.num_states, lm.num_arcs, hot.num_states, hot.num_arcs))
-
-    def fst(m, start=True):
-        return (m.offsets.data_ptr(), m.ilabel.data_ptr(), m.weight.data_ptr(), m.nextstate.data_ptr(),
-                m.final.data_ptr(), m.num_states, m.num_arcs) + ((m.start,) if start else ()) + (m.backoff_id,
-                                                                                                 m.label_offset)
     for T, B in ((240, 32), (1000, 32)):
         g = torch.Generator().manual_seed(T)
         lp = torch.log_softmax(torch.randn(T, B, C, generator=g).to(dev), -1)
@@ -125,21 +111,7 @@ def main():
         if parent is not None:
             variants.append(("one-FST search, parent's library", one(parent)))
         variants.append(("two-FST stream, chunks of 8 (rows + advance)", streamed))
-        times = {name: [] for name, _ in variants}
-
-        def once(fn):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            return e0.elapsed_time(e1)
-        for _ in range(args.warmup):
-            for name, fn in variants:
-                once(fn)
-        for _ in range(args.runs):
-            for name, fn in variants:           # alternating
-                times[name].append(once(fn))
+        times = measure(variants, args.warmup, args.runs)
         med = {name: statistics.median(times[name]) for name, _ in variants}
         for name, _ in variants:
             t = times[name]

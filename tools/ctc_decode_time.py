@@ -16,7 +16,7 @@ import sys
 
 import torch
 
-import pika_amd  # noqa: F401  (first: places the HIP runtime flag before torch initialises it)
+from ctc_timing import measure  # (first: it puts the repository on sys.path)
 from pika_amd import _lib, ctc
 
 HBM_PEAK = 8.0e12   # bytes / s
@@ -80,22 +80,7 @@ def main():
                                        row_variants[4], row_variants[3], ("search, beam 16", search),
                                        ("ctc_greedy_decode (whole call)", lambda: ctc.ctc_greedy_decode(lp, il)),
                                        ("ctc_beam_search (whole call)", lambda: ctc.ctc_beam_search(lp, il, beam=beam))]
-        times = {name: [] for name, _ in variants}
-
-        def once(fn):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            return e0.elapsed_time(e1)
-
-        for _ in range(args.warmup):
-            for name, fn in variants:
-                once(fn)
-        for _ in range(args.runs):
-            for name, fn in variants:           # alternating
-                times[name].append(once(fn))
+        times = measure(variants, args.warmup, args.runs)
         print("\nT = %d, B = %d, C = %d, beam = %d" % (T, B, C, beam))
         nbytes = 4.0 * T * B * C
         for name, _ in variants:

@@ -15,50 +15,13 @@ alike, each call is bracketed by two events on the current stream, and median, m
 Nothing here is asserted anywhere.  Needs a GPU.
 """
 import argparse
-import os
 import statistics
 import sys
 
-import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import pika_amd  # noqa: F401  (first: places the HIP runtime flag before torch initialises it)
+from ctc_timing import bigram_lm, fst_args, measure, unigram_lm  # (first: it puts the repository on sys.path)
 from pika_amd import _lib, ctc
-from pika_amd.decoder.ngram_fst import NgramFst
-
-
-def bigram_lm(C, blank, per_state, seed):
-    """(fst, backoff_id): state 0 the unigram state, state 1 the start state, state 2 + i the bigram state of the i-th
-    non-blank class."""
-    rng = np.random.RandomState(seed)
-    classes = np.array([c for c in range(C) if c != blank])
-    n, backoff_id = len(classes), C + 1
-    state_of = np.zeros(C, dtype=np.int64)
-    state_of[classes] = 2 + np.arange(n)
-    offsets, ilabel, nextstate = [0], [], []
-
-    def push(labels, targets):
-        ilabel.append(labels)
-        nextstate.append(targets)
-        offsets.append(offsets[-1] + len(labels))
-    push(classes + 1, state_of[classes])
-    for _ in range(n + 1):                                  # the start state, then the bigram states
-        own = np.sort(rng.choice(classes, size=per_state, replace=False))
-        push(np.concatenate([own + 1, [backoff_id]]), np.concatenate([state_of[own], [0]]))
-    ilabel, nextstate = np.concatenate(ilabel), np.concatenate(nextstate)
-    weight = rng.uniform(0.3, 5.0, size=len(ilabel)).astype(np.float32)
-    final = np.full(n + 2, np.inf, dtype=np.float32)
-    final[0] = 1.0
-    return NgramFst(offsets, ilabel, weight, nextstate, final, start=1), backoff_id
-
-
-def unigram_lm(C, blank, seed):
-    rng = np.random.RandomState(seed)
-    classes = np.array([c for c in range(C) if c != blank])
-    weight = rng.uniform(0.3, 5.0, size=len(classes)).astype(np.float32)
-    return NgramFst([0, len(classes)], classes + 1, weight, np.zeros(len(classes), np.int32),
-                    np.array([1.0], np.float32), start=0), C + 1
 
 
 def main():
@@ -111,9 +74,7 @@ def main():
             def run():
                 _lib.check(lib.pika_ctc_lm_beam_search(
                     lp.data_ptr(), lp.stride(0), lp.stride(1), None, blank_lp.data_ptr(), rows[K][0].data_ptr(),
-                    rows[K][1].data_ptr(), il.data_ptr(), B, T, C, 0, beam, 1, lm.offsets.data_ptr(),
-                    lm.ilabel.data_ptr(), lm.weight.data_ptr(), lm.nextstate.data_ptr(), lm.final.data_ptr(),
-                    lm.num_states, lm.num_arcs, lm.start, lm.backoff_id, lm.label_offset, K, 0.5, 0.0, 1,
+                    rows[K][1].data_ptr(), il.data_ptr(), B, T, C, 0, beam, 1, *fst_args(lm), K, 0.5, 0.0, 1,
                     tokens.data_ptr(), lengths.data_ptr(), scores.data_ptr(), am.data_ptr(), scratch.data_ptr(),
                     stream()), "pika_ctc_lm_beam_search")
             return run
@@ -126,22 +87,7 @@ def main():
                     ("ctc_beam_search (whole call)", lambda: ctc.ctc_beam_search(lp, il, beam=beam)),
                     ("ctc_beam_search_lm (whole call)", lambda: ctc.ctc_beam_search_lm(lp, il, lm2, beam=beam,
                                                                                       candidates=32))]
-        times = {name: [] for name, _ in variants}
-
-        def once(fn):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            return e0.elapsed_time(e1)
-
-        for _ in range(args.warmup):
-            for name, fn in variants:
-                once(fn)
-        for _ in range(args.runs):
-            for name, fn in variants:           # alternating
-                times[name].append(once(fn))
+        times = measure(variants, args.warmup, args.runs)
         print("\nT = %d, B = %d, C = %d, beam = %d" % (T, B, C, beam))
         med = {name: statistics.median(times[name]) for name, _ in variants}
         for name, _ in variants:

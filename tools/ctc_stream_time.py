@@ -2,7 +2,7 @@
 
     python tools/ctc_stream_time.py [--runs 30] [--warmup 5] [--parent-lib PATH] > profiles/ctc_stream_time.txt
 
-Shape: (T,B,C) = (240,32,5000), beam 16, plain and LM-fused (candidates 32, the seeded bigram LM of tools/ctc_lm_time.py).
+Shape: (T,B,C) = (240,32,5000), beam 16, plain and LM-fused (candidates 32, the seeded bigram LM of tools/ctc_timing.py).
 The utterance is fed to a `CtcBeamStream` in chunks of 8, 16 and 40 frames -- per chunk one row pass and one advance,
 whole Python calls; the reset happens before the timed bracket and is timed on its own -- and the total is printed with
 the per-chunk overhead: (total - the one-shot whole call) / chunks.  The same feed with one `results(nbest=1)` per chunk
@@ -18,39 +18,13 @@ two events on the current stream, and median, minimum and maximum are printed.  
 Needs a GPU.
 """
 import argparse
-import contextlib
-import ctypes
-import os
 import statistics
 import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import pika_amd  # noqa: F401  (first: places the HIP runtime flag before torch initialises it)
+from ctc_timing import bigram_lm, library, load_parent, measure  # (first: it puts the repository on sys.path)
 from pika_amd import _lib, ctc
-from ctc_lm_time import bigram_lm  # noqa: E402  (tools/ is the script's directory)
-
-
-def load_parent(path):
-    """The parent commit's library with the signatures it shares with this tree."""
-    handle = ctypes.CDLL(path)
-    for name, (res, args) in _lib.SIGNATURES.items():
-        fn = getattr(handle, name, None)
-        if fn is not None:
-            fn.restype, fn.argtypes = res, args
-    return handle
-
-
-@contextlib.contextmanager
-def library(handle):
-    """The Python surface on another library for the length of a call."""
-    mine = _lib.lib()
-    _lib._lib = handle
-    try:
-        yield
-    finally:
-        _lib._lib = mine
 
 
 def main():
@@ -72,27 +46,6 @@ def main():
     beam, C, cand, B = 16, 5000, 32, 32
     fst, backoff_id = bigram_lm(C, 0, 20, 11)
     lm = ctc.CtcNgramLm(fst, backoff_id, device=dev)
-
-    def once(fn):
-        if isinstance(fn, tuple):               # (what happens before the bracket, what is timed)
-            fn[0]()
-            fn = fn[1]
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-
-    def measure(variants):
-        times = {name: [] for name, _ in variants}
-        for _ in range(args.warmup):
-            for _, fn in variants:
-                once(fn)
-        for _ in range(args.runs):
-            for name, fn in variants:           # alternating
-                times[name].append(once(fn))
-        return times
 
     for T in (240, 1000):
         g = torch.Generator().manual_seed(T)
@@ -135,7 +88,7 @@ def main():
                         name = "stream %s, chunks of %d%s" % (kind, k, ", results(nbest=1) per chunk" if look else "")
                         chunked[name] = (kind, k, look)
                         variants.append((name, feed(stream, k, look)))
-        times = measure(variants)
+        times = measure(variants, args.warmup, args.runs)
         print("\nT = %d, B = %d, C = %d, beam = %d, candidates = %d" % (T, B, C, beam, cand))
         med = {name: statistics.median(t) for name, t in times.items()}
         base = {"plain": med["ctc_beam_search (whole call), parent" if parent else "ctc_beam_search (whole call), this tree"],
