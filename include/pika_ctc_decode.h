@@ -88,13 +88,16 @@ int pika_ctc_beam_search(const float *x, long long stride_t, long long stride_b,
  * the one-shot's with T := max_frames.  Layout, with N = the smallest power of two >= max(64, 2 max_frames beam):
  *   [0, 8 B N)                 the B tables of pika_ctc_beam_scratch_bytes(B, max_frames, beam)
  *   then B records of PIKA_CTC_STREAM_RECORD_BYTES, record b of stream b:
- *     i32 n (slots in the beam) | i32 frames (consumed so far) | i32 overflow | i32 pad | f64 off | f64 (unused here) |
+ *     i32 n (slots in the beam) | i32 frames (held: consumed, less what a commit gave back) | i32 overflow |
+ *     i32 retired (frames given back by commits; 0 without one) | f64 off | f64 (unused here) |
  *     the beam, seven arrays of 64 (slots [0,n) hold values): i32 node, last, parent node, len; f32 p_b, p_nb, tot
- * `frames` and `overflow` of stream b may be read at PIKA_CTC_STREAM_FRAMES_OFFSET / _OVERFLOW_OFFSET of its record;
- * everything else is the library's.  A blob must be reset before its first advance. */
+ * `frames`, `overflow` and `retired` of stream b may be read at PIKA_CTC_STREAM_FRAMES_OFFSET / _OVERFLOW_OFFSET /
+ * _RETIRED_OFFSET of its record; everything else is the library's.  frames + retired is the number of frames the stream
+ * has consumed, max_frames - frames the number it can still take.  A blob must be reset before its first advance. */
 #define PIKA_CTC_STREAM_RECORD_BYTES 1824
 #define PIKA_CTC_STREAM_FRAMES_OFFSET 4
 #define PIKA_CTC_STREAM_OVERFLOW_OFFSET 8
+#define PIKA_CTC_STREAM_RETIRED_OFFSET 12
 
 /* Bytes of the blob: pika_ctc_beam_scratch_bytes(B, max_frames, beam) + B * PIKA_CTC_STREAM_RECORD_BYTES; 0 for
  * dimensions the calls refuse. */
@@ -119,6 +122,30 @@ int pika_ctc_stream_advance(const float *x, long long stride_t, long long stride
  * than L (possible only for L < frames) keeps its length and its first L labels.  lengths, scores (B,nbest). */
 int pika_ctc_stream_results(const void *state, int B, int max_frames, int beam, int nbest, int L, int *tokens,
                             int *lengths, float *scores, void *stream);
+
+/* ---- Commit: emit the stable prefix, give capacity back --------------------------------------------------------------
+ * The labels on the path from the root to the common ancestor of the beam's slots are shared by every hypothesis the
+ * stream can still produce: they are final.  A commit writes them out, makes that ancestor the root (every slot's length
+ * drops by their number d) and rebuilds the table with the nodes between the new root and the slots only.  `frames` is
+ * then lowered to the smallest value >= max(ceil(live keys / beam), longest remaining prefix) that is congruent to the
+ * old one modulo 8 (the renormalisation keeps its phase), and the difference is added to `retired`.  The beam's order,
+ * scores, offsets and automaton states are untouched: the frames that follow give bit for bit what they would have
+ * given without the commit, pika_ctc_stream_results returns the uncommitted tails (lengths relative to the commit,
+ * scores absolute), and the stream may consume more than max_frames frames as long as commits keep `frames` below it.
+ *   which     i32 (B,) or NULL, as in the reset: a stream with which[b] == 0 is not touched and gets lengths[b] = 0
+ *   max_tail  < 0: the exact commit above.  m >= 0: FORCED -- if the best slot (slot 0 of the stored beam) would keep
+ *             more than m uncommitted labels, the new root is its ancestor m labels up, and the slots that do not descend
+ *             from it are dropped; the others keep their order.  This changes the search (finalisation by best path).
+ *   tokens    i32 (B,L)  the labels that became final in this call, -1 beyond lengths[b]; L >= 1 is the width the caller
+ *             allocated: labels at or beyond L are not written (d <= frames <= max_frames)
+ *   lengths   i32 (B,)   d
+ *   scratch   pika_ctc_stream_commit_scratch_bytes(B, max_frames, beam) bytes (4 B max_frames beam: per slot the labels
+ *             of its path, from which the table is rebuilt parents first); 0 for dimensions the calls refuse
+ * PIKA_EINVAL for a NULL state / tokens / lengths / scratch and for L <= 0; the dimension limits of the reset. */
+size_t pika_ctc_stream_commit_scratch_bytes(int B, int max_frames, int beam);
+
+int pika_ctc_stream_commit(void *state, int B, int max_frames, int beam, const int *which, int max_tail, int L,
+                           int *tokens, int *lengths, void *scratch, void *stream);
 
 #ifdef __cplusplus
 }

@@ -110,6 +110,13 @@ int pika_ctc_lm_stream_results(const void *state, int B, int max_frames, int bea
                                int backoff_id, int label_offset, float lm_weight, int use_final, int nbest, int L,
                                int *tokens, int *lengths, float *scores, float *am_scores, void *stream);
 
+/* pika_ctc_stream_commit (pika_ctc_decode.h) on the LM record: the LM state and the bonus of a slot travel with it, and
+ * the length bonus lives in `bonus`, not in the length, so no score moves.  Scratch as the plain commit's. */
+size_t pika_ctc_lm_stream_commit_scratch_bytes(int B, int max_frames, int beam, int candidates);
+
+int pika_ctc_lm_stream_commit(void *state, int B, int max_frames, int beam, int candidates, const int *which,
+                              int max_tail, int L, int *tokens, int *lengths, void *scratch, void *stream);
+
 /* ---- A second automaton beside the LM: contextual biasing (hotwords), or a second, domain LM ---------------------------
  * The pika_ctc_lm2_* calls are their pika_ctc_lm_* counterparts with a second FST of the same layout (fst2_*, its own
  * backoff_id2 / label_offset2) and its weight:
@@ -170,6 +177,11 @@ int pika_ctc_lm2_stream_results(const void *state, int B, int max_frames, int be
                                 int num_states2, int num_arcs2, int backoff_id2, int label_offset2, float lm_weight,
                                 float bias_weight, int use_final, int nbest, int L, int *tokens, int *lengths,
                                 float *scores, float *am_scores, void *stream);
+
+size_t pika_ctc_lm2_stream_commit_scratch_bytes(int B, int max_frames, int beam, int candidates);
+
+int pika_ctc_lm2_stream_commit(void *state, int B, int max_frames, int beam, int candidates, const int *which,
+                               int max_tail, int L, int *tokens, int *lengths, void *scratch, void *stream);
 
 #ifdef __cplusplus
 }

@@ -54,6 +54,8 @@ SIGNATURES = {
     "pika_ctc_stream_reset": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "pika_ctc_stream_advance": (_i, [_vp, _ll, _ll] + [_vp] * 5 + [_i] * 5 + [_vp, _i, _vp]),
     "pika_ctc_stream_results": (_i, [_vp] + [_i] * 5 + [_vp] * 4),
+    "pika_ctc_stream_commit_scratch_bytes": (_sz, [_i, _i, _i]),
+    "pika_ctc_stream_commit": (_i, [_vp] + [_i] * 3 + [_vp, _i, _i] + [_vp] * 4),
     # include/pika_ctc_lm.h
     "pika_ctc_lm_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "pika_ctc_lm_beam_search": (_i, [_vp, _ll, _ll] + [_vp] * 5 + [_i] * 6 + [_vp] * 5 + [_i] * 6 + [_f, _f, _i]
@@ -63,6 +65,8 @@ SIGNATURES = {
     "pika_ctc_lm_stream_advance": (_i, [_vp, _ll, _ll] + [_vp] * 5 + [_i] * 5 + [_vp] * 5 + [_i] * 5 + [_f, _f]
                                    + [_vp, _i, _vp]),
     "pika_ctc_lm_stream_results": (_i, [_vp] + [_i] * 4 + [_vp] * 5 + [_i] * 4 + [_f] + [_i] * 3 + [_vp] * 5),
+    "pika_ctc_lm_stream_commit_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "pika_ctc_lm_stream_commit": (_i, [_vp] + [_i] * 4 + [_vp, _i, _i] + [_vp] * 4),
     "pika_ctc_lm2_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "pika_ctc_lm2_beam_search": (_i, [_vp, _ll, _ll] + [_vp] * 5 + [_i] * 6 + [_vp] * 5 + [_i] * 5 + [_vp] * 5
                                  + [_i] * 6 + [_f, _f, _f, _i] + [_vp] * 6),
@@ -72,6 +76,8 @@ SIGNATURES = {
                                     + [_i] * 5 + [_f, _f, _f] + [_vp, _i, _vp]),
     "pika_ctc_lm2_stream_results": (_i, [_vp] + [_i] * 4 + [_vp] * 5 + [_i] * 4 + [_vp] * 5 + [_i] * 4 + [_f, _f]
                                     + [_i] * 3 + [_vp] * 5),
+    "pika_ctc_lm2_stream_commit_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "pika_ctc_lm2_stream_commit": (_i, [_vp] + [_i] * 4 + [_vp, _i, _i] + [_vp] * 4),
     # include/pika_bmuf.h
     "pika_bmuf_delta": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "pika_bmuf_nan_flag": (_i, [_vp, _sz, _vp, _vp]),

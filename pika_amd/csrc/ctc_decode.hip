@@ -593,4 +593,14 @@ int pika_ctc_stream_results(const void *state, int B, int max_frames, int beam, 
     return (int)hipGetLastError();
 }
 
+size_t pika_ctc_stream_commit_scratch_bytes(int B, int max_frames, int beam) {
+    if (check_search_dims(B, max_frames, beam, 1)) return 0;
+    return commit_scratch_bytes(B, max_frames, beam);
+}
+
+int pika_ctc_stream_commit(void *state, int B, int max_frames, int beam, const int *which, int max_tail, int L,
+                           int *tokens, int *lengths, void *scratch, void *stream) {
+    return commit_streams<Beam>(state, B, max_frames, beam, 1, which, max_tail, L, tokens, lengths, scratch, stream);
+}
+
 }  // extern "C"

@@ -139,6 +139,12 @@ __device__ __forceinline__ void copy_slot(LmBeam &D, const LmBeam &G, int r) {
     D.bonus[r] = G.bonus[r];
 }
 
+__device__ __forceinline__ void move_slot(LmBeam &D, int j, const LmBeam &G, int r) {
+    move_slot(static_cast<Beam &>(D), j, static_cast<const Beam &>(G), r);
+    D.lmst[j] = G.lmst[r];
+    D.bonus[j] = G.bonus[r];
+}
+
 // the beam of the search with a second automaton; bonus holds both terms
 struct Lm2Beam : LmBeam {
     int st2[MAX_BEAM];  // its state in the second FST
@@ -152,6 +158,11 @@ __device__ __forceinline__ void root_slot(Lm2Beam &A, int start, int start2) {
 __device__ __forceinline__ void copy_slot(Lm2Beam &D, const Lm2Beam &G, int r) {
     copy_slot(static_cast<LmBeam &>(D), static_cast<const LmBeam &>(G), r);
     D.st2[r] = G.st2[r];
+}
+
+__device__ __forceinline__ void move_slot(Lm2Beam &D, int j, const Lm2Beam &G, int r) {
+    move_slot(static_cast<LmBeam &>(D), j, static_cast<const LmBeam &>(G), r);
+    D.st2[j] = G.st2[r];
 }
 
 // the second automaton of a launch: a kernel takes none or one as its last argument
@@ -616,6 +627,17 @@ int pika_ctc_lm_stream_results(const void *state, int B, int max_frames, int bea
                           scores, am_scores, stream);
 }
 
+size_t pika_ctc_lm_stream_commit_scratch_bytes(int B, int max_frames, int beam, int candidates) {
+    if (check_search_dims(B, max_frames, beam, candidates)) return 0;
+    return commit_scratch_bytes(B, max_frames, beam);
+}
+
+int pika_ctc_lm_stream_commit(void *state, int B, int max_frames, int beam, int candidates, const int *which,
+                              int max_tail, int L, int *tokens, int *lengths, void *scratch, void *stream) {
+    return commit_streams<LmBeam>(state, B, max_frames, beam, candidates, which, max_tail, L, tokens, lengths, scratch,
+                                  stream);
+}
+
 // ---- the same with a second automaton ----------------------------------------------------------------------------
 
 size_t pika_ctc_lm2_scratch_bytes(int B, int T, int beam, int candidates) {
@@ -687,6 +709,16 @@ int pika_ctc_lm2_stream_results(const void *state, int B, int max_frames, int be
     if (int rc = check_fst(g.f, g.start)) return rc;
     return stream_results(state, B, max_frames, beam, candidates, f, lm_weight, use_final, nbest, L, tokens, lengths,
                           scores, am_scores, stream, g);
+}
+
+size_t pika_ctc_lm2_stream_commit_scratch_bytes(int B, int max_frames, int beam, int candidates) {
+    return pika_ctc_lm_stream_commit_scratch_bytes(B, max_frames, beam, candidates);
+}
+
+int pika_ctc_lm2_stream_commit(void *state, int B, int max_frames, int beam, int candidates, const int *which,
+                               int max_tail, int L, int *tokens, int *lengths, void *scratch, void *stream) {
+    return commit_streams<Lm2Beam>(state, B, max_frames, beam, candidates, which, max_tail, L, tokens, lengths, scratch,
+                                   stream);
 }
 
 }  // extern "C"

@@ -42,6 +42,12 @@ __device__ __forceinline__ void copy_slot(Beam &D, const Beam &G, int r) {
     D.pb[r] = G.pb[r]; D.pnb[r] = G.pnb[r]; D.tot[r] = G.tot[r];
 }
 
+// slot r of G into slot j of D (the commit closes the gaps that dropped slots leave)
+__device__ __forceinline__ void move_slot(Beam &D, int j, const Beam &G, int r) {
+    D.node[j] = G.node[r]; D.last[j] = G.last[r]; D.pnode[j] = G.pnode[r]; D.len[j] = G.len[r];
+    D.pb[j] = G.pb[r]; D.pnb[j] = G.pnb[r]; D.tot[j] = G.tot[r];
+}
+
 __device__ inline unsigned long long trie_key(int parent, int token) {
     return ((unsigned long long)(unsigned)parent << 32) | (unsigned)token;
 }
@@ -175,9 +181,12 @@ struct StreamHdr {
     int n;         // slots of the beam
     int frames;    // frames consumed: the phase of the renormalisation, and the table's fill
     int overflow;  // frames were dropped because max_frames was reached
-    int pad;
+    int retired;   // frames a commit has given back: frames + retired is what the stream consumed
     double off, boff;  // what was moved out of tot (and, with an LM, out of bonus)
 };
+
+static_assert(offsetof(StreamHdr, retired) == PIKA_CTC_STREAM_RETIRED_OFFSET && sizeof(StreamHdr) == 32,
+              "the header the C ABI documents");
 
 template <class BeamT>
 struct StreamRec {
@@ -207,9 +216,136 @@ __global__ __launch_bounds__(256) void ctc_stream_reset_kernel(unsigned long lon
     for (size_t i = (size_t)blockIdx.y * 256 + threadIdx.x; i < slots; i += (size_t)gridDim.y * 256) table[i] = EMPTY;
     if (blockIdx.y == 0 && threadIdx.x == 0) {
         StreamRec<BeamT> &R = recs[b];
-        R.h.n = 1; R.h.frames = 0; R.h.overflow = 0; R.h.pad = 0;
+        R.h.n = 1; R.h.frames = 0; R.h.overflow = 0; R.h.retired = 0;
         R.h.off = 0.0; R.h.boff = 0.0;
         root_slot(R.beam, start...);
+    }
+}
+
+// Commit, one kernel for every record type.  grid = B, block = 256; streams with which[b] == 0 keep their state and get
+// length 0.  The prefix that every slot of the beam shares -- the path from the root to the slots' common ancestor -- can
+// never change again: it goes to tokens[b], the trie is re-rooted at the ancestor, and the table is rebuilt with the
+// nodes on the paths from the new root to the slots and nothing else.  max_tail >= 0: when slot 0 would keep more than
+// max_tail labels, the new root is slot 0's ancestor max_tail labels up, and the slots that do not descend from it are
+// dropped (the others keep their order).  A node's identity is the table slot of its (parent, token) key, so a rebuilt
+// table needs the parents first: wave 0's lane r walks slot r up to the new root and leaves the labels it meets in
+// paths[b][r][0, tail), root side first; the table is cleared; the lane replays its labels through trie_node from ROOT.
+// Lanes that share a prefix find each other's keys.  Then `frames` is lowered to what the live keys and the longest
+// tail need, in the same phase of the renormalisation, and the difference goes to `retired`.  Everything read from the
+// record bounds loops and stores through load_hdr and the clamp of len, and every walk by a step count: a blob that was
+// never reset ends with some beam, inside its own memory.
+template <class BeamT>
+__global__ __launch_bounds__(256) void ctc_stream_commit_kernel(unsigned long long *tables, unsigned mask,
+                                                                StreamRec<BeamT> *recs, const int *__restrict__ which,
+                                                                int beam, int max_frames, int max_tail, int L,
+                                                                int *__restrict__ tokens, int *__restrict__ lengths,
+                                                                int *__restrict__ paths) {
+    __shared__ BeamT S;
+    __shared__ int s_depth, s_live, s_tail, s_n;
+    const int b = blockIdx.x, tid = threadIdx.x, r = tid;
+    int *out = tokens + (size_t)b * L;
+    if (which && which[b] == 0) {  // workgroup-uniform
+        for (int p = tid; p < L; p += 256) out[p] = -1;
+        if (tid == 0) lengths[b] = 0;
+        return;
+    }
+    unsigned long long *table = tables + (size_t)b * ((size_t)mask + 1);
+    StreamRec<BeamT> &R = recs[b];
+    const StreamHdr h = load_hdr(R.h, beam, max_frames);
+    const int n = h.n;
+    // one step towards the root; whatever a node holds, the load stays inside the table
+    auto up = [&](int node) __attribute__((always_inline)) {
+        return node == ROOT ? ROOT : (int)(unsigned)(trie_load(table, mask, node) >> 32);
+    };
+    int tail = -1, j = 0;  // wave 0, lane r: the labels slot r keeps (-1: the slot is dropped), its slot afterwards
+    if (tid < 64) {        // wave 0: lane r owns beam slot r
+        const bool act = r < n;
+        if (act) copy_slot(S, R.beam, r);
+        const int node = act ? R.beam.node[r] : ROOT;
+        const int len = act ? clampi(R.beam.len[r], 0, h.frames) : 0;
+        // the common ancestor: every slot up to the depth of the shallowest, then all of them in step until they meet
+        int lmin = act ? len : 0x7fffffff;
+        for (int o = 32; o > 0; o >>= 1) lmin = min(lmin, __shfl_xor(lmin, o));
+        if (n == 0) lmin = 0;
+        int cur = node;
+        for (int k = len - lmin; k > 0; --k) cur = up(cur);  // (no slot: len = 0, no step)
+        int steps = 0, first;
+        bool same;
+        for (;; ++steps) {  // wave-uniform
+            first = __shfl(cur, 0);
+            same = __all(!act || cur == first);
+            if (same || steps >= lmin) break;
+            cur = up(cur);
+        }
+        int depth = same ? lmin - steps : 0;  // labels from the root to the new root
+        int root = same ? first : ROOT;       // (no meeting point within lmin steps: not a trie; nothing is shared)
+        const int len0 = __shfl(len, 0);
+        if (max_tail >= 0 && n > 0 && len0 - depth > max_tail) {  // wave-uniform: forced
+            int c = node;
+            if (r == 0)
+                for (int k = 0; k < max_tail; ++k) c = up(c);  // max_tail < len0 <= frames
+            root = __shfl(c, 0);
+            depth = len0 - max_tail;
+        }
+        if (r == 0) {  // the committed labels, back from the new root; L may be narrower than the prefix
+            int c = root;
+            for (int p = depth - 1; p >= 0; --p) {
+                int tok = -1;
+                if (c != ROOT) {
+                    const unsigned long long key = trie_load(table, mask, c);
+                    tok = (int)(unsigned)(key & 0xffffffffull);
+                    c = (int)(unsigned)(key >> 32);
+                }
+                if (p < L) out[p] = tok;
+            }
+            lengths[b] = depth;
+            s_depth = depth;
+            s_live = 0;
+        }
+        // the labels between the new root and the slot; a slot stays if that walk ends at the new root
+        if (act && len >= depth) {
+            const int tl = len - depth;  // <= frames <= max_frames
+            int *path = paths + ((size_t)b * beam + r) * max_frames;
+            int c = node;
+            for (int k = 0; k < tl; ++k) {
+                const unsigned long long key = trie_load(table, mask, c);
+                path[tl - 1 - k] = (int)(unsigned)(key & 0xffffffffull);
+                c = c == ROOT ? ROOT : (int)(unsigned)(key >> 32);
+            }
+            if (c == root) tail = tl;
+        }
+        const unsigned long long kept = __ballot(tail >= 0);
+        j = __popcll(kept & ((1ull << r) - 1ull));
+        int tmax = tail;
+        for (int o = 32; o > 0; o >>= 1) tmax = max(tmax, __shfl_xor(tmax, o));
+        if (r == 0) { s_n = __popcll(kept); s_tail = max(tmax, 0); }
+    }
+    __syncthreads();  // every walk through the old table is over; S holds the beam
+    for (int p = s_depth + tid; p < L; p += 256) out[p] = -1;
+    for (size_t i = tid; i <= (size_t)mask; i += 256) table[i] = EMPTY;
+    __syncthreads();  // the table is empty
+    if (tail >= 0) {  // (wave 0's lanes of the slots that stay)
+        const int *path = paths + ((size_t)b * beam + r) * max_frames;
+        int node = ROOT, pnode = NONE;
+        for (int k = 0; k < tail; ++k) {
+            pnode = node;
+            node = trie_node(table, mask, node, path[k]);
+        }
+        move_slot(R.beam, j, S, r);
+        R.beam.node[j] = node; R.beam.pnode[j] = pnode; R.beam.len[j] = tail;
+    }
+    __syncthreads();  // the table holds the live keys
+    int live = 0;
+    for (size_t i = tid; i <= (size_t)mask; i += 256) live += trie_load(table, mask, (int)i) != EMPTY;
+    if (live) atomicAdd(&s_live, live);
+    __syncthreads();
+    if (tid == 0) {
+        // the fewest frames that account for the live keys (beam per frame) and for the longest prefix, in the phase
+        // of the renormalisation that `frames` had; never more than before
+        const int need = max((s_live + beam - 1) / beam, s_tail);
+        int fnew = need + (((h.frames - need) % RENORM) + RENORM) % RENORM;
+        if (fnew > h.frames) fnew = h.frames;
+        R.h.n = s_n; R.h.frames = fnew; R.h.retired += h.frames - fnew;
     }
 }
 
@@ -261,6 +397,27 @@ static int reset_streams(void *state, int B, int max_frames, int beam, int class
                        dim3((unsigned)B, (unsigned)(y < 1 ? 1 : (y > 256 ? 256 : y))), dim3(256), 0,
                        static_cast<hipStream_t>(stream), static_cast<unsigned long long *>(state), slots,
                        stream_recs<StreamRec<BeamT>>(state, B, max_frames, beam), which, start...);
+    return (int)hipGetLastError();
+}
+
+// what a commit needs beside the state: per stream and slot, the labels of a prefix of max_frames frames (a quarter of
+// the tables at most)
+static inline size_t commit_scratch_bytes(int B, int max_frames, int beam) {
+    return sizeof(int) * (size_t)B * beam * max_frames;
+}
+
+// the whole of a commit entry point behind its own arguments' checks (`classes` as check_search_dims)
+template <class BeamT>
+static int commit_streams(void *state, int B, int max_frames, int beam, int classes, const int *which, int max_tail, int L,
+                          int *tokens, int *lengths, void *scratch, void *stream) {
+    if (L <= 0) return PIKA_EINVAL;
+    if (int rc = check_search_dims(B, max_frames, beam, classes)) return rc;
+    if (!state || !tokens || !lengths || !scratch) return PIKA_EINVAL;
+    hipLaunchKernelGGL((ctc_stream_commit_kernel<BeamT>), dim3((unsigned)B), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), static_cast<unsigned long long *>(state),
+                       (unsigned)(table_slots(max_frames, beam) - 1),
+                       stream_recs<StreamRec<BeamT>>(state, B, max_frames, beam), which, beam, max_frames, max_tail, L,
+                       tokens, lengths, static_cast<int *>(scratch));
     return (int)hipGetLastError();
 }
 

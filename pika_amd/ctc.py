@@ -34,7 +34,7 @@ and both searches with their state carried across calls, for audio that arrives 
     CtcBeamStream(batch, max_frames, beam=16, blank=0, lm=None, lm_weight=0.5, length_bonus=0.0, candidates=None,
                   device=None)
         .reset(which=None)  .advance(log_probs, lengths=None)  .advance_from_logits(logits, lengths=None)
-        .results(nbest=1, use_final=True)  .frames  .overflowed
+        .results(nbest=1, use_final=True)  .commit(which=None, max_tail=None)  .frames  .consumed  .room  .overflowed
 
 Differences from torch, on purpose:
 
@@ -67,6 +67,7 @@ MAX_BACKOFF_HOPS = 8
 # a stream's record behind the tables of its blob (include/pika_ctc_decode.h): i32 words n, frames, overflow, ...
 STREAM_FRAMES_WORD = 1      # PIKA_CTC_STREAM_FRAMES_OFFSET / 4
 STREAM_OVERFLOW_WORD = 2    # PIKA_CTC_STREAM_OVERFLOW_OFFSET / 4
+STREAM_RETIRED_WORD = 3     # PIKA_CTC_STREAM_RETIRED_OFFSET / 4
 
 
 def _ptr(t):
@@ -721,7 +722,22 @@ class CtcBeamStream(object):
     reset(which=None)   every stream back to the empty prefix, or those selected by `which` ((B,) bool / int tensor or
         sequence, host or device); the others' state, tables included, is not touched, so one stream of a serving
         batch can start a new utterance while its neighbours continue.
-    frames       (B,) int32 device tensor: frames consumed per stream (a view of the state: it follows the stream)
+    commit(which=None, max_tail=None)   -> (tokens (B,max_frames) i32, lengths (B,) i32): the labels that became FINAL in
+        this call, -1 beyond lengths[b]; the caller concatenates them over the calls.  The prefix that every entry of the
+        beam shares can never change again; the commit emits it, re-roots the trie of prefixes there and rebuilds the
+        table with the live nodes only, which gives capacity back (`room`).  Decoding goes on and gives the same bits as
+        without the commit: results() then returns the uncommitted tails -- `lengths` relative to the commit, scores
+        unchanged and absolute -- and committed + tail is the one-shot call's hypothesis.  `which` as in reset(): the
+        other streams are not touched and get length 0.  max_tail=m >= 0 is the FORCED commit, for audio on which the
+        beam does not converge: when the best entry (the first of the stored beam, before any `use_final` re-sort)
+        would keep more than m uncommitted labels, everything but its last m labels is committed and the entries that
+        do not start with that prefix are DROPPED.  This changes the search -- it is the usual finalisation by best
+        path -- while max_tail=None never does.  No host synchronisation; capturable in a `torch.cuda.graph` (the
+        scratch is allocated once, at the first call: make that call before the capture).
+    frames       (B,) int32 device tensor: frames held per stream -- consumed, less what commits gave back (a view of the
+                 state: it follows the stream)
+    consumed     (B,) int32 device tensor: frames consumed per stream since its reset (== frames without a commit)
+    room         (B,) int32 device tensor: frames a stream can still take, max_frames - frames
     overflowed   (B,) bool device tensor: frames were dropped because the stream was full
 
     lm may be a `CtcBiasedLm` -- an LM with a second automaton (hotwords) beside it, as in `ctc_beam_search_lm`: the
@@ -732,7 +748,9 @@ class CtcBeamStream(object):
     reset() and raises ValueError before launching anything once the sum would exceed max_frames; this bound is
     conservative (it ignores `lengths`) and needs no synchronisation.  A partial reset does not lower it: the streams
     that continue still hold their frames.  What the host cannot see -- replays of a captured graph -- the device
-    handles: a stream takes frames up to max_frames, ignores the rest of the chunk and sets `overflowed`.
+    handles: a stream takes frames up to max_frames, ignores the rest of the chunk and sets `overflowed`.  The host
+    cannot see what a commit freed either: from the first commit() until the next full reset() the host-side sum is not
+    enforced and the device rule stands alone -- watch `room` and `overflowed`.
 
     Argument checks as the one-shot functions (1 <= nbest <= beam <= 64, 1 <= candidates <= 128 with None meaning
     min(2 * beam, 128), the LM's device, its backoff_id against C).  No autograd; no host synchronisation in `advance`
@@ -758,6 +776,8 @@ class CtcBeamStream(object):
         rec = (nbytes - tables) // batch                # the record's size is the library's: the blob is tables + records
         self.classes = None                             # C, fixed by the first advance
         self._fed = 0                                   # chunk widths since the last full reset
+        self._committed = False                         # a commit since then: the host's bound is off
+        self._commit_scratch = None
         with torch.cuda.device(self.device):
             self._state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self._hdr = self._state[tables:].view(torch.int32).view(batch, rec // 4)
@@ -773,7 +793,16 @@ class CtcBeamStream(object):
     def overflowed(self):
         return self._hdr[:, STREAM_OVERFLOW_WORD] != 0
 
-    def reset(self, which=None):
+    @property
+    def consumed(self):
+        return self._hdr[:, STREAM_FRAMES_WORD] + self._hdr[:, STREAM_RETIRED_WORD]
+
+    @property
+    def room(self):
+        return self.max_frames - self._hdr[:, STREAM_FRAMES_WORD]
+
+    def _which(self, which):
+        """A selection of streams as the C ABI takes it: None, or (B,) int32 on the device."""
         if which is not None:
             which = torch.as_tensor(which)
             if which.dtype not in (torch.bool, torch.int32, torch.int64):
@@ -781,11 +810,36 @@ class CtcBeamStream(object):
             which = which.reshape(-1).to(self.device, torch.int32).contiguous()
             if which.numel() != self.batch:
                 raise ValueError("which must hold batch = %d entries" % self.batch)
+        return which
+
+    def reset(self, which=None):
+        which = self._which(which)
         v = self._search
         with torch.cuda.device(self.device):
             v.call("stream_reset", *((_ptr(self._state),) + self._dims + self._starts + (_ptr(which), _stream())))
         if which is None:
             self._fed = 0
+            self._committed = False
+
+    def commit(self, which=None, max_tail=None):
+        which = self._which(which)
+        if max_tail is None:
+            max_tail = -1
+        else:
+            max_tail = int(max_tail)
+            if max_tail < 0:
+                raise ValueError("max_tail must be None or >= 0, got %d" % max_tail)
+        B, L, dev, v = self.batch, self.max_frames, self.device, self._search
+        with torch.cuda.device(dev):
+            if self._commit_scratch is None:
+                nbytes = v.size("stream_commit_scratch_bytes", B, L, self.beam)
+                self._commit_scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            tokens = torch.empty((B, L), dtype=torch.int32, device=dev)
+            lengths = torch.empty(B, dtype=torch.int32, device=dev)
+            v.call("stream_commit", *((_ptr(self._state),) + self._dims + (
+                _ptr(which), max_tail, L, _ptr(tokens), _ptr(lengths), _ptr(self._commit_scratch), _stream())))
+        self._committed = True
+        return tokens, lengths
 
     def _advance(self, x, what, lengths, logits):
         x, _ = _check_input(x, what, "CtcBeamStream", self.blank)
@@ -798,7 +852,7 @@ class CtcBeamStream(object):
             raise ValueError("the stream lives on %s, %s on %s" % (self.device, what, x.device))
         v = self._search
         v.check_against(C, self.device, "the stream")
-        if self._fed + Tc > self.max_frames:
+        if not self._committed and self._fed + Tc > self.max_frames:
             raise ValueError("%d frames were fed since the last full reset: %d more exceed max_frames = %d"
                              % (self._fed, Tc, self.max_frames))
         if lengths is None:
