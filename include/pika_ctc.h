@@ -95,6 +95,44 @@ int pika_ctc_fused_backward(const float *logits, const float *lse, const int *in
 int pika_ctc_align(const void *workspace, const int *input_lengths, const int *target_lengths, int B, int T, int U_max,
                    float *scores, int *frame_labels, void *scratch, void *stream);
 
+/* n-best alignment: for every hypothesis of an n-best list -- what pika_ctc_beam_search, pika_ctc_lm_beam_search and the
+ * stream results calls return -- its full-sum score, its best path's score, and per token the frames of that path's run
+ * and the run's summed log-probability.  One workgroup per hypothesis over the utterance's own rows of x: the input is
+ * not replicated and no plane is written.
+ *   x, stride_t, stride_b   f32, row (t,b) at x + t * stride_t + b * stride_b (strides in ELEMENTS), C contiguous classes,
+ *                  as in pika_ctc_decode.h; rows t >= T_b are never read; values below -1e30 (-inf, NaN) read as -1e30
+ *   lse            f32 (T,B) the rows' log-sum-exps as pika_ctc_decode_rows writes them: x holds raw logits and every value
+ *                  is logit - lse rounded once; NULL: x holds log-probs
+ *   input_lengths  i32 (B,)     T_b, clamped on the device to [1,T]
+ *   tokens         i32 (B,N,L)  hypothesis (b,k) at tokens + (b N + k) L; entries at or beyond its length are never read
+ *   lengths        i32 (B,N)    U; below 0: a missing entry
+ *   full_scores    f32 (B,N)    log of the sum over ALL alignments of the hypothesis: -cost of pika_ctc_loss_forward for
+ *                               that transcript, with its numerics (fp32 states, the running maximum moved into an fp64
+ *                               offset every 8 frames)
+ *   best_scores    f32 (B,N)    log-probability of the best (Viterbi) path: fp32 max-plus and the tie rule of pika_ctc_align
+ *                               (at the end state S-1 over S-2; in the back-trace stay, then s-1, then s-2)
+ *   starts, ends   i32 (B,N,L)  first and last frame (inclusive) of the run in which that path emits token j
+ *   token_scores   f32 (B,N,L)  sum over t = starts[j] .. ends[j] of the value of token j's class at frame t, in fp32 in
+ *                               increasing t; exp(token_scores / (ends - starts + 1)) is the geometric mean of the
+ *                               token's frame posteriors
+ * Beyond an entry's length starts / ends are -1 and token_scores -inf.  A missing entry, and an INFEASIBLE one
+ * (T_b < U + adjacent repeats, a token outside [0,C), a token equal to blank), has both scores -inf, times -1 and token
+ * scores -inf: not a fault, and nothing is read through such a token.  An entry LONGER than min(U_max, L) has both scores
+ * NaN and the per-token outputs of a missing entry.  An empty hypothesis (U = 0) has full = best = the sum of the blank's
+ * values.  Every output element is written.  Everything read from input_lengths, lengths and tokens bounds loops and
+ * stores through clamps.  No atomics: two runs give bit-identical outputs.
+ * Limits: 2 U_max + 1 <= 1024 (the limit is on U_max, the state axis one workgroup spans, not on the row width L of
+ * `tokens`); B, N <= 65535 (the grid's extents); PIKA_ETOOBIG beyond, and for a scratch size beyond size_t.
+ * PIKA_EINVAL for a null pointer (lse excepted), B, N, L, T, C < 1, U_max < 0, blank outside [0,C).
+ *
+ * Scratch: back-pointers at TWO BITS per cell -- four frames of one state to a byte -- in rows of Wp bytes (Wp = 2 U_max
+ * + 1 rounded up to a multiple of 64): B N ceil(T / 4) Wp bytes; 0 for refused dimensions. */
+size_t pika_ctc_nbest_align_scratch_bytes(int B, int N, int T, int U_max);
+int pika_ctc_nbest_align(const float *x, long long stride_t, long long stride_b, const float *lse,
+                         const int *input_lengths, const int *tokens, const int *lengths, int B, int N, int L, int T,
+                         int C, int blank, int U_max, float *full_scores, float *best_scores, int *starts, int *ends,
+                         float *token_scores, void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

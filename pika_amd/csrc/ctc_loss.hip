@@ -21,6 +21,9 @@
 //               order is fixed, two runs are bit-identical.
 //   align     : max-plus over the same plane, one byte of back-pointer per cell in the caller's scratch; the
 //               back-trace stages the scratch through LDS a chunk of frames at a time and is walked by one thread.
+//   n-best    : for the n-best list of a search, one workgroup per hypothesis straight on the (T,B,C) input -- no plane,
+//               no replicated input: the scaled sum and the max-plus in one sweep, two bits of back-pointer per cell,
+//               and per token the frames and the summed value of its run on the best path.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -456,6 +459,204 @@ __global__ __launch_bounds__(MULTI ? 1024 : 64) void ctc_align_kernel(Ctc L, con
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// n-best alignment.  grid = (N, B): one workgroup per hypothesis, block = Wp, thread s owns state s of ITS hypothesis.
+// No plane: the workgroup derives class, skip and validity of its states from `tokens` (an LDS row) and reads every
+// frame's value straight from x[t * stride_t + b * stride_b + cls(s)] (minus lse[t,b] for logits), UNR frames ahead.
+// One sweep over t advances BOTH recurrences on that value -- the scaled sum of ctc_alpha_beta_kernel (same operations,
+// same renormalisation frames, fp64 offset) and the max-plus of ctc_align_kernel (same comparison order) -- with one
+// neighbour exchange: the edge lanes of both go through LDS behind the same barrier.  Back-pointers: TWO BITS per cell,
+// four frames of one state to a byte (a lane packs its own four values in a register and stores one byte), rows of Wp
+// bytes per group of four frames.  The back-trace is ctc_align_kernel's, chunked through LDS, and leaves the first and
+// last frame of every visited state in LDS; lane 2j+1 then writes token j's times and sums its own run in time order.
+// ---------------------------------------------------------------------------------------------
+template <bool MULTI>
+__device__ inline void shift_up2(Edges &Ea, Edges &Ev, float a, float v, int step, float &a1, float &a2, float &v1,
+                                 float &v2) {
+    float a63 = NEG, a62 = NEG, v63 = NEG, v62 = NEG;
+    if constexpr (MULTI) {
+        const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = blockDim.x >> 6;
+        if (l >= 62 && w + 1 < nw) {
+            Ea.e[step & 1][w + 1][l - 62] = a;
+            Ev.e[step & 1][w + 1][l - 62] = v;
+        }
+        __syncthreads();
+        a62 = Ea.e[step & 1][w][0];
+        a63 = Ea.e[step & 1][w][1];
+        v62 = Ev.e[step & 1][w][0];
+        v63 = Ev.e[step & 1][w][1];
+    }
+    a1 = wave_shr1(a, a63);
+    a2 = wave_shr1(a1, a62);
+    v1 = wave_shr1(v, v63);
+    v2 = wave_shr1(v1, v62);
+}
+
+__host__ __device__ inline int nbest_groups(int T) { return (T + 3) / 4; }  // back-pointer rows: four frames to a byte
+
+template <bool MULTI, bool LOGITS>
+__global__ __launch_bounds__(MULTI ? 1024 : 64) void ctc_nbest_align_kernel(
+    const float *__restrict__ x, long long stride_t, long long stride_b, const float *__restrict__ lse,
+    const int *__restrict__ Tn_, const int *__restrict__ tokens, const int *__restrict__ lengths, int B, int N, int L,
+    int T, int C, int blank, int U_max, float *__restrict__ full, float *__restrict__ best, int *__restrict__ starts,
+    int *__restrict__ ends, float *__restrict__ tscores, unsigned char *__restrict__ bp_) {
+    __shared__ Edges Ea, Ev;
+    __shared__ unsigned int chunk[CHUNK_BYTES / 4];
+    __shared__ int tokL[MAX_WAVES * 32];
+    __shared__ int firstL[MAX_WAVES * 64], lastL[MAX_WAVES * 64];
+    __shared__ int badToken;
+    const int b = blockIdx.y, s = threadIdx.x, Wp = blockDim.x;
+    const size_t h = (size_t)b * N + blockIdx.x;
+    const int Tn = clampi(Tn_[b], 1, T);
+    const int U = lengths[h];
+    int *so = starts + h * L, *eo = ends + h * L;
+    float *to = tscores + h * L;
+    // an entry that has no alignment: times -1, token scores -inf, both scores `score`
+    auto refuse = [&](float score) __attribute__((always_inline)) {
+        for (int j = s; j < L; j += Wp) {
+            so[j] = -1;
+            eo[j] = -1;
+            to[j] = -__builtin_inff();
+        }
+        if (s == 0) {
+            full[h] = score;
+            best[h] = score;
+        }
+    };
+    if (U < 0 || U > min(U_max, L)) {  // workgroup-uniform: missing (-inf), or longer than the state axis (NaN)
+        refuse(U < 0 ? -__builtin_inff() : __builtin_nanf(""));
+        return;
+    }
+    const int S = 2 * U + 1;
+    if (s == 0) badToken = 0;
+    firstL[s] = -1;
+    lastL[s] = -1;
+    edges_init(Ea);
+    edges_init(Ev);
+    for (int j = s; j < U; j += Wp) {
+        const int c = tokens[h * L + j];
+        tokL[j] = c;
+        if (c < 0 || c >= C || c == blank) badToken = 1;
+    }
+    __syncthreads();
+    if (badToken) {  // workgroup-uniform; nothing was read through the token
+        refuse(-__builtin_inff());
+        return;
+    }
+    const bool valid = s < S;
+    const int cls = (valid && (s & 1)) ? tokL[s >> 1] : blank;  // in [0,C) from here on
+    const bool skip = valid && (s & 1) && s >= 3 && cls != tokL[(s >> 1) - 1];
+    const float *xs = x + (long long)b * stride_b + cls;
+    unsigned char *bp = bp_ + h * (size_t)nbest_groups(T) * Wp;
+    auto value = [&](int t) __attribute__((always_inline)) {  // t in [0, T_n)
+        float e = xs[(long long)t * stride_t];
+        if constexpr (LOGITS) e -= lse[(size_t)t * B + b];
+        return fmaxf(e, NEG);
+    };
+
+    float cur[UNR], nx[UNR];
+    auto load = [&](float *dst, int t0) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < UNR; ++i) dst[i] = value(min(t0 + i, Tn - 1));
+    };
+    float a = s == 0 ? 0.0f : NEG, v = a;
+    double off = 0.0;  // sum of the subtracted maxima (identical in every thread)
+    unsigned int pk = 0;
+    load(cur, 0);
+    for (int t0 = 0; t0 < Tn; t0 += UNR) {
+        load(nx, t0 + UNR);
+#pragma unroll
+        for (int i = 0; i < UNR; ++i) {
+            const int t = t0 + i;
+            if (t < Tn) {  // workgroup-uniform
+                float a1, a2, v1, v2;
+                shift_up2<MULTI>(Ea, Ev, a, v, t, a1, a2, v1, v2);
+                const float an = cur[i] + lse3(a, a1, skip ? a2 : NEG);
+                a = valid ? fmaxf(an, NEG) : NEG;
+                float top = v;
+                unsigned int k = 0;
+                if (s >= 1 && v1 > top) { top = v1; k = 1; }
+                if (skip && v2 > top) { top = v2; k = 2; }
+                v = valid ? fmaxf(cur[i] + top, NEG) : NEG;
+                pk |= k << (2 * (i & 3));  // t0 is a multiple of 4: i & 3 == t & 3
+                if ((i & 3) == 3 || t == Tn - 1) {
+                    bp[(size_t)(t >> 2) * Wp + s] = (unsigned char)pk;
+                    pk = 0;
+                }
+                if (i == UNR - 1) {  // t = RENORM - 1 (mod RENORM)
+                    float m = max_all<MULTI>(Ea, a, t / RENORM);
+                    m = m > NEG_HALF ? m : 0.0f;
+                    a = a > NEG_HALF ? a - m : NEG;
+                    off += (double)m;
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < UNR; ++i) cur[i] = nx[i];
+    }
+    if (s == S - 1) { Ea.fin[0] = a; Ev.fin[0] = v; }
+    if (s == S - 2) { Ea.fin[1] = a; Ev.fin[1] = v; }  // S == 1: stays NEG
+    __syncthreads();  // fin and (workgroup-scope) the back-pointers are written
+    const float fa0 = Ea.fin[0], fa1 = Ea.fin[1], fv0 = Ev.fin[0], fv1 = Ev.fin[1];
+    const float ma = fmaxf(fa0, fa1);
+    const bool second = S >= 2 && fv1 > fv0;  // a tie ends in the final blank
+    const float vb = second ? fv1 : fv0;
+    if (!(ma > NEG_HALF) || !(vb > NEG_HALF)) {  // workgroup-uniform: no path reaches the end
+        refuse(-__builtin_inff());
+        return;
+    }
+    if (s == 0) {
+        full[h] = (float)(off + (double)ma + log(exp((double)(fa0 - ma)) + exp((double)(fa1 - ma))));
+        best[h] = vb;
+    }
+    // back-trace, a chunk of four-frame rows at a time through LDS
+    const int rows = CHUNK_BYTES / Wp;
+    int cs = second ? S - 2 : S - 1, prev = -1;
+    for (int ghi = (Tn - 1) >> 2; ghi >= 0; ghi -= rows) {  // workgroup-uniform
+        const int glo = max(ghi - rows + 1, 0);
+        const unsigned int *src = reinterpret_cast<const unsigned int *>(bp + (size_t)glo * Wp);
+        const int words = (ghi - glo + 1) * (Wp / 4);
+        __syncthreads();  // the previous chunk is walked
+        for (int i = s; i < words; i += Wp) chunk[i] = src[i];
+        __syncthreads();
+        if (s == 0) {
+            const unsigned char *cb = reinterpret_cast<const unsigned char *>(chunk);
+            for (int t = min(4 * ghi + 3, Tn - 1); t >= 4 * glo; --t) {
+                if (cs != prev) {
+                    lastL[cs] = t;
+                    prev = cs;
+                }
+                firstL[cs] = t;
+                cs -= (cb[(size_t)((t >> 2) - glo) * Wp + cs] >> (2 * (t & 3))) & 3;
+            }
+        }
+    }
+    __syncthreads();
+    for (int j = U + s; j < L; j += Wp) {
+        so[j] = -1;
+        eo[j] = -1;
+        to[j] = -__builtin_inff();
+    }
+    if (valid && (s & 1)) {  // a label state: on the path of every feasible hypothesis
+        const int t0 = clampi(firstL[s], 0, Tn - 1), t1 = clampi(lastL[s], t0, Tn - 1);
+        float acc = 0.0f;
+        for (int t = t0; t <= t1; ++t) acc += value(t);
+        so[s >> 1] = t0;
+        eo[s >> 1] = t1;
+        to[s >> 1] = acc;
+    }
+}
+
+// what the n-best call refuses, dimensions first
+int check_nbest_dims(int B, int N, int T, int U) {
+    if (B <= 0 || N <= 0 || T <= 0 || U < 0) return PIKA_EINVAL;
+    if (U > 511 || B > 65535 || N > 65535) return PIKA_ETOOBIG;  // 2U+1 <= 1024; N and B are the grid's extents
+    size_t n;
+    if (__builtin_mul_overflow((size_t)B * (size_t)N, (size_t)nbest_groups(T) * (size_t)state_width(U), &n))
+        return PIKA_ETOOBIG;
+    return PIKA_OK;
+}
+
 // gather + the two recurrences: what both forward calls enqueue
 template <bool LOGITS>
 int forward(const float *x, const int *targets, const int *toff, const int *Tn, const int *Un, int B, int T, int U, int C,
@@ -539,6 +740,39 @@ int pika_ctc_align(const void *workspace, const int *input_lengths, const int *t
     else
         hipLaunchKernelGGL(ctc_align_kernel<true>, dim3((unsigned)B), dim3((unsigned)L.Wp), 0, s, L, input_lengths,
                            target_lengths, scores, frame_labels, bp, T, U_max);
+    return (int)hipGetLastError();
+}
+
+size_t pika_ctc_nbest_align_scratch_bytes(int B, int N, int T, int U_max) {
+    if (check_nbest_dims(B, N, T, U_max)) return 0;
+    return (size_t)B * N * nbest_groups(T) * state_width(U_max);
+}
+
+int pika_ctc_nbest_align(const float *x, long long stride_t, long long stride_b, const float *lse,
+                         const int *input_lengths, const int *tokens, const int *lengths, int B, int N, int L, int T,
+                         int C, int blank, int U_max, float *full_scores, float *best_scores, int *starts, int *ends,
+                         float *token_scores, void *scratch, void *stream) {
+    if (L <= 0 || C <= 0 || blank < 0 || blank >= C) return PIKA_EINVAL;
+    if (int rc = check_nbest_dims(B, N, T, U_max)) return rc;
+    if (!x || !input_lengths || !tokens || !lengths || !full_scores || !best_scores || !starts || !ends ||
+        !token_scores || !scratch)
+        return PIKA_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int Wp = state_width(U_max);
+    const dim3 grid((unsigned)N, (unsigned)B), block((unsigned)Wp);
+    unsigned char *bp = static_cast<unsigned char *>(scratch);
+#define PIKA_NBEST_LAUNCH(MULTI, LOGITS)                                                                              \
+    hipLaunchKernelGGL((ctc_nbest_align_kernel<MULTI, LOGITS>), grid, block, 0, s, x, stride_t, stride_b, lse,        \
+                       input_lengths, tokens, lengths, B, N, L, T, C, blank, U_max, full_scores, best_scores, starts, \
+                       ends, token_scores, bp)
+    if (Wp == 64) {
+        if (lse) PIKA_NBEST_LAUNCH(false, true);
+        else PIKA_NBEST_LAUNCH(false, false);
+    } else {
+        if (lse) PIKA_NBEST_LAUNCH(true, true);
+        else PIKA_NBEST_LAUNCH(true, false);
+    }
+#undef PIKA_NBEST_LAUNCH
     return (int)hipGetLastError();
 }
 

@@ -36,6 +36,12 @@ and both searches with their state carried across calls, for audio that arrives 
         .reset(which=None)  .advance(log_probs, lengths=None)  .advance_from_logits(logits, lengths=None)
         .results(nbest=1, use_final=True)  .commit(which=None, max_tail=None)  .frames  .consumed  .room  .overflowed
 
+and, for the n-best list any of these searches returns, what `ctc_align` and `ctc_loss` give for one transcript:
+
+    ctc_nbest_align(log_probs, input_lengths, tokens, lengths, blank=0, max_len=None)
+        -> (full_scores (B,N), best_scores (B,N), starts (B,N,L), ends (B,N,L), token_scores (B,N,L))
+    ctc_nbest_align_from_logits(logits, ...same...)
+
 Differences from torch, on purpose:
 
 * THE GRADIENT IS THE TRUE DERIVATIVE.  torch's native CTC backward returns `exp(log_probs) - occ` for d/d log_probs,
@@ -281,9 +287,8 @@ def ctc_align_from_logits(logits, targets, input_lengths, target_lengths, blank=
     return _align(logits, "logits", targets, input_lengths, target_lengths, blank, True)
 
 
-def _decode_rows(x, what, input_lengths, blank, K, logits):
-    """Checks + the row pass: (x as (T,B,C) with unit class stride, il i32, blank_lp, top_val, top_idx, lse or None,
-    unbatched)."""
+def _rows_input(x, what, input_lengths, blank):
+    """The checks of the calls that read x row by row: (x as (T,B,C) with unit class stride, il i32, unbatched)."""
     x, unbatched = _check_input(x, what, "ctc decode", blank)
     x = x.detach()
     T, B, C = x.shape
@@ -296,6 +301,14 @@ def _decode_rows(x, what, input_lengths, blank, K, logits):
     # the kernels take the two outer strides: only the class axis has to be dense (one copy when it is not)
     if C > 1 and x.stride(2) != 1:
         x = x.contiguous()
+    return x, il, unbatched
+
+
+def _decode_rows(x, what, input_lengths, blank, K, logits):
+    """Checks + the row pass: (x as (T,B,C) with unit class stride, il i32, blank_lp, top_val, top_idx, lse or None,
+    unbatched)."""
+    x, il, unbatched = _rows_input(x, what, input_lengths, blank)
+    T, B, C = x.shape
     lib = _lib.lib()
     with torch.cuda.device(x.device):
         blank_lp = torch.empty((T, B), dtype=torch.float32, device=x.device)
@@ -885,3 +898,90 @@ class CtcBeamStream(object):
             v.call("stream_results", *((_ptr(self._state),) + self._dims + self._fsts + v.results_weights + (
                 (int(bool(use_final)),) if v.fused else ()) + (nbest, L) + tuple(_ptr(o) for o in out) + (_stream(),)))
         return out
+
+
+def _nbest_align(x, what, input_lengths, tokens, lengths, blank, max_len, logits):
+    blank = int(blank)
+    tokens, lengths = torch.as_tensor(tokens), torch.as_tensor(lengths)
+    for name, t in (("tokens", tokens), ("lengths", lengths)):
+        if t.dtype not in (torch.int32, torch.int64):
+            raise TypeError("%s must be int32 or int64, got %s" % (name, t.dtype))
+    if tokens.dim() not in (2, 3) or lengths.dim() != tokens.dim() - 1 or tokens.shape[:-1] != lengths.shape:
+        raise ValueError("tokens must be (B,N,L) and lengths (B,N) -- (N,L) and (N,) for (T,C) input -- got %s and %s"
+                         % (tuple(tokens.shape), tuple(lengths.shape)))
+    N, L = int(tokens.shape[-2]), int(tokens.shape[-1])
+    if N < 1 or L < 1:
+        raise ValueError("tokens has an empty dimension: %s" % (tuple(tokens.shape),))
+    max_len = min(L, (MAX_STATES - 1) // 2) if max_len is None else int(max_len)
+    if max_len < 0 or 2 * max_len + 1 > MAX_STATES:
+        raise ValueError("need 0 <= max_len and 2*max_len+1 <= %d, got max_len=%d" % (MAX_STATES, max_len))
+    if logits:      # the row pass with K = 1 writes the (T,B) log-sum-exps
+        x, il, _, _, _, lse, unbatched = _decode_rows(x, what, input_lengths, blank, 1, True)
+    else:
+        (x, il, unbatched), lse = _rows_input(x, what, input_lengths, blank), None
+    T, B, C = x.shape
+    if unbatched != (tokens.dim() == 2) or (not unbatched and tokens.shape[0] != B):
+        raise ValueError("%s is %s: tokens must be %s, got %s" % (
+            what, tuple(x.shape[::2]) if unbatched else tuple(x.shape), "(N,L)" if unbatched else "(%d,N,L)" % B,
+            tuple(tokens.shape)))
+    tokens = tokens.to(x.device, torch.int32).contiguous()
+    lengths = lengths.to(x.device, torch.int32).contiguous()
+    lib = _lib.lib()
+    nbytes = lib.pika_ctc_nbest_align_scratch_bytes(B, N, T, max_len)
+    if nbytes == 0:
+        raise ValueError("(B,N,T,max_len) = (%d,%d,%d,%d) not supported" % (B, N, T, max_len))
+    with torch.cuda.device(x.device):
+        out = (torch.empty((B, N), dtype=torch.float32, device=x.device),
+               torch.empty((B, N), dtype=torch.float32, device=x.device),
+               torch.empty((B, N, L), dtype=torch.int32, device=x.device),
+               torch.empty((B, N, L), dtype=torch.int32, device=x.device),
+               torch.empty((B, N, L), dtype=torch.float32, device=x.device))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        _lib.check(lib.pika_ctc_nbest_align(_ptr(x), x.stride(0), x.stride(1), _ptr(lse), _ptr(il), _ptr(tokens),
+                                            _ptr(lengths), B, N, L, T, C, blank, max_len, *(
+                                                tuple(_ptr(o) for o in out) + (_ptr(scratch), _stream()))),
+                   "pika_ctc_nbest_align")
+    return tuple(o[0] for o in out) if unbatched else out
+
+
+def ctc_nbest_align(log_probs, input_lengths, tokens, lengths, blank=0, max_len=None):
+    """Token times, token scores and full-sum scores for an n-best list: what `ctc_align` and `ctc_loss` give for one
+    transcript per utterance, for the `nbest` hypotheses of every utterance, without replicating the input.
+
+    log_probs (T,B,C) or (T,C) float32 on a HIP device, any outer strides (one copy only when the class stride is not
+    1); input_lengths (B,) int32 or int64, on the CPU or the device, clamped on the device to [1,T].  tokens (B,N,L)
+    and lengths (B,N), int32 or int64, on either side: exactly what `ctc_beam_search*`, `ctc_beam_search_lm*` and
+    `CtcBeamStream.results` return.  L need not equal T; a length below 0 marks a missing entry; tokens at or beyond an
+    entry's length are never read.  (T,C) input takes (N,L) / (N,) and returns outputs without the batch axis.
+    `max_len` (a host int; default min(L, 511)) sizes the state axis: ValueError when 2 * max_len + 1 > 1024 or
+    max_len < 0.  The limit is on max_len, not on L.
+
+    Returns (full_scores (B,N) f32, best_scores (B,N) f32, starts (B,N,L) i32, ends (B,N,L) i32, token_scores (B,N,L)
+    f32), per hypothesis of length U over its utterance's T_b frames:
+      full_scores   log of the sum over ALL alignments: -ctc_loss(reduction='none') for that transcript, with the
+                    loss's numerics.  The search's `scores` / `am_scores` sum only the paths the beam kept: a lower
+                    bound that depends on `beam` and `candidates`; this does not.
+      best_scores   the log-probability of the best (Viterbi) path, `ctc_align`'s value and tie rule: at the end the
+                    final blank is preferred to the last label; in the back-trace stay, then s-1, then s-2.
+      starts, ends  the first and last frame (inclusive) of the run in which that path emits token j
+      token_scores  the sum over t = starts[j] .. ends[j] of log_probs[t, b, token j], in fp32 in increasing t;
+                    exp(token_scores / (ends - starts + 1)) is the token's confidence, the geometric mean of its
+                    frame posteriors.
+    Beyond an entry's length starts / ends are -1 and token_scores -inf.  A missing entry has both scores -inf, times
+    -1 and token scores -inf; so has an infeasible one (T_b < U + adjacent repeats, a token outside [0,C), a token
+    equal to blank) -- not a fault.  An entry longer than max_len has both scores NaN (per-token outputs as a missing
+    entry), which tells it from an infeasible one.  The empty hypothesis has full = best = the sum of the blank's
+    log-probs.
+
+    No autograd, no host synchronisation; capturable in a `torch.cuda.graph` with all lengths on the device; two runs
+    give bit-identical outputs.
+
+    Streams: `CtcBeamStream.results` tails are relative to the last commit, and a stream does not keep its
+    log-probabilities.  A caller who keeps them aligns committed + tail against the whole input."""
+    return _nbest_align(log_probs, "log_probs", input_lengths, tokens, lengths, blank, max_len, False)
+
+
+def ctc_nbest_align_from_logits(logits, input_lengths, tokens, lengths, blank=0, max_len=None):
+    """`ctc_nbest_align` of log_softmax(logits, -1) without materialising the log-probabilities: every value is
+    logit - lse rounded once, the rows' log-sum-exps coming from the decoders' row pass."""
+    return _nbest_align(logits, "logits", input_lengths, tokens, lengths, blank, max_len, True)
