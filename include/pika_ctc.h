@@ -133,6 +133,41 @@ int pika_ctc_nbest_align(const float *x, long long stride_t, long long stride_b,
                          int C, int blank, int U_max, float *full_scores, float *best_scores, int *starts, int *ends,
                          float *token_scores, void *scratch, void *stream);
 
+/* n-best loss: the full-sum scores of an n-best list and the gradient of sum_k grad_scores[b,k] * full_scores[b,k] with
+ * respect to the UN-replicated (T,B,C) input -- the primitive under MWER / MBR training over the list.  x, stride_t,
+ * stride_b, lse, input_lengths, tokens, lengths, B, N, L, T, C, blank, U_max: as pika_ctc_nbest_align, with its
+ * classification of an entry, made before anything is read through a token: a missing entry (length < 0) and an
+ * infeasible one (a token outside [0,C), a token equal to blank, no path to the end) score -inf, an entry longer than
+ * min(U_max, L) scores NaN.  Every such entry is DEAD: it contributes nothing to the gradient and its grad_scores entry
+ * is never brought into arithmetic -- NaN and +-inf there (what a softmax over -inf scores leaves) do not reach `grads`.
+ *   full_scores  f32 (B,N)    as pika_ctc_nbest_align's, with the same numerics
+ *   grad_scores  f32 (B,N)    g[b,k], the weight of hypothesis k (autograd's grad_output)
+ *   grads        f32 (T,B,C)  contiguous, DENSE: every element is written.  Rows t >= T_b are exactly zero; for t < T_b
+ *       log-probs (lse NULL):  grads[t,b,c] = sum_k g[b,k] occ_k(t,c)
+ *       logits:                grads[t,b,c] = sum_k g[b,k] occ_k(t,c) - (sum_{k live} g[b,k]) softmax_t(c)
+ *       occ_k(t,c) = sum_{s : l'_s = c} exp(alpha_t(s) + beta_t(s) - value_t(c) - ll_k), the exponent assembled in fp64
+ *     (the sign is that of full = -cost).  The sum runs over k in increasing order and, inside a hypothesis, over the
+ *     states of a class in increasing order; no atomics: two runs give bit-identical gradients.
+ * The forward runs one workgroup per hypothesis and direction; the backward one per (t,b) row, which writes the row once
+ * and then adds hypothesis after hypothesis into it: there are never N dense gradients.  Frames t >= T_b of x and tokens
+ * at or beyond an entry's length are never read.  `workspace` is filled by the forward and read by the backward, which
+ * takes the same x, strides, lse and input_lengths.
+ * Limits and codes as pika_ctc_nbest_align: PIKA_EINVAL for a null pointer (lse excepted), B, N, L, T, C < 1, U_max < 0,
+ * blank outside [0,C); PIKA_ETOOBIG for U_max > 511, B or N > 65535, a size beyond size_t; all before any launch.
+ *
+ * Workspace, with Wp = 2 U_max + 1 rounded up to a multiple of 64; 0 for refused dimensions:
+ *   2 f32 planes [B][N][T][Wp]   (alpha, beta, each minus its offset and INCLUDING the frame's own value)   8 B N T Wp
+ *   2 f64 offset rows [B][N][T] + ll [B][N] f64 (-1e30: a dead entry)                                16 B N T + 8 B N
+ *   3 i32 state rows [B][N][Wp]  (class, -1 beyond S; bit 0 skip allowed, bit 1 first of its class;
+ *                                 next state of the same class, -1 at the last)                             12 B N Wp */
+size_t pika_ctc_nbest_loss_workspace_bytes(int B, int N, int T, int U_max);
+int pika_ctc_nbest_loss_forward(const float *x, long long stride_t, long long stride_b, const float *lse,
+                                const int *input_lengths, const int *tokens, const int *lengths, int B, int N, int L,
+                                int T, int C, int blank, int U_max, float *full_scores, void *workspace, void *stream);
+int pika_ctc_nbest_loss_backward(const float *x, long long stride_t, long long stride_b, const float *lse,
+                                 const int *input_lengths, int B, int N, int T, int C, int blank, int U_max,
+                                 const float *grad_scores, const void *workspace, float *grads, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,7 +58,9 @@ HIP_GRAPHS_SAFE_TO_ALTERNATE = _hip_graph_workaround()
 _CTC_EXPORTS = ("ctc_loss", "ctc_loss_from_logits", "CTCLoss", "ctc_align", "ctc_align_from_logits",
                 "ctc_greedy_decode", "ctc_greedy_decode_from_logits", "ctc_beam_search", "ctc_beam_search_from_logits",
                 "CtcNgramLm", "ctc_beam_search_lm", "ctc_beam_search_lm_from_logits", "CtcBeamStream",
-                "CtcHotwords", "CtcBiasedLm", "ctc_nbest_align", "ctc_nbest_align_from_logits")
+                "CtcHotwords", "CtcBiasedLm", "ctc_nbest_align", "ctc_nbest_align_from_logits",
+                "ctc_nbest_loss", "ctc_nbest_loss_from_logits", "ctc_mwer_loss", "ctc_mwer_loss_from_logits",
+                "ctc_nbest_errors")
 
 
 def __getattr__(name):

@@ -47,6 +47,9 @@ SIGNATURES = {
     "pika_ctc_align": (_i, [_vp] * 3 + [_i] * 3 + [_vp] * 4),
     "pika_ctc_nbest_align_scratch_bytes": (_sz, [_i] * 4),
     "pika_ctc_nbest_align": (_i, [_vp, _ll, _ll] + [_vp] * 4 + [_i] * 7 + [_vp] * 7),
+    "pika_ctc_nbest_loss_workspace_bytes": (_sz, [_i] * 4),
+    "pika_ctc_nbest_loss_forward": (_i, [_vp, _ll, _ll] + [_vp] * 4 + [_i] * 7 + [_vp] * 3),
+    "pika_ctc_nbest_loss_backward": (_i, [_vp, _ll, _ll] + [_vp] * 2 + [_i] * 6 + [_vp] * 4),
     # include/pika_ctc_decode.h
     "pika_ctc_decode_rows": (_i, [_vp, _ll, _ll, _vp] + [_i] * 6 + [_vp] * 5),
     "pika_ctc_greedy": (_i, [_vp] * 4 + [_i] * 4 + [_vp] * 5),

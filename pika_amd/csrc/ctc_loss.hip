@@ -24,6 +24,9 @@
 //   n-best    : for the n-best list of a search, one workgroup per hypothesis straight on the (T,B,C) input -- no plane,
 //               no replicated input: the scaled sum and the max-plus in one sweep, two bits of back-pointer per cell,
 //               and per token the frames and the summed value of its run on the best path.
+//   n-best loss: the full-sum scores again, differentiable: one workgroup per (hypothesis, direction) leaves alpha, beta,
+//               offsets and state rows per hypothesis; the backward, one workgroup per (t, b) row, writes the dense row
+//               once and adds every hypothesis's weighted occupancies to it in increasing k -- no N dense gradients.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -242,6 +245,22 @@ __device__ inline float max_all(Edges &E, float v, int count) {  // workgroup-wi
     return m;
 }
 
+// One frame of the scaled sum, shared by every sweep that carries it: v = the frame's value of the state's class, a its
+// own previous value, q1 and q2 the neighbours' one and two states away.
+__device__ inline float sum_step(float v, float a, float q1, float q2, bool skip, bool valid) {
+    const float an = v + lse3(a, q1, skip ? q2 : NEG);
+    return valid ? fmaxf(an, NEG) : NEG;
+}
+// ... and the renormalisation that follows every RENORM-th frame: the running maximum moves into the fp64 offset.
+template <bool MULTI>
+__device__ inline float renorm(Edges &E, float a, int count, double &off) {
+    float m = max_all<MULTI>(E, a, count);
+    m = m > NEG_HALF ? m : 0.0f;
+    a = a > NEG_HALF ? a - m : NEG;
+    off += (double)m;
+    return a;
+}
+
 // ---------------------------------------------------------------------------------------------
 // alpha / beta.  grid = (2, B): blockIdx.x 0 = alpha, 1 = beta.  block = Wp threads, thread s owns state s.
 //   alpha_t(s) = lp_t(s) + lse(alpha_{t-1}(s), alpha_{t-1}(s-1), [alpha_{t-1}(s-2) if skip(s)]),  alpha_{-1} = [0, NEG, ...]
@@ -287,14 +306,8 @@ __global__ __launch_bounds__(MULTI ? 1024 : 64) void ctc_alpha_beta_kernel(Ctc L
                 float q1, q2;
                 if (fwd) shift_up<MULTI>(E, a, j, q1, q2);
                 else shift_down<MULTI>(E, a, j, q1, q2);
-                const float v = cur[i] + lse3(a, q1, skip ? q2 : NEG);
-                a = valid ? fmaxf(v, NEG) : NEG;
-                if (i == UNR - 1) {  // j = RENORM - 1 (mod RENORM)
-                    float m = max_all<MULTI>(E, a, j / RENORM);
-                    m = m > NEG_HALF ? m : 0.0f;
-                    a = a > NEG_HALF ? a - m : NEG;
-                    off += (double)m;
-                }
+                a = sum_step(cur[i], a, q1, q2, skip, valid);
+                if (i == UNR - 1) a = renorm<MULTI>(E, a, j / RENORM, off);  // j = RENORM - 1 (mod RENORM)
                 out[(size_t)frame(j) * Wp] = a;
                 if (s == 0) offs[frame(j)] = off;
             }
@@ -571,8 +584,7 @@ __global__ __launch_bounds__(MULTI ? 1024 : 64) void ctc_nbest_align_kernel(
             if (t < Tn) {  // workgroup-uniform
                 float a1, a2, v1, v2;
                 shift_up2<MULTI>(Ea, Ev, a, v, t, a1, a2, v1, v2);
-                const float an = cur[i] + lse3(a, a1, skip ? a2 : NEG);
-                a = valid ? fmaxf(an, NEG) : NEG;
+                a = sum_step(cur[i], a, a1, a2, skip, valid);
                 float top = v;
                 unsigned int k = 0;
                 if (s >= 1 && v1 > top) { top = v1; k = 1; }
@@ -583,12 +595,7 @@ __global__ __launch_bounds__(MULTI ? 1024 : 64) void ctc_nbest_align_kernel(
                     bp[(size_t)(t >> 2) * Wp + s] = (unsigned char)pk;
                     pk = 0;
                 }
-                if (i == UNR - 1) {  // t = RENORM - 1 (mod RENORM)
-                    float m = max_all<MULTI>(Ea, a, t / RENORM);
-                    m = m > NEG_HALF ? m : 0.0f;
-                    a = a > NEG_HALF ? a - m : NEG;
-                    off += (double)m;
-                }
+                if (i == UNR - 1) a = renorm<MULTI>(Ea, a, t / RENORM, off);  // t = RENORM - 1 (mod RENORM)
             }
         }
 #pragma unroll
@@ -647,12 +654,265 @@ __global__ __launch_bounds__(MULTI ? 1024 : 64) void ctc_nbest_align_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// n-best loss: the full-sum scores of an n-best list WITH their gradient.  The lattice of hypothesis (b, k) in the
+// caller's workspace, what ctc_grad_kernel reads per utterance, per hypothesis -- and no lp plane: forward and backward
+// both read the value of a state's class straight from the utterance's own rows of x.
+// ---------------------------------------------------------------------------------------------
+struct Nbl {
+    float *alpha;   // [B][N][T][Wp] alpha minus off_a[b][k][t]
+    float *beta;    // [B][N][T][Wp] beta  minus off_b[b][k][t]
+    double *off_a;  // [B][N][T]
+    double *off_b;  // [B][N][T]
+    double *ll;     // [B][N] log-likelihood; NEG: a dead entry (missing, infeasible, too long) -- its planes are never read
+    int *cls;       // [B][N][Wp] as Ctc::cls, skp, nxt
+    int *skp;
+    int *nxt;
+    int Wp;
+};
+
+inline Nbl carve_nbest(void *ws, int B, int N, int T, int U) {
+    Nbl W;
+    W.Wp = state_width(U);
+    const size_t hn = (size_t)B * N, n = hn * T * W.Wp;  // n: a multiple of 64, what follows stays 8-byte aligned
+    float *p = static_cast<float *>(ws);
+    W.alpha = p;
+    W.beta = p + n;
+    double *q = reinterpret_cast<double *>(p + 2 * n);
+    W.off_a = q;
+    W.off_b = q + hn * T;
+    W.ll = q + 2 * hn * T;
+    W.cls = reinterpret_cast<int *>(W.ll + hn);
+    W.skp = W.cls + hn * W.Wp;
+    W.nxt = W.skp + hn * W.Wp;
+    return W;
+}
+
+// forward.  grid = (2, N, B): blockIdx.x 0 = alpha, 1 = beta, both concurrent; block = Wp, thread s owns state s of
+// hypothesis (b, k).  The recurrences and their numerics are ctc_alpha_beta_kernel's (the alpha side is the scaled sum of
+// ctc_nbest_align_kernel, operation for operation), the classification of an entry is ctc_nbest_align_kernel's and
+// happens in both workgroups alike; the alpha workgroup also writes the state rows, ll and full_scores.
+template <bool MULTI, bool LOGITS>
+__global__ __launch_bounds__(MULTI ? 1024 : 64) void ctc_nbest_loss_kernel(
+    const float *__restrict__ x, long long stride_t, long long stride_b, const float *__restrict__ lse,
+    const int *__restrict__ Tn_, const int *__restrict__ tokens, const int *__restrict__ lengths, int B, int N, int L,
+    int T, int C, int blank, int U_max, float *__restrict__ full, Nbl W) {
+    __shared__ Edges E;
+    __shared__ int tokL[MAX_WAVES * 32];
+    __shared__ int badToken;
+    const bool fwd = blockIdx.x == 0;
+    const int b = blockIdx.z, s = threadIdx.x, Wp = blockDim.x;
+    const size_t h = (size_t)b * N + blockIdx.y;
+    const int Tn = clampi(Tn_[b], 1, T);
+    const int U = lengths[h];
+    // a dead entry: ll as the loss marks an infeasible utterance, so the backward skips it
+    auto refuse = [&](float score) __attribute__((always_inline)) {
+        if (fwd && s == 0) {
+            W.ll[h] = (double)NEG;
+            full[h] = score;
+        }
+    };
+    if (U < 0 || U > min(U_max, L)) {  // workgroup-uniform: missing (-inf), or longer than the state axis (NaN)
+        refuse(U < 0 ? -__builtin_inff() : __builtin_nanf(""));
+        return;
+    }
+    const int S = 2 * U + 1;
+    if (s == 0) badToken = 0;
+    edges_init(E);
+    for (int j = s; j < U; j += Wp) {
+        const int c = tokens[h * L + j];
+        tokL[j] = c;
+        if (c < 0 || c >= C || c == blank) badToken = 1;
+    }
+    __syncthreads();
+    if (badToken) {  // workgroup-uniform; nothing was read through the token
+        refuse(-__builtin_inff());
+        return;
+    }
+    const bool valid = s < S;
+    const int cls = (valid && (s & 1)) ? tokL[s >> 1] : blank;  // in [0,C) from here on
+    // is the transition over two states into this state (alpha) / out of it (beta) allowed
+    const bool skip_in = valid && (s & 1) && s >= 3 && cls != tokL[(s >> 1) - 1];
+    const bool skip_out = (s & 1) && s + 2 < S && tokL[(s >> 1) + 1] != cls;
+    const bool skip = fwd ? skip_in : skip_out;
+    if (fwd) {  // the state rows: first of its class, next of its class (blank: the even states; a label: its repeats)
+        int first = valid, next = -1;
+        if (valid && (s & 1)) {
+            for (int j = 0; j < (s >> 1); ++j)
+                if (tokL[j] == cls) { first = 0; break; }
+            for (int j = (s >> 1) + 1; j < U; ++j)
+                if (tokL[j] == cls) { next = 2 * j + 1; break; }
+        } else if (valid) {
+            first = s == 0;
+            next = s + 2 < S ? s + 2 : -1;
+        }
+        W.cls[h * Wp + s] = valid ? cls : -1;
+        W.skp[h * Wp + s] = (int)skip_in | (first << 1);
+        W.nxt[h * Wp + s] = next;
+    }
+    const float *xs = x + (long long)b * stride_b + cls;
+    auto value = [&](int t) __attribute__((always_inline)) {  // t in [0, T_n)
+        float e = xs[(long long)t * stride_t];
+        if constexpr (LOGITS) e -= lse[(size_t)t * B + b];
+        return fmaxf(e, NEG);
+    };
+    // frame of step j: alpha walks up from 0, beta down from T_n - 1
+    auto frame = [&](int j) __attribute__((always_inline)) { return fwd ? j : Tn - 1 - j; };
+    float *out = (fwd ? W.alpha : W.beta) + h * (size_t)T * Wp + s;
+    double *offs = (fwd ? W.off_a : W.off_b) + h * (size_t)T;
+
+    float cur[UNR], nx[UNR];
+    auto load = [&](float *dst, int j0) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < UNR; ++i) dst[i] = value(frame(min(j0 + i, Tn - 1)));
+    };
+    float a = (fwd ? s == 0 : s == S - 1) ? 0.0f : NEG;
+    double off = 0.0;  // sum of the subtracted maxima (identical in every thread)
+    load(cur, 0);
+    for (int j0 = 0; j0 < Tn; j0 += UNR) {
+        load(nx, j0 + UNR);
+#pragma unroll
+        for (int i = 0; i < UNR; ++i) {
+            const int j = j0 + i;
+            if (j < Tn) {  // workgroup-uniform
+                float q1, q2;
+                if (fwd) shift_up<MULTI>(E, a, j, q1, q2);
+                else shift_down<MULTI>(E, a, j, q1, q2);
+                a = sum_step(cur[i], a, q1, q2, skip, valid);
+                if (i == UNR - 1) a = renorm<MULTI>(E, a, j / RENORM, off);  // j = RENORM - 1 (mod RENORM)
+                out[(size_t)frame(j) * Wp] = a;
+                if (s == 0) offs[frame(j)] = off;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < UNR; ++i) cur[i] = nx[i];
+    }
+    if (fwd) {
+        if (s == S - 1) E.fin[0] = a;
+        if (s == S - 2) E.fin[1] = a;  // S == 1: stays NEG
+        __syncthreads();
+        if (s == 0) {
+            const float fa0 = E.fin[0], fa1 = E.fin[1], ma = fmaxf(fa0, fa1);
+            if (ma > NEG_HALF) {
+                const double ll = off + (double)ma + log(exp((double)(fa0 - ma)) + exp((double)(fa1 - ma)));
+                W.ll[h] = ll;
+                full[h] = (float)ll;
+            } else {  // no path reaches the end: infeasible
+                refuse(-__builtin_inff());
+            }
+        }
+    }
+}
+
+// backward.  grid = (T, B), block = 256: row (t, b) of d sum_k g[b,k] * full[b,k] / d x, written once.  First the whole
+// row -- zeros, or -(sum of the live g) * softmax for logits -- then, hypothesis by hypothesis in increasing k, the first
+// state of every class walks its chain in increasing state order and adds g[b,k] * occ_k to the class's entry of the row,
+// which the workgroup revisits in global memory: any C, no table of classes, no atomics.  One barrier per live
+// hypothesis: e[] alternates, and the barrier that completes hypothesis k's e[] also orders every earlier store to the
+// row (the fill, the entries of the hypotheses before) ahead of k's read-modify-writes.
+template <bool LOGITS>
+__global__ __launch_bounds__(256) void ctc_nbest_grad_kernel(Nbl W, const float *__restrict__ x, long long stride_t,
+                                                             long long stride_b, const float *__restrict__ lse,
+                                                             const int *__restrict__ Tn_,
+                                                             const float *__restrict__ grad_scores, int B, int N, int T,
+                                                             int C, float *g) {
+    __shared__ float e[2][MAX_WAVES * 64];
+    __shared__ float gsum;
+    __shared__ int nlive;
+    const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, Wp = W.Wp;
+    const int Tn = clampi(Tn_[b], 1, T);
+    const bool in_time = t < Tn;  // workgroup-uniform; rows t >= T_b of x are never read
+    float *out = g + ((size_t)t * B + b) * C;
+    const float *in = x + (long long)t * stride_t + (long long)b * stride_b;
+    const double *lls = W.ll + (size_t)b * N;
+    const float *gs = grad_scores + (size_t)b * N;
+    if (in_time) {
+        if (tid == 0) {  // in increasing k; the weight of a dead entry is never loaded
+            float sum = 0.0f;
+            int n = 0;
+            for (int k = 0; k < N; ++k)
+                if (lls[k] > (double)NEG_HALF) {
+                    sum += gs[k];
+                    ++n;
+                }
+            gsum = sum;
+            nlive = n;
+        }
+        __syncthreads();
+    }
+    const bool live = in_time && nlive > 0;  // workgroup-uniform
+    const float l = (LOGITS && live) ? lse[(size_t)t * B + b] : 0.0f;
+    const float gt = live ? gsum : 0.0f;
+    // the whole row once: zeros, or -gt * softmax
+    auto fill = [&](float v) __attribute__((always_inline)) { return (LOGITS && live) ? 0.0f - gt * expf(v - l) : 0.0f; };
+    if (C % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
+        (!LOGITS || (reinterpret_cast<uintptr_t>(in) & 15) == 0)) {
+        v4f *out4 = reinterpret_cast<v4f *>(out);
+        for (int i = tid; i < C / 4; i += 256) {
+            v4f v = {0.f, 0.f, 0.f, 0.f};
+            if (LOGITS && live) {
+                const v4f u = reinterpret_cast<const v4f *>(in)[i];
+                v.x = fill(u.x); v.y = fill(u.y); v.z = fill(u.z); v.w = fill(u.w);
+            }
+            out4[i] = v;
+        }
+    } else {
+        for (int i = tid; i < C; i += 256) out[i] = (LOGITS && live) ? fill(in[i]) : 0.0f;
+    }
+    if (!live) return;
+    int buf = 0;
+    for (int k = 0; k < N; ++k) {
+        const size_t h = (size_t)b * N + k;
+        const double ll = lls[k];
+        if (!(ll > (double)NEG_HALF)) continue;  // workgroup-uniform
+        const float gk = gs[k];
+        const int *cls = W.cls + h * Wp, *skp = W.skp + h * Wp, *nxt = W.nxt + h * Wp;
+        const double off = W.off_a[h * T + t] + W.off_b[h * T + t] - ll;
+        float *ek = e[buf];
+        for (int s = tid; s < Wp; s += 256) {
+            const size_t o = (h * T + t) * Wp + s;
+            const int c = cls[s];
+            float v = 0.0f;
+            if (c >= 0 && c < C) {
+                const float val = fmaxf(LOGITS ? in[c] - l : in[c], NEG);
+                const double arg = off + ((double)W.alpha[o] + (double)W.beta[o] - (double)val);
+                v = expf((float)fmax(arg, -1.0e30));
+            }
+            ek[s] = v;
+        }
+        __syncthreads();
+        for (int s = tid; s < Wp; s += 256) {
+            const int c = cls[s];
+            if ((skp[s] & 2) && c >= 0 && c < C) {  // first state of its class: sums the class in state order
+                float occ = 0.0f;
+                for (int q = s; q >= 0; q = nxt[q]) occ += ek[q];
+                out[c] += gk * occ;
+            }
+        }
+        buf ^= 1;
+    }
+}
+
 // what the n-best call refuses, dimensions first
 int check_nbest_dims(int B, int N, int T, int U) {
     if (B <= 0 || N <= 0 || T <= 0 || U < 0) return PIKA_EINVAL;
     if (U > 511 || B > 65535 || N > 65535) return PIKA_ETOOBIG;  // 2U+1 <= 1024; N and B are the grid's extents
     size_t n;
     if (__builtin_mul_overflow((size_t)B * (size_t)N, (size_t)nbest_groups(T) * (size_t)state_width(U), &n))
+        return PIKA_ETOOBIG;
+    return PIKA_OK;
+}
+
+// the n-best loss's workspace: two planes, two offset rows, ll, three state rows
+inline size_t nbest_loss_bytes(int B, int N, int T, int U) {
+    const size_t hn = (size_t)B * N, Wp = (size_t)state_width(U);
+    return 8 * hn * T * Wp + 16 * hn * T + 8 * hn + 12 * hn * Wp;
+}
+int check_nbest_loss_dims(int B, int N, int T, int U) {
+    if (B <= 0 || N <= 0 || T <= 0 || U < 0) return PIKA_EINVAL;
+    if (U > 511 || B > 65535 || N > 65535) return PIKA_ETOOBIG;  // 2U+1 <= 1024; N and B are the grid's extents
+    size_t n;  // the small rows together stay below 24 times the cells of one plane
+    if (__builtin_mul_overflow((size_t)B * (size_t)N, (size_t)T * (size_t)state_width(U), &n) || n > SIZE_MAX / 32)
         return PIKA_ETOOBIG;
     return PIKA_OK;
 }
@@ -773,6 +1033,52 @@ int pika_ctc_nbest_align(const float *x, long long stride_t, long long stride_b,
         else PIKA_NBEST_LAUNCH(true, false);
     }
 #undef PIKA_NBEST_LAUNCH
+    return (int)hipGetLastError();
+}
+
+size_t pika_ctc_nbest_loss_workspace_bytes(int B, int N, int T, int U_max) {
+    if (check_nbest_loss_dims(B, N, T, U_max)) return 0;
+    return nbest_loss_bytes(B, N, T, U_max);
+}
+
+int pika_ctc_nbest_loss_forward(const float *x, long long stride_t, long long stride_b, const float *lse,
+                                const int *input_lengths, const int *tokens, const int *lengths, int B, int N, int L,
+                                int T, int C, int blank, int U_max, float *full_scores, void *workspace, void *stream) {
+    if (L <= 0 || C <= 0 || blank < 0 || blank >= C) return PIKA_EINVAL;
+    if (int rc = check_nbest_loss_dims(B, N, T, U_max)) return rc;
+    if (!x || !input_lengths || !tokens || !lengths || !full_scores || !workspace) return PIKA_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Nbl W = carve_nbest(workspace, B, N, T, U_max);
+    const dim3 grid(2, (unsigned)N, (unsigned)B), block((unsigned)W.Wp);
+#define PIKA_NBEST_LAUNCH(MULTI, LOGITS)                                                                             \
+    hipLaunchKernelGGL((ctc_nbest_loss_kernel<MULTI, LOGITS>), grid, block, 0, s, x, stride_t, stride_b, lse,        \
+                       input_lengths, tokens, lengths, B, N, L, T, C, blank, U_max, full_scores, W)
+    if (W.Wp == 64) {
+        if (lse) PIKA_NBEST_LAUNCH(false, true);
+        else PIKA_NBEST_LAUNCH(false, false);
+    } else {
+        if (lse) PIKA_NBEST_LAUNCH(true, true);
+        else PIKA_NBEST_LAUNCH(true, false);
+    }
+#undef PIKA_NBEST_LAUNCH
+    return (int)hipGetLastError();
+}
+
+int pika_ctc_nbest_loss_backward(const float *x, long long stride_t, long long stride_b, const float *lse,
+                                 const int *input_lengths, int B, int N, int T, int C, int blank, int U_max,
+                                 const float *grad_scores, const void *workspace, float *grads, void *stream) {
+    if (C <= 0 || blank < 0 || blank >= C) return PIKA_EINVAL;
+    if (int rc = check_nbest_loss_dims(B, N, T, U_max)) return rc;
+    if (!x || !input_lengths || !grad_scores || !workspace || !grads) return PIKA_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Nbl W = carve_nbest(const_cast<void *>(workspace), B, N, T, U_max);
+    const dim3 grid((unsigned)T, (unsigned)B), block(256);
+    if (lse)
+        hipLaunchKernelGGL(ctc_nbest_grad_kernel<true>, grid, block, 0, s, W, x, stride_t, stride_b, lse, input_lengths,
+                           grad_scores, B, N, T, C, grads);
+    else
+        hipLaunchKernelGGL(ctc_nbest_grad_kernel<false>, grid, block, 0, s, W, x, stride_t, stride_b, lse,
+                           input_lengths, grad_scores, B, N, T, C, grads);
     return (int)hipGetLastError();
 }
 

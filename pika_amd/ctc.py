@@ -42,6 +42,13 @@ and, for the n-best list any of these searches returns, what `ctc_align` and `ct
         -> (full_scores (B,N), best_scores (B,N), starts (B,N,L), ends (B,N,L), token_scores (B,N,L))
     ctc_nbest_align_from_logits(logits, ...same...)
 
+and the same full-sum scores with autograd to the un-replicated input, and MWER training over the list on top of them:
+
+    ctc_nbest_loss(log_probs, input_lengths, tokens, lengths, blank=0, max_len=None) -> full_scores (B,N)
+    ctc_mwer_loss(log_probs, input_lengths, tokens, lengths, errors, blank=0, max_len=None, reduction='mean')
+    ctc_nbest_loss_from_logits(logits, ...), ctc_mwer_loss_from_logits(logits, ...)
+    ctc_nbest_errors(tokens, lengths, targets, target_lengths) -> errors (B,N)      host code: edit distances
+
 Differences from torch, on purpose:
 
 * THE GRADIENT IS THE TRUE DERIVATIVE.  torch's native CTC backward returns `exp(log_probs) - occ` for d/d log_probs,
@@ -900,7 +907,9 @@ class CtcBeamStream(object):
         return out
 
 
-def _nbest_align(x, what, input_lengths, tokens, lengths, blank, max_len, logits):
+def _nbest_input(x, what, input_lengths, tokens, lengths, blank, max_len, logits):
+    """The checks and device copies the n-best calls share: (x as (T,B,C) with unit class stride, detached; il i32;
+    lse (T,B) or None; tokens i32 (B,N,L); lengths i32 (B,N); max_len; unbatched)."""
     blank = int(blank)
     tokens, lengths = torch.as_tensor(tokens), torch.as_tensor(lengths)
     for name, t in (("tokens", tokens), ("lengths", lengths)):
@@ -924,8 +933,16 @@ def _nbest_align(x, what, input_lengths, tokens, lengths, blank, max_len, logits
         raise ValueError("%s is %s: tokens must be %s, got %s" % (
             what, tuple(x.shape[::2]) if unbatched else tuple(x.shape), "(N,L)" if unbatched else "(%d,N,L)" % B,
             tuple(tokens.shape)))
-    tokens = tokens.to(x.device, torch.int32).contiguous()
-    lengths = lengths.to(x.device, torch.int32).contiguous()
+    tokens = tokens.to(x.device, torch.int32).contiguous().reshape(B, N, L)
+    lengths = lengths.to(x.device, torch.int32).contiguous().reshape(B, N)
+    return x, il, lse, tokens, lengths, max_len, unbatched
+
+
+def _nbest_align(x, what, input_lengths, tokens, lengths, blank, max_len, logits):
+    blank = int(blank)
+    x, il, lse, tokens, lengths, max_len, unbatched = _nbest_input(x, what, input_lengths, tokens, lengths, blank,
+                                                                   max_len, logits)
+    (T, B, C), (N, L) = x.shape, tokens.shape[1:]
     lib = _lib.lib()
     nbytes = lib.pika_ctc_nbest_align_scratch_bytes(B, N, T, max_len)
     if nbytes == 0:
@@ -973,8 +990,8 @@ def ctc_nbest_align(log_probs, input_lengths, tokens, lengths, blank=0, max_len=
     entry), which tells it from an infeasible one.  The empty hypothesis has full = best = the sum of the blank's
     log-probs.
 
-    No autograd, no host synchronisation; capturable in a `torch.cuda.graph` with all lengths on the device; two runs
-    give bit-identical outputs.
+    No autograd here -- `ctc_nbest_loss` returns the same `full_scores` with their gradient; no host synchronisation;
+    capturable in a `torch.cuda.graph` with all lengths on the device; two runs give bit-identical outputs.
 
     Streams: `CtcBeamStream.results` tails are relative to the last commit, and a stream does not keep its
     log-probabilities.  A caller who keeps them aligns committed + tail against the whole input."""
@@ -985,3 +1002,159 @@ def ctc_nbest_align_from_logits(logits, input_lengths, tokens, lengths, blank=0,
     """`ctc_nbest_align` of log_softmax(logits, -1) without materialising the log-probabilities: every value is
     logit - lse rounded once, the rows' log-sum-exps coming from the decoders' row pass."""
     return _nbest_align(logits, "logits", input_lengths, tokens, lengths, blank, max_len, True)
+
+
+class _NbestLossFn(torch.autograd.Function):
+    """full_scores (B,N) of an n-best list; backward writes the dense (T,B,C) gradient once, every hypothesis's
+    occupancies already weighted by grad_output.  `x` carries the graph; `xd` is the same data as the kernels read it."""
+
+    @staticmethod
+    def forward(ctx, x, xd, lse, il, tokens, lengths, blank, max_len):
+        lib = _lib.lib()
+        (T, B, C), (N, L) = xd.shape, tokens.shape[1:]
+        nbytes = lib.pika_ctc_nbest_loss_workspace_bytes(B, N, T, max_len)
+        if nbytes == 0:
+            raise ValueError("(B,N,T,max_len) = (%d,%d,%d,%d) not supported" % (B, N, T, max_len))
+        with torch.cuda.device(xd.device):
+            full = torch.empty((B, N), dtype=torch.float32, device=xd.device)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=xd.device)
+            _lib.check(lib.pika_ctc_nbest_loss_forward(_ptr(xd), xd.stride(0), xd.stride(1), _ptr(lse), _ptr(il),
+                                                       _ptr(tokens), _ptr(lengths), B, N, L, T, C, blank, max_len,
+                                                       _ptr(full), _ptr(ws), _stream()), "pika_ctc_nbest_loss_forward")
+        ctx.save_for_backward(*((xd, il, ws) + ((lse,) if lse is not None else ())))
+        ctx.dims = (T, B, C, N, blank, max_len, tuple(x.shape))
+        return full
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_scores):
+        T, B, C, N, blank, max_len, shape = ctx.dims
+        xd, il, ws = ctx.saved_tensors[:3]
+        lse = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+        lib = _lib.lib()
+        gs = grad_scores.to(torch.float32).contiguous()
+        with torch.cuda.device(ws.device):
+            grads = torch.empty((T, B, C), dtype=torch.float32, device=ws.device)
+            _lib.check(lib.pika_ctc_nbest_loss_backward(_ptr(xd), xd.stride(0), xd.stride(1), _ptr(lse), _ptr(il), B, N,
+                                                        T, C, blank, max_len, _ptr(gs), _ptr(ws), _ptr(grads),
+                                                        _stream()), "pika_ctc_nbest_loss_backward")
+        return grads.reshape(shape), None, None, None, None, None, None, None
+
+
+def _nbest_loss(x, what, input_lengths, tokens, lengths, blank, max_len, logits):
+    blank = int(blank)
+    xd, il, lse, tokens, lengths, max_len, unbatched = _nbest_input(x, what, input_lengths, tokens, lengths, blank,
+                                                                    max_len, logits)
+    full = _NbestLossFn.apply(x, xd, lse, il, tokens, lengths, blank, max_len)
+    return full[0] if unbatched else full
+
+
+def ctc_nbest_loss(log_probs, input_lengths, tokens, lengths, blank=0, max_len=None):
+    """The full-sum scores of an n-best list, DIFFERENTIABLE: `ctc_nbest_align`'s `full_scores` (B,N) f32 -- per
+    hypothesis -ctc_loss(reduction='none') of that transcript, with the loss's numerics -- carrying autograd to
+    `log_probs`, without replicating the (T,B,C) input N times.  Whatever is built on the scores with torch (MWER as
+    `ctc_mwer_loss`, sMBR-style risks, cross-entropy over the list) back-propagates through ONE dense (T,B,C) gradient.
+
+    Arguments, checks, strides, the (T,C) form (tokens (N,L), lengths (N,), result (N,)) and `max_len` are
+    `ctc_nbest_align`'s, and so is the classification of an entry: a missing one (length < 0) and an infeasible one
+    (T_b < U + adjacent repeats, a token outside [0,C), a token equal to blank) score -inf, one longer than max_len NaN.
+    Such an entry is dead: it adds nothing to the gradient, and the gradient that arrives for it is ignored -- NaN or
+    +-inf there (a softmax over -inf scores produces them) never reaches the input's gradient.
+
+    The gradient is the true derivative, as `ctc_loss`'s: for weights g = d L / d full_scores,
+    grad[t,b,c] = sum_k g[b,k] * occ_k(t,c) for t < T_b and exactly 0 beyond; it is dense, contiguous and written once,
+    the hypotheses summed in increasing k without atomics, so two runs are bit-identical.  No double backward.  The
+    backward workspace, 8 * B * N * T * Wp bytes of planes (Wp = 2 * max_len + 1 rounded up to 64) plus small rows, is
+    filled whether or not the input requires grad; pass `max_len` = the longest hypothesis to keep it small.
+
+    No host synchronisation; forward and backward are capturable in a `torch.cuda.graph` with all lengths on the
+    device."""
+    return _nbest_loss(log_probs, "log_probs", input_lengths, tokens, lengths, blank, max_len, False)
+
+
+def ctc_nbest_loss_from_logits(logits, input_lengths, tokens, lengths, blank=0, max_len=None):
+    """`ctc_nbest_loss` of log_softmax(logits, -1) without materialising the log-probabilities: every value is
+    logit - lse rounded once, the rows' log-sum-exps coming from the decoders' row pass, and the backward writes
+    d/d logits: grad[t,b,c] = sum_k g[b,k] * occ_k(t,c) - (sum of g over the live entries of b) * softmax_t(c)."""
+    return _nbest_loss(logits, "logits", input_lengths, tokens, lengths, blank, max_len, True)
+
+
+def _mwer(full, errors, reduction):
+    if reduction not in ("none", "mean", "sum"):
+        raise ValueError("%r is not a valid value for reduction" % (reduction,))
+    errors = torch.as_tensor(errors)
+    if not errors.is_floating_point():
+        raise TypeError("errors must be a float tensor, got %s" % errors.dtype)
+    if tuple(errors.shape) != tuple(full.shape):
+        raise ValueError("errors must be %s as the n-best list, got %s" % (tuple(full.shape), tuple(errors.shape)))
+    live = torch.isfinite(full)                               # a dead entry scores -inf or NaN
+    err = torch.where(live, errors.to(full.device, full.dtype), torch.zeros_like(full))
+    score = torch.where(live, full, torch.full_like(full, float("-inf")))
+    top = score.detach().max(-1, keepdim=True).values
+    top = torch.where(torch.isfinite(top), top, torch.zeros_like(top))     # no live entry: exp(-inf - 0) = 0
+    w = torch.where(live, (score - top).exp(), torch.zeros_like(full))
+    total = w.sum(-1, keepdim=True)
+    p = w / torch.where(total > 0, total, torch.ones_like(total))
+    count = live.sum(-1, keepdim=True).clamp(min=1).to(full.dtype)
+    risk = (p * (err - err.sum(-1, keepdim=True) / count)).sum(-1)
+    if reduction == "mean":
+        return risk.mean()
+    if reduction == "sum":
+        return risk.sum()
+    return risk
+
+
+def ctc_mwer_loss(log_probs, input_lengths, tokens, lengths, errors, blank=0, max_len=None, reduction='mean'):
+    """Minimum word error rate (MWER / minimum Bayes risk) training over an n-best list, the CTC counterpart of
+    `pika_amd.mbr`: plain torch on top of `ctc_nbest_loss`, one dense gradient whatever N is.
+
+    `errors` (B,N) -- (N,) for (T,C) input -- is a float tensor of per-hypothesis error counts supplied by the caller
+    (`ctc_nbest_errors` gives token edit distances), on the CPU or the device.  Over the LIVE entries of every utterance
+    (finite full-sum score): P = softmax(full_scores), risk_b = sum_k P_k * (errors_k - mean_live(errors)).  Dead entries
+    (missing, infeasible, longer than max_len: `ctc_nbest_loss`) get weight 0 and their `errors` are ignored; an
+    utterance with no live entry has risk 0 and a zero gradient.  reduction: 'none' -> (B,), 'sum', 'mean' (the average
+    over the batch).  The other arguments, synchronisation and graph capture are `ctc_nbest_loss`'s."""
+    full = ctc_nbest_loss(log_probs, input_lengths, tokens, lengths, blank, max_len)
+    return _mwer(full, errors, reduction)
+
+
+def ctc_mwer_loss_from_logits(logits, input_lengths, tokens, lengths, errors, blank=0, max_len=None, reduction='mean'):
+    """`ctc_mwer_loss` of log_softmax(logits, -1) without materialising the log-probabilities."""
+    full = ctc_nbest_loss_from_logits(logits, input_lengths, tokens, lengths, blank, max_len)
+    return _mwer(full, errors, reduction)
+
+
+def ctc_nbest_errors(tokens, lengths, targets, target_lengths):
+    """Token edit (Levenshtein) distances of an n-best list to the reference transcripts, the `errors` of
+    `ctc_mwer_loss`: (B,N) float32 on the device of `tokens` (the CPU for a sequence).
+
+    tokens (B,N,L) and lengths (B,N) as a search returns them; targets (B,S) padded and target_lengths (B,), int32 or
+    int64, on either side.  (N,L) / (N,) with 1-D targets and a scalar length for one utterance: (N,).  An entry with
+    length < 0 (missing) gets 0; a length beyond L counts L tokens.  HOST CODE (`pika_amd.mbr.edit_distances`): inputs
+    on the device are copied to the host, which SYNCHRONISES -- call it outside a captured graph."""
+    from .mbr import edit_distances
+    tokens, lengths = torch.as_tensor(tokens), torch.as_tensor(lengths)
+    targets, target_lengths = torch.as_tensor(targets), torch.as_tensor(target_lengths)
+    for name, t in (("tokens", tokens), ("lengths", lengths), ("targets", targets), ("target_lengths", target_lengths)):
+        if t.dtype not in (torch.int32, torch.int64):
+            raise TypeError("%s must be int32 or int64, got %s" % (name, t.dtype))
+    unbatched = tokens.dim() == 2
+    if unbatched:
+        tokens, lengths = tokens.unsqueeze(0), lengths.unsqueeze(0)
+        targets, target_lengths = targets.reshape(1, -1), target_lengths.reshape(1)
+    if tokens.dim() != 3 or tuple(lengths.shape) != tuple(tokens.shape[:2]):
+        raise ValueError("tokens must be (B,N,L) and lengths (B,N) -- (N,L) and (N,) for one utterance -- got %s and %s"
+                         % (tuple(tokens.shape), tuple(lengths.shape)))
+    B, N, L = tokens.shape
+    if targets.dim() != 2 or targets.shape[0] != B or tuple(target_lengths.shape) != (B,):
+        raise ValueError("targets must be (B,S) = (%d,S) and target_lengths (%d,), got %s and %s"
+                         % (B, B, tuple(targets.shape), tuple(target_lengths.shape)))
+    tok, ln = tokens.cpu().tolist(), lengths.cpu().tolist()
+    tg, tl = targets.cpu().tolist(), target_lengths.cpu().tolist()
+    where = [(b, k) for b in range(B) for k in range(N) if ln[b][k] >= 0]
+    dist = edit_distances([(tok[b][k][:min(ln[b][k], L)], tg[b][:max(0, min(tl[b], len(tg[b])))]) for b, k in where])
+    out = torch.zeros((B, N), dtype=torch.float32)
+    for (b, k), d in zip(where, dist):
+        out[b, k] = float(d)
+    out = out.to(tokens.device)
+    return out[0] if unbatched else out
