@@ -23,17 +23,24 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def chunk_lists(numels):
+    """(chunk_tensor, chunk_off, chunk_len) of include/pika_optim.h for a list of tensor sizes: every tensor cut into
+    chunks of <= CHUNK elements, an empty tensor into none."""
+    ct, co, cl = [], [], []
+    for t, n in enumerate(numels):
+        for off in range(0, n, CHUNK):
+            ct.append(t)
+            co.append(off)
+            cl.append(min(CHUNK, n - off))
+    return ct, co, cl
+
+
 class _Tables(object):
     """Device chunk tables for a fixed list of tensor sizes + pinned staging for the pointer tables (gradients are
     re-allocated every step by zero_grad(set_to_none=True), so their addresses are uploaded per call)."""
 
     def __init__(self, numels, device):
-        ct, co, cl = [], [], []
-        for t, n in enumerate(numels):
-            for off in range(0, n, CHUNK):
-                ct.append(t)
-                co.append(off)
-                cl.append(min(CHUNK, n - off))
+        ct, co, cl = chunk_lists(numels)
         self.n_chunks, self.n = len(ct), len(numels)
         self.ct = torch.tensor(ct, dtype=torch.int32, device=device)
         self.co = torch.tensor(co, dtype=torch.int64, device=device)
@@ -133,13 +140,20 @@ class SGD(_TorchSGD):
               and not any(p.grad.is_sparse for p in params))
         if not ok:
             return super().step(closure)
-        first = "momentum_buffer" not in self.state[params[0]] or self.state[params[0]]["momentum_buffer"] is None
+        # "first" is per parameter, as in torch: a step in which some parameter had no gradient went to the stock
+        # implementation and left buffers for the others only.  No buffer anywhere: the kernel's first-step form
+        # (b = g).  Some: the missing ones start as zeros and every tensor takes the general form, 0 * m + g == g.
+        missing = [p for p in params if self.state[p].get("momentum_buffer") is None]
+        first = len(missing) == len(params)
         if first:
             flat = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=params[0].device)
             off = 0
             for p in params:
                 self.state[p]["momentum_buffer"] = flat[off:off + p.numel()].view(p.shape)
                 off += p.numel()
+        else:
+            for p in missing:
+                self.state[p]["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
         bufs = [self.state[p]["momentum_buffer"] for p in params]
         tb = _tables(params)
         lib = _lib.lib()

@@ -79,6 +79,6 @@ def adam_state(model, optim):
     ps = [p for p in model.parameters()]
     st = [optim.state[p] for p in ps]
     return (flat(model),
-            torch.cat([s["exp_avg"].reshape(-1) for s in st]).numpy().copy(),
-            torch.cat([s["exp_avg_sq"].reshape(-1) for s in st]).numpy().copy(),
+            torch.cat([s["exp_avg"].reshape(-1) for s in st]).cpu().numpy().copy(),
+            torch.cat([s["exp_avg_sq"].reshape(-1) for s in st]).cpu().numpy().copy(),
             np.array([float(s["step"]) for s in st]))

@@ -12,6 +12,7 @@ import torch.multiprocessing as mp
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bmuf_common as C  # noqa: E402
+import optim_common as Y  # noqa: E402
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bmuf_ws2.npz")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -138,6 +139,8 @@ def test_fused_kernels_match_reference_math(hip_device):
         assert torch.allclose(dpd.cpu(), ref_dp, rtol=1e-6, atol=1e-7)
         assert torch.allclose(Gd.cpu(), ref_G, rtol=1e-6, atol=1e-7)
         assert torch.equal(Ld, Gd)
+        y_dp, y_G = Y.bmuf_update(summed.cpu().numpy(), dp.numpy(), G.numpy(), world, bm, blr)   # the float32 yardstick: equal
+        assert Y.same(dpd.cpu().numpy(), y_dp) and Y.same(Gd.cpu().numpy(), y_G)
         flag = torch.zeros(1, dtype=torch.int32, device=hip_device)
         _lib.check(lib.pika_bmuf_nan_flag(delta.data_ptr(), n, flag.data_ptr(), st), "nan")
         assert flag.item() == 0
@@ -162,8 +165,10 @@ def test_trainer_on_hip_single_rank(hip_device, tmp_path):
     cpu_model = C.make_model(0)
     G = torch.from_numpy(C.flat(cpu_model))
     dprev = torch.zeros_like(G)
+    y_G, y_dprev = G.numpy().copy(), np.zeros(G.numel(), dtype=np.float32)     # the float32 yardstick's own run
     for rnd in range(C.ROUNDS):
         C.local_step(cpu_model, 0, rnd)
+        local = C.flat(cpu_model)
         with torch.no_grad():
             for p, q in zip(model.parameters(), cpu_model.parameters()):
                 p.copy_(q)
@@ -173,6 +178,8 @@ def test_trainer_on_hip_single_rank(hip_device, tmp_path):
         G = G - (1 + C.BM) * dprev
         torch.nn.utils.vector_to_parameters(G.clone(), cpu_model.parameters())
         assert np.allclose(C.flat(model), G.numpy(), rtol=1e-6, atol=1e-7)
+        y_dprev, y_G = Y.bmuf_update(y_G - local, y_dprev, y_G, 1, C.BM, C.BLR)
+        assert Y.same(C.flat(model), y_G) and Y.same(tr.delta_prev.cpu().numpy(), y_dprev), rnd
     dist.destroy_process_group()
 
 
@@ -289,3 +296,5 @@ def test_adam_moments_kernel_matches_the_torch_op_sequence(hip_device):
     for got_x, got_b, w in ((x1, b1, want[0]), (x2, b2, want[1])):
         assert torch.equal(got_x, got_b)
         assert torch.allclose(got_b, w, rtol=2e-7, atol=0), float((got_b - w).abs().max())
+    for x0, b0, got_b, cc in ((keep[0], keep[1], b1, c[0]), (keep[2], keep[3], b2, c[1])):     # the float32 yardstick: equal
+        assert Y.same(got_b.cpu().numpy(), Y.adam_moments(x0.cpu().numpy(), b0.cpu().numpy(), W, *cc))
