@@ -168,6 +168,27 @@ int pika_ctc_nbest_loss_backward(const float *x, long long stride_t, long long s
                                  const int *input_lengths, int B, int N, int T, int C, int blank, int U_max,
                                  const float *grad_scores, const void *workspace, float *grads, void *stream);
 
+/* n-best edit distances: the token edit (Levenshtein, unit costs) distance between every entry of a list `a` and every
+ * entry of a list `r` of the same utterance -- `a` an n-best list and `r` the reference transcript (Nr = 1) for the
+ * `errors` of MWER training; `a` = `r` = the list for the pairwise distances of MBR decoding.
+ *   a_tokens   i32 (B,Na,La)  entry (b,i) at a_tokens + (b Na + i) La
+ *   a_lengths  i32 (B,Na)     below 0: a missing entry; beyond La: La tokens
+ *   r_tokens   i32 (B,Nr,Lr), r_lengths i32 (B,Nr): likewise, beyond Lr: Lr tokens
+ *   out        i32 (B,Na,Nr)  out[b,i,j] = distance(a[b,i], r[b,j]); -1 where either entry is missing
+ * All contiguous.  Tokens are compared as plain int32, any value; what lies at or beyond an entry's length is never
+ * read.  An empty entry (length 0; La = 0 or Lr = 0, the token pointer may then be NULL) is at the other side's length
+ * from everything.  Every element of `out` is written; integer arithmetic, no atomics: two runs are identical.
+ * One wave per pair over a flat grid (no extent is bound by 65535): Myers' bit-vector recurrence in blocks of 64
+ * reference positions, the wave's ballot as the machine word -- La ceil(S / 64) steps for a pair instead of La S cells.
+ * PIKA_EINVAL for a negative size and, with B Na Nr > 0, a null pointer; PIKA_ETOOBIG for Lr > 4096 (64 blocks, one per
+ * lane) and for B Na Nr > 2^31 - 1; both before any launch.  B Na Nr = 0 succeeds and does nothing.
+ * pika_ctc_edit_distance_host: the same on HOST pointers, on the calling thread -- the same recurrence in the same block
+ * order with the match vector built by a loop; the CPU path of the Python functions and the reference of the tests. */
+int pika_ctc_edit_distance(const int *a_tokens, const int *a_lengths, int Na, int La, const int *r_tokens,
+                           const int *r_lengths, int Nr, int Lr, int B, int *out, void *stream);
+int pika_ctc_edit_distance_host(const int *a_tokens, const int *a_lengths, int Na, int La, const int *r_tokens,
+                                const int *r_lengths, int Nr, int Lr, int B, int *out);
+
 #ifdef __cplusplus
 }
 #endif

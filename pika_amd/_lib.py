@@ -50,6 +50,8 @@ SIGNATURES = {
     "pika_ctc_nbest_loss_workspace_bytes": (_sz, [_i] * 4),
     "pika_ctc_nbest_loss_forward": (_i, [_vp, _ll, _ll] + [_vp] * 4 + [_i] * 7 + [_vp] * 3),
     "pika_ctc_nbest_loss_backward": (_i, [_vp, _ll, _ll] + [_vp] * 2 + [_i] * 6 + [_vp] * 4),
+    "pika_ctc_edit_distance": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "pika_ctc_edit_distance_host": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
     # include/pika_ctc_decode.h
     "pika_ctc_decode_rows": (_i, [_vp, _ll, _ll, _vp] + [_i] * 6 + [_vp] * 5),
     "pika_ctc_greedy": (_i, [_vp] * 4 + [_i] * 4 + [_vp] * 5),

@@ -49,6 +49,13 @@ and the same full-sum scores with autograd to the un-replicated input, and MWER 
     ctc_nbest_loss_from_logits(logits, ...), ctc_mwer_loss_from_logits(logits, ...)
     ctc_nbest_errors(tokens, lengths, targets, target_lengths) -> errors (B,N)      host code: edit distances
 
+and the same edit distances on the device (csrc/ctc_edit.hip), which closes the chain search -> errors -> MWER loss into
+one capturable sequence, with MBR decoding over the list on top of them:
+
+    ctc_nbest_edit_distance(tokens, lengths, targets, target_lengths) -> errors (B,N)   = ctc_nbest_errors, no host sync
+    ctc_nbest_pairwise_distance(tokens, lengths) -> distances (B,N,N)
+    ctc_nbest_mbr_decode(tokens, lengths, scores, scale=1.0) -> (best (B,), risks (B,N))
+
 Differences from torch, on purpose:
 
 * THE GRADIENT IS THE TRUE DERIVATIVE.  torch's native CTC backward returns `exp(log_probs) - occ` for d/d log_probs,
@@ -1158,3 +1165,128 @@ def ctc_nbest_errors(tokens, lengths, targets, target_lengths):
         out[b, k] = float(d)
     out = out.to(tokens.device)
     return out[0] if unbatched else out
+
+
+MAX_EDIT_REF = 4096     # PIKA_EDIT_MAX_REF: 64 blocks of 64 reference positions, one block's state per lane
+
+
+def _edit_list(tokens, lengths, who):
+    """The checks on an n-best list the edit-distance calls share: (tokens (B,N,L), lengths (B,N), unbatched)."""
+    tokens, lengths = torch.as_tensor(tokens), torch.as_tensor(lengths)
+    for name, t in (("tokens", tokens), ("lengths", lengths)):
+        if t.dtype not in (torch.int32, torch.int64):
+            raise TypeError("%s must be int32 or int64, got %s" % (name, t.dtype))
+    unbatched = tokens.dim() == 2
+    if unbatched:
+        tokens, lengths = tokens.unsqueeze(0), lengths.unsqueeze(0)
+    if tokens.dim() != 3 or tuple(lengths.shape) != tuple(tokens.shape[:2]):
+        raise ValueError("%s: tokens must be (B,N,L) and lengths (B,N) -- (N,L) and (N,) for one utterance -- got %s and %s"
+                         % (who, tuple(tokens.shape[1:] if unbatched else tokens.shape),
+                            tuple(lengths.shape[1:] if unbatched else lengths.shape)))
+    return tokens, lengths, unbatched
+
+
+def _edit_distance(a_tokens, a_lengths, r_tokens, r_lengths):
+    """(B,Na,La), (B,Na), (B,Nr,Lr), (B,Nr) on one device -> (B,Na,Nr) int32, -1 where either entry is missing: the
+    kernel for device tensors (no synchronisation), the host entry for CPU tensors."""
+    dev = a_tokens.device
+    a_tokens, a_lengths, r_tokens, r_lengths = (t.to(dev, torch.int32).contiguous()
+                                                for t in (a_tokens, a_lengths, r_tokens, r_lengths))
+    (B, Na, La), (Nr, Lr) = a_tokens.shape, r_tokens.shape[1:]
+    out = torch.empty((B, Na, Nr), dtype=torch.int32, device=dev)
+    lib = _lib.lib()
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            _lib.check(lib.pika_ctc_edit_distance(_ptr(a_tokens), _ptr(a_lengths), Na, La, _ptr(r_tokens),
+                                                  _ptr(r_lengths), Nr, Lr, B, _ptr(out), _stream()),
+                       "pika_ctc_edit_distance")
+    else:
+        _lib.check(lib.pika_ctc_edit_distance_host(_ptr(a_tokens), _ptr(a_lengths), Na, La, _ptr(r_tokens),
+                                                   _ptr(r_lengths), Nr, Lr, B, _ptr(out)),
+                   "pika_ctc_edit_distance_host")
+    return out
+
+
+def ctc_nbest_edit_distance(tokens, lengths, targets, target_lengths):
+    """`ctc_nbest_errors` WITHOUT the host: the token edit (Levenshtein) distances of an n-best list to the reference
+    transcripts, (B,N) float32 on the device of `tokens`, `torch.equal` to `ctc_nbest_errors` on the same inputs.
+
+    Arguments, shapes, dtypes, the (N,L) / (N,) form with 1-D targets and a scalar length, and the exceptions are
+    `ctc_nbest_errors`'s.  A missing entry (length < 0) gets 0; a length beyond L counts L tokens; the target length is
+    clamped to [0, S] (a negative one is an empty transcript).  ValueError for S > 4096.  Tokens are compared as int32.
+
+    With all four tensors on the device of `tokens` there is no host synchronisation and the call can be captured in a
+    `torch.cuda.graph` -- search, this, and `ctc_mwer_loss` forward and backward make ONE graph.  A tensor that lives
+    elsewhere is copied to that device first.  CPU `tokens` take the library's host entry (the same recurrence, one
+    thread).  One wave per (hypothesis, reference) pair, Myers' bit-vector recurrence (include/pika_ctc.h,
+    `pika_ctc_edit_distance`); integers throughout: two runs are identical.  No autograd."""
+    tokens, lengths, unbatched = _edit_list(tokens, lengths, "ctc_nbest_edit_distance")
+    targets, target_lengths = torch.as_tensor(targets), torch.as_tensor(target_lengths)
+    for name, t in (("targets", targets), ("target_lengths", target_lengths)):
+        if t.dtype not in (torch.int32, torch.int64):
+            raise TypeError("%s must be int32 or int64, got %s" % (name, t.dtype))
+    if unbatched:
+        targets, target_lengths = targets.reshape(1, -1), target_lengths.reshape(1)
+    B = tokens.shape[0]
+    if targets.dim() != 2 or targets.shape[0] != B or tuple(target_lengths.shape) != (B,):
+        raise ValueError("targets must be (B,S) = (%d,S) and target_lengths (%d,), got %s and %s"
+                         % (B, B, tuple(targets.shape), tuple(target_lengths.shape)))
+    S = int(targets.shape[1])
+    if S > MAX_EDIT_REF:
+        raise ValueError("targets are %d wide: at most %d reference tokens" % (S, MAX_EDIT_REF))
+    dev = tokens.device
+    tl = target_lengths.to(dev).clamp(min=0, max=S)         # with torch: below 0 is empty here, not "missing"
+    out = _edit_distance(tokens, lengths.to(dev), targets.to(dev).unsqueeze(1), tl.unsqueeze(1))
+    out = out[:, :, 0].clamp(min=0).to(torch.float32)       # -1, a missing entry: 0
+    return out[0] if unbatched else out
+
+
+def ctc_nbest_pairwise_distance(tokens, lengths):
+    """The token edit distances between the entries of an n-best list: (B,N,N) float32 -- (N,N) for (N,L) / (N,) -- on
+    the device of `tokens`, d[b,i,j] = distance(entry i, entry j) of utterance b.  Exactly symmetric, zero on the
+    diagonal, and 0 wherever either entry is missing (length < 0); a length beyond L counts L tokens.  ValueError for
+    L > 4096.  tokens / lengths as a search returns them, int32 or int64.  Device tensors: the kernel of
+    `ctc_nbest_edit_distance` with the list on both sides, no host synchronisation, capturable; CPU: the host entry."""
+    tokens, lengths, unbatched = _edit_list(tokens, lengths, "ctc_nbest_pairwise_distance")
+    if tokens.shape[2] > MAX_EDIT_REF:
+        raise ValueError("tokens are %d wide: at most %d tokens per entry" % (tokens.shape[2], MAX_EDIT_REF))
+    lengths = lengths.to(tokens.device)
+    out = _edit_distance(tokens, lengths, tokens, lengths).clamp(min=0).to(torch.float32)
+    return out[0] if unbatched else out
+
+
+def ctc_nbest_mbr_decode(tokens, lengths, scores, scale=1.0):
+    """Minimum-Bayes-risk decoding over an n-best list: the entry with the least expected token edit distance to the
+    list under the list's own posterior.  Returns (best (B,) int64, risks (B,N) float32) -- a 0-d index and (N,) for
+    (N,L) / (N,) / (N,) -- on the device of `tokens`.
+
+    `scores` (B,N) float: a search's `scores` or `ctc_nbest_align`'s `full_scores`.  An entry is LIVE when its length is
+    at least 0 and its score is finite.  P = softmax(scale * scores) over the live entries; risks[b,i] = sum_j P_j *
+    d(i,j) for live i (d: `ctc_nbest_pairwise_distance`) and +inf for a dead one; best[b] = the arg-min, the lowest index
+    on ties, -1 for an utterance with no live entry.  Plain torch on the pairwise distances: no host synchronisation, no
+    autograd; ValueError for L > 4096."""
+    tokens, lengths, unbatched = _edit_list(tokens, lengths, "ctc_nbest_mbr_decode")
+    scores = torch.as_tensor(scores)
+    if not scores.is_floating_point():
+        raise TypeError("scores must be a float tensor, got %s" % scores.dtype)
+    if unbatched:
+        scores = scores.unsqueeze(0)
+    if tuple(scores.shape) != tuple(lengths.shape):
+        raise ValueError("scores must be %s as the n-best list, got %s" % (
+            tuple(lengths.shape[1:] if unbatched else lengths.shape), tuple(scores.shape[1:] if unbatched else scores.shape)))
+    dev = tokens.device
+    dist = ctc_nbest_pairwise_distance(tokens, lengths)                                     # (B,N,N)
+    scores = scores.detach().to(dev, torch.float32)
+    live = (lengths.to(dev) >= 0) & torch.isfinite(scores)
+    score = torch.where(live, float(scale) * scores, torch.full_like(scores, float("-inf")))
+    top = score.max(-1, keepdim=True).values
+    top = torch.where(torch.isfinite(top), top, torch.zeros_like(top))     # no live entry: exp(-inf - 0) = 0
+    w = torch.where(live, (score - top).exp(), torch.zeros_like(score))
+    total = w.sum(-1, keepdim=True)
+    p = w / torch.where(total > 0, total, torch.ones_like(total))
+    risks = torch.where(live, (p.unsqueeze(-2) * dist).sum(-1), torch.full_like(score, float("inf")))
+    index = torch.arange(risks.shape[-1], device=dev).expand_as(risks)
+    lowest = risks.min(-1, keepdim=True).values
+    best = torch.where(live & (risks == lowest), index, torch.full_like(index, risks.shape[-1])).min(-1).values
+    best = torch.where(live.any(-1), best, torch.full_like(best, -1))
+    return (best[0], risks[0]) if unbatched else (best, risks)
