@@ -189,6 +189,52 @@ int pika_ctc_edit_distance(const int *a_tokens, const int *a_lengths, int Na, in
 int pika_ctc_edit_distance_host(const int *a_tokens, const int *a_lengths, int Na, int La, const int *r_tokens,
                                 const int *r_lengths, int Nr, int Lr, int B, int *out);
 
+/* Long-form alignment: the best (Viterbi) path of ONE transcript per recording, with the state axis cut into tiles -- no
+ * limit of 511 labels and no fp32 plane: an hour of audio against its whole transcript.  The outputs per token are those
+ * of pika_ctc_nbest_align; the path is that of pika_ctc_align (same tie rule) wherever both can run.
+ *   x, stride_t, stride_b, lse, input_lengths   as pika_ctc_nbest_align: value_t(c) is x (lse NULL: log-probs) or
+ *                  logit - lse rounded once; anything below -1e30 (-inf, NaN) reads as -1e30; rows t >= T_b are never read
+ *   targets        i32 (B,U_max) padded; entries at or beyond target_lengths[b] are never read
+ *   target_lengths i32 (B,) U_b, clamped on the device to [0,U_max]
+ *   scores         f32 (B,)  the log-probability of the best path, fl32(fp64(v_end) + sum_{t<T_b} fp64(m_t))
+ *   starts, ends   i32 (B,U_max)  first and last frame (inclusive) of the run in which the path emits token j
+ *   token_scores   f32 (B,U_max)  sum over the run of value_t(y_j), in fp32 in increasing t
+ * Beyond a length starts / ends are -1 and token_scores -inf.  An INFEASIBLE transcript (a token outside [0,C), a token
+ * equal to blank, v_end <= -1e29: no path, e.g. T_b < U_b + adjacent repeats) has score -inf, times -1 and token scores
+ * -inf; nothing is read through a bad token.  Every output element is written; everything read from the length and token
+ * arrays bounds loops and stores through clamps; no atomics: two runs give bit-identical outputs.
+ *
+ * The recurrence, in fp32 over the states s of l' = (blank, y_1, blank, ..., y_U, blank), S = 2U + 1:
+ *   m_t    = max_c value_t(c)                       (logits: also maxlogit_t, the maximum of the clamped logits)
+ *   e_t(s) = fl32(value_t(l'_s) - m_t)              (logits: fl32(logit_t(l'_s) - maxlogit_t), independent of lse); <= 0
+ *   v_0(0) = e_0(0), v_0(1) = e_0(1), v_0(s) = -1e30 otherwise
+ *   v_t(s) = fl32(e_t(s) + max(v_{t-1}(s), v_{t-1}(s-1) [s >= 1], v_{t-1}(s-2) [s odd, >= 3, l'_s != l'_{s-2}]))
+ * the back-pointer being the first maximal predecessor in the order stay, s-1, s-2; at the end S-1 is preferred over S-2
+ * (U = 0: state 0 alone).  Subtracting the row maximum moves every path by the same amount -- the arg-max is unchanged --
+ * and keeps a well-aligned path near 0 over 1e5 frames.  For logits m_t = fl32(maxlogit_t - lse_t).
+ *
+ * Launches: one row pass (reads x once), ceil(T / 64) recurrence launches (a frame block each; grid = tiles of 896 owned
+ * states x B; a tile recomputes the 128 states below it from the state column at the block's first frame, which is kept
+ * ping-pong in scratch), one back-trace (a wave per recording), one launch for the per-token outputs.  Tiles depend on
+ * one another through stream order only: no workgroup waits on another.  The launch sequence depends on (T, U_max) alone;
+ * no host synchronisation; capturable.
+ * Limits: U_max <= 2^28 (state indices and the padded state axis fit an int), B <= 65535 (a grid extent), a scratch size
+ * within size_t; PIKA_ETOOBIG beyond.  PIKA_EINVAL for a null pointer (lse excepted; targets may be NULL when U_max == 0),
+ * B, T, C < 1, U_max < 0, blank outside [0,C).  All refusals come before any launch: a negative size first, then a size
+ * that is too big, then pointers.
+ *
+ * Scratch, with Sp = ceil((2 U_max + 1) / 896) * 896 and Tp = T rounded up to a multiple of 4; 0 for refused dimensions:
+ *   back-pointers, two bits per cell, four frames of one state to a byte, rows of Sp bytes      B ceil(T / 4) Sp
+ *   2 f32 state columns [B][Sp] (ping-pong)                                                      8 B Sp
+ *   the per-frame state of the path, i32 [B][Tp]                                                 4 B Tp
+ *   the rows' maxima (m_t for log-probs, maxlogit_t for logits), f32 [B][Tp]                     4 B Tp
+ *   per recording: feasible, end state (4 i32)                                                   16 B */
+size_t pika_ctc_long_align_scratch_bytes(int B, int T, int U_max);
+int pika_ctc_long_align(const float *x, long long stride_t, long long stride_b, const float *lse,
+                        const int *input_lengths, const int *targets, const int *target_lengths, int B, int T, int C,
+                        int blank, int U_max, float *scores, int *starts, int *ends, float *token_scores,
+                        void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

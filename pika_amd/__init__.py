@@ -60,7 +60,8 @@ _CTC_EXPORTS = ("ctc_loss", "ctc_loss_from_logits", "CTCLoss", "ctc_align", "ctc
                 "CtcNgramLm", "ctc_beam_search_lm", "ctc_beam_search_lm_from_logits", "CtcBeamStream",
                 "CtcHotwords", "CtcBiasedLm", "ctc_nbest_align", "ctc_nbest_align_from_logits",
                 "ctc_nbest_loss", "ctc_nbest_loss_from_logits", "ctc_mwer_loss", "ctc_mwer_loss_from_logits",
-                "ctc_nbest_errors", "ctc_nbest_edit_distance", "ctc_nbest_pairwise_distance", "ctc_nbest_mbr_decode")
+                "ctc_nbest_errors", "ctc_nbest_edit_distance", "ctc_nbest_pairwise_distance", "ctc_nbest_mbr_decode",
+                "ctc_long_align", "ctc_long_align_from_logits", "ctc_segment_scores")
 
 
 def __getattr__(name):

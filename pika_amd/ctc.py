@@ -56,6 +56,14 @@ one capturable sequence, with MBR decoding over the list on top of them:
     ctc_nbest_pairwise_distance(tokens, lengths) -> distances (B,N,N)
     ctc_nbest_mbr_decode(tokens, lengths, scores, scale=1.0) -> (best (B,), risks (B,N))
 
+and long-form alignment (csrc/ctc_long.hip): the Viterbi path with the state axis tiled, for transcripts beyond the 511
+labels every call above is bound by and recordings too long for a plane -- an hour of audio against its whole transcript:
+
+    ctc_long_align(log_probs, targets, input_lengths=None, target_lengths=None, blank=0)
+        -> (scores (B,), starts (B,U), ends (B,U), token_scores (B,U))
+    ctc_long_align_from_logits(logits, ...same...)
+    ctc_segment_scores(starts, ends, token_scores, segment_offsets) -> (seg_start, seg_end, seg_confidence)   (B,G)
+
 Differences from torch, on purpose:
 
 * THE GRADIENT IS THE TRUE DERIVATIVE.  torch's native CTC backward returns `exp(log_probs) - occ` for d/d log_probs,
@@ -1290,3 +1298,140 @@ def ctc_nbest_mbr_decode(tokens, lengths, scores, scale=1.0):
     best = torch.where(live & (risks == lowest), index, torch.full_like(index, risks.shape[-1])).min(-1).values
     best = torch.where(live.any(-1), best, torch.full_like(best, -1))
     return (best[0], risks[0]) if unbatched else (best, risks)
+
+
+LONG_ALIGN_TILE = 896       # states a workgroup of the tiled recurrence owns (csrc/ctc_long.hip: LW)
+LONG_ALIGN_FRAMES = 64      # frames per recurrence launch (LF); a tile recomputes the 2 * LONG_ALIGN_FRAMES states below it
+
+
+def _long_align(x, what, targets, input_lengths, target_lengths, blank, logits):
+    blank = int(blank)
+    x, unbatched = _check_input(x, what, "ctc_long_align", blank)
+    T, B, C = x.shape
+    dev = x.device
+    targets = torch.as_tensor(targets)
+    if targets.dtype not in (torch.int32, torch.int64):
+        raise TypeError("targets must be int32 or int64, got %s" % targets.dtype)
+    if targets.dim() != (1 if unbatched else 2) or (not unbatched and targets.shape[0] != B):
+        raise ValueError("%s is %s: targets must be %s, got %s" % (
+            what, tuple(x.shape[::2]) if unbatched else tuple(x.shape), "(U,)" if unbatched else "(%d,U)" % B,
+            tuple(targets.shape)))
+    U = int(targets.shape[-1])
+    targets = targets.to(dev, torch.int32).contiguous().reshape(B, U)
+    lengths = []
+    for name, t, full in (("input_lengths", input_lengths, T), ("target_lengths", target_lengths, U)):
+        if t is None:
+            lengths.append(torch.full((B,), full, dtype=torch.int32, device=dev))
+            continue
+        t = torch.as_tensor(t)
+        if t.dtype not in (torch.int32, torch.int64):
+            raise TypeError("%s must be int32 or int64, got %s" % (name, t.dtype))
+        t = t.reshape(-1).to(dev, torch.int32).contiguous()
+        if t.numel() != B:
+            raise ValueError("%s must hold B = %d entries" % (name, B))
+        lengths.append(t)
+    il, tl = lengths
+    if logits:      # the decoders' row pass with K = 1 writes the (T,B) log-sum-exps
+        x, il, _, _, _, lse, _ = _decode_rows(x, what, il, blank, 1, True)
+    else:
+        (x, il, _), lse = _rows_input(x, what, il, blank), None
+    lib = _lib.lib()
+    nbytes = lib.pika_ctc_long_align_scratch_bytes(B, T, U)
+    if nbytes == 0:
+        raise ValueError("(B,T,U_max) = (%d,%d,%d) not supported" % (B, T, U))
+    with torch.cuda.device(dev):
+        out = (torch.empty(B, dtype=torch.float32, device=dev), torch.empty((B, U), dtype=torch.int32, device=dev),
+               torch.empty((B, U), dtype=torch.int32, device=dev), torch.empty((B, U), dtype=torch.float32, device=dev))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        # the output pointers are never written through when U = 0; an empty tensor's may be null
+        ptrs = tuple(_ptr(o) or _ptr(scratch) for o in out)
+        _lib.check(lib.pika_ctc_long_align(_ptr(x), x.stride(0), x.stride(1), _ptr(lse), _ptr(il),
+                                           _ptr(targets) if U else None, _ptr(tl), B, T, C, blank, U, *(
+                                               ptrs + (_ptr(scratch), _stream()))), "pika_ctc_long_align")
+    return tuple(o[0] for o in out) if unbatched else out
+
+
+def ctc_long_align(log_probs, targets, input_lengths=None, target_lengths=None, blank=0):
+    """Long-form forced alignment: the best (Viterbi) path of one transcript per recording, with no limit of 511 labels
+    and no plane in memory -- an hour of audio against its whole transcript, which is what cuts audiobooks, meetings and
+    broadcast into utterances, and what gives a long stream's committed text its time stamps.
+
+    log_probs (T,B,C) or (T,C) float32 on a HIP device, any outer strides (one copy only when the class stride is not
+    1).  targets (B,U) -- (U,) for (T,C) input -- int32 or int64, padded; entries at or beyond a length are never read.
+    input_lengths / target_lengths (B,) int32 or int64 on either side, None meaning full (T, U); clamped on the device
+    to [1,T] and [0,U].
+
+    Returns (scores (B,) f32, starts (B,U) i32, ends (B,U) i32, token_scores (B,U) f32), detached -- without the batch
+    axis for (T,C) input:
+      scores        the log-probability of the best path
+      starts, ends  the first and last frame (inclusive) of the run in which the path emits token j
+      token_scores  the sum over that run of log_probs[t, b, token j], in fp32 in increasing t
+    Beyond a length starts / ends are -1 and token_scores -inf.  An infeasible transcript (a token outside [0,C), a token
+    equal to blank, T_b < U_b + adjacent repeats) has score -inf, times -1 and token scores -inf: not a fault.
+
+    The path is `ctc_align`'s wherever both run (the same fp32 max-plus and tie rule: at the end the final blank over the
+    last label; in the back-trace stay, then s-1, then s-2), and the per-token outputs are `ctc_nbest_align`'s.  Inside,
+    every frame's values are taken relative to the frame's maximum, which moves all paths alike and keeps a good path's
+    running score near 0 over 1e5 frames; the state axis is cut into tiles of LONG_ALIGN_TILE states and time into
+    blocks of LONG_ALIGN_FRAMES frames, one launch per block.  Back-pointers take two bits per cell: T * (2U+1) / 4
+    bytes of scratch per recording.
+
+    A wildcard ("star") token needs no kernel support: append a class column holding whatever score garbage should get
+    and put that class into `targets` wherever unknown speech may sit.
+
+    No autograd; no host synchronisation; capturable in a `torch.cuda.graph` with the lengths on the device; two runs
+    give bit-identical outputs.  `ctc_segment_scores` turns the result into utterance cuts."""
+    return _long_align(log_probs, "log_probs", targets, input_lengths, target_lengths, blank, False)
+
+
+def ctc_long_align_from_logits(logits, targets, input_lengths=None, target_lengths=None, blank=0):
+    """`ctc_long_align` of log_softmax(logits, -1) without materialising the log-probabilities: every value is
+    logit - lse rounded once, the rows' log-sum-exps coming from the decoders' row pass.  The recurrence itself runs on
+    logit minus the row's largest logit, which does not depend on lse."""
+    return _long_align(logits, "logits", targets, input_lengths, target_lengths, blank, True)
+
+
+def ctc_segment_scores(starts, ends, token_scores, segment_offsets):
+    """An alignment cut into segments (utterances): (seg_start (B,G) int, seg_end (B,G) int, seg_confidence (B,G) f32).
+
+    starts, ends, token_scores (B,U) -- or (U,) -- as `ctc_long_align` / `ctc_nbest_align` return them, on either
+    device.  segment_offsets (G+1,) shared by the batch, or (B,G+1): token indices, segment g covering tokens
+    [o_g, o_{g+1}).  seg_start is the start of the segment's first token, seg_end the end of its last token, and
+    seg_confidence = exp(sum token_scores / sum (ends - starts + 1)), the geometric mean of the frame posteriors of the
+    segment's tokens.  An empty segment, and any segment that holds a token without a run (an infeasible row, tokens
+    beyond a length), gives -1, -1 and NaN.  Plain torch (cumsum and gather): no host synchronisation, no autograd."""
+    starts, ends, ts = torch.as_tensor(starts), torch.as_tensor(ends), torch.as_tensor(token_scores).detach()
+    if starts.dim() not in (1, 2) or starts.shape != ends.shape or starts.shape != ts.shape:
+        raise ValueError("starts, ends and token_scores must share one shape (B,U) or (U,), got %s, %s, %s"
+                         % (tuple(starts.shape), tuple(ends.shape), tuple(ts.shape)))
+    unbatched = starts.dim() == 1
+    if unbatched:
+        starts, ends, ts = starts.unsqueeze(0), ends.unsqueeze(0), ts.unsqueeze(0)
+    B, U = starts.shape
+    dev = starts.device
+    off = torch.as_tensor(segment_offsets).to(dev)
+    if off.dtype not in (torch.int32, torch.int64):
+        raise TypeError("segment_offsets must be int32 or int64, got %s" % off.dtype)
+    if off.dim() == 1:
+        off = off.unsqueeze(0).expand(B, -1)
+    if off.dim() != 2 or off.shape[0] != B or off.shape[1] < 1:
+        raise ValueError("segment_offsets must be (G+1,) or (%d,G+1), got %s" % (B, tuple(off.shape)))
+    off = off.long().clamp(0, U)
+    o0, o1 = off[:, :-1], off[:, 1:]
+    has = (starts >= 0) & (ends >= starts)
+    zero = torch.zeros((B, 1), dtype=torch.float64, device=dev)
+
+    def between(v):     # sum of v over tokens [o0, o1), by a running sum with a leading zero
+        run = torch.cat([zero, v.to(torch.float64).cumsum(1)], 1)
+        return run.gather(1, o1) - run.gather(1, o0)
+    score = between(torch.where(has, ts.to(dev), torch.zeros_like(ts)))
+    frames = between(torch.where(has, ends - starts + 1, torch.zeros_like(starts)))
+    good = (o1 > o0) & (between(has) == (o1 - o0))
+    pad = torch.full((B, 1), -1, dtype=starts.dtype, device=dev)    # a column to gather from when U = 0
+    seg_start = torch.cat([starts, pad], 1).gather(1, o0)
+    seg_end = torch.cat([ends, pad], 1).gather(1, (o1 - 1).clamp(min=0))
+    seg_start = torch.where(good, seg_start, torch.full_like(seg_start, -1))
+    seg_end = torch.where(good, seg_end, torch.full_like(seg_end, -1))
+    conf = torch.where(good, (score / frames.clamp(min=1)).exp(), torch.full_like(score, float("nan"))).float()
+    out = (seg_start, seg_end, conf)
+    return tuple(o[0] for o in out) if unbatched else out
