@@ -235,6 +235,65 @@ int pika_ctc_long_align(const float *x, long long stride_t, long long stride_b, 
                         int blank, int U_max, float *scores, int *starts, int *ends, float *token_scores,
                         void *scratch, void *stream);
 
+/* Long-form loss: cost and gradient of pika_ctc_loss_forward / _backward (log-probs) and pika_ctc_fused_* (logits) with
+ * the state axis cut into tiles -- no limit of 511 labels.  Sum-product over the tiling of pika_ctc_long_align: the same
+ * dependency cone (alpha at (t,s) needs s, s-1, s-2 at t-1; beta is its mirror image), both planes kept for the backward.
+ *   x, stride_t, stride_b, lse, input_lengths, targets, target_lengths   as pika_ctc_long_align: strides in ELEMENTS, C
+ *                  contiguous classes; lse (T,B) as pika_ctc_decode_rows writes it and x raw logits, or NULL and x
+ *                  log-probs; anything below -1e30 (-inf, NaN) reads as -1e30; rows t >= T_b are never read; targets
+ *                  (B,U_max) padded, entries at or beyond target_lengths[b] never read; lengths clamped on the device
+ *   costs          f32 (B,) -log P(y_b | x_b); +inf for an infeasible utterance
+ *   grad_costs     f32 (B,) the weight of utterance b's cost (autograd's grad_output); NULL: all ones
+ *   grads          f32 (T,B,C) contiguous, DENSE: every element is written.  For t < T_b
+ *       log-probs:  grads[t,b,c] = -grad_costs[b] occ_t(c)            (the true derivative, as pika_ctc_loss_backward)
+ *       logits:     grads[t,b,c] = grad_costs[b] (softmax_t(c) - occ_t(c))
+ *       occ_t(c) = sum_{s : l'_s = c} exp(alpha_t(s) + beta_t(s) - value_t(c) - ll_b), the exponent assembled in fp64 from
+ *     planes and offsets and rounded once; rows t >= T_b are exactly zero.
+ * A label is classified as pika_ctc_loss_forward classifies it: one outside [0,C) makes its state impossible and nothing is
+ * read through it; one equal to blank is a state of the blank class that no transition skips into.  An INFEASIBLE
+ * utterance (T_b < U_b + adjacent repeats, a label outside [0,C)) costs +inf and EVERY row of its gradient is zero; its
+ * neighbours in the batch are not affected.
+ *
+ * Numerics: log-space fp32, -1e30 for "impossible", the usual guarded log-sum-exp.  Every frame's values are taken relative
+ * to the row maximum r_t: e_t(s) = fl32(x_t(l'_s) - r_t) <= 0; and at the start of every block of 64 frames every tile takes
+ * the same amount R out of all its states: the largest value of the state column the launch before left, which it reads
+ * as one maximum per tile (max is exact and order-free, so every tile gets the same bits).  R and M_t = r_t (- lse_t for
+ * logits) are summed in fp64 into one offset per frame and direction: alpha_t(s) = plane_a[t][s] + off_a[t], beta alike.
+ * Both include the frame's own emission.  ll_b = off_a[T_b-1] + logsumexp(plane_a[T_b-1][S-1], plane_a[T_b-1][S-2]) in fp64
+ * (state 0 alone at U_b = 0).
+ *
+ * Launches of the forward: one row pass (reads x once); one launch that sorts every transcript's labels by (class,
+ * position), by counting ranks (U_max > 0); ceil(T / 64) recurrence launches, grid = tiles of 896 owned states x B x 2
+ * directions: launch k advances alpha over frame block k and beta over frame block ceil(T / 64) - 1 - k.  A tile recomputes
+ * 128 states beside its own (below for alpha, above for beta) from the state column at the block's edge, which is kept
+ * ping-pong; beta of utterance b starts at T_b - 1 inside whichever block holds it.  Then a launch with a thread per
+ * utterance for ll and the cost.  The backward is ONE launch, a workgroup per (t,b) row: it writes the row once (zeros, or
+ * grad_costs softmax; 16-byte stores where C % 4 == 0 and the row is aligned) and then the class entries -- blank from the
+ * even states, thread-strided partial sums joined in a fixed tree; the labels in sorted order, a contiguous chunk per
+ * thread, a class that spans chunks joined in chunk order.  No float atomics; the order of every sum depends on
+ * (t, T_b, U_b) alone: two runs give bit-identical outputs.  Tiles depend on one another through stream order only: no
+ * workgroup waits on another.  The launch sequence depends on (T, U_max) alone; no host synchronisation; capturable.
+ * `workspace` is filled by the forward and read by the backward, which takes the same x, strides, lse and lengths.
+ * Limits: U_max <= 2^28, B <= 65535 (a grid extent), a workspace size within size_t; PIKA_ETOOBIG beyond.  PIKA_EINVAL for
+ * a null pointer (lse and grad_costs excepted; targets may be NULL when U_max == 0), B, T, C < 1, U_max < 0, blank outside
+ * [0,C).  All refusals come before any launch: a negative size first, then a size that is too big, then pointers.
+ *
+ * Workspace, with Sp = ceil((2 U_max + 1) / 896) * 896; 0 for refused dimensions:
+ *   2 f32 planes [B][T][Sp] (alpha, beta, each minus its offset)                                  8 B T Sp
+ *   2 f64 offset rows [B][T] + ll [B] f64 (-1e30: infeasible)                                     16 B T + 8 B
+ *   4 f32 state columns [B][Sp] (direction x ping-pong)                                           16 B Sp
+ *   their per-tile maxima, 4 f32 [B][Sp / 896]                                                    16 B Sp / 896
+ *   the rows' maxima r_t, f32 [B][T]                                                              4 B T
+ *   the sorted labels: position and class, 2 i32 [B][U_max]                                       8 B U_max
+ * The planes are kept, not recomputed: about 8 B T Sp bytes, 29 GB for an hour (T = 90 000) against 20 000 labels. */
+size_t pika_ctc_long_loss_workspace_bytes(int B, int T, int U_max);
+int pika_ctc_long_loss_forward(const float *x, long long stride_t, long long stride_b, const float *lse,
+                               const int *input_lengths, const int *targets, const int *target_lengths, int B, int T,
+                               int C, int blank, int U_max, float *costs, void *workspace, void *stream);
+int pika_ctc_long_loss_backward(const float *x, long long stride_t, long long stride_b, const float *lse,
+                                const int *input_lengths, const int *target_lengths, int B, int T, int C, int blank,
+                                int U_max, const float *grad_costs, const void *workspace, float *grads, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,7 +61,8 @@ _CTC_EXPORTS = ("ctc_loss", "ctc_loss_from_logits", "CTCLoss", "ctc_align", "ctc
                 "CtcHotwords", "CtcBiasedLm", "ctc_nbest_align", "ctc_nbest_align_from_logits",
                 "ctc_nbest_loss", "ctc_nbest_loss_from_logits", "ctc_mwer_loss", "ctc_mwer_loss_from_logits",
                 "ctc_nbest_errors", "ctc_nbest_edit_distance", "ctc_nbest_pairwise_distance", "ctc_nbest_mbr_decode",
-                "ctc_long_align", "ctc_long_align_from_logits", "ctc_segment_scores")
+                "ctc_long_align", "ctc_long_align_from_logits", "ctc_segment_scores",
+                "ctc_long_loss", "ctc_long_loss_from_logits")
 
 
 def __getattr__(name):

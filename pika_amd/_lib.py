@@ -54,6 +54,9 @@ SIGNATURES = {
     "pika_ctc_edit_distance_host": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
     "pika_ctc_long_align_scratch_bytes": (_sz, [_i] * 3),
     "pika_ctc_long_align": (_i, [_vp, _ll, _ll] + [_vp] * 4 + [_i] * 5 + [_vp] * 6),
+    "pika_ctc_long_loss_workspace_bytes": (_sz, [_i] * 3),
+    "pika_ctc_long_loss_forward": (_i, [_vp, _ll, _ll] + [_vp] * 4 + [_i] * 5 + [_vp] * 3),
+    "pika_ctc_long_loss_backward": (_i, [_vp, _ll, _ll] + [_vp] * 3 + [_i] * 5 + [_vp] * 4),
     # include/pika_ctc_decode.h
     "pika_ctc_decode_rows": (_i, [_vp, _ll, _ll, _vp] + [_i] * 6 + [_vp] * 5),
     "pika_ctc_greedy": (_i, [_vp] * 4 + [_i] * 4 + [_vp] * 5),

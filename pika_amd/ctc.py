@@ -64,6 +64,12 @@ labels every call above is bound by and recordings too long for a plane -- an ho
     ctc_long_align_from_logits(logits, ...same...)
     ctc_segment_scores(starts, ends, token_scores, segment_offsets) -> (seg_start, seg_end, seg_confidence)   (B,G)
 
+and the long-form loss (csrc/ctc_long_loss.hip): `ctc_loss` over the same tiling, alpha and beta, for transcripts beyond
+511 labels -- `ctc_loss`, `ctc_loss_from_logits` and `CTCLoss` route to it by themselves when 2 * U_max + 1 > 1024:
+
+    ctc_long_loss(log_probs, targets, input_lengths, target_lengths, blank=0, reduction='mean', zero_infinity=False)
+    ctc_long_loss_from_logits(logits, ...same...)
+
 Differences from torch, on purpose:
 
 * THE GRADIENT IS THE TRUE DERIVATIVE.  torch's native CTC backward returns `exp(log_probs) - occ` for d/d log_probs,
@@ -125,9 +131,9 @@ def _check_input(x, what, who, blank):
     return x, unbatched
 
 
-def _prepare(x, what, targets, input_lengths, target_lengths, blank):
+def _prepare(x, what, targets, input_lengths, target_lengths, blank, tiled=False):
     """Checks and device copies: (x as (T,B,C), any stride; targets i32; offsets i32 or None; il i32; tl i32; U_max;
-    unbatched)."""
+    unbatched).  `tiled`: the caller has the tiled path for a state axis wider than one workgroup."""
     x, unbatched = _check_input(x, what, "ctc_loss", blank)
     B, dev = x.shape[1], x.device
     targets = torch.as_tensor(targets)
@@ -162,7 +168,7 @@ def _prepare(x, what, targets, input_lengths, target_lengths, blank):
         toff = (torch.cumsum(wide, 0) - wide).to(torch.int32)
     else:
         raise ValueError("targets must be (B,S) or 1-D, got %s" % (tuple(targets.shape),))
-    if 2 * U + 1 > MAX_STATES:
+    if 2 * U + 1 > MAX_STATES and not tiled:
         raise ValueError("2*U_max+1 = %d > %d not supported" % (2 * U + 1, MAX_STATES))
     targets = targets.to(dev, torch.int32).contiguous()
     return x, targets, toff, il, tl, U, unbatched
@@ -219,13 +225,16 @@ class _CTCFn(torch.autograd.Function):
         return grads, None, None, None, None, None, None, None
 
 
-def _loss(x, what, targets, input_lengths, target_lengths, blank, reduction, zero_infinity, logits):
+def _loss(x, what, targets, input_lengths, target_lengths, blank, reduction, zero_infinity, logits, tiled=False):
     if reduction not in ("none", "mean", "sum"):
         raise ValueError("%r is not a valid value for reduction" % (reduction,))
     blank = int(blank)
-    x, tg, toff, il, tl, U, unbatched = _prepare(x, what, targets, input_lengths, target_lengths, blank)
-    # (any stride: the kernels read the one contiguous copy the forward makes when it is needed)
-    costs = _CTCFn.apply(x, tg, toff, il, tl, U, blank, logits)
+    x, tg, toff, il, tl, U, unbatched = _prepare(x, what, targets, input_lengths, target_lengths, blank, True)
+    if tiled or 2 * U + 1 > MAX_STATES:     # a state axis beyond one workgroup: the tiled path (csrc/ctc_long_loss.hip)
+        costs = _CTCLongFn.apply(x, _padded_targets(tg, toff, tl, U), il, tl, U, blank, logits, what)
+    else:
+        # (any stride: the kernels read the one contiguous copy the forward makes when it is needed)
+        costs = _CTCFn.apply(x, tg, toff, il, tl, U, blank, logits)
     if zero_infinity:
         costs = torch.where(torch.isinf(costs), torch.zeros_like(costs), costs)
     # the reduction acts on the (B,) costs: its factors reach the kernel folded into grad_costs, so no pass over the
@@ -246,7 +255,10 @@ def ctc_loss(log_probs, targets, input_lengths, target_lengths, blank=0, reducti
 
     The gradient is the true derivative -occ with respect to log_probs -- torch's native kernel returns
     exp(log_probs) - occ, which equals it only after a log_softmax backward (module docstring).  Infeasible utterances
-    cost +inf (0 with zero_infinity) and have an all-zero gradient.  Host synchronisation: module docstring."""
+    cost +inf (0 with zero_infinity) and have an all-zero gradient.  Host synchronisation: module docstring.
+
+    Any transcript length: up to 511 labels (2 * U_max + 1 <= 1024) one workgroup spans the state axis; beyond, the call
+    is `ctc_long_loss`, which tiles it."""
     return _loss(log_probs, "log_probs", targets, input_lengths, target_lengths, blank, reduction, zero_infinity, False)
 
 
@@ -300,7 +312,7 @@ def ctc_align(log_probs, targets, input_lengths, target_lengths, blank=0):
     repeats and dropping blanks gives the transcript back.  Tie rule: the path ends in the final blank rather than the
     last label, and in the back-trace staying in a state is preferred to coming from s-1, and that to s-2.  An
     infeasible transcript scores <= -1e30 and still yields a path of valid states.  Inputs as `ctc_loss`; no autograd;
-    same host-synchronisation behaviour."""
+    same host-synchronisation behaviour.  At most 511 labels (ValueError beyond): `ctc_long_align` has no such limit."""
     return _align(log_probs, "log_probs", targets, input_lengths, target_lengths, blank, False)
 
 
@@ -1435,3 +1447,95 @@ def ctc_segment_scores(starts, ends, token_scores, segment_offsets):
     conf = torch.where(good, (score / frames.clamp(min=1)).exp(), torch.full_like(score, float("nan"))).float()
     out = (seg_start, seg_end, conf)
     return tuple(o[0] for o in out) if unbatched else out
+
+
+LONG_LOSS_TILE = 896        # states a workgroup of the tiled recurrences owns (csrc/ctc_long_loss.hip: QW)
+LONG_LOSS_FRAMES = 64       # frames per recurrence launch (QF); a tile recomputes 2 * LONG_LOSS_FRAMES states beside its own
+
+
+def _padded_targets(targets, toff, tl, U):
+    """Targets as the tiled kernels take them, (B,U) padded: the 1-D form is spread out by torch, without a host
+    synchronisation (U is already known on the host)."""
+    if toff is None:
+        return targets
+    B, n = tl.numel(), targets.numel()
+    if U == 0 or n == 0:
+        return targets.new_zeros((B, U))
+    pos = torch.arange(U, device=targets.device)[None, :]
+    idx = (toff.to(torch.int64)[:, None] + pos).clamp(0, n - 1)
+    return torch.where(pos < tl[:, None], targets[idx], torch.zeros_like(idx, dtype=targets.dtype)).contiguous()
+
+
+class _CTCLongFn(torch.autograd.Function):
+    """`_CTCFn` on the tiled kernels: per-utterance costs (B,), any number of labels; the backward writes the dense
+    (T,B,C) gradient once, already scaled by grad_output.  Reads x through its two outer strides."""
+
+    @staticmethod
+    def forward(ctx, x, targets, il, tl, U, blank, logits, what):
+        xd = x.detach()
+        if logits:      # the decoders' row pass with K = 1 writes the (T,B) log-sum-exps
+            xd, il, _, _, _, lse, _ = _decode_rows(xd, what, il, blank, 1, True)
+        else:
+            (xd, il, _), lse = _rows_input(xd, what, il, blank), None
+        T, B, C = xd.shape
+        lib = _lib.lib()
+        nbytes = lib.pika_ctc_long_loss_workspace_bytes(B, T, U)
+        if nbytes == 0:
+            raise ValueError("(B,T,U_max) = (%d,%d,%d) not supported" % (B, T, U))
+        with torch.cuda.device(xd.device):
+            costs = torch.empty(B, dtype=torch.float32, device=xd.device)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=xd.device)
+            _lib.check(lib.pika_ctc_long_loss_forward(_ptr(xd), xd.stride(0), xd.stride(1), _ptr(lse), _ptr(il),
+                                                      _ptr(targets) if U else None, _ptr(tl), B, T, C, blank, U,
+                                                      _ptr(costs), _ptr(ws), _stream()), "pika_ctc_long_loss_forward")
+        ctx.save_for_backward(xd, il, tl, ws, *((lse,) if logits else ()))
+        ctx.dims = (T, B, C, U, blank)
+        return costs
+
+    @staticmethod
+    def backward(ctx, grad_costs):
+        T, B, C, U, blank = ctx.dims
+        xd, il, tl, ws = ctx.saved_tensors[:4]
+        lse = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
+        lib = _lib.lib()
+        gc = grad_costs.to(torch.float32).contiguous()
+        with torch.cuda.device(ws.device):
+            grads = torch.empty((T, B, C), dtype=torch.float32, device=ws.device)
+            _lib.check(lib.pika_ctc_long_loss_backward(_ptr(xd), xd.stride(0), xd.stride(1), _ptr(lse), _ptr(il), _ptr(tl),
+                                                       B, T, C, blank, U, _ptr(gc), _ptr(ws), _ptr(grads), _stream()),
+                       "pika_ctc_long_loss_backward")
+        return grads, None, None, None, None, None, None, None
+
+
+def ctc_long_loss(log_probs, targets, input_lengths, target_lengths, blank=0, reduction='mean', zero_infinity=False):
+    """`ctc_loss` with the state axis tiled: the same arguments, shapes, reductions and gradient convention, and no limit
+    of 511 labels -- a character-level model on 20-30 s segments, or training on what `ctc_long_align` can align.
+    `ctc_loss` itself routes here when 2 * U_max + 1 > 1024; calling it directly runs the tiled kernels at any length.
+
+    log_probs (T,B,C) or (T,C) float32 on a HIP device, read through its outer strides (one copy only when the class
+    stride is not 1); targets (B,S) padded or 1-D concatenated (spread out to (B,U_max) by torch); lengths (B,), int32
+    or int64, on the CPU or the device, clamped on the device to [1,T] and [0,U_max].  The gradient is the true
+    derivative -occ with respect to log_probs; an infeasible utterance (T_b < U_b + adjacent repeats, a label outside
+    [0,C)) costs +inf (0 with zero_infinity) and has an all-zero gradient.  The reduction's factors reach the kernel
+    folded into grad_costs.
+
+    Inside (csrc/ctc_long_loss.hip): the state axis is cut into tiles of LONG_LOSS_TILE states and time into blocks of
+    LONG_LOSS_FRAMES frames; one launch per block advances alpha on block k and beta on block n-1-k, a tile recomputing
+    the 2 * LONG_LOSS_FRAMES states beside its own, so tiles meet through stream order only.  Values are fp32 relative
+    to each frame's row maximum and, once per block, to the column's maximum; both go into fp64 offsets.  Against
+    `ctc_loss`, which renormalises every 8 frames, the fp32 state values are up to LONG_LOSS_FRAMES / 8 times larger.
+
+    MEMORY: both planes are stored for the backward, about 8 * B * T * (2 * U_max + 1) bytes (rounded up to whole
+    tiles) -- 0.7 GB for (T,B,U) = (3000,8,1500); an hour against its whole transcript does not fit.  No host
+    synchronisation with padded targets and lengths on the device: forward and backward can be captured in one
+    `torch.cuda.graph`; two runs give bit-identical results.  No double backward."""
+    return _loss(log_probs, "log_probs", targets, input_lengths, target_lengths, blank, reduction, zero_infinity, False,
+                 True)
+
+
+def ctc_long_loss_from_logits(logits, targets, input_lengths, target_lengths, blank=0, reduction='mean',
+                              zero_infinity=False):
+    """`ctc_long_loss` of log_softmax(logits, -1) without materialising the log-probabilities: the rows' log-sum-exps
+    come from the decoders' row pass and the backward writes d/d logits = grad * (softmax - occ), as
+    `ctc_loss_from_logits` does."""
+    return _loss(logits, "logits", targets, input_lengths, target_lengths, blank, reduction, zero_infinity, True, True)
