@@ -573,13 +573,31 @@ __global__ __launch_bounds__(256) void rnnt_rowmeta_kernel(
 
 // ---------------------------------------------------------------------------------------------
 // grad: flat streaming writer.  Thread -> PT 16-byte groups, 256 groups apart, so each wave
-// instruction stores one 1 KiB-aligned contiguous KiB and workgroups are dispatched in address
-// order.  A wave instruction (64 groups) spans at most two V-rows when V/4 >= 64, so both rows'
+// instruction stores one 1 KiB-aligned contiguous KiB and a workgroup one contiguous chunk
+// (address order within groups of 512 workgroups, see grad_chunk).  A wave instruction (64 groups) spans at most two V-rows when V/4 >= 64, so both rows'
 // metadata arrive through the scalar cache (s_load) and the per-lane work is two compares.
 // Hardware A/B (tools/grad_sweep.hip, MI355X, 32.64 GB tensor): PT=2 + scalar metadata 4.65 ms
 // (7.0 TB/s) vs per-lane metadata PT=4 5.3 ms, hipMemsetAsync 5.1-5.5 ms, row-structured
 // writers 7-9 ms.
+// The scalar-metadata writer does not take its 8 KiB chunk straight from blockIdx.x: workgroups
+// are dealt to the 8 XCDs round-robin, so under the linear map every XCD writes every eighth chunk.
+// grad_chunk permutes each aligned group of 8 * GRAD_RUN workgroups so that workgroups b, b+8,
+// b+16, .. take GRAD_RUN consecutive chunks (512 KiB runs).  Same sweep, same tensor: linear 4.72-
+// 4.75 ms, runs of 4 chunks 5.4-5.6 (worse), 16: 4.53-4.57, 64 to 16384: 4.50-4.55 (a plateau),
+// one eighth of the tensor per residue 4.67.  The map is a bijection on the chunk indices whatever
+// the placement is (only the speed rests on it); the last, partial group keeps the linear map, so
+// every chunk, the tail's partial one included, is written exactly once.  Workgroup size, PT and
+// wave-contiguous spans all lost to 256 threads x PT=2 (DESIGN.md has the table).
 // ---------------------------------------------------------------------------------------------
+constexpr int GRAD_RUN_SHIFT = 6;  // GRAD_RUN = 64 chunks
+
+__device__ inline unsigned grad_chunk(unsigned b, unsigned nblocks) {
+    constexpr unsigned gmask = (8u << GRAD_RUN_SHIFT) - 1;
+    if ((b | gmask) >= nblocks) return b;  // the last group is partial: linear
+    const unsigned j = b & gmask;
+    return (b & ~gmask) | ((j & 7u) << GRAD_RUN_SHIFT) | (j >> 3);
+}
+
 __device__ inline v4f blend_row(int q, int qb, int cb, float gb, float ge, int ye) {
     const int qe = ye >> 2, ce = ye & 3;  // ye = -1 -> qe = -1: never matches
     v4f v = {0.f, 0.f, 0.f, 0.f};
@@ -602,7 +620,7 @@ __global__ __launch_bounds__(256) void rnnt_grad_kernel(const RowMeta *__restric
     if constexpr (SCALAR_META) {  // requires V4 >= 64
         const int lane = threadIdx.x & 63;
         // first group of this wave's first store (wave-uniform, made provably so)
-        size_t i0 = (size_t)blockIdx.x * (256 * PT) + (threadIdx.x & ~63);
+        size_t i0 = (size_t)grad_chunk(blockIdx.x, gridDim.x) * (256 * PT) + (threadIdx.x & ~63);
         i0 = ((size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(i0 >> 32)) << 32) |
              (unsigned)__builtin_amdgcn_readfirstlane((int)i0);
         size_t row0 = i0 / (unsigned)V4;
