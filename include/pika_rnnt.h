@@ -218,6 +218,65 @@ int pika_rnnt_align(const void *workspace, const int *frames_lengths, const int 
                     const int *label_offsets, int B, int T, int U1, float *scores, int *emit_frames,
                     void *scratch, void *stream);
 
+/* Pruned RNN-T: the loss on a banded lattice (k2 / icefall rnnt_loss_pruned; Kuang et al. 2022, arXiv:2206.13236).
+ * Every frame keeps S consecutive label positions, so the joint output, the vocabulary product and the dense
+ * gradient are (B, T, S, V) instead of (B, T, U1, V).
+ *   ranges         i32 (B, T)      s_t = ranges[n][t], the first label position of frame t's band; every entry is
+ *                                  clamped on the device to [0, max(0, U_n + 1 - S)]
+ *   log_probs / logits f32 (B, T, S, V); row j of frame t is the distribution of lattice cell (t, s_t + j)
+ *   labels         i32 (B, U1-1), lengths and costs as above
+ * A cell (t, u) of the (T_n, U_n + 1) lattice is live iff s_t <= u < s_t + S; both outgoing log-probabilities of any
+ * other cell are log zero, so the cost is -log of the sum over the paths from (0, 0) to the final blank out of
+ * (T_n-1, U_n) that visit live cells only: the full loss on a (B, T, U1, V) tensor holding the band's rows at their
+ * cells and -1e30 everywhere else.  The gradient is dense (B, T, S, V), every element written; rows with t >= T_n or
+ * s_t + j > U_n are zero.  FastEmit as in pika_rnnt_loss_backward_fe.
+ * A band connects the lattice's corners when, for t < T_n, s_0 = 0, s_{T_n-1} = max(0, U_n + 1 - S) and
+ * 0 <= s_{t+1} - s_t <= S - 1 (pika_prnnt_prune_ranges returns such ranges).  On any other ranges the calls still read
+ * and write inside their buffers and the other utterances of the batch are unaffected; the cost of that utterance is
+ * unspecified.
+ * `workspace` is that of the padded (B, T, U1) batch, pika_rnnt_workspace_bytes(B, T, U1); pika_rnnt_align works on
+ * the planes these forwards leave (with the same B, T, U1 and lengths): the best path through live cells.
+ * The fused pair takes RAW logits (V % 4 == 0, V <= 8192) and lse (B*T*S), out_dtype / ld_out as
+ * pika_rnnt_fused_backward.  S < 1 or S > U1: PIKA_EINVAL; U1 > 1024, B*T*S > 0x7fffffff: PIKA_ETOOBIG.
+ * (The family is pika_prnnt_*, not pika_rnnt_*: tests/test_rnnt_abi_rejections.py pins the set of pika_rnnt_* entry
+ * points to the table recorded for them.) */
+int pika_prnnt_forward(const float *log_probs, const int *frames_lengths, const int *labels_lengths, const int *labels,
+                       const int *ranges, int B, int T, int U1, int S, int V, int blank, float *costs, void *workspace,
+                       void *stream);
+/* grads == NULL: row metadata (of the B*T*S band rows) only, as pika_rnnt_loss_backward. */
+int pika_prnnt_backward(const int *frames_lengths, const int *labels_lengths, const int *labels, const int *ranges, int B,
+                        int T, int U1, int S, int V, int blank, const float *grad_costs, const void *workspace,
+                        float *grads, float fastemit_lambda, void *stream);
+int pika_prnnt_fused_forward(const float *logits, const int *frames_lengths, const int *labels_lengths, const int *labels,
+                             const int *ranges, int B, int T, int U1, int S, int V, int blank, float *costs, float *lse,
+                             void *workspace, void *stream);
+int pika_prnnt_fused_backward(const float *logits, const float *lse, const int *frames_lengths, const int *labels_lengths,
+                              const int *labels, const int *ranges, int B, int T, int U1, int S, int V, int blank,
+                              const float *grad_costs, const void *workspace, void *grad_logits, int out_dtype,
+                              long long ld_out, float fastemit_lambda, void *stream);
+
+/* The loss of a lattice given directly by its two planes (the "simple" loss of a joiner that is am + lm):
+ *   blank_lp, label_lp  f32 (B, T, U1): log-probability of the blank edge (t, u) -> (t+1, u) and of the label edge
+ *                       (t, u) -> (t, u+1); label_lp[.., u] is not read for u >= U_n; they need not be normalised
+ *   blank_occ, label_occ f32 (B, T, U1), written: the occupation probabilities exp(alpha + lp + beta' - ll) of the two
+ *                       edges of every cell (zero outside the sub-lattice); d cost / d lp = -occ.
+ * The planes are skewed into `workspace` (pika_rnnt_workspace_bytes(B, T, U1)), so pika_rnnt_align works on it. */
+int pika_prnnt_planes_forward(const float *blank_lp, const float *label_lp, const int *frames_lengths,
+                              const int *labels_lengths, int B, int T, int U1, float *costs, float *blank_occ,
+                              float *label_occ, void *workspace, void *stream);
+
+/* Band search.  occ(t, u) = blank_occ + label_occ, s_max = max(0, U_n + 1 - S); for every utterance
+ *   1. raw(t) = argmax over 0 <= s <= s_max of sum_{u = s}^{min(s + S - 1, U_n)} occ(t, u), ties to the smallest s,
+ *      for t < T_n; then raw(T_n - 1) = s_max;
+ *   2. m(t) = min_{t' >= t} raw(t');
+ *   3. f(0) = 0, f(t) = min(m(t), f(t-1) + S - 1);
+ *   4. ranges[n][t] = max(f(t), s_max - (T_n - 1 - t)(S - 1)); s_max for t >= T_n.
+ * The result connects the corners (above) whenever (T_n - 1)(S - 1) >= s_max; otherwise no band of that width does,
+ * and ranges[n][0] > 0 says so.  One workgroup per utterance, any T.  S < 1 or S > U1: PIKA_EINVAL; U1 > 1024:
+ * PIKA_ETOOBIG. */
+int pika_prnnt_prune_ranges(const float *blank_occ, const float *label_occ, const int *frames_lengths,
+                            const int *labels_lengths, int B, int T, int U1, int S, int *ranges, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,12 +65,20 @@ _CTC_EXPORTS = ("ctc_loss", "ctc_loss_from_logits", "CTCLoss", "ctc_align", "ctc
                 "ctc_long_loss", "ctc_long_loss_from_logits")
 
 
+# The pruned RNN-T surface (pika_amd/rnnt.py), resolved the same way.
+_RNNT_EXPORTS = ("rnnt_loss_pruned", "rnnt_loss_pruned_from_logits", "rnnt_loss_from_planes", "rnnt_prune_ranges",
+                 "rnnt_simple_planes", "rnnt_prune_lm")
+
+
 def __getattr__(name):
     if name in _CTC_EXPORTS:
         from . import ctc
         return getattr(ctc, name)
+    if name in _RNNT_EXPORTS:
+        from . import rnnt
+        return getattr(rnnt, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
 def __dir__():
-    return sorted(list(globals()) + list(_CTC_EXPORTS))
+    return sorted(list(globals()) + list(_CTC_EXPORTS) + list(_RNNT_EXPORTS))

@@ -37,6 +37,13 @@ SIGNATURES = {
                                               _ll, _f, _vp]),
     "pika_rnnt_align_scratch_bytes": (_sz, [_i, _i, _i]),
     "pika_rnnt_align": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    # include/pika_rnnt.h, the pruned (banded) lattice
+    "pika_prnnt_forward": (_i, [_vp] * 5 + [_i] * 6 + [_vp] * 3),
+    "pika_prnnt_backward": (_i, [_vp] * 4 + [_i] * 6 + [_vp] * 3 + [_f, _vp]),
+    "pika_prnnt_fused_forward": (_i, [_vp] * 5 + [_i] * 6 + [_vp] * 4),
+    "pika_prnnt_fused_backward": (_i, [_vp] * 6 + [_i] * 6 + [_vp] * 3 + [_i, _ll, _f, _vp]),
+    "pika_prnnt_planes_forward": (_i, [_vp] * 4 + [_i] * 3 + [_vp] * 5),
+    "pika_prnnt_prune_ranges": (_i, [_vp] * 4 + [_i] * 4 + [_vp] * 2),
     # include/pika_ctc.h
     "pika_ctc_workspace_bytes": (_sz, [_i, _i, _i]),
     "pika_ctc_align_scratch_bytes": (_sz, [_i, _i, _i]),

@@ -28,6 +28,10 @@
 //               V-row) reach only 3.5-4.7 TB/s because rows start on non-128-byte boundaries;
 //               the flat form runs at the hipMemsetAsync rate (5.7-5.9 TB/s).
 //
+//   pruned    : the loss on a banded lattice (B,T,S,V) is the BANDED layout of gather / rowmeta over the same planes and
+//               the same alpha/beta, writer and d(logits) kernels; with it the loss of a lattice given by its two
+//               planes, its occupation probabilities and the band search (the end of the kernel section).
+//
 // Algorithmic HBM bytes per utterance (T=1000,U1=51,V=5000): 1.020 GB gradient write + ~1.2 MB
 // lattice traffic; see DESIGN.md.
 
@@ -127,6 +131,15 @@ inline size_t workspace_bytes(int B, int T, int U1) {
 
 __device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// How the (rows, V) tensor of a call maps to lattice cells: the padded (B,T,U1,V) batch, the packed (N, V) rows, or the
+// banded (B,T,S,V) rows of a pruned lattice (pika_rnnt.h: row j of frame t is cell (t, s_t + j)).
+enum Layout { PADDED = 0, PACKED = 1, BANDED = 2 };
+
+// s_t of a banded call: the frame's entry of `ranges`, clamped so that the band stays inside the utterance's columns
+__device__ inline int band_start(const int *__restrict__ ranges, int b, int T, int t, int Un, int S) {
+    return clampi(ranges[(size_t)b * T + t], 0, max(0, Un + 1 - S));
+}
+
 // log(exp(x)+exp(y)) on the transcendental pipe (v_exp_f32 / v_log_f32).
 __device__ inline float lae(float x, float y) {
     const float m = fmaxf(x, y);
@@ -162,41 +175,69 @@ __device__ inline float wave_max(float v) {
 // first wait.  Cells outside the (Tn, Un+1) sub-lattice (and columns >= U1) get NEG.
 // PACKED: log_probs are the (N, V) rows of the packed layout -- cell (t, u) of utterance b is row
 // roff[b] + t (Un+1) + u, its label labels[loff[b] + u] -- and the planes are the same as above.
+// BANDED: log_probs are (B,T,S,V); cell (t, u) is row (b T + t) S + (u - s_t) when s_t <= u < s_t + S and dead (NEG in
+// both planes) otherwise.
 // grid = (ceil(D / (4 * GATHER_ROWS)), Wp / 64, B), block = 256.
 // ---------------------------------------------------------------------------------------------
 constexpr int GATHER_ROWS = 4;
 
-template <bool PACKED = false>
+template <int LAYOUT = PADDED>
 __global__ __launch_bounds__(256) void rnnt_gather_kernel(
     const float *__restrict__ lp, const int *__restrict__ labels, const int *__restrict__ Tn_,
     const int *__restrict__ Un_, int B, int T, int U1, int V, int blank, float *__restrict__ lpb,
     float *__restrict__ lpe, int Wp, int D, const int *__restrict__ roff = nullptr,
-    const int *__restrict__ loff = nullptr) {
+    const int *__restrict__ loff = nullptr, const int *__restrict__ ranges = nullptr, int S = 0) {
+    constexpr bool PACKED = LAYOUT == Layout::PACKED, BANDED = LAYOUT == Layout::BANDED;
     const int b = blockIdx.z;
     const int d0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * GATHER_ROWS;
     const int u = blockIdx.y * 64 + (threadIdx.x & 63);
     if (d0 >= D) return;
     const int Tn = clampi(Tn_[b], 1, T), Un = clampi(Un_[b], 0, U1 - 1);
     // row of cell (0, u) and the row step of t
-    const size_t r0 = PACKED ? (size_t)roff[b] + u : (size_t)b * T * U1 + u;
-    const size_t rt = PACKED ? (size_t)(Un + 1) : (size_t)U1;
+    const size_t r0 = PACKED ? (size_t)roff[b] + u : BANDED ? (size_t)b * T * S : (size_t)b * T * U1 + u;
+    const size_t rt = PACKED ? (size_t)(Un + 1) : BANDED ? (size_t)S : (size_t)U1;
     const int *lab = PACKED ? labels + loff[b] : labels + (size_t)b * (U1 - 1);
     const int y = u < Un ? lab[u] : -1;
     const bool emits = y >= 0 && y < V;
     float vb[GATHER_ROWS], ve[GATHER_ROWS];
+    if constexpr (BANDED) {
+        int j[GATHER_ROWS];  // the band row of cell (t, u); -1: outside the sub-lattice or the band
 #pragma unroll
-    for (int r = 0; r < GATHER_ROWS; ++r) {
-        const int t = d0 + r - u;
-        vb[r] = NEG;
-        if (u <= Un && t >= 0 && t < Tn)
-            vb[r] = fmaxf(lp[(r0 + (size_t)t * rt) * V + blank], NEG);
-    }
+        for (int r = 0; r < GATHER_ROWS; ++r) {
+            const int t = d0 + r - u;
+            j[r] = -1;
+            if (u <= Un && t >= 0 && t < Tn) {
+                const int k = u - band_start(ranges, b, T, t, Un, S);
+                if (k >= 0 && k < S) j[r] = k;
+            }
+        }
 #pragma unroll
-    for (int r = 0; r < GATHER_ROWS; ++r) {
-        const int t = d0 + r - u;
-        ve[r] = NEG;
-        if (emits && t >= 0 && t < Tn)
-            ve[r] = fmaxf(lp[(r0 + (size_t)t * rt) * V + y], NEG);
+        for (int r = 0; r < GATHER_ROWS; ++r) {
+            const int t = d0 + r - u;
+            vb[r] = NEG;
+            if (j[r] >= 0) vb[r] = fmaxf(lp[(r0 + (size_t)t * rt + j[r]) * V + blank], NEG);
+        }
+#pragma unroll
+        for (int r = 0; r < GATHER_ROWS; ++r) {
+            const int t = d0 + r - u;
+            ve[r] = NEG;
+            if (emits && j[r] >= 0) ve[r] = fmaxf(lp[(r0 + (size_t)t * rt + j[r]) * V + y], NEG);
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < GATHER_ROWS; ++r) {
+            const int t = d0 + r - u;
+            vb[r] = NEG;
+            if (u <= Un && t >= 0 && t < Tn)
+                vb[r] = fmaxf(lp[(r0 + (size_t)t * rt) * V + blank], NEG);
+        }
+#pragma unroll
+        for (int r = 0; r < GATHER_ROWS; ++r) {
+            const int t = d0 + r - u;
+            ve[r] = NEG;
+            if (emits && t >= 0 && t < Tn)
+                ve[r] = fmaxf(lp[(r0 + (size_t)t * rt) * V + y], NEG);
+        }
     }
 #pragma unroll
     for (int r = 0; r < GATHER_ROWS; ++r) {
@@ -507,7 +548,8 @@ __global__ __launch_bounds__(NW * 64) void rnnt_alpha_beta_kernel(
 // rowmeta: the two non-zeros of every V-row of the gradient.  The label entry carries the FastEmit
 // factor lscale = 1 + lambda (Yu et al. 2021: d/d lp of every emission scaled, costs unchanged);
 // 1.0f leaves it exact.  PACKED: row r of the (N, V) packed layout, utterance found by a binary
-// search over the row offsets roff (T_n >= 1: strictly increasing).
+// search over the row offsets roff (T_n >= 1: strictly increasing).  BANDED: row (b T + t) S + j of the banded layout is
+// cell (t, s_t + j); a row past the utterance's last column is zero like a row past its last frame.
 // ---------------------------------------------------------------------------------------------
 __device__ inline int packed_utterance(const int *__restrict__ roff, int B, long r) {
     int lo = 0, hi = B - 1;
@@ -518,7 +560,7 @@ __device__ inline int packed_utterance(const int *__restrict__ roff, int B, long
     return lo;
 }
 
-template <bool PACKED = false>
+template <int LAYOUT = PADDED>
 __global__ __launch_bounds__(256) void rnnt_rowmeta_kernel(
     const int *__restrict__ labels, const int *__restrict__ Tn_, const int *__restrict__ Un_,
     int B, int T, int U1, int V, const float *__restrict__ grad_costs,
@@ -526,9 +568,10 @@ __global__ __launch_bounds__(256) void rnnt_rowmeta_kernel(
     const float *__restrict__ beta, const double *__restrict__ off_a,
     const double *__restrict__ off_b, const double *__restrict__ ll, int Wp, int D,
     RowMeta *__restrict__ meta, float lscale, const int *__restrict__ roff = nullptr,
-    const int *__restrict__ loff = nullptr, long npacked = 0) {
+    const int *__restrict__ loff = nullptr, long npacked = 0, const int *__restrict__ ranges = nullptr, int S = 0) {
+    constexpr bool PACKED = LAYOUT == Layout::PACKED, BANDED = LAYOUT == Layout::BANDED;
     const long row = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long nrows = PACKED ? npacked : (long)B * T * U1;
+    const long nrows = PACKED ? npacked : BANDED ? (long)B * T * S : (long)B * T * U1;
     if (row >= nrows) return;
     float gb = 0.f, ge = 0.f;
     int ye = -1;
@@ -541,6 +584,11 @@ __global__ __launch_bounds__(256) void rnnt_rowmeta_kernel(
         t = i / w;
         u = i - t * w;
         lab = labels + loff[b];
+    } else if constexpr (BANDED) {
+        t = (int)((row / S) % T);
+        b = (int)(row / ((long)S * T));
+        u = (int)(row % S) + band_start(ranges, b, T, t, clampi(Un_[b], 0, U1 - 1), S);
+        lab = labels + (size_t)b * (U1 - 1);
     } else {
         u = (int)(row % U1);
         t = (int)((row / U1) % T);
@@ -1171,12 +1219,15 @@ __device__ inline float fwave_sum(float v) {
 
 // PACKED: `logits` are the (N, V) rows of the packed layout (rows = N, roff / loff the row and label offsets of the
 // utterances, B of them): the wave's utterance comes from a binary search over roff, everything else is the same.
-template <int CQ, bool PACKED = false>
+// BANDED: `logits` are (B,T,S,V), rows = B*T*S; row (b T + t) S + j is cell (t, s_t + j).  Only live cells are written:
+// the caller fills both planes with NEG first (rnnt_fill_neg_kernel), which is what the dead cells keep.
+template <int CQ, int LAYOUT = PADDED>
 __global__ __launch_bounds__(256) void rnnt_lse_gather_kernel(
     const float *__restrict__ logits, const int *__restrict__ labels, const int *__restrict__ Tn_,
     const int *__restrict__ Un_, long long rows, int T, int U1, int V, int blank, float *__restrict__ lse,
     float *__restrict__ lpb, float *__restrict__ lpe, int Wp, int D, const int *__restrict__ roff = nullptr,
-    const int *__restrict__ loff = nullptr, int B = 0) {
+    const int *__restrict__ loff = nullptr, int B = 0, const int *__restrict__ ranges = nullptr, int S = 0) {
+    constexpr bool PACKED = LAYOUT == Layout::PACKED, BANDED = LAYOUT == Layout::BANDED;
     const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
     const int lane = threadIdx.x & 63, c4 = V >> 2;
@@ -1189,6 +1240,11 @@ __global__ __launch_bounds__(256) void rnnt_lse_gather_kernel(
         t = i / w;
         u = i - t * w;
         lab = labels + loff[b];
+    } else if constexpr (BANDED) {
+        t = (int)((r / S) % T);
+        b = (int)(r / ((long long)S * T));
+        u = (int)(r % S) + band_start(ranges, b, T, t, clampi(Un_[b], 0, U1 - 1), S);
+        lab = labels + (size_t)b * (U1 - 1);
     } else {
         u = (int)(r % U1);
         t = (int)((r / U1) % T);
@@ -1334,6 +1390,155 @@ __global__ __launch_bounds__(256) void rnnt_dlogits_fused_kernel(const float *__
     }
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// Pruned (banded) lattice, pika_rnnt.h "Pruned RNN-T".  The banded loss itself is the BANDED layout of the gather /
+// log-sum-exp gather / row metadata kernels above; alpha/beta, the flat writer and the fused d(logits) kernel run
+// unchanged over the B*T*S band rows.  Below: the NEG fill under the banded log-sum-exp gather, the loss that takes the
+// two planes directly (the "simple" loss of an am + lm joiner) with its occupation probabilities, and the band search.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rnnt_fill_neg_kernel(v4f *__restrict__ p, size_t n4) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n4) p[i] = v4f{NEG, NEG, NEG, NEG};
+}
+
+// dense (B,T,U1) planes -> the skewed ones: NEG outside the sub-lattice, and in the label plane from column U_n on.
+// grid = (ceil(D / 4), Wp / 64, B), block = 256: a wave per skewed row, lane = u.
+__global__ __launch_bounds__(256) void rnnt_skew_planes_kernel(
+    const float *__restrict__ blank_lp, const float *__restrict__ label_lp, const int *__restrict__ Tn_,
+    const int *__restrict__ Un_, int T, int U1, float *__restrict__ lpb, float *__restrict__ lpe, int Wp, int D) {
+    const int b = blockIdx.z;
+    const int d = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int u = blockIdx.y * 64 + (threadIdx.x & 63);
+    if (d >= D) return;
+    const int Tn = clampi(Tn_[b], 1, T), Un = clampi(Un_[b], 0, U1 - 1);
+    const int t = d - u;
+    float vb = NEG, ve = NEG;
+    if (u <= Un && t >= 0 && t < Tn) {
+        const size_t i = ((size_t)b * T + t) * U1 + u;
+        vb = fmaxf(blank_lp[i], NEG);
+        if (u < Un) ve = fmaxf(label_lp[i], NEG);
+    }
+    const size_t o = ((size_t)b * D + d) * Wp + u;
+    lpb[o] = vb;
+    lpe[o] = ve;
+}
+
+// Occupation probabilities exp(alpha + lp + beta' - ll) of the blank and the label edge of every cell, un-skewed into
+// dense (B,T,U1) planes: the values of rnnt_rowmeta_kernel with unit grad_costs, without the sign.  Zero outside the
+// sub-lattice (and for the label edge of column U_n, the blank edge of the last frame below U_n).
+__global__ __launch_bounds__(256) void rnnt_occupancy_kernel(
+    const int *__restrict__ Tn_, const int *__restrict__ Un_, int B, int T, int U1, const float *__restrict__ lpb,
+    const float *__restrict__ lpe, const float *__restrict__ alpha, const float *__restrict__ beta,
+    const double *__restrict__ off_a, const double *__restrict__ off_b, const double *__restrict__ ll, int Wp, int D,
+    float *__restrict__ blank_occ, float *__restrict__ label_occ) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)B * T * U1) return;
+    const int u = (int)(idx % U1);
+    const int t = (int)((idx / U1) % T);
+    const int b = (int)(idx / ((size_t)U1 * T));
+    const int Tn = clampi(Tn_[b], 1, T), Un = clampi(Un_[b], 0, U1 - 1);
+    float eb = 0.f, ee = 0.f;
+    if (t < Tn && u <= Un) {
+        const int d = t + u;
+        const size_t o = ((size_t)b * D + d) * Wp + u;
+        const float a = alpha[o];
+        const double base = off_a[(size_t)b * D + d] - ll[b];
+        const float k1 = (d + 1 < D) ? (float)(base + off_b[(size_t)b * D + d + 1]) : 0.0f;
+        if (t < Tn - 1)
+            eb = __expf(k1 + (a + beta[o + Wp] + lpb[o]));
+        else if (u == Un)
+            eb = __expf((float)base + (a + lpb[o]));
+        if (u < Un) ee = __expf(k1 + (a + beta[o + Wp + 1] + lpe[o]));
+    }
+    blank_occ[idx] = eb;
+    label_occ[idx] = ee;
+}
+
+// Band search (pika_rnnt.h): one workgroup per utterance.  Phase 1, a wave per frame and a lane per band start s: the
+// window sums of occ = blank_occ + label_occ and their arg-max (ties to the smallest s), into ranges[b][t].  Phases 2 and
+// 3 run in place over that row in chunks of PRUNE_THREADS frames with a carried value: the suffix minimum m, then
+//   f(t) = min(m(t), f(t-1) + S-1), f(0) = 0   ==   t (S-1) + prefix-min of g,  g(0) = 0, g(t) = m(t) - t (S-1),
+// and the lower bound that still reaches s_max at the last frame.
+constexpr int PRUNE_THREADS = 1024;
+
+// inclusive prefix minimum over the workgroup's threads (sh: PRUNE_THREADS values; sh[PRUNE_THREADS - 1] is the total)
+__device__ inline long long block_prefix_min(long long v, long long *sh) {
+    const int i = threadIdx.x;
+    sh[i] = v;
+    __syncthreads();
+    for (int o = 1; o < PRUNE_THREADS; o <<= 1) {
+        const long long w = i >= o ? sh[i - o] : v;
+        __syncthreads();
+        v = w < v ? w : v;
+        sh[i] = v;
+        __syncthreads();
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(PRUNE_THREADS) void rnnt_prune_ranges_kernel(
+    const float *__restrict__ blank_occ, const float *__restrict__ label_occ, const int *__restrict__ Tn_,
+    const int *__restrict__ Un_, int T, int U1, int S, int *ranges) {
+    __shared__ long long sh[PRUNE_THREADS];
+    constexpr long long BIG = 0x7fffffffffffffffLL;
+    const int b = blockIdx.x;
+    const int Tn = clampi(Tn_[b], 1, T), Un = clampi(Un_[b], 0, U1 - 1);
+    const int smax = max(0, Un + 1 - S);
+    int *out = ranges + (size_t)b * T;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int t = wave; t < Tn; t += PRUNE_THREADS / 64) {  // wave-uniform
+        const float *ob = blank_occ + ((size_t)b * T + t) * U1;
+        const float *ol = label_occ + ((size_t)b * T + t) * U1;
+        float bv = -INFINITY;
+        int bs = 0;
+        for (int s = lane; s <= smax; s += 64) {
+            const int hi = min(s + S - 1, Un);
+            float sum = 0.f;
+            for (int u = s; u <= hi; ++u) sum += ob[u] + ol[u];
+            if (sum > bv) { bv = sum; bs = s; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float v2 = __shfl_xor(bv, o);
+            const int s2 = __shfl_xor(bs, o);
+            if (v2 > bv || (v2 == bv && s2 < bs)) { bv = v2; bs = s2; }
+        }
+        if (lane == 0) out[t] = t == Tn - 1 ? smax : bs;
+    }
+    __syncthreads();
+    // suffix minimum: thread i of a chunk takes its frames from the top, so the prefix scan over i is a suffix scan over t
+    long long carry = BIG;
+    for (int base = ((Tn - 1) / PRUNE_THREADS) * PRUNE_THREADS; base >= 0; base -= PRUNE_THREADS) {
+        const int t = base + (PRUNE_THREADS - 1 - (int)threadIdx.x);
+        long long v = t < Tn ? (long long)out[t] : BIG;
+        v = block_prefix_min(v, sh);
+        v = carry < v ? carry : v;
+        if (t < Tn) out[t] = (int)v;
+        const long long tot = sh[PRUNE_THREADS - 1];
+        carry = tot < carry ? tot : carry;
+        __syncthreads();
+    }
+    carry = BIG;
+    const long long step = S - 1;
+    for (int base = 0; base < T; base += PRUNE_THREADS) {
+        const int t = base + (int)threadIdx.x;
+        long long g = BIG;
+        if (t < Tn) g = t == 0 ? 0 : (long long)out[t] - t * step;
+        g = block_prefix_min(g, sh);
+        g = carry < g ? carry : g;
+        if (t < Tn) {
+            const long long f = g + t * step, lo = smax - (long long)(Tn - 1 - t) * step;
+            out[t] = (int)(f > lo ? f : lo);
+        } else if (t < T) {
+            out[t] = smax;
+        }
+        const long long tot = sh[PRUNE_THREADS - 1];
+        carry = tot < carry ? tot : carry;
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1354,7 +1559,7 @@ int pika_rnnt_loss_forward(const float *log_probs, const int *labels, const int 
     const Lattice L = carve(workspace, B, T, U1);
     const dim3 grid((unsigned)((L.D + 4 * GATHER_ROWS - 1) / (4 * GATHER_ROWS)), (unsigned)(L.Wp / 64),
                     (unsigned)B);
-    hipLaunchKernelGGL(rnnt_gather_kernel<false>, grid, dim3(256), 0, s,
+    hipLaunchKernelGGL(rnnt_gather_kernel<PADDED>, grid, dim3(256), 0, s,
                        log_probs, labels, frames_lengths, labels_lengths, B, T, U1, V, blank, L.lpb,
                        L.lpe, L.Wp, L.D);
     return finish_forward(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
@@ -1398,7 +1603,7 @@ int label_scale(float fastemit_lambda, float *lscale) {
 void launch_rowmeta(const Lattice &L, const int *labels, const int *Tn, const int *Un, int B, int T, int U1, int V,
                     const float *grad_costs, float lscale, hipStream_t s) {
     const size_t nrows = (size_t)B * T * U1;
-    hipLaunchKernelGGL(rnnt_rowmeta_kernel<false>, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s,
+    hipLaunchKernelGGL(rnnt_rowmeta_kernel<PADDED>, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s,
                        labels, Tn, Un, B, T, U1, V, grad_costs, L.lpb, L.lpe,
                        L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, L.meta, lscale,
                        static_cast<const int *>(nullptr), static_cast<const int *>(nullptr), 0L);
@@ -1408,7 +1613,7 @@ void launch_rowmeta(const Lattice &L, const int *labels, const int *Tn, const in
 void launch_rowmeta_packed(const Lattice &L, const int *labels, const int *Tn, const int *Un, const int *roff,
                            const int *loff, int B, int T, int U1, long long N, int V, const float *grad_costs,
                            float lscale, hipStream_t s) {
-    hipLaunchKernelGGL(rnnt_rowmeta_kernel<true>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s,
+    hipLaunchKernelGGL(rnnt_rowmeta_kernel<PACKED>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s,
                        labels, Tn, Un, B, T, U1, V, grad_costs, L.lpb, L.lpe,
                        L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, L.meta, lscale, roff, loff, (long)N);
 }
@@ -1618,7 +1823,7 @@ int pika_rnnt_packed_forward(const float *log_probs, const int *labels, const in
     const Lattice L = carve(workspace, B, T_max, U1_max);
     const dim3 grid((unsigned)((L.D + 4 * GATHER_ROWS - 1) / (4 * GATHER_ROWS)), (unsigned)(L.Wp / 64),
                     (unsigned)B);
-    hipLaunchKernelGGL(rnnt_gather_kernel<true>, grid, dim3(256), 0, s, log_probs, labels, frames_lengths,
+    hipLaunchKernelGGL(rnnt_gather_kernel<PACKED>, grid, dim3(256), 0, s, log_probs, labels, frames_lengths,
                        labels_lengths, B, T_max, U1_max, V, blank, L.lpb, L.lpe, L.Wp, L.D, row_offsets, label_offsets);
     return finish_forward(L, frames_lengths, labels_lengths, costs, B, T_max, U1_max, s);
 }
@@ -1651,7 +1856,7 @@ int pika_rnnt_packed_fused_forward(const float *logits, const int *labels, const
     if (!logits || !costs || !lse || !workspace || !logits_ok(logits, V)) return PIKA_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Lattice L = carve(workspace, B, T_max, U1_max);
-    PIKA_CQ(V, hipLaunchKernelGGL((rnnt_lse_gather_kernel<CQ, true>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, logits,
+    PIKA_CQ(V, hipLaunchKernelGGL((rnnt_lse_gather_kernel<CQ, PACKED>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, logits,
                                   labels, frames_lengths, labels_lengths, N, T_max, U1_max, V, blank, lse, L.lpb, L.lpe, L.Wp,
                                   L.D, row_offsets, label_offsets, B));
     return finish_forward(L, frames_lengths, labels_lengths, costs, B, T_max, U1_max, s);
@@ -1698,6 +1903,121 @@ int pika_rnnt_align(const void *workspace, const int *frames_lengths, const int 
                            label_offsets, scores, emit_frames, static_cast<unsigned long long *>(scratch), T, U1, L.Wp, L.D);
     });
     return ok ? (int)hipGetLastError() : PIKA_ETOOBIG;
+}
+
+// ---------------------------------------------------------------------------------------------
+// pruned (banded) lattice (pika_rnnt.h): the planes, alpha/beta and the workspace of the padded (B, T, U1) batch; gather,
+// row metadata and the row passes address the B*T*S band rows
+// ---------------------------------------------------------------------------------------------
+namespace {
+// the banded calls' shared checks: (B, T, U1, V, blank) as check_dims, 1 <= S <= U1, the lengths, the band starts and --
+// when some utterance can have a label -- the labels; B*T*S rows index the row kernels as an int
+int check_banded(int B, int T, int U1, int S, int V, int blank, const int *labels, const int *ranges,
+                 const int *frames_lengths, const int *labels_lengths) {
+    if (V <= 0 || blank < 0 || blank >= V || B <= 0 || T <= 0 || U1 <= 0) return PIKA_EINVAL;
+    if (S < 1 || S > U1) return PIKA_EINVAL;
+    if (U1 > 1024) return PIKA_ETOOBIG;
+    if (!frames_lengths || !labels_lengths || !ranges || (U1 > 1 && !labels)) return PIKA_EINVAL;
+    if ((long long)B * T * S > ROWS_MAX) return PIKA_ETOOBIG;
+    return PIKA_OK;
+}
+
+void launch_rowmeta_banded(const Lattice &L, const int *labels, const int *Tn, const int *Un, const int *ranges, int B,
+                           int T, int U1, int S, int V, const float *grad_costs, float lscale, hipStream_t s) {
+    const size_t nrows = (size_t)B * T * S;
+    hipLaunchKernelGGL(rnnt_rowmeta_kernel<BANDED>, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s, labels, Tn, Un,
+                       B, T, U1, V, grad_costs, L.lpb, L.lpe, L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, L.meta,
+                       lscale, static_cast<const int *>(nullptr), static_cast<const int *>(nullptr), 0L, ranges, S);
+}
+}  // namespace
+
+int pika_prnnt_forward(const float *log_probs, const int *frames_lengths, const int *labels_lengths, const int *labels,
+                       const int *ranges, int B, int T, int U1, int S, int V, int blank, float *costs, void *workspace,
+                       void *stream) {
+    if (int rc = check_banded(B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
+    if (!log_probs || !costs || !workspace) return PIKA_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Lattice L = carve(workspace, B, T, U1);
+    const dim3 grid((unsigned)((L.D + 4 * GATHER_ROWS - 1) / (4 * GATHER_ROWS)), (unsigned)(L.Wp / 64), (unsigned)B);
+    hipLaunchKernelGGL(rnnt_gather_kernel<BANDED>, grid, dim3(256), 0, s, log_probs, labels, frames_lengths, labels_lengths,
+                       B, T, U1, V, blank, L.lpb, L.lpe, L.Wp, L.D, static_cast<const int *>(nullptr),
+                       static_cast<const int *>(nullptr), ranges, S);
+    return finish_forward(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
+}
+
+int pika_prnnt_backward(const int *frames_lengths, const int *labels_lengths, const int *labels, const int *ranges, int B,
+                        int T, int U1, int S, int V, int blank, const float *grad_costs, const void *workspace,
+                        float *grads, float fastemit_lambda, void *stream) {
+    if (int rc = check_banded(B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
+    if (!workspace) return PIKA_EINVAL;
+    float lscale;
+    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
+    launch_rowmeta_banded(L, labels, frames_lengths, labels_lengths, ranges, B, T, U1, S, V, grad_costs, lscale, s);
+    if (!grads) return (int)hipGetLastError();
+    return write_dense_grads(L, (size_t)B * T * S, V, blank, grads, s);
+}
+
+int pika_prnnt_fused_forward(const float *logits, const int *frames_lengths, const int *labels_lengths, const int *labels,
+                             const int *ranges, int B, int T, int U1, int S, int V, int blank, float *costs, float *lse,
+                             void *workspace, void *stream) {
+    if (int rc = check_banded(B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
+    if (!logits || !costs || !lse || !workspace || !logits_ok(logits, V)) return PIKA_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Lattice L = carve(workspace, B, T, U1);
+    const size_t n4 = 2 * plane_elems(B, T, U1) / 4;     // lpb and lpe are adjacent; a plane is a multiple of 64 floats
+    hipLaunchKernelGGL(rnnt_fill_neg_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s,
+                       reinterpret_cast<v4f *>(L.lpb), n4);
+    const long long rows = (long long)B * T * S;
+    PIKA_CQ(V, hipLaunchKernelGGL((rnnt_lse_gather_kernel<CQ, BANDED>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,
+                                  logits, labels, frames_lengths, labels_lengths, rows, T, U1, V, blank, lse, L.lpb, L.lpe,
+                                  L.Wp, L.D, static_cast<const int *>(nullptr), static_cast<const int *>(nullptr), B, ranges,
+                                  S));
+    return finish_forward(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
+}
+
+int pika_prnnt_fused_backward(const float *logits, const float *lse, const int *frames_lengths, const int *labels_lengths,
+                              const int *labels, const int *ranges, int B, int T, int U1, int S, int V, int blank,
+                              const float *grad_costs, const void *workspace, void *grad_logits, int out_dtype,
+                              long long ld_out, float fastemit_lambda, void *stream) {
+    if (int rc = check_banded(B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
+    if (!logits || !lse || !workspace || !grad_logits) return PIKA_EINVAL;
+    if (int rc = check_dlogits_out(logits, V, grad_logits, out_dtype, ld_out)) return rc;
+    float lscale;
+    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
+    launch_rowmeta_banded(L, labels, frames_lengths, labels_lengths, ranges, B, T, U1, S, V, grad_costs, lscale, s);
+    return launch_dlogits_fused(L, logits, lse, (long long)B * T * S, V, blank, grad_logits, out_dtype, ld_out, s);
+}
+
+int pika_prnnt_planes_forward(const float *blank_lp, const float *label_lp, const int *frames_lengths,
+                              const int *labels_lengths, int B, int T, int U1, float *costs, float *blank_occ,
+                              float *label_occ, void *workspace, void *stream) {
+    if (int rc = check_lattice_dims(B, T, U1)) return rc;
+    if (!blank_lp || !label_lp || !frames_lengths || !labels_lengths || !costs || !blank_occ || !label_occ || !workspace)
+        return PIKA_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Lattice L = carve(workspace, B, T, U1);
+    hipLaunchKernelGGL(rnnt_skew_planes_kernel, dim3((unsigned)((L.D + 3) / 4), (unsigned)(L.Wp / 64), (unsigned)B), dim3(256),
+                       0, s, blank_lp, label_lp, frames_lengths, labels_lengths, T, U1, L.lpb, L.lpe, L.Wp, L.D);
+    if (int rc = finish_forward(L, frames_lengths, labels_lengths, costs, B, T, U1, s)) return rc;
+    const size_t cells = (size_t)B * T * U1;
+    hipLaunchKernelGGL(rnnt_occupancy_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, frames_lengths,
+                       labels_lengths, B, T, U1, L.lpb, L.lpe, L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, blank_occ,
+                       label_occ);
+    return (int)hipGetLastError();
+}
+
+int pika_prnnt_prune_ranges(const float *blank_occ, const float *label_occ, const int *frames_lengths,
+                            const int *labels_lengths, int B, int T, int U1, int S, int *ranges, void *stream) {
+    if (B <= 0 || T <= 0 || U1 <= 0 || S < 1 || S > U1) return PIKA_EINVAL;
+    if (U1 > 1024) return PIKA_ETOOBIG;
+    if (!blank_occ || !label_occ || !frames_lengths || !labels_lengths || !ranges) return PIKA_EINVAL;
+    hipLaunchKernelGGL(rnnt_prune_ranges_kernel, dim3((unsigned)B), dim3(PRUNE_THREADS), 0, static_cast<hipStream_t>(stream),
+                       blank_occ, label_occ, frames_lengths, labels_lengths, T, U1, S, ranges);
+    return (int)hipGetLastError();
 }
 
 }  // extern "C"

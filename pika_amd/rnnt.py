@@ -545,6 +545,10 @@ def rnnt_loss(log_probs, labels, frames_lengths, labels_lengths, average_frames=
     lam = _check_lambda(fastemit_lambda)
     fn = _PackedLossFn if compact else _RNNTLossFn
     costs = fn.apply(log_probs, labels, frames_lengths, labels_lengths, blank, lam)
+    return _reduce(costs, frames_lengths, average_frames, reduction)
+
+
+def _reduce(costs, frames_lengths, average_frames, reduction):
     if average_frames:
         costs = costs / frames_lengths.to(costs)
     if reduction == "sum":
@@ -605,6 +609,265 @@ def rnnt_align_from_logits(logits, labels, frames_lengths, labels_lengths, blank
     """`rnnt_align` of log_softmax(logits) without materialising the log-probabilities (V % 4 == 0, V <= 8192):
     the planes come from the one read of the raw logits `rnnt_loss_from_logits` makes."""
     return _align(logits, labels, frames_lengths, labels_lengths, blank, compact, "rnnt_align_from_logits")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Pruned RNN-T (k2 / icefall rnnt_loss_pruned; Kuang et al. 2022, arXiv:2206.13236): the loss on a banded lattice.
+#   planes  = rnnt_simple_planes(am, lm, labels)                      the am + lm joiner's two planes (torch)
+#   simple, bo, lo = rnnt_loss_from_planes(*planes, T_n, U_n, return_occupancy=True)
+#   ranges  = rnnt_prune_ranges(bo, lo, T_n, U_n, S)                  (B, T) int32
+#   logits  = joiner(am[:, :, None], rnnt_prune_lm(lm, ranges, S))    (B, T, S, V)
+#   pruned  = rnnt_loss_pruned_from_logits(logits, labels, ranges, T_n, U_n)
+# Nothing here reads a length on the host: every call can be captured in a torch.cuda.graph.
+# ---------------------------------------------------------------------------------------------------------------------
+def _check_pruned(x, what, labels, ranges, frames_lengths, labels_lengths, blank):
+    _check_tensors(x, what, labels, frames_lengths, labels_lengths, " (there is no CPU path)")
+    if ranges.dtype != torch.int32:
+        raise TypeError("ranges must be int32, got %s" % (ranges.dtype,))
+    if ranges.device != x.device:
+        raise RuntimeError("ranges is on %s but %s is on %s" % (ranges.device, what, x.device))
+    if x.dim() != 4:
+        raise ValueError("%s must be (B,T,S,V), got %s" % (what, tuple(x.shape)))
+    B, T, S, V = x.shape
+    if labels.dim() != 2 or labels.shape[0] != B:
+        raise ValueError("labels must be (B,U) with B=%d, got %s" % (B, tuple(labels.shape)))
+    U1 = labels.shape[1] + 1
+    if tuple(ranges.shape) != (B, T):
+        raise ValueError("ranges must be (B,T)=(%d,%d), got %s" % (B, T, tuple(ranges.shape)))
+    if frames_lengths.shape != (B,) or labels_lengths.shape != (B,):
+        raise ValueError("frames_lengths / labels_lengths must be (B,)")
+    if not 0 <= blank < V:
+        raise ValueError("blank=%d outside [0,%d)" % (blank, V))
+    if U1 > 1024:
+        raise ValueError("U+1=%d > 1024 not supported" % U1)
+    if not 1 <= S <= U1:
+        raise ValueError("the band width S=%d must be in [1, U+1=%d]" % (S, U1))
+    if B * T * S > 0x7fffffff:
+        raise ValueError("B*T*S = %d rows > 2^31 - 1" % (B * T * S))
+    return B, T, U1, S, V
+
+
+class _PrunedLossFn(torch.autograd.Function):
+    """RNN-T costs on the banded lattice from log-probs (B,T,S,V); dense gradient (B,T,S,V)."""
+
+    @staticmethod
+    def forward(ctx, log_probs, labels, ranges, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0):
+        B, T, U1, S, V = _check_pruned(log_probs, "log_probs", labels, ranges, frames_lengths, labels_lengths, blank)
+        lib = _lib.lib()
+        x = log_probs.detach().contiguous()
+        labels, ranges, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, ranges, frames_lengths,
+                                                                                   labels_lengths))
+        with torch.cuda.device(x.device):
+            costs = torch.empty(B, dtype=torch.float32, device=x.device)
+            ws = torch.empty(lib.pika_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8, device=x.device)
+            with _timed("fwd"):
+                _lib.check(lib.pika_prnnt_forward(_ptr(x), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(labels),
+                                                  _ptr(ranges), B, T, U1, S, V, blank, _ptr(costs), _ptr(ws), _stream()),
+                           "pika_prnnt_forward")
+        ctx.save_for_backward(labels, ranges, frames_lengths, labels_lengths, ws)
+        ctx.dims = (B, T, U1, S, V, blank)
+        ctx.fastemit_lambda = fastemit_lambda
+        return costs
+
+    @staticmethod
+    def backward(ctx, grad_costs):
+        labels, ranges, frames_lengths, labels_lengths, ws = ctx.saved_tensors
+        B, T, U1, S, V, blank = ctx.dims
+        gc = grad_costs.to(torch.float32).contiguous()
+        with torch.cuda.device(ws.device):
+            grads = torch.empty((B, T, S, V), dtype=torch.float32, device=ws.device)
+            with _timed("bwd"):
+                _lib.check(_lib.lib().pika_prnnt_backward(
+                    _ptr(frames_lengths), _ptr(labels_lengths), _ptr(labels), _ptr(ranges), B, T, U1, S, V, blank, _ptr(gc),
+                    _ptr(ws), _ptr(grads), ctx.fastemit_lambda, _stream()), "pika_prnnt_backward")
+        return grads, None, None, None, None, None, None
+
+
+class _PrunedLogitsLossFn(torch.autograd.Function):
+    """_FusedLogitsLossFn on the banded lattice: raw logits (B,T,S,V) in, d(logits) out, no log-prob tensor."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ranges, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0):
+        B, T, U1, S, V = _check_pruned(logits, "logits", labels, ranges, frames_lengths, labels_lengths, blank)
+        if not _fused_v_ok(V):
+            raise ValueError("rnnt_loss_pruned_from_logits: V = %d must be a multiple of 4 and <= %d" % (V, MAX_FUSED_V))
+        lib = _lib.lib()
+        x = logits.detach().contiguous()
+        labels, ranges, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, ranges, frames_lengths,
+                                                                                   labels_lengths))
+        with torch.cuda.device(x.device):
+            costs = torch.empty(B, dtype=torch.float32, device=x.device)
+            lse = torch.empty(B * T * S, dtype=torch.float32, device=x.device)
+            ws = torch.empty(lib.pika_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8, device=x.device)
+            with _timed("fwd"):
+                _lib.check(lib.pika_prnnt_fused_forward(_ptr(x), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(labels),
+                                                        _ptr(ranges), B, T, U1, S, V, blank, _ptr(costs), _ptr(lse),
+                                                        _ptr(ws), _stream()), "pika_prnnt_fused_forward")
+        ctx.save_for_backward(x, labels, ranges, frames_lengths, labels_lengths, ws, lse)
+        ctx.dims = (B, T, U1, S, V, blank)
+        ctx.fastemit_lambda = fastemit_lambda
+        return costs
+
+    @staticmethod
+    def backward(ctx, grad_costs):
+        x, labels, ranges, frames_lengths, labels_lengths, ws, lse = ctx.saved_tensors
+        B, T, U1, S, V, blank = ctx.dims
+        gc = grad_costs.to(torch.float32).contiguous()
+        with torch.cuda.device(x.device):
+            grads = torch.empty_like(x)
+            with _timed("bwd"):
+                _lib.check(_lib.lib().pika_prnnt_fused_backward(
+                    _ptr(x), _ptr(lse), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(labels), _ptr(ranges), B, T, U1, S,
+                    V, blank, _ptr(gc), _ptr(ws), _ptr(grads), 0, V, ctx.fastemit_lambda, _stream()),
+                    "pika_prnnt_fused_backward")
+        return grads, None, None, None, None, None, None
+
+
+def rnnt_loss_pruned(log_probs, labels, ranges, frames_lengths, labels_lengths, average_frames=False, reduction=None,
+                     blank=0, fastemit_lambda=0.0):
+    """RNN-T costs on a pruned (banded) lattice, differentiable w.r.t. log_probs.
+
+    log_probs (B, T, S, V) f32: row j of frame t is the distribution of lattice cell (t, ranges[b, t] + j); labels
+    (B, U) int32; ranges (B, T) int32, every entry clamped on the device to [0, max(0, U_n + 1 - S)].  Only cells inside
+    the band carry probability: the cost is that of `rnnt_loss` on a (B, T, U+1, V) tensor holding the band's rows at
+    their cells and -1e30 elsewhere.  The gradient is dense (B, T, S, V); rows past T_n or U_n are zero.  With S = U + 1
+    and all-zero ranges this is `rnnt_loss`, bit for bit.  Keywords as in `rnnt_loss`; no host synchronisation."""
+    lam = _check_lambda(fastemit_lambda)
+    costs = _PrunedLossFn.apply(log_probs, labels, ranges, frames_lengths, labels_lengths, blank, lam)
+    return _reduce(costs, frames_lengths, average_frames, reduction)
+
+
+def rnnt_loss_pruned_from_logits(logits, labels, ranges, frames_lengths, labels_lengths, average_frames=False,
+                                 reduction=None, blank=0, fastemit_lambda=0.0):
+    """`rnnt_loss_pruned` of log_softmax(logits) for raw logits (B, T, S, V), V % 4 == 0 and V <= 8192, differentiable
+    w.r.t. the logits: the log-probabilities and their dense gradient never exist."""
+    lam = _check_lambda(fastemit_lambda)
+    costs = _PrunedLogitsLossFn.apply(logits, labels, ranges, frames_lengths, labels_lengths, blank, lam)
+    return _reduce(costs, frames_lengths, average_frames, reduction)
+
+
+def _check_planes(a, b, frames_lengths, labels_lengths, names):
+    for name, t in zip(names, (a, b)):
+        if not t.is_cuda:
+            raise RuntimeError("pika_amd RNNTLoss: %s must live on a HIP device (there is no CPU path)" % name)
+        if t.dtype != torch.float32:
+            raise TypeError("%s must be float32, got %s" % (name, t.dtype))
+    if a.dim() != 3 or a.shape != b.shape:
+        raise ValueError("%s and %s must both be (B,T,U+1), got %s and %s" % (names + (tuple(a.shape), tuple(b.shape))))
+    B, T, U1 = a.shape
+    for name, t in (("frames_lengths", frames_lengths), ("labels_lengths", labels_lengths)):
+        if t.dtype != torch.int32:
+            raise TypeError("%s must be int32, got %s" % (name, t.dtype))
+        if t.device != a.device or b.device != a.device:
+            raise RuntimeError("%s is on %s but %s is on %s" % (name, t.device, names[0], a.device))
+        if t.shape != (B,):
+            raise ValueError("frames_lengths / labels_lengths must be (B,)")
+    if U1 > 1024:
+        raise ValueError("U+1=%d > 1024 not supported" % U1)
+    return B, T, U1
+
+
+class _PlanesLossFn(torch.autograd.Function):
+    """RNN-T costs of a lattice given by its blank and label planes; also returns the two occupancy planes (detached)."""
+
+    @staticmethod
+    def forward(ctx, blank_lp, label_lp, frames_lengths, labels_lengths):
+        B, T, U1 = _check_planes(blank_lp, label_lp, frames_lengths, labels_lengths, ("blank_lp", "label_lp"))
+        lib = _lib.lib()
+        pb, pl = blank_lp.detach().contiguous(), label_lp.detach().contiguous()
+        frames_lengths, labels_lengths = frames_lengths.contiguous(), labels_lengths.contiguous()
+        with torch.cuda.device(pb.device):
+            costs = torch.empty(B, dtype=torch.float32, device=pb.device)
+            occ_b, occ_l = torch.empty_like(pb), torch.empty_like(pb)
+            ws = torch.empty(lib.pika_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8, device=pb.device)
+            with _timed(None):
+                _lib.check(lib.pika_prnnt_planes_forward(_ptr(pb), _ptr(pl), _ptr(frames_lengths), _ptr(labels_lengths), B, T,
+                                                         U1, _ptr(costs), _ptr(occ_b), _ptr(occ_l), _ptr(ws), _stream()),
+                           "pika_prnnt_planes_forward")
+        ctx.save_for_backward(occ_b, occ_l)
+        ctx.mark_non_differentiable(occ_b, occ_l)
+        return costs, occ_b, occ_l
+
+    @staticmethod
+    def backward(ctx, grad_costs, _gb, _gl):
+        occ_b, occ_l = ctx.saved_tensors
+        g = -grad_costs.to(torch.float32).view(-1, 1, 1)
+        return occ_b * g, occ_l * g, None, None
+
+
+def rnnt_loss_from_planes(blank_lp, label_lp, frames_lengths, labels_lengths, reduction=None, return_occupancy=False):
+    """RNN-T costs of a lattice given directly by its two planes, differentiable w.r.t. both.
+
+    blank_lp, label_lp (B, T, U+1) f32: the log-probability of the blank edge and of the label edge out of every cell
+    (label_lp[.., u] is not read for u >= U_n); they need not be normalised.  This is the "simple" loss of pruned RNN-T
+    on the planes of `rnnt_simple_planes`.  return_occupancy=True: (costs, blank_occ, label_occ), the two detached
+    (B, T, U+1) planes of per-edge occupation probabilities -d cost / d lp, what `rnnt_prune_ranges` takes."""
+    costs, occ_b, occ_l = _PlanesLossFn.apply(blank_lp, label_lp, frames_lengths, labels_lengths)
+    costs = _reduce(costs, frames_lengths, False, reduction)
+    return (costs, occ_b, occ_l) if return_occupancy else costs
+
+
+def rnnt_prune_ranges(blank_occ, label_occ, frames_lengths, labels_lengths, s_range):
+    """The band of `s_range` label positions every frame keeps: (B, T) int32 band starts.
+
+    With occ = blank_occ + label_occ (B, T, U+1), S = s_range and s_max = max(0, U_n + 1 - S): raw(t) is the start of the
+    window of S columns with the largest occupancy sum (ties to the smallest start; raw(T_n - 1) = s_max), m its suffix
+    minimum, f(0) = 0, f(t) = min(m(t), f(t-1) + S - 1), and s_t = max(f(t), s_max - (T_n - 1 - t)(S - 1)); s_max for
+    t >= T_n.  The band connects (0, 0) with (T_n - 1, U_n) -- s_0 = 0, s_{T_n-1} = s_max, steps in [0, S-1] -- whenever
+    (T_n - 1)(S - 1) >= s_max; otherwise none of that width does and s_0 > 0."""
+    S = int(s_range)
+    B, T, U1 = _check_planes(blank_occ, label_occ, frames_lengths, labels_lengths, ("blank_occ", "label_occ"))
+    if not 1 <= S <= U1:
+        raise ValueError("s_range=%d must be in [1, U+1=%d]" % (S, U1))
+    ob, ol = blank_occ.detach().contiguous(), label_occ.detach().contiguous()
+    frames_lengths, labels_lengths = frames_lengths.contiguous(), labels_lengths.contiguous()
+    with torch.cuda.device(ob.device):
+        ranges = torch.empty((B, T), dtype=torch.int32, device=ob.device)
+        _lib.check(_lib.lib().pika_prnnt_prune_ranges(_ptr(ob), _ptr(ol), _ptr(frames_lengths), _ptr(labels_lengths), B, T,
+                                                      U1, S, _ptr(ranges), _stream()), "pika_prnnt_prune_ranges")
+    return ranges
+
+
+def rnnt_simple_planes(am, lm, labels, blank=0):
+    """The two planes of the joiner that is am + lm (plain torch, differentiable): (blank_lp, label_lp), (B, T, U+1).
+
+    am (B, T, V) encoder logits, lm (B, U+1, V) prediction logits, labels (B, U).  Cell (t, u) has the distribution
+    log_softmax(am[b, t] + lm[b, u]); its normaliser over V is a max-shifted exp-matmul, so no (B, T, U+1, V) tensor
+    exists.  label_lp[.., u] = that distribution at labels[b, u] (padding labels are clamped into [0, V): the loss never
+    reads u >= U_n); its last column u = U is -1e30."""
+    if am.dim() != 3 or lm.dim() != 3 or am.shape[0] != lm.shape[0] or am.shape[2] != lm.shape[2]:
+        raise ValueError("am must be (B,T,V) and lm (B,U+1,V), got %s and %s" % (tuple(am.shape), tuple(lm.shape)))
+    B, U1, V = lm.shape
+    if labels.dim() != 2 or labels.shape != (B, U1 - 1):
+        raise ValueError("labels must be (B,U)=(%d,%d), got %s" % (B, U1 - 1, tuple(labels.shape)))
+    if not 0 <= blank < V:
+        raise ValueError("blank=%d outside [0,%d)" % (blank, V))
+    am, lm = am.float(), lm.float()
+    am_max, lm_max = am.amax(2, keepdim=True), lm.amax(2, keepdim=True)                    # (B,T,1), (B,U1,1)
+    prod = torch.matmul((am - am_max).exp(), (lm - lm_max).exp().transpose(1, 2))          # (B,T,U1)
+    norm = prod.clamp_min(torch.finfo(torch.float32).tiny).log() + am_max + lm_max.transpose(1, 2)
+    blank_lp = am[:, :, blank].unsqueeze(2) + lm[:, :, blank].unsqueeze(1) - norm
+    y = labels.long().clamp(0, V - 1)                                                      # (B,U)
+    am_y = torch.gather(am, 2, y.unsqueeze(1).expand(B, am.shape[1], U1 - 1))              # (B,T,U)
+    lm_y = torch.gather(lm[:, :U1 - 1], 2, y.unsqueeze(2)).squeeze(2)                      # (B,U)
+    label_lp = am_y + lm_y.unsqueeze(1) - norm[:, :, :U1 - 1]
+    label_lp = torch.cat([label_lp, label_lp.new_full((B, am.shape[1], 1), -1.0e30)], 2)
+    return blank_lp, label_lp
+
+
+def rnnt_prune_lm(lm, ranges, s_range):
+    """The prediction-network rows of every frame's band: lm (B, U+1, D), ranges (B, T) -> (B, T, S, D), entry
+    [b, t, j] = lm[b, s_t + j] with s_t clamped to [0, max(0, U + 1 - S)] and the row index to U (plain torch)."""
+    S = int(s_range)
+    B, U1, D = lm.shape
+    if tuple(ranges.shape[:1]) != (B,) or ranges.dim() != 2:
+        raise ValueError("ranges must be (B,T) with B=%d, got %s" % (B, tuple(ranges.shape)))
+    if not 1 <= S <= U1:
+        raise ValueError("s_range=%d must be in [1, U+1=%d]" % (S, U1))
+    T = ranges.shape[1]
+    idx = ranges.long().clamp(0, max(0, U1 - S)).unsqueeze(2) + torch.arange(S, device=ranges.device)   # (B,T,S)
+    idx = idx.clamp_max(U1 - 1)
+    return torch.gather(lm.unsqueeze(1).expand(B, T, U1, D), 2, idx.unsqueeze(3).expand(B, T, S, D))
 
 
 class RNNTLoss(object):
