@@ -35,6 +35,27 @@ int pika_joint_gate_bwd(const void *dh, int dh_dtype, const float *e1, const flo
                         const float *pg, float *de1, float *dp1, float *deg, float *dpg,
                         int B, int T, int U, int H, void *stream);
 
+/* The gate on a pruned (banded) lattice (pika_rnnt.h "Pruned RNN-T"): frame t keeps S of the U prediction rows, those
+ * from s_t = clamp(ranges[b,t], 0, U - S); ranges (B,T) i32.  (U counts prediction rows: the loss's U + 1.)
+ *   h[b,t,j,:] = gate(e1[b,t,:] + p1[b,s_t+j,:], eg[b,t,:] + pg[b,s_t+j,:]),  j = 0 .. S-1,  h (B,T,S,H)
+ * which is pika_joint_gate_fwd on the rows rnnt_prune_lm gathers, without gathering them: clamps, NaN rule, bf16 rounding
+ * and refusals are those of pika_joint_gate_fwd, and S == U with all-zero ranges gives its output bit for bit.  Lengths
+ * are no argument: every (b,t,j) is computed.  Also PIKA_EINVAL: null ranges, S <= 0, S > U. */
+int pika_joint_gate_banded_fwd(const float *e1, const float *p1, const float *eg, const float *pg,
+                               const int *ranges, void *h, int out_dtype, int B, int T, int U, int S, int H,
+                               void *stream);
+
+/* Backward of the banded gate given dh (B,T,S,H), dh_dtype PIKA_F32 | PIKA_BF16, dz1 / dzg as for pika_joint_gate_bwd:
+ *   de1/deg[b,t,:] = sum over j = 0 .. S-1 (in that order) of dz[b,t,j,:]
+ *   dp1/dpg[b,u,:] = sum over the frames t with s_t <= u < s_t + S (in increasing t) of dz[b,t,u-s_t,:]
+ * One accumulator per output element and no atomics: two runs give the same bits.  Every element of the four outputs is
+ * written; a row u that no frame's band covers gets +0.  The ranges need not be monotone (a valid band's covering frames
+ * are an interval; nothing relies on it).  Rows the loss treats as dead are expected to arrive with dh = 0.  S == U with
+ * all-zero ranges gives pika_joint_gate_bwd's four outputs bit for bit.  Refusals as for pika_joint_gate_banded_fwd. */
+int pika_joint_gate_banded_bwd(const void *dh, int dh_dtype, const float *e1, const float *p1, const float *eg,
+                               const float *pg, const int *ranges, float *de1, float *dp1, float *deg, float *dpg,
+                               int B, int T, int U, int S, int H, void *stream);
+
 /* In place on x (rows, cols) f32 with pitch ld >= cols: x = log_softmax(scale * x) per row.  Columns [cols, ld) and rows
  * beyond `rows` are neither read into a result nor written.  Any cols, ld and alignment of x are accepted (cols % 4 == 0,
  * ld % 4 == 0, x 16-byte aligned and cols <= 8192 take the wave-per-row kernels, everything else the block kernel).

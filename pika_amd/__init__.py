@@ -67,7 +67,10 @@ _CTC_EXPORTS = ("ctc_loss", "ctc_loss_from_logits", "CTCLoss", "ctc_align", "ctc
 
 # The pruned RNN-T surface (pika_amd/rnnt.py), resolved the same way.
 _RNNT_EXPORTS = ("rnnt_loss_pruned", "rnnt_loss_pruned_from_logits", "rnnt_loss_from_planes", "rnnt_prune_ranges",
-                 "rnnt_simple_planes", "rnnt_prune_lm")
+                 "rnnt_simple_planes", "rnnt_prune_lm", "rnnt_pruned_joint_loss")
+
+# The joint network on the band (pika_amd/model/ops.py).
+_OPS_EXPORTS = ("joint_pruned",)
 
 
 def __getattr__(name):
@@ -77,8 +80,11 @@ def __getattr__(name):
     if name in _RNNT_EXPORTS:
         from . import rnnt
         return getattr(rnnt, name)
+    if name in _OPS_EXPORTS:
+        from .model import ops
+        return getattr(ops, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
 def __dir__():
-    return sorted(list(globals()) + list(_CTC_EXPORTS) + list(_RNNT_EXPORTS))
+    return sorted(list(globals()) + list(_CTC_EXPORTS) + list(_RNNT_EXPORTS) + list(_OPS_EXPORTS))

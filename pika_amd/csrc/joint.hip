@@ -116,6 +116,115 @@ __global__ void gate_bwd_kernel(const TD *__restrict__ dh, const float *__restri
     }
 }
 
+// ---- the gate on a pruned (banded) lattice: frame t keeps the S prediction rows s_t .. s_t + S - 1, s_t =
+// clamp(ranges[b,t], 0, U - S) (rnnt_prune_lm's index); h and dh are (B,T,S,H).  Same device functions, same summation
+// orders as the kernels above, so S = U with all-zero ranges gives their bits. ----
+__device__ inline int band_start(const int *__restrict__ ranges, int b, int T, int t, int smax) {
+    return min(max(ranges[(size_t)b * T + t], 0), smax);
+}
+
+// grid (T, B), block H/4 threads (<= 1024): thread owns 4 channels, loops over the band's rows.
+template <typename TOUT>
+__global__ void gate_banded_fwd_kernel(const float *__restrict__ e1, const float *__restrict__ p1,
+                                       const float *__restrict__ eg, const float *__restrict__ pg,
+                                       const int *__restrict__ ranges, TOUT *__restrict__ h, int T, int U, int S,
+                                       int H) {
+    const int b = blockIdx.y, t = blockIdx.x;
+    const int H4 = H >> 2;
+    const int s = band_start(ranges, b, T, t, U - S);
+    for (int c = threadIdx.x; c < H4; c += blockDim.x) {
+        const f32x4 a1 = reinterpret_cast<const f32x4 *>(e1 + ((size_t)b * T + t) * H)[c];
+        const f32x4 ag = reinterpret_cast<const f32x4 *>(eg + ((size_t)b * T + t) * H)[c];
+        for (int j = 0; j < S; ++j) {
+            const f32x4 b1 = reinterpret_cast<const f32x4 *>(p1 + ((size_t)b * U + s + j) * H)[c];
+            const f32x4 bg = reinterpret_cast<const f32x4 *>(pg + ((size_t)b * U + s + j) * H)[c];
+            const f32x4 r = gate4(a1 + b1, ag + bg);
+            TOUT *dst = h + (((size_t)b * T + t) * S + j) * H + 4 * c;
+            if constexpr (sizeof(TOUT) == 4)
+                *reinterpret_cast<f32x4 *>(dst) = r;
+            else
+                *reinterpret_cast<bf16x4 *>(dst) = __builtin_convertvector(r, bf16x4);
+        }
+    }
+}
+
+// Encoder side, grid (T, B): de1/deg[b,t,:] = sum over the band's rows j = 0 .. S-1, in that order.
+template <typename TD>
+__global__ void gate_banded_bwd_enc_kernel(const TD *__restrict__ dh, const float *__restrict__ e1,
+                                           const float *__restrict__ p1, const float *__restrict__ eg,
+                                           const float *__restrict__ pg, const int *__restrict__ ranges,
+                                           float *__restrict__ o1, float *__restrict__ og, int T, int U, int S,
+                                           int H) {
+    const int b = blockIdx.y, t = blockIdx.x;
+    const int H4 = H >> 2;
+    const int s = band_start(ranges, b, T, t, U - S);
+    for (int c = threadIdx.x; c < H4; c += blockDim.x) {
+        f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, sg = {0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < S; ++j) {
+            const int u = s + j;
+            const f32x4 z1 = reinterpret_cast<const f32x4 *>(e1 + ((size_t)b * T + t) * H)[c] +
+                             reinterpret_cast<const f32x4 *>(p1 + ((size_t)b * U + u) * H)[c];
+            const f32x4 zg = reinterpret_cast<const f32x4 *>(eg + ((size_t)b * T + t) * H)[c] +
+                             reinterpret_cast<const f32x4 *>(pg + ((size_t)b * U + u) * H)[c];
+            const f32x4 d = load_dh4<TD>(dh + (((size_t)b * T + t) * S + j) * H + 4 * c);
+            float a, g;
+            gate_grads(z1.x, zg.x, d.x, a, g); s1.x += a; sg.x += g;
+            gate_grads(z1.y, zg.y, d.y, a, g); s1.y += a; sg.y += g;
+            gate_grads(z1.z, zg.z, d.z, a, g); s1.z += a; sg.z += g;
+            gate_grads(z1.w, zg.w, d.w, a, g); s1.w += a; sg.w += g;
+        }
+        const size_t o = ((size_t)b * T + t) * H;
+        reinterpret_cast<f32x4 *>(o1 + o)[c] = s1;
+        reinterpret_cast<f32x4 *>(og + o)[c] = sg;
+    }
+}
+
+// Prediction side, grid (U, B), block a multiple of 64 threads: dp1/dpg[b,u,:] = sum over the frames t whose band holds
+// row u (s_t <= u < s_t + S), in increasing t; one accumulator per output element, no atomics, +0 for a row no band
+// covers.  Every wave scans ranges[b,:] itself, 64 frames per load: lane l tests frame base + l, the ballot of the test is
+// the (wave-uniform) set of covering frames of the chunk, walked from its lowest bit.  Nothing assumes monotone ranges.
+template <typename TD>
+__global__ void gate_banded_bwd_pred_kernel(const TD *__restrict__ dh, const float *__restrict__ e1,
+                                            const float *__restrict__ p1, const float *__restrict__ eg,
+                                            const float *__restrict__ pg, const int *__restrict__ ranges,
+                                            float *__restrict__ o1, float *__restrict__ og, int T, int U, int S,
+                                            int H) {
+    const int b = blockIdx.y, u = blockIdx.x;
+    const int H4 = H >> 2, lane = threadIdx.x & 63, smax = U - S;
+    for (int c0 = 0; c0 < H4; c0 += blockDim.x) {          // uniform trip count: every lane reaches the ballots
+        const int c = c0 + threadIdx.x;
+        const bool live = c < H4;
+        f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, sg = {0.f, 0.f, 0.f, 0.f};
+        for (int base = 0; base < T; base += 64) {
+            const int tl = base + lane;
+            const int jl = tl < T ? u - band_start(ranges, b, T, tl, smax) : -1;
+            unsigned long long m = __builtin_amdgcn_ballot_w64(jl >= 0 && jl < S);
+            while (m) {
+                const int k = __builtin_ctzll(m);
+                m &= m - 1;
+                const int t = base + k, j = __builtin_amdgcn_readlane(jl, k);
+                if (live) {
+                    const f32x4 z1 = reinterpret_cast<const f32x4 *>(e1 + ((size_t)b * T + t) * H)[c] +
+                                     reinterpret_cast<const f32x4 *>(p1 + ((size_t)b * U + u) * H)[c];
+                    const f32x4 zg = reinterpret_cast<const f32x4 *>(eg + ((size_t)b * T + t) * H)[c] +
+                                     reinterpret_cast<const f32x4 *>(pg + ((size_t)b * U + u) * H)[c];
+                    const f32x4 d = load_dh4<TD>(dh + (((size_t)b * T + t) * S + j) * H + 4 * c);
+                    float a, g;
+                    gate_grads(z1.x, zg.x, d.x, a, g); s1.x += a; sg.x += g;
+                    gate_grads(z1.y, zg.y, d.y, a, g); s1.y += a; sg.y += g;
+                    gate_grads(z1.z, zg.z, d.z, a, g); s1.z += a; sg.z += g;
+                    gate_grads(z1.w, zg.w, d.w, a, g); s1.w += a; sg.w += g;
+                }
+            }
+        }
+        if (live) {
+            const size_t o = ((size_t)b * U + u) * H;
+            reinterpret_cast<f32x4 *>(o1 + o)[c] = s1;
+            reinterpret_cast<f32x4 *>(og + o)[c] = sg;
+        }
+    }
+}
+
 // ---- row kernels: one 256-thread workgroup per row, strided scalar passes over the row; taken for every call the
 // wave-per-row kernels below do not take (wave_row_ok(): cols, pitch or base not a multiple of four floats, cols > 8192) ----
 constexpr int ROW_THREADS = 256;
@@ -339,6 +448,49 @@ int pika_joint_gate_bwd(const void *dh, int dh_dtype, const float *e1, const flo
                            dp1, dpg, T, U, H);
     } else {
         return PIKA_EINVAL;
+    }
+    return (int)hipGetLastError();
+}
+
+int pika_joint_gate_banded_fwd(const float *e1, const float *p1, const float *eg, const float *pg,
+                               const int *ranges, void *h, int out_dtype, int B, int T, int U, int S, int H,
+                               void *stream) {
+    if (!e1 || !p1 || !eg || !pg || !ranges || !h || B <= 0 || T <= 0 || U <= 0 || S <= 0 || H <= 0 || (H & 3) ||
+        S > U || (out_dtype != PIKA_F32 && out_dtype != PIKA_BF16))
+        return PIKA_EINVAL;
+    if (B > 65535) return PIKA_ETOOBIG;
+    const int threads = min(1024, ((H / 4 + 63) / 64) * 64);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (out_dtype == PIKA_F32)
+        hipLaunchKernelGGL(gate_banded_fwd_kernel<float>, dim3(T, B), dim3(threads), 0, s, e1, p1, eg, pg, ranges,
+                           static_cast<float *>(h), T, U, S, H);
+    else
+        hipLaunchKernelGGL(gate_banded_fwd_kernel<__bf16>, dim3(T, B), dim3(threads), 0, s, e1, p1, eg, pg, ranges,
+                           static_cast<__bf16 *>(h), T, U, S, H);
+    return (int)hipGetLastError();
+}
+
+int pika_joint_gate_banded_bwd(const void *dh, int dh_dtype, const float *e1, const float *p1, const float *eg,
+                               const float *pg, const int *ranges, float *de1, float *dp1, float *deg, float *dpg,
+                               int B, int T, int U, int S, int H, void *stream) {
+    if (!dh || !e1 || !p1 || !eg || !pg || !ranges || !de1 || !dp1 || !deg || !dpg || B <= 0 || T <= 0 ||
+        U <= 0 || S <= 0 || H <= 0 || (H & 3) || S > U || (dh_dtype != PIKA_F32 && dh_dtype != PIKA_BF16))
+        return PIKA_EINVAL;
+    if (B > 65535) return PIKA_ETOOBIG;
+    const int threads = min(1024, ((H / 4 + 63) / 64) * 64);      // a multiple of 64: the ballots need whole waves
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dh_dtype == PIKA_F32) {
+        const float *d = static_cast<const float *>(dh);
+        hipLaunchKernelGGL(gate_banded_bwd_enc_kernel<float>, dim3(T, B), dim3(threads), 0, s, d, e1, p1, eg, pg,
+                           ranges, de1, deg, T, U, S, H);
+        hipLaunchKernelGGL(gate_banded_bwd_pred_kernel<float>, dim3(U, B), dim3(threads), 0, s, d, e1, p1, eg, pg,
+                           ranges, dp1, dpg, T, U, S, H);
+    } else {
+        const __bf16 *d = static_cast<const __bf16 *>(dh);
+        hipLaunchKernelGGL(gate_banded_bwd_enc_kernel<__bf16>, dim3(T, B), dim3(threads), 0, s, d, e1, p1, eg, pg,
+                           ranges, de1, deg, T, U, S, H);
+        hipLaunchKernelGGL(gate_banded_bwd_pred_kernel<__bf16>, dim3(U, B), dim3(threads), 0, s, d, e1, p1, eg, pg,
+                           ranges, dp1, dpg, T, U, S, H);
     }
     return (int)hipGetLastError();
 }

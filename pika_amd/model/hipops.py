@@ -480,6 +480,54 @@ class GateFn(torch.autograd.Function):
         return de1, dp1, deg, dpg
 
 
+class BandedGateFn(torch.autograd.Function):
+    """GateFn on a pruned lattice: h[b,t,j,:] = gate(e1[b,t]+p1[b,s_t+j], eg[b,t]+pg[b,s_t+j]), j < s_range, with
+    s_t = clamp(ranges[b,t], 0, U - s_range) -- the rows `rnnt_prune_lm` gathers, read in place (include/pika_joint.h).
+
+    Output (B,T,S,H), bf16 / fp32 as GateFn's.  Only the four small inputs and ranges are saved; the backward recomputes
+    the gate, sums the prediction side per row in frame order (no atomics: two runs agree bit for bit) and returns no
+    gradient for ranges."""
+
+    @staticmethod
+    def forward(ctx, e1, p1, eg, pg, ranges, s_range):
+        e1, p1, eg, pg = [t.contiguous() for t in (e1, p1, eg, pg)]
+        Bn, T, H = e1.shape
+        U, S = p1.shape[1], int(s_range)
+        if ranges.dtype != torch.int32 or tuple(ranges.shape) != (Bn, T) or ranges.device != e1.device:
+            raise ValueError("ranges must be int32 (B,T)=(%d,%d) on %s, got %s %s on %s" % (
+                Bn, T, e1.device, ranges.dtype, tuple(ranges.shape), ranges.device))
+        if not 1 <= S <= U:
+            raise ValueError("s_range=%d must be in [1, U+1=%d]" % (S, U))
+        ranges = ranges.contiguous()
+        dt = torch.bfloat16 if G.joint_in_bf16() else torch.float32
+        h = torch.empty((Bn, T, S, H), dtype=dt, device=e1.device)
+        with torch.cuda.device(e1.device):
+            _lib.check(_lib.lib().pika_joint_gate_banded_fwd(
+                e1.data_ptr(), p1.data_ptr(), eg.data_ptr(), pg.data_ptr(), ranges.data_ptr(), h.data_ptr(),
+                G.PIKA_F32 if dt == torch.float32 else G.PIKA_BF16, Bn, T, U, S, H, _stream()),
+                "pika_joint_gate_banded_fwd")
+        ctx.save_for_backward(e1, p1, eg, pg, ranges)
+        ctx.s_range = S
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        e1, p1, eg, pg, ranges = ctx.saved_tensors
+        Bn, T, H = e1.shape
+        U = p1.shape[1]
+        if dh.dtype not in (torch.float32, torch.bfloat16):
+            dh = dh.float()
+        dh = dh.contiguous()
+        de1, deg = torch.empty_like(e1), torch.empty_like(eg)
+        dp1, dpg = torch.empty_like(p1), torch.empty_like(pg)
+        with torch.cuda.device(dh.device):
+            _lib.check(_lib.lib().pika_joint_gate_banded_bwd(
+                dh.data_ptr(), G.PIKA_F32 if dh.dtype == torch.float32 else G.PIKA_BF16, e1.data_ptr(), p1.data_ptr(),
+                eg.data_ptr(), pg.data_ptr(), ranges.data_ptr(), de1.data_ptr(), dp1.data_ptr(), deg.data_ptr(),
+                dpg.data_ptr(), Bn, T, U, ctx.s_range, H, _stream()), "pika_joint_gate_banded_bwd")
+        return de1, dp1, deg, dpg, None, None
+
+
 class LogSoftmaxFn(torch.autograd.Function):
     """log_softmax(scale * x) over the last dim, IN PLACE on x (the (B,T,U,V) logits buffer is
     7.8 GB at config 2); backward rewrites the incoming dense gradient in place as well."""

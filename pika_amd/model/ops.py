@@ -431,3 +431,40 @@ def joint(enc, pred, fc1, fc_gate, fc2, log_softmax=True, scale=1.0, labels=None
     if log_softmax:
         out = F.log_softmax(out if scale == 1.0 else scale * out, dim=-1)
     return out
+
+
+def joint_pruned(enc, pred, ranges, s_range, fc1, fc_gate, fc2, log_softmax=False, scale=1.0):
+    """Gated joint network on a pruned (banded) lattice: the rows of `joint` that frame t's band keeps.
+
+    enc (B,T,H), pred (B,U+1,H), ranges (B,T) int32 band starts (`rnnt_prune_ranges`) -> (B,T,S,V), S = s_range: row j of
+    frame t is the joint of enc[b,t] with pred[b, s_t + j], s_t = clamp(ranges[b,t], 0, U+1-S) -- `rnnt_prune_lm`'s rows.
+    The weights are split into halves as in `joint`; on the GPU the four small products run on the MFMA kernels, the gate
+    on the banded gate kernels (hipops.BandedGateFn: nothing of size (B,T,S,H) is kept for the backward, the prediction
+    rows are never expanded) and fc2 on the (B*T*S, H) rows.  log_softmax=False returns the logits
+    `rnnt_loss_pruned_from_logits` takes.  With s_range = U+1 and all-zero ranges this is `joint`'s plain chain, bit for
+    bit.  CPU tensors, or widths the GEMM kernels do not take, run the same formula in plain torch."""
+    H = enc.shape[-1]
+    S = int(s_range)
+    w1e, w1p = fc1.weight[:, :H], fc1.weight[:, H:]
+    wge, wgp = fc_gate.weight[:, :H], fc_gate.weight[:, H:]
+    if _hip(enc) and _gemm_ok(H, fc2.weight.shape[1]):
+        from .hipops import BandedGateFn, LogSoftmaxFn
+        e1 = linear(enc, w1e.contiguous(), fc1.bias)
+        p1 = linear(pred, w1p.contiguous())
+        eg = linear(enc, wge.contiguous(), fc_gate.bias)
+        pg = linear(pred, wgp.contiguous())
+        h = BandedGateFn.apply(e1, p1, eg, pg, ranges, S)
+        out = linear(h, fc2.weight, fc2.bias)
+        if log_softmax:
+            out = LogSoftmaxFn.apply(out, scale)
+        return out
+    from ..rnnt import rnnt_prune_lm
+    e1 = F.linear(enc, w1e, fc1.bias)
+    eg = F.linear(enc, wge, fc_gate.bias)
+    p1 = rnnt_prune_lm(F.linear(pred, w1p), ranges, S)
+    pg = rnnt_prune_lm(F.linear(pred, wgp), ranges, S)
+    h = torch.tanh(e1.unsqueeze(2) + p1) * torch.sigmoid(eg.unsqueeze(2) + pg)
+    out = F.linear(h, fc2.weight, fc2.bias)
+    if log_softmax:
+        out = F.log_softmax(out if scale == 1.0 else scale * out, dim=-1)
+    return out

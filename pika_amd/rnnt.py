@@ -870,6 +870,39 @@ def rnnt_prune_lm(lm, ranges, s_range):
     return torch.gather(lm.unsqueeze(1).expand(B, T, U1, D), 2, idx.unsqueeze(3).expand(B, T, S, D))
 
 
+def rnnt_pruned_joint_loss(enc, pred, labels, frames_lengths, labels_lengths, fc1, fc_gate, fc2, simple_am, simple_lm,
+                           s_range=5, blank=0, fastemit_lambda=0.0, reduction="sum"):
+    """The two losses of pruned RNN-T training in one call: (simple_loss, pruned_loss, ranges).
+
+    enc (B, T, H) encoder output, pred (B, U+1, H) prediction-network output, labels (B, U) int32, lengths (B,) int32;
+    fc1 / fc_gate (nn.Linear(2H, J)) and fc2 (nn.Linear(J, V)) are the gated joint network of `pika_amd.model.ops.joint`,
+    simple_am / simple_lm (nn.Linear(H, V)) the two projections of the simple joiner am + lm.  The chain is the one above:
+    `rnnt_simple_planes` of the two projections -> `rnnt_loss_from_planes(return_occupancy=True)` (the simple loss, trained
+    through the planes) -> `rnnt_prune_ranges` (the band, s_range rows per frame, no gradient) -> `joint_pruned` (the
+    gated joint on the band's rows only, (B, T, S, V)) -> `rnnt_loss_pruned_from_logits`.  A vocabulary that call does
+    not take (V % 4 != 0 or V > 8192) goes through `joint_pruned(log_softmax=True)` and `rnnt_loss_pruned`.  The caller
+    mixes the two losses (icefall: simple_scale * simple + pruned).  fastemit_lambda acts on the pruned loss; reduction
+    ('sum', 'mean', None) on both.  No length is read on the host: forward plus backward capture into one torch.cuda.graph."""
+    from .model.ops import joint_pruned, linear
+    S = int(s_range)
+    lam = _check_lambda(fastemit_lambda)
+    am = linear(enc, simple_am.weight, simple_am.bias)
+    lm = linear(pred, simple_lm.weight, simple_lm.bias)
+    blank_lp, label_lp = rnnt_simple_planes(am, lm, labels, blank=blank)
+    simple, occ_b, occ_l = rnnt_loss_from_planes(blank_lp, label_lp, frames_lengths, labels_lengths, reduction=reduction,
+                                                 return_occupancy=True)
+    ranges = rnnt_prune_ranges(occ_b, occ_l, frames_lengths, labels_lengths, S)
+    if _fused_v_ok(fc2.weight.shape[0]):
+        logits = joint_pruned(enc, pred, ranges, S, fc1, fc_gate, fc2, log_softmax=False)
+        pruned = rnnt_loss_pruned_from_logits(logits, labels, ranges, frames_lengths, labels_lengths, reduction=reduction,
+                                              blank=blank, fastemit_lambda=lam)
+    else:
+        log_probs = joint_pruned(enc, pred, ranges, S, fc1, fc_gate, fc2, log_softmax=True)
+        pruned = rnnt_loss_pruned(log_probs, labels, ranges, frames_lengths, labels_lengths, reduction=reduction,
+                                  blank=blank, fastemit_lambda=lam)
+    return simple, pruned, ranges
+
+
 class RNNTLoss(object):
     """`RNNTLoss(blank=0, reduction='sum').apply(...)` exactly as the reference scripts use it.
 
