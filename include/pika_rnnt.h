@@ -277,6 +277,38 @@ int pika_prnnt_planes_forward(const float *blank_lp, const float *label_lp, cons
 int pika_prnnt_prune_ranges(const float *blank_occ, const float *label_occ, const int *frames_lengths,
                             const int *labels_lengths, int B, int T, int U1, int S, int *ranges, void *stream);
 
+/* Smoothed simple planes: the planes pika_prnnt_planes_forward takes, of the joiner am + lm interpolated with an lm-only
+ * and an am-times-batch-unigram distribution (k2's get_rnnt_logprobs_smoothed, regular topology).
+ * These two calls do everything that touches (B, T, V); the caller prepares what is (B, U1, V)- or (V,)-sized.
+ * With c = 1 - lm_only_scale - am_only_scale, y_bu = labels[b][u] clamped into [0, V) (y_bU = blank) and
+ * NC = U1 + (am_only_scale != 0):
+ *   am        f32 (B, T, V) encoder logits
+ *   elm       f32 (B, NC, V): rows u < U1 are exp(lm[b][u] - lmax[b][u]), lmax the row maximum; row U1 (when present)
+ *             is the batch unigram q
+ *   side      f32 (B, U1, 5): {lm[b][u][blank] - lmax, lm[b][u][y_bu] - lmax, Zl[b][u] - lmax, log q[blank], log q[y_bu]}
+ *   labels    i32 (B, U1 - 1); may be NULL when U1 == 1
+ * forward writes
+ *   amax      f32 (B, T)      row maxima of am
+ *   gathered  f32 (B, T, U1)  am[b][t][y_bu]
+ *   sums      f32 (B, T, NC)  sum_v exp(am[b][t][v] - amax[b][t]) * elm[b][j][v]
+ *   blank_lp, label_lp f32 (B, T, U1): lp(b, t, u, blank) and lp(b, t, u, y_bu), label_lp[..][U1 - 1] = -1e30, where
+ *             lp(k) = c (am_k + lm_k - Z) + lm_only_scale (lm_k - Zl) + am_only_scale (am_k + log q_k - Za).
+ * backward takes amax and elm again and
+ *   w         f32 (B, T, NC): c (gB + gL)[b][t][u] / sums[b][t][u]; column U1: am_only_scale * sum_u (gB + gL) / sums
+ *   sg        f32 (B, T, U1): (c + am_only_scale) gL[b][t][u]; column U1 - 1: (c + am_only_scale) sum_u gB[b][t][u]
+ * (gB, gL the gradients of the planes, gL[..][U1 - 1] = 0) and writes, every element,
+ *   d_am      f32 (B, T, V) = sum_u sg[b][t][u] [v == y_bu]  -  exp(am - amax) * sum_j w[b][t][j] elm[b][j][v]
+ *   m         f32 (B, NC, V) = sum_t w[b][t][j] exp(am[b][t][v] - amax[b][t]),
+ * from which the caller forms d lm = -elm * m + ... and d q = -sum_b m[b][U1] + ...  No atomics: every sum runs in a
+ * fixed order.  Any T, any V >= 1.  Null pointers, non-positive sizes, blank outside [0, V), scales that are negative,
+ * not finite or sum to >= 1: PIKA_EINVAL; U1 > 1024, B > 65535: PIKA_ETOOBIG; all before any launch. */
+int pika_prnnt_smoothed_fwd(const float *am, const float *elm, const float *side, const int *labels, int B, int T, int U1,
+                            int V, int blank, float lm_only_scale, float am_only_scale, float *amax, float *gathered,
+                            float *sums, float *blank_lp, float *label_lp, void *stream);
+int pika_prnnt_smoothed_bwd(const float *am, const float *amax, const float *elm, const float *w, const float *sg,
+                            const int *labels, int B, int T, int U1, int V, int blank, float lm_only_scale,
+                            float am_only_scale, float *d_am, float *m, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -883,12 +883,19 @@ def rnnt_pruned_joint_loss(enc, pred, labels, frames_lengths, labels_lengths, fc
     not take (V % 4 != 0 or V > 8192) goes through `joint_pruned(log_softmax=True)` and `rnnt_loss_pruned`.  The caller
     mixes the two losses (icefall: simple_scale * simple + pruned).  fastemit_lambda acts on the pruned loss; reduction
     ('sum', 'mean', None) on both.  No length is read on the host: forward plus backward capture into one torch.cuda.graph."""
+    return _pruned_joint_chain(rnnt_simple_planes, enc, pred, labels, frames_lengths, labels_lengths, fc1, fc_gate, fc2,
+                               simple_am, simple_lm, s_range, blank, fastemit_lambda, reduction)
+
+
+def _pruned_joint_chain(planes, enc, pred, labels, frames_lengths, labels_lengths, fc1, fc_gate, fc2, simple_am, simple_lm,
+                        s_range, blank, fastemit_lambda, reduction):
+    # the chain of `rnnt_pruned_joint_loss`; planes(am, lm, labels, blank=) gives the simple joiner's two planes
     from .model.ops import joint_pruned, linear
     S = int(s_range)
     lam = _check_lambda(fastemit_lambda)
     am = linear(enc, simple_am.weight, simple_am.bias)
     lm = linear(pred, simple_lm.weight, simple_lm.bias)
-    blank_lp, label_lp = rnnt_simple_planes(am, lm, labels, blank=blank)
+    blank_lp, label_lp = planes(am, lm, labels, blank=blank)
     simple, occ_b, occ_l = rnnt_loss_from_planes(blank_lp, label_lp, frames_lengths, labels_lengths, reduction=reduction,
                                                  return_occupancy=True)
     ranges = rnnt_prune_ranges(occ_b, occ_l, frames_lengths, labels_lengths, S)
@@ -901,6 +908,200 @@ def rnnt_pruned_joint_loss(enc, pred, labels, frames_lengths, labels_lengths, fc
         pruned = rnnt_loss_pruned(log_probs, labels, ranges, frames_lengths, labels_lengths, reduction=reduction,
                                   blank=blank, fastemit_lambda=lam)
     return simple, pruned, ranges
+
+
+_TINY = torch.finfo(torch.float32).tiny
+
+
+def _check_scales(lm_only_scale, am_only_scale):
+    try:
+        ll, la = float(lm_only_scale), float(am_only_scale)
+    except (TypeError, ValueError):
+        raise ValueError("lm_only_scale / am_only_scale must be Python floats")
+    if not (ll >= 0.0 and la >= 0.0 and ll + la < 1.0):
+        raise ValueError("lm_only_scale=%r, am_only_scale=%r must be >= 0 and sum to < 1" % (lm_only_scale, am_only_scale))
+    return ll, la
+
+
+def _check_simple(am, lm, labels, blank):
+    if am.dim() != 3 or lm.dim() != 3 or am.shape[0] != lm.shape[0] or am.shape[2] != lm.shape[2]:
+        raise ValueError("am must be (B,T,V) and lm (B,U+1,V), got %s and %s" % (tuple(am.shape), tuple(lm.shape)))
+    B, U1, V = lm.shape
+    if labels.dim() != 2 or labels.shape != (B, U1 - 1):
+        raise ValueError("labels must be (B,U)=(%d,%d), got %s" % (B, U1 - 1, tuple(labels.shape)))
+    if labels.is_floating_point():
+        raise ValueError("labels must be an integer tensor, got %s" % labels.dtype)
+    if B < 1 or am.shape[1] < 1 or U1 < 1 or V < 1:
+        raise ValueError("am (B,T,V) and lm (B,U+1,V) must not be empty, got %s and %s" % (tuple(am.shape), tuple(lm.shape)))
+    if not 0 <= blank < V:
+        raise ValueError("blank=%d outside [0,%d)" % (blank, V))
+    if U1 > 1024:
+        raise ValueError("U+1=%d > 1024 not supported" % U1)
+    if lm.device != am.device or labels.device != am.device:
+        raise RuntimeError("am is on %s, lm on %s, labels on %s" % (am.device, lm.device, labels.device))
+    return B, am.shape[1], U1, V
+
+
+def _labels_ext(labels, blank, V):
+    # (B, U+1): the clamped labels, then `blank` for the last lattice column
+    y = labels.long().clamp(0, V - 1)
+    return torch.cat([y, y.new_full((y.shape[0], 1), blank)], 1)
+
+
+def _smoothed_planes_torch(am, lm, labels, blank, ll, la):
+    """The definition (DESIGN.md section 3 "Smoothed simple planes") in plain torch: max-shifted, differentiable, no
+    (B, T, U+1, V) tensor.  The kernels' fp64 reference, and the path of CPU and float64 tensors."""
+    B, T, V = am.shape
+    U1 = lm.shape[1]
+    c = 1.0 - ll - la
+    am_max, lm_max = am.amax(2, keepdim=True), lm.amax(2, keepdim=True)                    # (B,T,1), (B,U1,1)
+    e_am = (am - am_max).exp()
+    norm = torch.matmul(e_am, (lm - lm_max).exp().transpose(1, 2)).clamp_min(_TINY).log() + am_max + lm_max.transpose(1, 2)
+    yy = _labels_ext(labels, blank, V)                                                     # (B,U1)
+    am_b = am[:, :, blank].unsqueeze(2)                                                    # (B,T,1)
+    am_y = torch.gather(am, 2, yy.unsqueeze(1).expand(B, T, U1))                           # (B,T,U1)
+    lm_b = lm[:, :, blank].unsqueeze(1)                                                    # (B,1,U1)
+    lm_y = torch.gather(lm, 2, yy.unsqueeze(2)).squeeze(2).unsqueeze(1)                    # (B,1,U1)
+    blank_lp, label_lp = c * (am_b + lm_b - norm), c * (am_y + lm_y - norm)
+    if ll != 0.0:
+        zl = torch.logsumexp(lm, 2).unsqueeze(1)                                           # (B,1,U1)
+        blank_lp, label_lp = blank_lp + ll * (lm_b - zl), label_lp + ll * (lm_y - zl)
+    if la != 0.0:
+        q = torch.softmax(lm, 2).reshape(B * U1, V).mean(0) + _TINY                        # the batch unigram
+        log_q = q.log()
+        za = torch.matmul(e_am, q).unsqueeze(2).clamp_min(_TINY).log() + am_max            # (B,T,1)
+        blank_lp = blank_lp + la * (am_b + log_q[blank] - za)
+        label_lp = label_lp + la * (am_y + log_q[yy].unsqueeze(1) - za)
+    label_lp = torch.cat([label_lp[:, :, :U1 - 1], label_lp.new_full((B, T, 1), -1.0e30)], 2)
+    return blank_lp, label_lp
+
+
+class _SmoothedPlanesFn(torch.autograd.Function):
+    """The smoothed planes on the kernels of csrc/rnnt_simple.hip; what is (B, U+1, V)- or (V,)-sized is torch."""
+
+    @staticmethod
+    def forward(ctx, am, lm, labels, blank, ll, la):
+        B, T, V = am.shape
+        U1 = lm.shape[1]
+        lib = _lib.lib()
+        am_c, lm_c = am.detach().contiguous(), lm.detach().contiguous()
+        lab = labels.to(torch.int32).contiguous()
+        yy = _labels_ext(lab, blank, V)
+        with torch.cuda.device(am_c.device):
+            sh = lm_c - lm_c.amax(2, keepdim=True)
+            elm = sh.exp()
+            zl = elm.sum(2).log()                                                          # Zl - lmax, (B,U1)
+            lm_b, lm_y = sh[:, :, blank], torch.gather(sh, 2, yy.unsqueeze(2)).squeeze(2)
+            if la != 0.0:
+                q = (elm * (-zl).exp().unsqueeze(2)).reshape(B * U1, V).mean(0) + _TINY
+                log_q = q.log()
+                side = torch.stack([lm_b, lm_y, zl, log_q[blank].expand(B, U1), log_q[yy]], 2).contiguous()
+                e_all = torch.cat([elm, q.expand(B, 1, V)], 1)
+            else:
+                q = None
+                side = torch.stack([lm_b, lm_y, zl, torch.zeros_like(zl), torch.zeros_like(zl)], 2).contiguous()
+                e_all = elm
+            NC = e_all.shape[1]
+            amax = torch.empty((B, T), dtype=torch.float32, device=am_c.device)
+            gathered = torch.empty((B, T, U1), dtype=torch.float32, device=am_c.device)
+            sums = torch.empty((B, T, NC), dtype=torch.float32, device=am_c.device)
+            blank_lp, label_lp = torch.empty_like(gathered), torch.empty_like(gathered)
+            with _timed("fwd"):
+                _lib.check(lib.pika_prnnt_smoothed_fwd(_ptr(am_c), _ptr(e_all), _ptr(side), _ptr(lab) if U1 > 1 else None, B, T,
+                                                       U1, V, blank, ll, la, _ptr(amax), _ptr(gathered), _ptr(sums),
+                                                       _ptr(blank_lp), _ptr(label_lp), _stream()),
+                           "pika_prnnt_smoothed_fwd")
+        ctx.save_for_backward(am_c, e_all, amax, sums, lab, yy, zl, q)
+        ctx.args = (blank, ll, la)
+        return blank_lp, label_lp
+
+    @staticmethod
+    def backward(ctx, g_blank, g_label):
+        am_c, e_all, amax, sums, lab, yy, zl, q = ctx.saved_tensors
+        blank, ll, la = ctx.args
+        B, T, V = am_c.shape
+        NC = e_all.shape[1]
+        U1 = yy.shape[1]
+        c = 1.0 - ll - la
+        lib = _lib.lib()
+        with torch.cuda.device(am_c.device):
+            zeros = torch.zeros((B, T, U1), dtype=torch.float32, device=am_c.device)
+            gb = zeros if g_blank is None else g_blank.to(torch.float32)
+            gl = zeros if g_label is None else torch.cat([g_label.to(torch.float32)[:, :, :U1 - 1], zeros[:, :, :1]], 2)
+            g = gb + gl
+            s = sums.clamp_min(_TINY)
+            w = torch.empty_like(sums)
+            w[:, :, :U1] = c * g / s[:, :, :U1]
+            if la != 0.0:
+                w[:, :, U1] = la * g.sum(2) / s[:, :, U1]
+            sg = (c + la) * gl
+            sg[:, :, U1 - 1] = (c + la) * gb.sum(2)
+            d_am = torch.empty_like(am_c)
+            m = torch.empty_like(e_all)
+            with _timed("bwd"):
+                _lib.check(lib.pika_prnnt_smoothed_bwd(_ptr(am_c), _ptr(amax), _ptr(e_all), _ptr(w), _ptr(sg),
+                                                       _ptr(lab) if U1 > 1 else None, B, T, U1, V, blank, ll, la,
+                                                       _ptr(d_am), _ptr(m), _stream()), "pika_prnnt_smoothed_bwd")
+            # the (B, U+1, V)-sized tail: scatter terms one row at a time (no index collides), softmax and unigram terms
+            gbs, gls = gb.sum(1), gl.sum(1)                                                # (B,U1)
+            ar = torch.arange(V, device=am_c.device)
+            sc = gbs.unsqueeze(2) * (ar == blank) + gls.unsqueeze(2) * (ar == yy.unsqueeze(2))
+            elm = e_all[:, :U1]
+            d_lm = (c + ll) * sc - elm * m[:, :U1]
+            if ll != 0.0 or la != 0.0:
+                sm = elm * (-zl).exp().unsqueeze(2)
+            if ll != 0.0:
+                d_lm -= ll * (gbs + gls).unsqueeze(2) * sm
+            if la != 0.0:
+                dq = la * sc.sum((0, 1)) / q - m[:, U1].sum(0)
+                d_lm += sm * (dq - (sm * dq).sum(2, keepdim=True)) / float(B * U1)
+        return d_am, d_lm, None, None, None, None
+
+
+def rnnt_smoothed_planes(am, lm, labels, blank=0, lm_only_scale=0.0, am_only_scale=0.0):
+    """The two planes of k2's smoothed simple joiner (get_rnnt_logprobs_smoothed, regular topology): (blank_lp, label_lp),
+    (B, T, U+1), differentiable w.r.t. am and lm.
+
+    am (B, T, V), lm (B, U+1, V), labels (B, U) int (padding labels are clamped into [0, V)).  With c = 1 - lm_only_scale
+    - am_only_scale, Z = logsumexp_v(am + lm), Zl = logsumexp_v lm, q the mean of softmax(lm) over all B (U+1) rows plus
+    finfo(float32).tiny (the batch unigram; gradients flow through it) and Za = log sum_v exp(am) q, a class k scores
+        c (am_k + lm_k - Z) + lm_only_scale (lm_k - Zl) + am_only_scale (am_k + log q_k - Za);
+    blank_lp takes k = blank, label_lp[.., u] k = labels[b, u], label_lp[.., U] = -1e30.  Scales (0, 0) give
+    `rnnt_simple_planes`' definition; the recipes train with (0.25, 0).  The scales are Python floats, >= 0, summing to
+    < 1 (ValueError otherwise).  float32 tensors on a HIP device run the kernels of csrc/rnnt_simple.hip; CPU tensors and
+    float64 tensors run the same definition in plain torch."""
+    ll, la = _check_scales(lm_only_scale, am_only_scale)
+    blank = int(blank)
+    _check_simple(am, lm, labels, blank)
+    if am.is_cuda and am.dtype == torch.float32 and lm.dtype == torch.float32:
+        return _SmoothedPlanesFn.apply(am, lm, labels, blank, ll, la)
+    if am.dtype != torch.float64 or lm.dtype != torch.float64:
+        am, lm = am.float(), lm.float()
+    return _smoothed_planes_torch(am, lm, labels, blank, ll, la)
+
+
+def rnnt_loss_smoothed(am, lm, labels, frames_lengths, labels_lengths, blank=0, lm_only_scale=0.0, am_only_scale=0.0,
+                       reduction=None, return_occupancy=False):
+    """k2's rnnt_loss_smoothed: `rnnt_smoothed_planes` followed by `rnnt_loss_from_planes` (whose arguments and returns
+    these are); differentiable w.r.t. am and lm."""
+    blank_lp, label_lp = rnnt_smoothed_planes(am, lm, labels, blank=blank, lm_only_scale=lm_only_scale,
+                                              am_only_scale=am_only_scale)
+    return rnnt_loss_from_planes(blank_lp, label_lp, frames_lengths, labels_lengths, reduction=reduction,
+                                 return_occupancy=return_occupancy)
+
+
+def rnnt_pruned_joint_loss_smoothed(enc, pred, labels, frames_lengths, labels_lengths, fc1, fc_gate, fc2, simple_am,
+                                    simple_lm, s_range=5, blank=0, fastemit_lambda=0.0, reduction="sum",
+                                    lm_only_scale=0.0, am_only_scale=0.0):
+    """`rnnt_pruned_joint_loss` with the planes of `rnnt_smoothed_planes`: the same chain, the same triple (simple_loss,
+    pruned_loss, ranges), the simple loss smoothed as the pruned-transducer recipes train it (lm_only_scale = 0.25).
+    Forward plus backward capture into one torch.cuda.graph."""
+    ll, la = _check_scales(lm_only_scale, am_only_scale)
+
+    def planes(am, lm, labels, blank):
+        return rnnt_smoothed_planes(am, lm, labels, blank=blank, lm_only_scale=ll, am_only_scale=la)
+    return _pruned_joint_chain(planes, enc, pred, labels, frames_lengths, labels_lengths, fc1, fc_gate, fc2, simple_am,
+                               simple_lm, s_range, blank, fastemit_lambda, reduction)
 
 
 class RNNTLoss(object):
