@@ -309,6 +309,55 @@ int pika_prnnt_smoothed_bwd(const float *am, const float *amax, const float *elm
                             const int *labels, int B, int T, int U1, int V, int blank, float lm_only_scale,
                             float am_only_scale, float *d_am, float *m, void *stream);
 
+/* Modified topology (k2's rnnt_loss / rnnt_loss_pruned with modified=True): every frame emits exactly one symbol, a
+ * blank or one label, so the label edge runs (t, u) -> (t+1, u+1) instead of (t, u) -> (t, u+1).  Per utterance, with
+ * blank_lp(t, u) and label_lp(t, u) for 0 <= t < T_n, 0 <= u <= U_n (label_lp(t, U_n) is dead):
+ *   alpha(0, 0) = 0, every other alpha(0, u) log zero;
+ *   alpha(t+1, u) = logaddexp(alpha(t, u) + blank_lp(t, u), alpha(t, u-1) + label_lp(t, u-1)),  0 <= t < T_n;
+ *   ll = alpha(T_n, U_n): row T_n is terminal and both edge kinds out of frame T_n - 1 reach it, so a label may be
+ *   emitted on the last frame; cost = -ll; beta is the mirror image with beta(T_n, U_n) = 0;
+ *   occ_blank(t, u) = exp(alpha(t, u) + blank_lp(t, u) + beta(t+1, u) - ll),
+ *   occ_label(t, u) = exp(alpha(t, u) + label_lp(t, u) + beta(t+1, u+1) - ll),   d cost / d lp = -occ.
+ * Feasible iff U_n <= T_n.  An infeasible utterance, or a band that holds no path, costs +inf and has an all-zero
+ * gradient and all-zero occupancies; the other utterances of the batch are not disturbed.  Lengths are clamped on the
+ * device as everywhere above.  FastEmit as in pika_rnnt_loss_backward_fe.  No float atomics: two runs give the same bits.
+ *
+ * The calls mirror the pika_prnnt_* ones above, argument for argument, over a workspace of
+ * pika_prnnt_mod_workspace_bytes(B, T, U1) bytes (the regular members over T + 1 un-skewed plane rows; NOT a workspace
+ * pika_rnnt_align or pika_rnnt_export_lattice can read).  forward / backward / fused_forward / fused_backward take the
+ * banded layout (B, T, S, V) with `ranges`, or -- ranges == NULL, which requires S == U1 -- the padded (B, T, U1, V)
+ * one; with S == U1 and all-zero ranges the banded calls give the padded calls' bits.  The row metadata they leave is
+ * that of the regular calls (16 bytes per row of the B*T*S), and the dense and d(logits) writers are the regular ones.
+ * Error codes as for the pika_prnnt_* calls. */
+size_t pika_prnnt_mod_workspace_bytes(int B, int T, int U1);
+int pika_prnnt_mod_forward(const float *log_probs, const int *frames_lengths, const int *labels_lengths, const int *labels,
+                           const int *ranges, int B, int T, int U1, int S, int V, int blank, float *costs, void *workspace,
+                           void *stream);
+int pika_prnnt_mod_backward(const int *frames_lengths, const int *labels_lengths, const int *labels, const int *ranges, int B,
+                            int T, int U1, int S, int V, int blank, const float *grad_costs, const void *workspace,
+                            float *grads, float fastemit_lambda, void *stream);
+int pika_prnnt_mod_fused_forward(const float *logits, const int *frames_lengths, const int *labels_lengths,
+                                 const int *labels, const int *ranges, int B, int T, int U1, int S, int V, int blank,
+                                 float *costs, float *lse, void *workspace, void *stream);
+int pika_prnnt_mod_fused_backward(const float *logits, const float *lse, const int *frames_lengths,
+                                  const int *labels_lengths, const int *labels, const int *ranges, int B, int T, int U1, int S,
+                                  int V, int blank, const float *grad_costs, const void *workspace, void *grad_logits,
+                                  int out_dtype, long long ld_out, float fastemit_lambda, void *stream);
+/* pika_prnnt_planes_forward in the modified topology: blank_lp is the edge (t, u) -> (t+1, u), label_lp the edge
+ * (t, u) -> (t+1, u+1); the occupancies are those defined above. */
+int pika_prnnt_mod_planes_forward(const float *blank_lp, const float *label_lp, const int *frames_lengths,
+                                  const int *labels_lengths, int B, int T, int U1, float *costs, float *blank_occ,
+                                  float *label_occ, void *workspace, void *stream);
+/* Band search with step bound 1: steps 1 and 2 of pika_prnnt_prune_ranges, then
+ *   3. f(0) = 0, f(t) = min(m(t), f(t-1) + 1);
+ *   4. ranges[n][t] = max(f(t), s_max - (T_n - 1 - t)); s_max for t >= T_n.
+ * The result has s_0 = 0, 0 <= s_{t+1} - s_t <= 1 and s_{T_n-1} = s_max whenever T_n - 1 >= s_max (otherwise s_0 > 0
+ * says so), and such a band holds a path whenever U_n <= T_n: u_t = min(t, s_t + S - 1) stays inside it, moves by 0 or
+ * 1 per frame and reaches U_n at row T_n.  (A band of pika_prnnt_prune_ranges may move S - 1 columns per frame, which
+ * no path of this topology can follow.) */
+int pika_prnnt_mod_prune_ranges(const float *blank_occ, const float *label_occ, const int *frames_lengths,
+                                const int *labels_lengths, int B, int T, int U1, int S, int *ranges, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,7 +68,10 @@ _CTC_EXPORTS = ("ctc_loss", "ctc_loss_from_logits", "CTCLoss", "ctc_align", "ctc
 # The pruned RNN-T surface (pika_amd/rnnt.py), resolved the same way.
 _RNNT_EXPORTS = ("rnnt_loss_pruned", "rnnt_loss_pruned_from_logits", "rnnt_loss_from_planes", "rnnt_prune_ranges",
                  "rnnt_simple_planes", "rnnt_prune_lm", "rnnt_pruned_joint_loss",
-                 "rnnt_smoothed_planes", "rnnt_loss_smoothed", "rnnt_pruned_joint_loss_smoothed")
+                 "rnnt_smoothed_planes", "rnnt_loss_smoothed", "rnnt_pruned_joint_loss_smoothed",
+                 "rnnt_loss_from_planes_modified", "rnnt_prune_ranges_modified", "rnnt_loss_pruned_modified",
+                 "rnnt_loss_pruned_modified_from_logits", "rnnt_loss_modified", "rnnt_loss_modified_from_logits",
+                 "rnnt_pruned_joint_loss_modified")
 
 # The joint network on the band (pika_amd/model/ops.py).
 _OPS_EXPORTS = ("joint_pruned",)

@@ -46,6 +46,14 @@ SIGNATURES = {
     "pika_prnnt_prune_ranges": (_i, [_vp] * 4 + [_i] * 4 + [_vp] * 2),
     "pika_prnnt_smoothed_fwd": (_i, [_vp] * 4 + [_i] * 5 + [_f] * 2 + [_vp] * 6),
     "pika_prnnt_smoothed_bwd": (_i, [_vp] * 6 + [_i] * 5 + [_f] * 2 + [_vp] * 3),
+    # include/pika_rnnt.h, the modified topology
+    "pika_prnnt_mod_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pika_prnnt_mod_forward": (_i, [_vp] * 5 + [_i] * 6 + [_vp] * 3),
+    "pika_prnnt_mod_backward": (_i, [_vp] * 4 + [_i] * 6 + [_vp] * 3 + [_f, _vp]),
+    "pika_prnnt_mod_fused_forward": (_i, [_vp] * 5 + [_i] * 6 + [_vp] * 4),
+    "pika_prnnt_mod_fused_backward": (_i, [_vp] * 6 + [_i] * 6 + [_vp] * 3 + [_i, _ll, _f, _vp]),
+    "pika_prnnt_mod_planes_forward": (_i, [_vp] * 4 + [_i] * 3 + [_vp] * 5),
+    "pika_prnnt_mod_prune_ranges": (_i, [_vp] * 4 + [_i] * 4 + [_vp] * 2),
     # include/pika_ctc.h
     "pika_ctc_workspace_bytes": (_sz, [_i, _i, _i]),
     "pika_ctc_align_scratch_bytes": (_sz, [_i, _i, _i]),

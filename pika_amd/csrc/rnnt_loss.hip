@@ -181,7 +181,8 @@ __device__ inline float wave_max(float v) {
 // ---------------------------------------------------------------------------------------------
 constexpr int GATHER_ROWS = 4;
 
-template <int LAYOUT = PADDED>
+// MOD (the modified topology, below): the planes are NOT skewed -- cell (t, u) lives at [t][u], D = T + 1 rows.
+template <int LAYOUT = PADDED, bool MOD = false>
 __global__ __launch_bounds__(256) void rnnt_gather_kernel(
     const float *__restrict__ lp, const int *__restrict__ labels, const int *__restrict__ Tn_,
     const int *__restrict__ Un_, int B, int T, int U1, int V, int blank, float *__restrict__ lpb,
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(256) void rnnt_gather_kernel(
         int j[GATHER_ROWS];  // the band row of cell (t, u); -1: outside the sub-lattice or the band
 #pragma unroll
         for (int r = 0; r < GATHER_ROWS; ++r) {
-            const int t = d0 + r - u;
+            const int t = d0 + r - (MOD ? 0 : u);
             j[r] = -1;
             if (u <= Un && t >= 0 && t < Tn) {
                 const int k = u - band_start(ranges, b, T, t, Un, S);
@@ -213,27 +214,27 @@ __global__ __launch_bounds__(256) void rnnt_gather_kernel(
         }
 #pragma unroll
         for (int r = 0; r < GATHER_ROWS; ++r) {
-            const int t = d0 + r - u;
+            const int t = d0 + r - (MOD ? 0 : u);
             vb[r] = NEG;
             if (j[r] >= 0) vb[r] = fmaxf(lp[(r0 + (size_t)t * rt + j[r]) * V + blank], NEG);
         }
 #pragma unroll
         for (int r = 0; r < GATHER_ROWS; ++r) {
-            const int t = d0 + r - u;
+            const int t = d0 + r - (MOD ? 0 : u);
             ve[r] = NEG;
             if (emits && j[r] >= 0) ve[r] = fmaxf(lp[(r0 + (size_t)t * rt + j[r]) * V + y], NEG);
         }
     } else {
 #pragma unroll
         for (int r = 0; r < GATHER_ROWS; ++r) {
-            const int t = d0 + r - u;
+            const int t = d0 + r - (MOD ? 0 : u);
             vb[r] = NEG;
             if (u <= Un && t >= 0 && t < Tn)
                 vb[r] = fmaxf(lp[(r0 + (size_t)t * rt) * V + blank], NEG);
         }
 #pragma unroll
         for (int r = 0; r < GATHER_ROWS; ++r) {
-            const int t = d0 + r - u;
+            const int t = d0 + r - (MOD ? 0 : u);
             ve[r] = NEG;
             if (emits && t >= 0 && t < Tn)
                 ve[r] = fmaxf(lp[(r0 + (size_t)t * rt) * V + y], NEG);
@@ -560,7 +561,9 @@ __device__ inline int packed_utterance(const int *__restrict__ roff, int B, long
     return lo;
 }
 
-template <int LAYOUT = PADDED>
+// MOD (the modified topology, below): un-skewed planes, both edges of cell (t, u) end in row t + 1 -- the blank edge in
+// (t+1, u), the label edge in (t+1, u+1) -- and row T_n is terminal, so the last frame has no special case.
+template <int LAYOUT = PADDED, bool MOD = false>
 __global__ __launch_bounds__(256) void rnnt_rowmeta_kernel(
     const int *__restrict__ labels, const int *__restrict__ Tn_, const int *__restrict__ Un_,
     int B, int T, int U1, int V, const float *__restrict__ grad_costs,
@@ -596,7 +599,23 @@ __global__ __launch_bounds__(256) void rnnt_rowmeta_kernel(
         lab = labels + (size_t)b * (U1 - 1);
     }
     const int Tn = clampi(Tn_[b], 1, T), Un = clampi(Un_[b], 0, U1 - 1);
-    if (t < Tn && u <= Un) {
+    if constexpr (MOD) {
+        if (t < Tn && u <= Un) {
+            const size_t o = ((size_t)b * D + t) * Wp + u;
+            const float a = alpha[o];
+            const float sc = grad_costs ? grad_costs[b] : 1.0f;
+            // (ll = +inf where the utterance has no path: every exponent is -inf, every entry zero)
+            const float k1 = (float)(off_a[(size_t)b * D + t] - ll[b] + off_b[(size_t)b * D + t + 1]);
+            gb = -sc * __expf(k1 + (a + beta[o + Wp] + lpb[o]));
+            if (u < Un) {
+                const int y = lab[u];
+                if (y >= 0 && y < V) {
+                    ye = y;
+                    ge = -sc * lscale * __expf(k1 + (a + beta[o + Wp + 1] + lpe[o]));
+                }
+            }
+        }
+    } else if (t < Tn && u <= Un) {
         const int d = t + u;
         const size_t o = ((size_t)b * D + d) * Wp + u;
         const float a = alpha[o];
@@ -1221,7 +1240,7 @@ __device__ inline float fwave_sum(float v) {
 // utterances, B of them): the wave's utterance comes from a binary search over roff, everything else is the same.
 // BANDED: `logits` are (B,T,S,V), rows = B*T*S; row (b T + t) S + j is cell (t, s_t + j).  Only live cells are written:
 // the caller fills both planes with NEG first (rnnt_fill_neg_kernel), which is what the dead cells keep.
-template <int CQ, int LAYOUT = PADDED>
+template <int CQ, int LAYOUT = PADDED, bool MOD = false>
 __global__ __launch_bounds__(256) void rnnt_lse_gather_kernel(
     const float *__restrict__ logits, const int *__restrict__ labels, const int *__restrict__ Tn_,
     const int *__restrict__ Un_, long long rows, int T, int U1, int V, int blank, float *__restrict__ lse,
@@ -1282,7 +1301,7 @@ __global__ __launch_bounds__(256) void rnnt_lse_gather_kernel(
     const float l = m + __logf(fwave_sum(sum));
     if (lane == 0) {
         lse[r] = l;
-        const size_t o = ((size_t)b * D + (t + u)) * Wp + u;
+        const size_t o = ((size_t)b * D + (MOD ? t : t + u)) * Wp + u;   // MOD: un-skewed planes (the modified topology)
         lpb[o] = fmaxf(xb - l, NEG);
         lpe[o] = y_ok ? fmaxf(xy - l, NEG) : NEG;
     }
@@ -1404,6 +1423,8 @@ __global__ __launch_bounds__(256) void rnnt_fill_neg_kernel(v4f *__restrict__ p,
 
 // dense (B,T,U1) planes -> the skewed ones: NEG outside the sub-lattice, and in the label plane from column U_n on.
 // grid = (ceil(D / 4), Wp / 64, B), block = 256: a wave per skewed row, lane = u.
+// MOD (the modified topology): the same masking without the skew, row d is frame t.
+template <bool MOD = false>
 __global__ __launch_bounds__(256) void rnnt_skew_planes_kernel(
     const float *__restrict__ blank_lp, const float *__restrict__ label_lp, const int *__restrict__ Tn_,
     const int *__restrict__ Un_, int T, int U1, float *__restrict__ lpb, float *__restrict__ lpe, int Wp, int D) {
@@ -1412,7 +1433,7 @@ __global__ __launch_bounds__(256) void rnnt_skew_planes_kernel(
     const int u = blockIdx.y * 64 + (threadIdx.x & 63);
     if (d >= D) return;
     const int Tn = clampi(Tn_[b], 1, T), Un = clampi(Un_[b], 0, U1 - 1);
-    const int t = d - u;
+    const int t = MOD ? d : d - u;
     float vb = NEG, ve = NEG;
     if (u <= Un && t >= 0 && t < Tn) {
         const size_t i = ((size_t)b * T + t) * U1 + u;
@@ -1427,6 +1448,8 @@ __global__ __launch_bounds__(256) void rnnt_skew_planes_kernel(
 // Occupation probabilities exp(alpha + lp + beta' - ll) of the blank and the label edge of every cell, un-skewed into
 // dense (B,T,U1) planes: the values of rnnt_rowmeta_kernel with unit grad_costs, without the sign.  Zero outside the
 // sub-lattice (and for the label edge of column U_n, the blank edge of the last frame below U_n).
+// MOD (the modified topology): un-skewed planes, both edges end in row t + 1, no terminal blank.
+template <bool MOD = false>
 __global__ __launch_bounds__(256) void rnnt_occupancy_kernel(
     const int *__restrict__ Tn_, const int *__restrict__ Un_, int B, int T, int U1, const float *__restrict__ lpb,
     const float *__restrict__ lpe, const float *__restrict__ alpha, const float *__restrict__ beta,
@@ -1439,7 +1462,15 @@ __global__ __launch_bounds__(256) void rnnt_occupancy_kernel(
     const int b = (int)(idx / ((size_t)U1 * T));
     const int Tn = clampi(Tn_[b], 1, T), Un = clampi(Un_[b], 0, U1 - 1);
     float eb = 0.f, ee = 0.f;
-    if (t < Tn && u <= Un) {
+    if constexpr (MOD) {
+        if (t < Tn && u <= Un) {
+            const size_t o = ((size_t)b * D + t) * Wp + u;
+            const float a = alpha[o];
+            const float k1 = (float)(off_a[(size_t)b * D + t] - ll[b] + off_b[(size_t)b * D + t + 1]);
+            eb = __expf(k1 + (a + beta[o + Wp] + lpb[o]));
+            if (u < Un) ee = __expf(k1 + (a + beta[o + Wp + 1] + lpe[o]));
+        }
+    } else if (t < Tn && u <= Un) {
         const int d = t + u;
         const size_t o = ((size_t)b * D + d) * Wp + u;
         const float a = alpha[o];
@@ -1479,7 +1510,7 @@ __device__ inline long long block_prefix_min(long long v, long long *sh) {
 
 __global__ __launch_bounds__(PRUNE_THREADS) void rnnt_prune_ranges_kernel(
     const float *__restrict__ blank_occ, const float *__restrict__ label_occ, const int *__restrict__ Tn_,
-    const int *__restrict__ Un_, int T, int U1, int S, int *ranges) {
+    const int *__restrict__ Un_, int T, int U1, int S, int step_, int *ranges) {
     __shared__ long long sh[PRUNE_THREADS];
     constexpr long long BIG = 0x7fffffffffffffffLL;
     const int b = blockIdx.x;
@@ -1520,7 +1551,7 @@ __global__ __launch_bounds__(PRUNE_THREADS) void rnnt_prune_ranges_kernel(
         __syncthreads();
     }
     carry = BIG;
-    const long long step = S - 1;
+    const long long step = step_;  // S - 1; 1 in the modified topology (a label edge advances the frame)
     for (int base = 0; base < T; base += PRUNE_THREADS) {
         const int t = base + (int)threadIdx.x;
         long long g = BIG;
@@ -1537,6 +1568,209 @@ __global__ __launch_bounds__(PRUNE_THREADS) void rnnt_prune_ranges_kernel(
         carry = tot < carry ? tot : carry;
         __syncthreads();
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Modified topology (k2's rnnt_loss(modified=True), pika_rnnt.h "Modified topology"): every frame emits exactly one
+// symbol, so the label edge runs (t, u) -> (t+1, u+1) and the recurrence is the regular line with d read as t,
+//   A_{t+1}[u] = lae(A_t[u] + lpb_t[u], A_t[u-1] + lpe_t[u-1]),     ll = A_{T_n}[U_n],
+// over UN-skewed planes [B][T+1][Wp] (row = frame; row T_n is terminal, both edge kinds out of frame T_n - 1 reach it).
+// One workgroup per (direction, utterance), lane = u, Xchg<NW> at the wave edges, and the regular kernel's
+// renormalisation: every RENORM rows the running maximum leaves the fp32 values and is summed in fp64.
+// A cell is LIVE iff a path through it exists at all: u <= min(t, U_n) (reachable from (0, 0)) and U_n - u <= T_n - t
+// (can still reach (T_n, U_n)); every other cell is held at NEG in both sweeps, so the maximum that is subtracted is
+// one of cells that carry probability.  No cell is live when U_n > T_n, and a band may leave none in some row: a row
+// whose maximum is log-zero subtracts nothing, and an utterance whose ll is log-zero costs +inf; its ll is stored as
+// +inf, which zeroes every occupancy and gradient entry of it (exp(-inf)) without touching its neighbours.
+// The plane loads need no mask: a live cell reads its own row's lpb / lpe (beta) or those of (t-1, u), (t-1, u-1)
+// (alpha), cells of the sub-lattice, which every gather writes (NEG outside the band); what else a lane loads only
+// reaches values the live-select discards.
+// Row centres: a whole frame's log-probs may sit far from zero (unnormalised planes), and every path crosses every
+// frame exactly once, so the largest live log-prob c_t of frame t (rnnt_mod_rowcentre_kernel; 0 for a frame with none) is
+// taken out of both planes' values before they meet the running fp32 values and summed into the fp64 offsets instead.
+// grid = (2, B): blockIdx.x 0 = alpha, 1 = beta; block = NW * 64 = lattice_width(U1).
+// ---------------------------------------------------------------------------------------------
+// a wave per plane row (b, t): rowc[b][t] = max over the sub-lattice's columns of max(lpb, lpe); 0 when that is log zero
+// or t >= T_n.  grid = ceil(B * D / 4), block = 256.
+__global__ __launch_bounds__(256) void rnnt_mod_rowcentre_kernel(
+    const float *__restrict__ lpb, const float *__restrict__ lpe, const int *__restrict__ Tn_,
+    const int *__restrict__ Un_, int B, int T, int U1, int Wp, int D, float *__restrict__ rowc) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= B * D) return;
+    const int b = row / D, t = row - b * D;
+    const int Tn = clampi(Tn_[b], 1, T), Un = clampi(Un_[b], 0, U1 - 1);
+    float m = NEG;
+    if (t < Tn)
+        for (int u = lane; u <= Un; u += 64) {
+            const size_t o = (size_t)row * Wp + u;
+            m = fmaxf(m, fmaxf(lpb[o], lpe[o]));
+        }
+    m = wave_max(m);
+    if (lane == 0) rowc[row] = m > NEG_HALF ? m : 0.0f;
+}
+
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void rnnt_mod_alpha_beta_kernel(
+    const float *__restrict__ lpb_, const float *__restrict__ lpe_, float *__restrict__ alpha_,
+    float *__restrict__ beta_, double *__restrict__ off_a_, double *__restrict__ off_b_,
+    const int *__restrict__ Tn_, const int *__restrict__ Un_, double *__restrict__ ll_,
+    double *__restrict__ ll_a_, float *__restrict__ costs, const float *__restrict__ rowc_, int T, int U1, int Wp,
+    int D) {
+    __shared__ float lds[2 * (NW + 1) + 2 * NW];
+    Xchg<NW> xc{lds, lds + 2 * (NW + 1)};
+    if constexpr (NW > 1) {
+        if (threadIdx.x < 2 * (NW + 1) + 2 * NW) lds[threadIdx.x] = NEG;
+        __syncthreads();
+    }
+    const int b = blockIdx.y;
+    const int u = threadIdx.x;
+    const int Tn = clampi(Tn_[b], 1, T), Un = clampi(Un_[b], 0, U1 - 1);
+    const size_t base = (size_t)b * D * Wp + u;
+    const float *lpb = lpb_ + base;
+    const float *lpe = lpe_ + base;
+    const float *rowc = rowc_ + (size_t)b * D;
+    // cell (t, u) is live for tlo <= t <= thi (never, when u > U_n or U_n > T_n)
+    const int tlo = u <= Un ? u : T + 2, thi = Tn - Un + u;
+    auto live = [&](int t) __attribute__((always_inline)) { return t >= tlo && t <= thi; };
+
+    float pbv[2][UNR], pev[2][UNR], cv[2][UNR];
+    double off = 0.0;  // sum of subtracted maxima and row centres (identical in every thread)
+    // subtract the row maximum m (workgroup-uniform) unless the whole row is log-zero
+    auto renorm = [&](float &v, float m) __attribute__((always_inline)) {
+        m = m > NEG_HALF ? m : 0.0f;
+        v = v > NEG_HALF ? v - m : NEG;
+        off += (double)m;
+    };
+    if (blockIdx.x == 0) {
+        float *alpha = alpha_ + base;
+        double *offs = off_a_ + (size_t)b * D;
+        float a = live(0) ? 0.0f : NEG;  // (0, 0), when the utterance has a path at all
+        alpha[0] = a;
+        if (u == 0) offs[0] = 0.0;
+        auto load = [&](int buf, int t0) __attribute__((always_inline)) {  // rows t0-1 .. t0+UNR-2
+#pragma unroll
+            for (int i = 0; i < UNR; ++i) {
+                const int r = min(t0 + i - 1, T - 1);
+                pbv[buf][i] = lpb[(size_t)r * Wp];
+                pev[buf][i] = lpe[(size_t)r * Wp];
+                cv[buf][i] = rowc[r];
+            }
+        };
+        // rows t0 .. t0+UNR-1 (<= Tn); t0 = 1 (mod RENORM) at the first half of a group
+        auto steps = [&](int buf, int t0, auto second_half) __attribute__((always_inline)) {
+#pragma unroll
+            for (int i = 0; i < UNR; ++i) {
+                const int t = t0 + i;
+                if (t <= Tn) {  // workgroup-uniform
+                    const float c = cv[buf][i];  // the centre of row t - 1, uniform: off the dependent chain
+                    const float x = a + (pbv[buf][i] - c);
+                    const float y = xc.up(a + (pev[buf][i] - c), t);
+                    a = live(t) ? lae(x, y) : NEG;
+                    off += (double)c;
+                    if (decltype(second_half)::value && i == UNR - 1) renorm(a, xc.max_all(a, t));  // t = 0 (mod RENORM)
+                    alpha[(size_t)t * Wp] = a;
+                    if (u == 0) offs[t] = off;
+                }
+            }
+        };
+        load(0, 1);
+        for (int t0 = 1; t0 <= Tn; t0 += 2 * UNR) {
+            load(1, t0 + UNR);
+            steps(0, t0, std::false_type{});
+            load(0, t0 + 2 * UNR);
+            steps(1, t0 + UNR, std::true_type{});
+        }
+        if (u == Un) ll_a_[b] = a > NEG_HALF ? (double)a + off : -(double)INFINITY;
+    } else {
+        float *beta = beta_ + base;
+        double *offs = off_b_ + (size_t)b * D;
+        float bt = (u == Un && live(Tn)) ? 0.0f : NEG;  // the terminal row: (T_n, U_n)
+        beta[(size_t)Tn * Wp] = bt;
+        if (u == 0) offs[Tn] = 0.0;
+        auto load = [&](int buf, int t0) __attribute__((always_inline)) {  // rows t0, t0-1, ..., t0-UNR+1
+#pragma unroll
+            for (int i = 0; i < UNR; ++i) {
+                const int r = max(t0 - i, 0);
+                pbv[buf][i] = lpb[(size_t)r * Wp];
+                pev[buf][i] = lpe[(size_t)r * Wp];
+                cv[buf][i] = rowc[r];
+            }
+        };
+        // rows t0, t0-1, ..., t0-UNR+1 (>= 0); step j = Tn - t, renormalised where j = 0 (mod RENORM)
+        auto steps = [&](int buf, int t0, auto second_half) __attribute__((always_inline)) {
+#pragma unroll
+            for (int i = 0; i < UNR; ++i) {
+                const int t = t0 - i;
+                if (t >= 0) {  // workgroup-uniform
+                    const int j = Tn - t;
+                    const float dn = xc.down(bt, j);
+                    const float c = cv[buf][i];  // the centre of row t
+                    const float x = bt + (pbv[buf][i] - c);
+                    const float y = dn + (pev[buf][i] - c);
+                    bt = live(t) ? lae(x, y) : NEG;
+                    off += (double)c;
+                    if (decltype(second_half)::value && i == UNR - 1) renorm(bt, xc.max_all(bt, j));
+                    beta[(size_t)t * Wp] = bt;
+                    if (u == 0) offs[t] = off;
+                }
+            }
+        };
+        load(0, Tn - 1);
+        for (int t0 = Tn - 1; t0 >= 0; t0 -= 2 * UNR) {
+            load(1, t0 - UNR);
+            steps(0, t0, std::false_type{});
+            load(0, t0 - 2 * UNR);
+            steps(1, t0 - UNR, std::true_type{});
+        }
+        if (u == 0) {
+            const bool path = bt > NEG_HALF;
+            ll_[b] = path ? (double)bt + off : (double)INFINITY;
+            costs[b] = path ? (float)(-((double)bt + off)) : INFINITY;
+        }
+    }
+}
+
+// The workspace of the modified topology: the regular one's members over D = T + 1 un-skewed rows.
+struct ModLattice : Lattice {
+    float *rowc;  // [B][D] row centres
+};
+
+inline ModLattice carve_mod(void *ws, int B, int T, int U1) {
+    ModLattice L;
+    L.Wp = lattice_width(U1);
+    L.D = T + 1;
+    const size_t n = (size_t)B * L.D * L.Wp;
+    float *p = static_cast<float *>(ws);
+    L.lpb = p;
+    L.lpe = p + n;
+    L.alpha = p + 2 * n;
+    L.beta = p + 3 * n;
+    double *q = reinterpret_cast<double *>(p + 4 * n);  // n is a multiple of 64: 8-byte aligned
+    L.off_a = q;
+    L.off_b = q + (size_t)B * L.D;
+    L.ll = q + 2 * (size_t)B * L.D;
+    L.ll_a = L.ll + B;
+    L.meta = reinterpret_cast<RowMeta *>(L.ll_a + B);  // 2BD+2B doubles: 16-byte aligned
+    L.rowc = reinterpret_cast<float *>(L.meta + (size_t)B * T * U1);
+    return L;
+}
+
+inline size_t workspace_bytes_mod(int B, int T, int U1) {
+    const size_t D = (size_t)T + 1;
+    return 4 * (size_t)B * D * lattice_width(U1) * sizeof(float) + (2 * (size_t)B * D + 2 * (size_t)B) * sizeof(double) +
+           (size_t)B * T * U1 * sizeof(RowMeta) + (size_t)B * D * sizeof(float);
+}
+
+int finish_forward_mod(const ModLattice &L, const int *frames_lengths, const int *labels_lengths, float *costs, int B, int T,
+                       int U1, hipStream_t s) {
+    hipLaunchKernelGGL(rnnt_mod_rowcentre_kernel, dim3((unsigned)(((size_t)B * L.D + 3) / 4)), dim3(256), 0, s, L.lpb, L.lpe,
+                       frames_lengths, labels_lengths, B, T, U1, L.Wp, L.D, L.rowc);
+    const bool ok = dispatch_nw(L.Wp / 64, [&](auto nw) {
+        constexpr int NW = decltype(nw)::value;
+        hipLaunchKernelGGL((rnnt_mod_alpha_beta_kernel<NW>), dim3(2, B), dim3(NW * 64), 0, s, L.lpb, L.lpe, L.alpha, L.beta,
+                           L.off_a, L.off_b, frames_lengths, labels_lengths, L.ll, L.ll_a, costs, L.rowc, T, U1, L.Wp, L.D);
+    });
+    return ok ? (int)hipGetLastError() : PIKA_ETOOBIG;
 }
 
 }  // namespace
@@ -2000,11 +2234,11 @@ int pika_prnnt_planes_forward(const float *blank_lp, const float *label_lp, cons
         return PIKA_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Lattice L = carve(workspace, B, T, U1);
-    hipLaunchKernelGGL(rnnt_skew_planes_kernel, dim3((unsigned)((L.D + 3) / 4), (unsigned)(L.Wp / 64), (unsigned)B), dim3(256),
+    hipLaunchKernelGGL(rnnt_skew_planes_kernel<false>, dim3((unsigned)((L.D + 3) / 4), (unsigned)(L.Wp / 64), (unsigned)B), dim3(256),
                        0, s, blank_lp, label_lp, frames_lengths, labels_lengths, T, U1, L.lpb, L.lpe, L.Wp, L.D);
     if (int rc = finish_forward(L, frames_lengths, labels_lengths, costs, B, T, U1, s)) return rc;
     const size_t cells = (size_t)B * T * U1;
-    hipLaunchKernelGGL(rnnt_occupancy_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, frames_lengths,
+    hipLaunchKernelGGL(rnnt_occupancy_kernel<false>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, frames_lengths,
                        labels_lengths, B, T, U1, L.lpb, L.lpe, L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, blank_occ,
                        label_occ);
     return (int)hipGetLastError();
@@ -2016,7 +2250,142 @@ int pika_prnnt_prune_ranges(const float *blank_occ, const float *label_occ, cons
     if (U1 > 1024) return PIKA_ETOOBIG;
     if (!blank_occ || !label_occ || !frames_lengths || !labels_lengths || !ranges) return PIKA_EINVAL;
     hipLaunchKernelGGL(rnnt_prune_ranges_kernel, dim3((unsigned)B), dim3(PRUNE_THREADS), 0, static_cast<hipStream_t>(stream),
-                       blank_occ, label_occ, frames_lengths, labels_lengths, T, U1, S, ranges);
+                       blank_occ, label_occ, frames_lengths, labels_lengths, T, U1, S, S - 1, ranges);
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// modified topology (pika_rnnt.h): un-skewed planes and their own alpha/beta over a workspace of
+// pika_prnnt_mod_workspace_bytes; the row metadata is the regular RowMeta, so the flat writer and the fused d(logits)
+// kernel run unchanged.  ranges == NULL: the padded (B, T, U1, V) layout (S must be U1); else the banded (B, T, S, V) one.
+// ---------------------------------------------------------------------------------------------
+namespace {
+int check_mod(int B, int T, int U1, int S, int V, int blank, const int *labels, const int *ranges, const int *frames_lengths,
+              const int *labels_lengths) {
+    static const int some = 0;  // a padded call has no ranges to test
+    if (int rc = check_banded(B, T, U1, S, V, blank, labels, ranges ? ranges : &some, frames_lengths, labels_lengths)) return rc;
+    return (!ranges && S != U1) ? PIKA_EINVAL : PIKA_OK;
+}
+
+void launch_rowmeta_mod(const Lattice &L, const int *labels, const int *Tn, const int *Un, const int *ranges, int B, int T,
+                        int U1, int S, int V, const float *grad_costs, float lscale, hipStream_t s) {
+    const size_t nrows = (size_t)B * T * S;
+    const dim3 grid((unsigned)((nrows + 255) / 256));
+    if (ranges)
+        hipLaunchKernelGGL((rnnt_rowmeta_kernel<BANDED, true>), grid, dim3(256), 0, s, labels, Tn, Un, B, T, U1, V, grad_costs,
+                           L.lpb, L.lpe, L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, L.meta, lscale,
+                           static_cast<const int *>(nullptr), static_cast<const int *>(nullptr), 0L, ranges, S);
+    else
+        hipLaunchKernelGGL((rnnt_rowmeta_kernel<PADDED, true>), grid, dim3(256), 0, s, labels, Tn, Un, B, T, U1, V, grad_costs,
+                           L.lpb, L.lpe, L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, L.meta, lscale,
+                           static_cast<const int *>(nullptr), static_cast<const int *>(nullptr), 0L,
+                           static_cast<const int *>(nullptr), 0);
+}
+}  // namespace
+
+size_t pika_prnnt_mod_workspace_bytes(int B, int T, int U1) {
+    if (check_lattice_dims(B, T, U1)) return 0;
+    return workspace_bytes_mod(B, T, U1);
+}
+
+int pika_prnnt_mod_forward(const float *log_probs, const int *frames_lengths, const int *labels_lengths, const int *labels,
+                           const int *ranges, int B, int T, int U1, int S, int V, int blank, float *costs, void *workspace,
+                           void *stream) {
+    if (int rc = check_mod(B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
+    if (!log_probs || !costs || !workspace) return PIKA_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const ModLattice L = carve_mod(workspace, B, T, U1);
+    const dim3 grid((unsigned)((L.D + 4 * GATHER_ROWS - 1) / (4 * GATHER_ROWS)), (unsigned)(L.Wp / 64), (unsigned)B);
+    if (ranges)
+        hipLaunchKernelGGL((rnnt_gather_kernel<BANDED, true>), grid, dim3(256), 0, s, log_probs, labels, frames_lengths,
+                           labels_lengths, B, T, U1, V, blank, L.lpb, L.lpe, L.Wp, L.D, static_cast<const int *>(nullptr),
+                           static_cast<const int *>(nullptr), ranges, S);
+    else
+        hipLaunchKernelGGL((rnnt_gather_kernel<PADDED, true>), grid, dim3(256), 0, s, log_probs, labels, frames_lengths,
+                           labels_lengths, B, T, U1, V, blank, L.lpb, L.lpe, L.Wp, L.D, static_cast<const int *>(nullptr),
+                           static_cast<const int *>(nullptr), static_cast<const int *>(nullptr), 0);
+    return finish_forward_mod(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
+}
+
+int pika_prnnt_mod_backward(const int *frames_lengths, const int *labels_lengths, const int *labels, const int *ranges, int B,
+                            int T, int U1, int S, int V, int blank, const float *grad_costs, const void *workspace,
+                            float *grads, float fastemit_lambda, void *stream) {
+    if (int rc = check_mod(B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
+    if (!workspace) return PIKA_EINVAL;
+    float lscale;
+    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const ModLattice L = carve_mod(const_cast<void *>(workspace), B, T, U1);
+    launch_rowmeta_mod(L, labels, frames_lengths, labels_lengths, ranges, B, T, U1, S, V, grad_costs, lscale, s);
+    if (!grads) return (int)hipGetLastError();
+    return write_dense_grads(L, (size_t)B * T * S, V, blank, grads, s);
+}
+
+int pika_prnnt_mod_fused_forward(const float *logits, const int *frames_lengths, const int *labels_lengths,
+                                 const int *labels, const int *ranges, int B, int T, int U1, int S, int V, int blank,
+                                 float *costs, float *lse, void *workspace, void *stream) {
+    if (int rc = check_mod(B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
+    if (!logits || !costs || !lse || !workspace || !logits_ok(logits, V)) return PIKA_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const ModLattice L = carve_mod(workspace, B, T, U1);
+    const long long rows = (long long)B * T * S;
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (ranges) {
+        const size_t n4 = 2 * ((size_t)B * L.D * L.Wp) / 4;  // lpb and lpe are adjacent; a plane is a multiple of 64 floats
+        hipLaunchKernelGGL(rnnt_fill_neg_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s,
+                           reinterpret_cast<v4f *>(L.lpb), n4);
+        PIKA_CQ(V, hipLaunchKernelGGL((rnnt_lse_gather_kernel<CQ, BANDED, true>), grid, dim3(256), 0, s, logits, labels,
+                                      frames_lengths, labels_lengths, rows, T, U1, V, blank, lse, L.lpb, L.lpe, L.Wp, L.D,
+                                      static_cast<const int *>(nullptr), static_cast<const int *>(nullptr), B, ranges, S));
+    } else {
+        PIKA_CQ(V, hipLaunchKernelGGL((rnnt_lse_gather_kernel<CQ, PADDED, true>), grid, dim3(256), 0, s, logits, labels,
+                                      frames_lengths, labels_lengths, rows, T, U1, V, blank, lse, L.lpb, L.lpe, L.Wp, L.D,
+                                      static_cast<const int *>(nullptr), static_cast<const int *>(nullptr), B,
+                                      static_cast<const int *>(nullptr), 0));
+    }
+    return finish_forward_mod(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
+}
+
+int pika_prnnt_mod_fused_backward(const float *logits, const float *lse, const int *frames_lengths,
+                                  const int *labels_lengths, const int *labels, const int *ranges, int B, int T, int U1, int S,
+                                  int V, int blank, const float *grad_costs, const void *workspace, void *grad_logits,
+                                  int out_dtype, long long ld_out, float fastemit_lambda, void *stream) {
+    if (int rc = check_mod(B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
+    if (!logits || !lse || !workspace || !grad_logits) return PIKA_EINVAL;
+    if (int rc = check_dlogits_out(logits, V, grad_logits, out_dtype, ld_out)) return rc;
+    float lscale;
+    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const ModLattice L = carve_mod(const_cast<void *>(workspace), B, T, U1);
+    launch_rowmeta_mod(L, labels, frames_lengths, labels_lengths, ranges, B, T, U1, S, V, grad_costs, lscale, s);
+    return launch_dlogits_fused(L, logits, lse, (long long)B * T * S, V, blank, grad_logits, out_dtype, ld_out, s);
+}
+
+int pika_prnnt_mod_planes_forward(const float *blank_lp, const float *label_lp, const int *frames_lengths,
+                                  const int *labels_lengths, int B, int T, int U1, float *costs, float *blank_occ,
+                                  float *label_occ, void *workspace, void *stream) {
+    if (int rc = check_lattice_dims(B, T, U1)) return rc;
+    if (!blank_lp || !label_lp || !frames_lengths || !labels_lengths || !costs || !blank_occ || !label_occ || !workspace)
+        return PIKA_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const ModLattice L = carve_mod(workspace, B, T, U1);
+    hipLaunchKernelGGL(rnnt_skew_planes_kernel<true>, dim3((unsigned)((L.D + 3) / 4), (unsigned)(L.Wp / 64), (unsigned)B),
+                       dim3(256), 0, s, blank_lp, label_lp, frames_lengths, labels_lengths, T, U1, L.lpb, L.lpe, L.Wp, L.D);
+    if (int rc = finish_forward_mod(L, frames_lengths, labels_lengths, costs, B, T, U1, s)) return rc;
+    const size_t cells = (size_t)B * T * U1;
+    hipLaunchKernelGGL(rnnt_occupancy_kernel<true>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, frames_lengths,
+                       labels_lengths, B, T, U1, L.lpb, L.lpe, L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, blank_occ,
+                       label_occ);
+    return (int)hipGetLastError();
+}
+
+int pika_prnnt_mod_prune_ranges(const float *blank_occ, const float *label_occ, const int *frames_lengths,
+                                const int *labels_lengths, int B, int T, int U1, int S, int *ranges, void *stream) {
+    if (B <= 0 || T <= 0 || U1 <= 0 || S < 1 || S > U1) return PIKA_EINVAL;
+    if (U1 > 1024) return PIKA_ETOOBIG;
+    if (!blank_occ || !label_occ || !frames_lengths || !labels_lengths || !ranges) return PIKA_EINVAL;
+    hipLaunchKernelGGL(rnnt_prune_ranges_kernel, dim3((unsigned)B), dim3(PRUNE_THREADS), 0, static_cast<hipStream_t>(stream),
+                       blank_occ, label_occ, frames_lengths, labels_lengths, T, U1, S, 1, ranges);
     return (int)hipGetLastError();
 }
 

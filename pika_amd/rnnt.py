@@ -1104,6 +1104,212 @@ def rnnt_pruned_joint_loss_smoothed(enc, pred, labels, frames_lengths, labels_le
                                simple_lm, s_range, blank, fastemit_lambda, reduction)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Modified topology (k2's rnnt_loss / rnnt_loss_pruned with modified=True; include/pika_rnnt.h "Modified topology"): every
+# frame emits exactly one symbol, the label edge runs (t, u) -> (t+1, u+1).  The same surface as the regular functions
+# above, name for name with a `_modified` in it, over the pika_prnnt_mod_* entries; feasible iff U_n <= T_n, an utterance
+# without a path costs +inf and has a zero gradient.  Nothing reads a length on the host.
+# ---------------------------------------------------------------------------------------------------------------------
+class _ModifiedLossFn(torch.autograd.Function):
+    """Modified-topology costs from log-probs or raw logits (`logits`), on the band (B,T,S,V) of `ranges` or -- ranges None
+    -- on the full lattice (B,T,U1,V); the gradient has the input's shape."""
+
+    @staticmethod
+    def forward(ctx, x, labels, ranges, frames_lengths, labels_lengths, blank, fastemit_lambda, logits, caller):
+        what = "logits" if logits else "log_probs"
+        if ranges is None:
+            _check_tensors(x, what, labels, frames_lengths, labels_lengths, " (there is no CPU path)")
+            if x.dim() != 4:
+                raise ValueError("%s must be (B,T,U+1,V), got %s" % (what, tuple(x.shape)))
+            B, T, U1, V = x.shape
+            S = U1
+            if labels.dim() != 2 or labels.shape[0] != B or labels.shape[1] != U1 - 1:
+                raise ValueError("labels must be (B,U)=(%d,%d), got %s" % (B, U1 - 1, tuple(labels.shape)))
+            if frames_lengths.shape != (B,) or labels_lengths.shape != (B,):
+                raise ValueError("frames_lengths / labels_lengths must be (B,)")
+            if not 0 <= blank < V:
+                raise ValueError("blank=%d outside [0,%d)" % (blank, V))
+            if U1 > 1024:
+                raise ValueError("U+1=%d > 1024 not supported" % U1)
+            if B * T * U1 > 0x7fffffff:
+                raise ValueError("B*T*(U+1) = %d rows > 2^31 - 1" % (B * T * U1))
+        else:
+            B, T, U1, S, V = _check_pruned(x, what, labels, ranges, frames_lengths, labels_lengths, blank)
+            ranges = ranges.contiguous()
+        if logits and not _fused_v_ok(V):
+            raise ValueError("%s: V = %d must be a multiple of 4 and <= %d" % (caller, V, MAX_FUSED_V))
+        lib = _lib.lib()
+        x = x.detach().contiguous()
+        labels, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, frames_lengths, labels_lengths))
+        with torch.cuda.device(x.device):
+            costs = torch.empty(B, dtype=torch.float32, device=x.device)
+            ws = torch.empty(lib.pika_prnnt_mod_workspace_bytes(B, T, U1), dtype=torch.uint8, device=x.device)
+            head = (_ptr(x), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(labels), _ptr(ranges), B, T, U1, S, V, blank,
+                    _ptr(costs))
+            with _timed("fwd"):
+                if logits:
+                    lse = torch.empty(B * T * S, dtype=torch.float32, device=x.device)
+                    _lib.check(lib.pika_prnnt_mod_fused_forward(*head, _ptr(lse), _ptr(ws), _stream()),
+                               "pika_prnnt_mod_fused_forward")
+                else:
+                    lse = None
+                    _lib.check(lib.pika_prnnt_mod_forward(*head, _ptr(ws), _stream()), "pika_prnnt_mod_forward")
+        ctx.save_for_backward(labels, frames_lengths, labels_lengths, ws, *((x, lse) if logits else ()))
+        ctx.ranges = ranges          # (not a differentiable input; None on the full lattice)
+        ctx.dims = (B, T, U1, S, V, blank)
+        ctx.fastemit_lambda = fastemit_lambda
+        ctx.shape = tuple(x.shape)
+        return costs
+
+    @staticmethod
+    def backward(ctx, grad_costs):
+        labels, frames_lengths, labels_lengths, ws = ctx.saved_tensors[:4]
+        B, T, U1, S, V, blank = ctx.dims
+        gc = grad_costs.to(torch.float32).contiguous()
+        tail = (_ptr(frames_lengths), _ptr(labels_lengths), _ptr(labels), _ptr(ctx.ranges), B, T, U1, S, V, blank, _ptr(gc),
+                _ptr(ws))
+        with torch.cuda.device(ws.device):
+            grads = torch.empty(ctx.shape, dtype=torch.float32, device=ws.device)
+            with _timed("bwd"):
+                if len(ctx.saved_tensors) > 4:
+                    x, lse = ctx.saved_tensors[4:]
+                    _lib.check(_lib.lib().pika_prnnt_mod_fused_backward(_ptr(x), _ptr(lse), *tail, _ptr(grads), 0, V,
+                                                                        ctx.fastemit_lambda, _stream()),
+                               "pika_prnnt_mod_fused_backward")
+                else:
+                    _lib.check(_lib.lib().pika_prnnt_mod_backward(*tail, _ptr(grads), ctx.fastemit_lambda, _stream()),
+                               "pika_prnnt_mod_backward")
+        return (grads,) + (None,) * 8
+
+
+def _modified_loss(x, labels, ranges, frames_lengths, labels_lengths, average_frames, reduction, blank, fastemit_lambda,
+                   logits, caller):
+    lam = _check_lambda(fastemit_lambda)
+    costs = _ModifiedLossFn.apply(x, labels, ranges, frames_lengths, labels_lengths, int(blank), lam, logits, caller)
+    return _reduce(costs, frames_lengths, average_frames, reduction)
+
+
+def rnnt_loss_modified(log_probs, labels, frames_lengths, labels_lengths, average_frames=False, reduction=None, blank=0,
+                       fastemit_lambda=0.0):
+    """`rnnt_loss` in the modified topology (k2's rnnt_loss(modified=True)): every frame emits exactly one symbol, so a
+    label edge runs (t, u) -> (t+1, u+1), row T_n is terminal (a label may be emitted on the last frame) and an utterance
+    is feasible iff U_n <= T_n; an infeasible one costs +inf, has a zero gradient and leaves the others alone.
+
+    log_probs (B, T, U+1, V) f32, padded layout only; the other arguments as in `rnnt_loss`.  The gradient is dense,
+    rows past T_n or U_n are zero.  No host synchronisation."""
+    return _modified_loss(log_probs, labels, None, frames_lengths, labels_lengths, average_frames, reduction, blank,
+                          fastemit_lambda, False, "rnnt_loss_modified")
+
+
+def rnnt_loss_modified_from_logits(logits, labels, frames_lengths, labels_lengths, average_frames=False, reduction=None,
+                                   blank=0, fastemit_lambda=0.0):
+    """`rnnt_loss_modified` of log_softmax(logits) for raw logits (B, T, U+1, V), V % 4 == 0 and V <= 8192, differentiable
+    w.r.t. the logits: the log-probabilities and their dense gradient never exist."""
+    return _modified_loss(logits, labels, None, frames_lengths, labels_lengths, average_frames, reduction, blank,
+                          fastemit_lambda, True, "rnnt_loss_modified_from_logits")
+
+
+def rnnt_loss_pruned_modified(log_probs, labels, ranges, frames_lengths, labels_lengths, average_frames=False,
+                              reduction=None, blank=0, fastemit_lambda=0.0):
+    """`rnnt_loss_pruned` in the modified topology (k2's rnnt_loss_pruned(modified=True)): the cost of
+    `rnnt_loss_modified` on a (B, T, U+1, V) tensor holding the band's rows at their cells and -1e30 elsewhere.
+
+    Arguments as in `rnnt_loss_pruned`.  A band from `rnnt_prune_ranges_modified` holds a path whenever U_n <= T_n; one
+    from `rnnt_prune_ranges` may move S - 1 columns per frame, which no path here can follow.  A band without a path costs
+    +inf and has a zero gradient.  With S = U + 1 and all-zero ranges this is `rnnt_loss_modified`, bit for bit."""
+    return _modified_loss(log_probs, labels, ranges, frames_lengths, labels_lengths, average_frames, reduction, blank,
+                          fastemit_lambda, False, "rnnt_loss_pruned_modified")
+
+
+def rnnt_loss_pruned_modified_from_logits(logits, labels, ranges, frames_lengths, labels_lengths, average_frames=False,
+                                          reduction=None, blank=0, fastemit_lambda=0.0):
+    """`rnnt_loss_pruned_modified` of log_softmax(logits) for raw logits (B, T, S, V), V % 4 == 0 and V <= 8192."""
+    return _modified_loss(logits, labels, ranges, frames_lengths, labels_lengths, average_frames, reduction, blank,
+                          fastemit_lambda, True, "rnnt_loss_pruned_modified_from_logits")
+
+
+class _ModifiedPlanesLossFn(torch.autograd.Function):
+    """`_PlanesLossFn` in the modified topology."""
+
+    @staticmethod
+    def forward(ctx, blank_lp, label_lp, frames_lengths, labels_lengths):
+        B, T, U1 = _check_planes(blank_lp, label_lp, frames_lengths, labels_lengths, ("blank_lp", "label_lp"))
+        lib = _lib.lib()
+        pb, pl = blank_lp.detach().contiguous(), label_lp.detach().contiguous()
+        frames_lengths, labels_lengths = frames_lengths.contiguous(), labels_lengths.contiguous()
+        with torch.cuda.device(pb.device):
+            costs = torch.empty(B, dtype=torch.float32, device=pb.device)
+            occ_b, occ_l = torch.empty_like(pb), torch.empty_like(pb)
+            ws = torch.empty(lib.pika_prnnt_mod_workspace_bytes(B, T, U1), dtype=torch.uint8, device=pb.device)
+            with _timed(None):
+                _lib.check(lib.pika_prnnt_mod_planes_forward(_ptr(pb), _ptr(pl), _ptr(frames_lengths), _ptr(labels_lengths),
+                                                             B, T, U1, _ptr(costs), _ptr(occ_b), _ptr(occ_l), _ptr(ws),
+                                                             _stream()), "pika_prnnt_mod_planes_forward")
+        ctx.save_for_backward(occ_b, occ_l)
+        ctx.mark_non_differentiable(occ_b, occ_l)
+        return costs, occ_b, occ_l
+
+    @staticmethod
+    def backward(ctx, grad_costs, _gb, _gl):
+        occ_b, occ_l = ctx.saved_tensors
+        g = -grad_costs.to(torch.float32).view(-1, 1, 1)
+        return occ_b * g, occ_l * g, None, None
+
+
+def rnnt_loss_from_planes_modified(blank_lp, label_lp, frames_lengths, labels_lengths, reduction=None,
+                                   return_occupancy=False):
+    """`rnnt_loss_from_planes` in the modified topology: blank_lp[b, t, u] is the edge (t, u) -> (t+1, u), label_lp[b, t, u]
+    the edge (t, u) -> (t+1, u+1), ll = alpha(T_n, U_n).  The planes of `rnnt_simple_planes` / `rnnt_smoothed_planes` are
+    topology-independent and are what this takes.  An utterance with U_n > T_n costs +inf; its gradient and occupancies
+    are zero."""
+    costs, occ_b, occ_l = _ModifiedPlanesLossFn.apply(blank_lp, label_lp, frames_lengths, labels_lengths)
+    costs = _reduce(costs, frames_lengths, False, reduction)
+    return (costs, occ_b, occ_l) if return_occupancy else costs
+
+
+def rnnt_prune_ranges_modified(blank_occ, label_occ, frames_lengths, labels_lengths, s_range):
+    """`rnnt_prune_ranges` with step bound 1, the band search of the modified topology: (B, T) int32 band starts.
+
+    raw and m as in `rnnt_prune_ranges`; f(0) = 0, f(t) = min(m(t), f(t-1) + 1), s_t = max(f(t), s_max - (T_n - 1 - t));
+    s_max for t >= T_n.  s_0 = 0, 0 <= s_{t+1} - s_t <= 1 and s_{T_n-1} = s_max whenever T_n - 1 >= s_max (otherwise
+    s_0 > 0); such a band holds the path u_t = min(t, s_t + S - 1) whenever U_n <= T_n."""
+    S = int(s_range)
+    B, T, U1 = _check_planes(blank_occ, label_occ, frames_lengths, labels_lengths, ("blank_occ", "label_occ"))
+    if not 1 <= S <= U1:
+        raise ValueError("s_range=%d must be in [1, U+1=%d]" % (S, U1))
+    ob, ol = blank_occ.detach().contiguous(), label_occ.detach().contiguous()
+    frames_lengths, labels_lengths = frames_lengths.contiguous(), labels_lengths.contiguous()
+    with torch.cuda.device(ob.device):
+        ranges = torch.empty((B, T), dtype=torch.int32, device=ob.device)
+        _lib.check(_lib.lib().pika_prnnt_mod_prune_ranges(_ptr(ob), _ptr(ol), _ptr(frames_lengths), _ptr(labels_lengths), B,
+                                                          T, U1, S, _ptr(ranges), _stream()), "pika_prnnt_mod_prune_ranges")
+    return ranges
+
+
+def rnnt_pruned_joint_loss_modified(enc, pred, labels, frames_lengths, labels_lengths, fc1, fc_gate, fc2, simple_am,
+                                    simple_lm, s_range=5, lm_only_scale=0.0, am_only_scale=0.0, blank=0,
+                                    fastemit_lambda=0.0, reduction="sum"):
+    """`rnnt_pruned_joint_loss_smoothed` in the modified topology: `rnnt_smoothed_planes` ->
+    `rnnt_loss_from_planes_modified` -> `rnnt_prune_ranges_modified` -> `joint_pruned` ->
+    `rnnt_loss_pruned_modified_from_logits` (`rnnt_loss_pruned_modified` for a vocabulary that call does not take).
+    Returns (simple_loss, pruned_loss, ranges).  Forward plus backward capture into one torch.cuda.graph."""
+    from .model.ops import joint_pruned, linear
+    ll, la = _check_scales(lm_only_scale, am_only_scale)
+    S = int(s_range)
+    lam = _check_lambda(fastemit_lambda)
+    am = linear(enc, simple_am.weight, simple_am.bias)
+    lm = linear(pred, simple_lm.weight, simple_lm.bias)
+    blank_lp, label_lp = rnnt_smoothed_planes(am, lm, labels, blank=blank, lm_only_scale=ll, am_only_scale=la)
+    simple, occ_b, occ_l = rnnt_loss_from_planes_modified(blank_lp, label_lp, frames_lengths, labels_lengths,
+                                                          reduction=reduction, return_occupancy=True)
+    ranges = rnnt_prune_ranges_modified(occ_b, occ_l, frames_lengths, labels_lengths, S)
+    fused = _fused_v_ok(fc2.weight.shape[0])
+    x = joint_pruned(enc, pred, ranges, S, fc1, fc_gate, fc2, log_softmax=not fused)
+    loss = rnnt_loss_pruned_modified_from_logits if fused else rnnt_loss_pruned_modified
+    pruned = loss(x, labels, ranges, frames_lengths, labels_lengths, reduction=reduction, blank=blank, fastemit_lambda=lam)
+    return simple, pruned, ranges
+
+
 class RNNTLoss(object):
     """`RNNTLoss(blank=0, reduction='sum').apply(...)` exactly as the reference scripts use it.
 
