@@ -31,6 +31,14 @@
 //   pruned    : the loss on a banded lattice (B,T,S,V) is the BANDED layout of gather / rowmeta over the same planes and
 //               the same alpha/beta, writer and d(logits) kernels; with it the loss of a lattice given by its two
 //               planes, its occupation probabilities and the band search (the end of the kernel section).
+//   modified  : k2's modified topology is the MOD instantiation of the same layout kernels over un-skewed planes, with
+//               its own alpha/beta walker and row centres.
+//
+// Host side (the end of the file): the kernels first, then ONE host path for all of them.  A `Call` says how a call's
+// (rows, V) tensor maps to lattice cells (layout PADDED / PACKED / BANDED, regular or modified topology); dispatch_layout
+// turns it into the compile-time pair of the five instantiated combinations; one launcher per kernel family
+// (launch_gather, launch_lse_gather, launch_rowmeta, finish_forward) and four bodies (loss_forward, loss_backward,
+// fused_forward, fused_backward) serve every layout.  An extern "C" entry is its own argument checks, a Call and a body.
 //
 // Algorithmic HBM bytes per utterance (T=1000,U1=51,V=5000): 1.020 GB gradient write + ~1.2 MB
 // lattice traffic; see DESIGN.md.
@@ -86,6 +94,8 @@ struct RowMeta {  // 16 bytes per lattice cell
     int pad;
 };
 
+// The workspace of every call.  mod (the modified topology, below): the planes are not skewed -- cell (t,u) at row t, col u,
+// D = T + 1 rows -- and every row has a centre.
 struct Lattice {
     float *lpb;    // [B][D][Wp] blank log-prob of cell (t,u) at row t+u, col u
     float *lpe;    // [B][D][Wp] log-prob of emitting y_{u+1} from cell (t,u)
@@ -96,18 +106,21 @@ struct Lattice {
     double *ll;    // [B] log-likelihood, beta side
     double *ll_a;  // [B] log-likelihood, alpha side (diagnostic)
     RowMeta *meta; // [B*T*U1]
+    float *rowc;   // [B][D] row centres; null unless mod
     int Wp, D;
 };
 
-inline size_t plane_elems(int B, int T, int U1) {
-    return (size_t)B * (size_t)(T + U1 - 1) * (size_t)lattice_width(U1);
+inline int lattice_rows(int T, int U1, bool mod) { return mod ? T + 1 : T + U1 - 1; }
+
+inline size_t plane_elems(int B, int T, int U1, bool mod) {
+    return (size_t)B * (size_t)lattice_rows(T, U1, mod) * (size_t)lattice_width(U1);
 }
 
-inline Lattice carve(void *ws, int B, int T, int U1) {
+inline Lattice carve(void *ws, int B, int T, int U1, bool mod = false) {
     Lattice L;
-    const size_t n = plane_elems(B, T, U1);
+    const size_t n = plane_elems(B, T, U1, mod);
     L.Wp = lattice_width(U1);
-    L.D = T + U1 - 1;
+    L.D = lattice_rows(T, U1, mod);
     float *p = static_cast<float *>(ws);
     L.lpb = p;
     L.lpe = p + n;
@@ -119,14 +132,15 @@ inline Lattice carve(void *ws, int B, int T, int U1) {
     L.ll = q + 2 * (size_t)B * L.D;
     L.ll_a = L.ll + B;
     L.meta = reinterpret_cast<RowMeta *>(L.ll_a + B);  // 2BD+2B doubles: 16-byte aligned
+    L.rowc = mod ? reinterpret_cast<float *>(L.meta + (size_t)B * T * U1) : nullptr;
     return L;
 }
 
-inline size_t workspace_bytes(int B, int T, int U1) {
-    const size_t D = (size_t)(T + U1 - 1);
-    return 4 * plane_elems(B, T, U1) * sizeof(float) +
+inline size_t workspace_bytes(int B, int T, int U1, bool mod) {
+    const size_t D = (size_t)lattice_rows(T, U1, mod);
+    return 4 * plane_elems(B, T, U1, mod) * sizeof(float) +
            (2 * (size_t)B * D + 2 * (size_t)B) * sizeof(double) +
-           (size_t)B * T * U1 * sizeof(RowMeta);
+           (size_t)B * T * U1 * sizeof(RowMeta) + (mod ? (size_t)B * D * sizeof(float) : 0);
 }
 
 __device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -1144,17 +1158,6 @@ __global__ __launch_bounds__(256) void rnnt_dlogits_compact8_kernel(const TI *__
     if (cs_blank != 0.f) atomicAdd(colsum + blank, cs_blank);
 }
 
-// What every forward does once its one launch has filled the lpb / lpe planes: alpha, beta and the costs.
-int finish_forward(const Lattice &L, const int *frames_lengths, const int *labels_lengths, float *costs, int B,
-                   int T, int U1, hipStream_t s) {
-    const bool ok = dispatch_nw(L.Wp / 64, [&](auto nw) {
-        constexpr int NW = decltype(nw)::value;
-        hipLaunchKernelGGL((rnnt_alpha_beta_kernel<NW>), dim3(2, B), dim3(NW * 64), 0, s, L.lpb, L.lpe, L.alpha, L.beta,
-                           L.off_a, L.off_b, frames_lengths, labels_lengths, L.ll, L.ll_a, costs, T, U1, L.Wp, L.D);
-    });
-    return ok ? (int)hipGetLastError() : PIKA_ETOOBIG;
-}
-
 // The arguments of a padded forward: the dimensions; then own_ok -- the entry point's own tests of its pointers, V and
 // pitches -- and the labels when some utterance can have one (PIKA_EINVAL); then, for the calls whose kernels index the
 // B*T*U1 rows as an int (`rows` given), the row count (PIKA_ETOOBIG).
@@ -1730,77 +1733,126 @@ __global__ __launch_bounds__(NW * 64) void rnnt_mod_alpha_beta_kernel(
     }
 }
 
-// The workspace of the modified topology: the regular one's members over D = T + 1 un-skewed rows.
-struct ModLattice : Lattice {
-    float *rowc;  // [B][D] row centres
+// ---------------------------------------------------------------------------------------------
+// Host side.  Every loss entry point is its own argument checks, a Call -- how the call's (rows, V) tensor maps to lattice
+// cells -- and one of four bodies (loss_forward, loss_backward, fused_forward, fused_backward) over one launcher per
+// kernel family.  A further layout or topology is a Call maker and a line of dispatch_layout.
+// ---------------------------------------------------------------------------------------------
+struct Call {
+    Layout layout;
+    bool mod;                // the modified topology
+    int B, T, U1, V, blank;  // (T, U1: T_max, U1_max of a packed batch)
+    long long rows;          // of the (rows, V) tensor: B*T*U1 padded, N packed, B*T*S banded
+    const int *labels, *frames_lengths, *labels_lengths;
+    const int *roff, *loff;  // packed: the utterances' row and label offsets
+    const int *ranges;       // banded: the band starts (B, T) ...
+    int S;                   // ... and the band's width
+    hipStream_t s;
 };
 
-inline ModLattice carve_mod(void *ws, int B, int T, int U1) {
-    ModLattice L;
-    L.Wp = lattice_width(U1);
-    L.D = T + 1;
-    const size_t n = (size_t)B * L.D * L.Wp;
-    float *p = static_cast<float *>(ws);
-    L.lpb = p;
-    L.lpe = p + n;
-    L.alpha = p + 2 * n;
-    L.beta = p + 3 * n;
-    double *q = reinterpret_cast<double *>(p + 4 * n);  // n is a multiple of 64: 8-byte aligned
-    L.off_a = q;
-    L.off_b = q + (size_t)B * L.D;
-    L.ll = q + 2 * (size_t)B * L.D;
-    L.ll_a = L.ll + B;
-    L.meta = reinterpret_cast<RowMeta *>(L.ll_a + B);  // 2BD+2B doubles: 16-byte aligned
-    L.rowc = reinterpret_cast<float *>(L.meta + (size_t)B * T * U1);
-    return L;
+Call padded_call(const int *labels, const int *frames_lengths, const int *labels_lengths, int B, int T, int U1, int V,
+                 int blank, void *stream, bool mod = false) {
+    return Call{PADDED, mod, B, T, U1, V, blank, (long long)B * T * U1, labels, frames_lengths, labels_lengths,
+                nullptr, nullptr, nullptr, 0, static_cast<hipStream_t>(stream)};
 }
 
-inline size_t workspace_bytes_mod(int B, int T, int U1) {
-    const size_t D = (size_t)T + 1;
-    return 4 * (size_t)B * D * lattice_width(U1) * sizeof(float) + (2 * (size_t)B * D + 2 * (size_t)B) * sizeof(double) +
-           (size_t)B * T * U1 * sizeof(RowMeta) + (size_t)B * D * sizeof(float);
+Call packed_call(const int *labels, const int *frames_lengths, const int *labels_lengths, const int *roff, const int *loff,
+                 int B, int T_max, int U1_max, long long N, int V, int blank, void *stream) {
+    return Call{PACKED, false, B, T_max, U1_max, V, blank, N, labels, frames_lengths, labels_lengths,
+                roff, loff, nullptr, 0, static_cast<hipStream_t>(stream)};
 }
 
-int finish_forward_mod(const ModLattice &L, const int *frames_lengths, const int *labels_lengths, float *costs, int B, int T,
-                       int U1, hipStream_t s) {
-    hipLaunchKernelGGL(rnnt_mod_rowcentre_kernel, dim3((unsigned)(((size_t)B * L.D + 3) / 4)), dim3(256), 0, s, L.lpb, L.lpe,
-                       frames_lengths, labels_lengths, B, T, U1, L.Wp, L.D, L.rowc);
-    const bool ok = dispatch_nw(L.Wp / 64, [&](auto nw) {
-        constexpr int NW = decltype(nw)::value;
-        hipLaunchKernelGGL((rnnt_mod_alpha_beta_kernel<NW>), dim3(2, B), dim3(NW * 64), 0, s, L.lpb, L.lpe, L.alpha, L.beta,
-                           L.off_a, L.off_b, frames_lengths, labels_lengths, L.ll, L.ll_a, costs, L.rowc, T, U1, L.Wp, L.D);
+// ranges null (the modified topology only, where S == U1): the padded layout
+Call banded_call(bool mod, const int *labels, const int *ranges, const int *frames_lengths, const int *labels_lengths, int B,
+                 int T, int U1, int S, int V, int blank, void *stream) {
+    return Call{ranges ? BANDED : PADDED, mod, B, T, U1, V, blank, (long long)B * T * S, labels, frames_lengths,
+                labels_lengths, nullptr, nullptr, ranges, ranges ? S : 0, static_cast<hipStream_t>(stream)};
+}
+
+// The (layout, topology) pairs the layout kernels are instantiated for: THE list.  f(LayoutOf<LAYOUT, MOD>{}) for the
+// call's pair; false when there is none.  (LayoutOf<PADDED, false> is the kernels' default template arguments: the
+// instantiations otherwise spelt rnnt_gather_kernel<>, rnnt_lse_gather_kernel<CQ> and rnnt_rowmeta_kernel<>.)
+template <int LAYOUT, bool MOD>
+struct LayoutOf {
+    static constexpr int layout = LAYOUT;
+    static constexpr bool mod = MOD;
+};
+template <class F, class... P>
+inline bool dispatch_layout(const Call &c, F f, P... pair) {
+    return ((c.layout == pair.layout && c.mod == pair.mod && (f(pair), true)) || ...);
+}
+template <class F>
+inline bool dispatch_layout(const Call &c, F f) {
+    return dispatch_layout(c, f, LayoutOf<PADDED, false>{}, LayoutOf<PACKED, false>{}, LayoutOf<BANDED, false>{},
+                           LayoutOf<PADDED, true>{}, LayoutOf<BANDED, true>{});
+}
+
+// One launcher per kernel family.  Each passes the full argument list: an instantiation does not read what its layout
+// does not have (null offsets, null ranges, S = 0).
+int launch_gather(const Call &c, const Lattice &L, const float *log_probs) {
+    const dim3 grid((unsigned)((L.D + 4 * GATHER_ROWS - 1) / (4 * GATHER_ROWS)), (unsigned)(L.Wp / 64), (unsigned)c.B);
+    const bool ok = dispatch_layout(c, [&](auto pair) {
+        using P = decltype(pair);
+        hipLaunchKernelGGL((rnnt_gather_kernel<P::layout, P::mod>), grid, dim3(256), 0, c.s, log_probs, c.labels,
+                           c.frames_lengths, c.labels_lengths, c.B, c.T, c.U1, c.V, c.blank, L.lpb, L.lpe, L.Wp, L.D, c.roff,
+                           c.loff, c.ranges, c.S);
     });
+    return ok ? PIKA_OK : PIKA_EINVAL;
+}
+
+int launch_lse_gather(const Call &c, const Lattice &L, const float *logits, float *lse) {
+    if (c.layout == BANDED) {  // the banded kernel writes the live cells only: NEG under it
+        const size_t n4 = 2 * ((size_t)c.B * L.D * L.Wp) / 4;  // lpb and lpe are adjacent; a plane is a multiple of 64 floats
+        hipLaunchKernelGGL(rnnt_fill_neg_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, c.s,
+                           reinterpret_cast<v4f *>(L.lpb), n4);
+    }
+    const dim3 grid((unsigned)((c.rows + 3) / 4));
+    const bool ok = dispatch_layout(c, [&](auto pair) {
+        using P = decltype(pair);
+        PIKA_CQ(c.V, hipLaunchKernelGGL((rnnt_lse_gather_kernel<CQ, P::layout, P::mod>), grid, dim3(256), 0, c.s, logits,
+                                        c.labels, c.frames_lengths, c.labels_lengths, c.rows, c.T, c.U1, c.V, c.blank, lse,
+                                        L.lpb, L.lpe, L.Wp, L.D, c.roff, c.loff, c.B, c.ranges, c.S));
+    });
+    return ok ? PIKA_OK : PIKA_EINVAL;
+}
+
+// row metadata of the call's rows
+int launch_rowmeta(const Call &c, const Lattice &L, const float *grad_costs, float lscale) {
+    const bool ok = dispatch_layout(c, [&](auto pair) {
+        using P = decltype(pair);
+        hipLaunchKernelGGL((rnnt_rowmeta_kernel<P::layout, P::mod>), dim3((unsigned)((c.rows + 255) / 256)), dim3(256), 0, c.s,
+                           c.labels, c.frames_lengths, c.labels_lengths, c.B, c.T, c.U1, c.V, grad_costs, L.lpb, L.lpe,
+                           L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, L.meta, lscale, c.roff, c.loff, (long)c.rows,
+                           c.ranges, c.S);
+    });
+    return ok ? PIKA_OK : PIKA_EINVAL;
+}
+
+// What every forward does once its one launch has filled the lpb / lpe planes: alpha, beta and the costs (the modified
+// topology: over the row centres).
+int finish_forward(const Call &c, const Lattice &L, float *costs) {
+    bool ok;
+    if (c.mod) {
+        hipLaunchKernelGGL(rnnt_mod_rowcentre_kernel, dim3((unsigned)(((size_t)c.B * L.D + 3) / 4)), dim3(256), 0, c.s, L.lpb,
+                           L.lpe, c.frames_lengths, c.labels_lengths, c.B, c.T, c.U1, L.Wp, L.D, L.rowc);
+        ok = dispatch_nw(L.Wp / 64, [&](auto nw) {
+            constexpr int NW = decltype(nw)::value;
+            hipLaunchKernelGGL((rnnt_mod_alpha_beta_kernel<NW>), dim3(2, c.B), dim3(NW * 64), 0, c.s, L.lpb, L.lpe, L.alpha,
+                               L.beta, L.off_a, L.off_b, c.frames_lengths, c.labels_lengths, L.ll, L.ll_a, costs, L.rowc, c.T,
+                               c.U1, L.Wp, L.D);
+        });
+    } else {
+        ok = dispatch_nw(L.Wp / 64, [&](auto nw) {
+            constexpr int NW = decltype(nw)::value;
+            hipLaunchKernelGGL((rnnt_alpha_beta_kernel<NW>), dim3(2, c.B), dim3(NW * 64), 0, c.s, L.lpb, L.lpe, L.alpha,
+                               L.beta, L.off_a, L.off_b, c.frames_lengths, c.labels_lengths, L.ll, L.ll_a, costs, c.T, c.U1,
+                               L.Wp, L.D);
+        });
+    }
     return ok ? (int)hipGetLastError() : PIKA_ETOOBIG;
 }
 
-}  // namespace
-
-extern "C" {
-
-int pika_amd_abi_version(void) { return 25; }
-
-size_t pika_rnnt_workspace_bytes(int B, int T, int U1) {
-    if (check_lattice_dims(B, T, U1)) return 0;
-    return workspace_bytes(B, T, U1);
-}
-
-int pika_rnnt_loss_forward(const float *log_probs, const int *labels, const int *frames_lengths,
-                           const int *labels_lengths, int B, int T, int U1, int V, int blank,
-                           float *costs, void *workspace, void *stream) {
-    if (int rc = forward_args_ok(B, T, U1, V, blank, log_probs && frames_lengths && labels_lengths && costs && workspace, labels))
-        return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Lattice L = carve(workspace, B, T, U1);
-    const dim3 grid((unsigned)((L.D + 4 * GATHER_ROWS - 1) / (4 * GATHER_ROWS)), (unsigned)(L.Wp / 64),
-                    (unsigned)B);
-    hipLaunchKernelGGL(rnnt_gather_kernel<PADDED>, grid, dim3(256), 0, s,
-                       log_probs, labels, frames_lengths, labels_lengths, B, T, U1, V, blank, L.lpb,
-                       L.lpe, L.Wp, L.D);
-    return finish_forward(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
-}
-
-namespace {
-// the streaming pass: dense (nrows, V) gradient from the row metadata in the workspace (nrows = B*T*U1 padded, N packed)
+// the streaming pass: dense (nrows, V) gradient from the row metadata in the workspace
 int write_dense_grads(const Lattice &L, size_t nrows, int V, int blank, float *grads, hipStream_t s) {
     const size_t n = nrows * (size_t)V;
     const bool vec4 = (V % 4 == 0) && ((reinterpret_cast<uintptr_t>(grads) & 15) == 0);
@@ -1826,6 +1878,19 @@ int write_dense_grads(const Lattice &L, size_t nrows, int V, int blank, float *g
     return (int)hipGetLastError();
 }
 
+// d(logits) of the fused route over `rows` rows, from the row metadata in L
+int launch_dlogits_fused(const Lattice &L, const float *logits, const float *lse, long long rows, int V, int blank,
+                         void *grad_logits, int out_dtype, long long ld_out, hipStream_t s) {
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (out_dtype == 0)
+        PIKA_CQ(ld_out, hipLaunchKernelGGL((rnnt_dlogits_fused_kernel<float, CQ>), grid, dim3(256), 0, s, logits, lse, L.meta,
+                                           static_cast<float *>(grad_logits), rows, V, ld_out, blank));
+    else
+        PIKA_CQ(ld_out, hipLaunchKernelGGL((rnnt_dlogits_fused_kernel<__bf16, CQ>), grid, dim3(256), 0, s, logits, lse, L.meta,
+                                           static_cast<__bf16 *>(grad_logits), rows, V, ld_out, blank));
+    return (int)hipGetLastError();
+}
+
 // FastEmit lambda -> the factor of the label entries of the row metadata (finite, >= 0; NaN fails the compare)
 int label_scale(float fastemit_lambda, float *lscale) {
     if (!(fastemit_lambda >= 0.0f && fastemit_lambda <= 3.4e38f)) return PIKA_EINVAL;
@@ -1833,23 +1898,75 @@ int label_scale(float fastemit_lambda, float *lscale) {
     return PIKA_OK;
 }
 
-// row metadata of the B*T*U1 rows of a padded batch
-void launch_rowmeta(const Lattice &L, const int *labels, const int *Tn, const int *Un, int B, int T, int U1, int V,
-                    const float *grad_costs, float lscale, hipStream_t s) {
-    const size_t nrows = (size_t)B * T * U1;
-    hipLaunchKernelGGL(rnnt_rowmeta_kernel<PADDED>, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s,
-                       labels, Tn, Un, B, T, U1, V, grad_costs, L.lpb, L.lpe,
-                       L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, L.meta, lscale,
-                       static_cast<const int *>(nullptr), static_cast<const int *>(nullptr), 0L);
+// the d(logits) arguments of the fused backward calls
+int check_dlogits_out(const float *logits, int V, const void *grad_logits, int out_dtype, long long ld_out) {
+    if (!logits_ok(logits, V) || ld_out < V || (ld_out & 3) || ld_out > V_MAX) return PIKA_EINVAL;
+    if (out_dtype != 0 && out_dtype != 1) return PIKA_EINVAL;   // PIKA_F32 / PIKA_BF16 (pika_gemm.h)
+    if (reinterpret_cast<uintptr_t>(grad_logits) & (out_dtype == 0 ? 15 : 7)) return PIKA_EINVAL;
+    return PIKA_OK;
 }
 
-// ... and of the N rows of a packed one
-void launch_rowmeta_packed(const Lattice &L, const int *labels, const int *Tn, const int *Un, const int *roff,
-                           const int *loff, int B, int T, int U1, long long N, int V, const float *grad_costs,
-                           float lscale, hipStream_t s) {
-    hipLaunchKernelGGL(rnnt_rowmeta_kernel<PACKED>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s,
-                       labels, Tn, Un, B, T, U1, V, grad_costs, L.lpb, L.lpe,
-                       L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, L.meta, lscale, roff, loff, (long)N);
+// The four bodies, after the entry point's own checks of its dimensions and pointers.
+int loss_forward(const Call &c, const float *log_probs, float *costs, void *workspace) {
+    const Lattice L = carve(workspace, c.B, c.T, c.U1, c.mod);
+    if (int rc = launch_gather(c, L, log_probs)) return rc;
+    return finish_forward(c, L, costs);
+}
+
+// grads null: row metadata only (pika_rnnt.h)
+int loss_backward(const Call &c, const float *grad_costs, float fastemit_lambda, const void *workspace, float *grads) {
+    float lscale;
+    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
+    const Lattice L = carve(const_cast<void *>(workspace), c.B, c.T, c.U1, c.mod);
+    if (int rc = launch_rowmeta(c, L, grad_costs, lscale)) return rc;
+    if (!grads) return (int)hipGetLastError();
+    return write_dense_grads(L, (size_t)c.rows, c.V, c.blank, grads, c.s);
+}
+
+int fused_forward(const Call &c, const float *logits, float *costs, float *lse, void *workspace) {
+    const Lattice L = carve(workspace, c.B, c.T, c.U1, c.mod);
+    if (int rc = launch_lse_gather(c, L, logits, lse)) return rc;
+    return finish_forward(c, L, costs);
+}
+
+int fused_backward(const Call &c, const float *logits, const float *lse, const float *grad_costs, float fastemit_lambda,
+                   const void *workspace, void *grad_logits, int out_dtype, long long ld_out) {
+    if (int rc = check_dlogits_out(logits, c.V, grad_logits, out_dtype, ld_out)) return rc;
+    float lscale;
+    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
+    if (c.rows > ROWS_MAX) return PIKA_ETOOBIG;  // (the padded call's test of its row count; the others have made theirs)
+    const Lattice L = carve(const_cast<void *>(workspace), c.B, c.T, c.U1, c.mod);
+    if (int rc = launch_rowmeta(c, L, grad_costs, lscale)) return rc;
+    return launch_dlogits_fused(L, logits, lse, c.rows, c.V, c.blank, grad_logits, out_dtype, ld_out, c.s);
+}
+
+// The loss of a lattice given by its two dense planes, and its occupation probabilities.
+template <bool MOD>
+int planes_forward(const float *blank_lp, const float *label_lp, const int *frames_lengths, const int *labels_lengths, int B,
+                   int T, int U1, float *costs, float *blank_occ, float *label_occ, void *workspace, void *stream) {
+    if (int rc = check_lattice_dims(B, T, U1)) return rc;
+    if (!blank_lp || !label_lp || !frames_lengths || !labels_lengths || !costs || !blank_occ || !label_occ || !workspace)
+        return PIKA_EINVAL;
+    const Call c = padded_call(nullptr, frames_lengths, labels_lengths, B, T, U1, 0, 0, stream, MOD);
+    const Lattice L = carve(workspace, B, T, U1, MOD);
+    hipLaunchKernelGGL(rnnt_skew_planes_kernel<MOD>, dim3((unsigned)((L.D + 3) / 4), (unsigned)(L.Wp / 64), (unsigned)B),
+                       dim3(256), 0, c.s, blank_lp, label_lp, frames_lengths, labels_lengths, T, U1, L.lpb, L.lpe, L.Wp, L.D);
+    if (int rc = finish_forward(c, L, costs)) return rc;
+    hipLaunchKernelGGL(rnnt_occupancy_kernel<MOD>, dim3((unsigned)((c.rows + 255) / 256)), dim3(256), 0, c.s, frames_lengths,
+                       labels_lengths, B, T, U1, L.lpb, L.lpe, L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, blank_occ,
+                       label_occ);
+    return (int)hipGetLastError();
+}
+
+// The band search; step: how far the band may move per frame (S - 1; 1 in the modified topology).
+int prune_ranges(int step, const float *blank_occ, const float *label_occ, const int *frames_lengths,
+                 const int *labels_lengths, int B, int T, int U1, int S, int *ranges, void *stream) {
+    if (B <= 0 || T <= 0 || U1 <= 0 || S < 1 || S > U1) return PIKA_EINVAL;
+    if (U1 > 1024) return PIKA_ETOOBIG;
+    if (!blank_occ || !label_occ || !frames_lengths || !labels_lengths || !ranges) return PIKA_EINVAL;
+    hipLaunchKernelGGL(rnnt_prune_ranges_kernel, dim3((unsigned)B), dim3(PRUNE_THREADS), 0, static_cast<hipStream_t>(stream),
+                       blank_occ, label_occ, frames_lengths, labels_lengths, T, U1, S, step, ranges);
+    return (int)hipGetLastError();
 }
 
 // the packed calls' shared checks: (B, T_max, U1_max) as check_dims, 0 < N <= B*T_max*U1_max (the metadata region) and
@@ -1863,7 +1980,82 @@ int check_packed(int B, int T, int U1, long long N, int V, int blank, const int 
     if (N > (long long)B * T * U1) return PIKA_EINVAL;
     return PIKA_OK;
 }
+
+// the banded calls' shared checks: (B, T, U1, V, blank) as check_dims, 1 <= S <= U1, the lengths, the band starts and --
+// when some utterance can have a label -- the labels; B*T*S rows index the row kernels as an int.  mod (the modified
+// topology): the band starts may be null, which is the padded layout and needs S == U1.
+int check_banded(bool mod, int B, int T, int U1, int S, int V, int blank, const int *labels, const int *ranges,
+                 const int *frames_lengths, const int *labels_lengths) {
+    if (V <= 0 || blank < 0 || blank >= V || B <= 0 || T <= 0 || U1 <= 0) return PIKA_EINVAL;
+    if (S < 1 || S > U1) return PIKA_EINVAL;
+    if (U1 > 1024) return PIKA_ETOOBIG;
+    if (!frames_lengths || !labels_lengths || (!ranges && !mod) || (U1 > 1 && !labels)) return PIKA_EINVAL;
+    if ((long long)B * T * S > ROWS_MAX) return PIKA_ETOOBIG;
+    return (!ranges && S != U1) ? PIKA_EINVAL : PIKA_OK;
+}
+
+// The four loss entries of the banded (B,T,S,V) tensor, pika_prnnt_* and pika_prnnt_mod_*: they differ in `mod` alone.
+int banded_forward(bool mod, const float *log_probs, const int *frames_lengths, const int *labels_lengths, const int *labels,
+                   const int *ranges, int B, int T, int U1, int S, int V, int blank, float *costs, void *workspace,
+                   void *stream) {
+    if (int rc = check_banded(mod, B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
+    if (!log_probs || !costs || !workspace) return PIKA_EINVAL;
+    return loss_forward(banded_call(mod, labels, ranges, frames_lengths, labels_lengths, B, T, U1, S, V, blank, stream),
+                        log_probs, costs, workspace);
+}
+
+int banded_backward(bool mod, const int *frames_lengths, const int *labels_lengths, const int *labels, const int *ranges,
+                    int B, int T, int U1, int S, int V, int blank, const float *grad_costs, const void *workspace,
+                    float *grads, float fastemit_lambda, void *stream) {
+    if (int rc = check_banded(mod, B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
+    if (!workspace) return PIKA_EINVAL;
+    return loss_backward(banded_call(mod, labels, ranges, frames_lengths, labels_lengths, B, T, U1, S, V, blank, stream),
+                         grad_costs, fastemit_lambda, workspace, grads);
+}
+
+int banded_fused_forward(bool mod, const float *logits, const int *frames_lengths, const int *labels_lengths,
+                         const int *labels, const int *ranges, int B, int T, int U1, int S, int V, int blank, float *costs,
+                         float *lse, void *workspace, void *stream) {
+    if (int rc = check_banded(mod, B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
+    if (!logits || !costs || !lse || !workspace || !logits_ok(logits, V)) return PIKA_EINVAL;
+    return fused_forward(banded_call(mod, labels, ranges, frames_lengths, labels_lengths, B, T, U1, S, V, blank, stream),
+                         logits, costs, lse, workspace);
+}
+
+int banded_fused_backward(bool mod, const float *logits, const float *lse, const int *frames_lengths,
+                          const int *labels_lengths, const int *labels, const int *ranges, int B, int T, int U1, int S, int V,
+                          int blank, const float *grad_costs, const void *workspace, void *grad_logits, int out_dtype,
+                          long long ld_out, float fastemit_lambda, void *stream) {
+    if (int rc = check_banded(mod, B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
+    if (!logits || !lse || !workspace || !grad_logits) return PIKA_EINVAL;
+    return fused_backward(banded_call(mod, labels, ranges, frames_lengths, labels_lengths, B, T, U1, S, V, blank, stream),
+                          logits, lse, grad_costs, fastemit_lambda, workspace, grad_logits, out_dtype, ld_out);
+}
+
 }  // namespace
+
+// ---------------------------------------------------------------------------------------------
+// The C ABI (pika_rnnt.h): each entry is its checks, in the order and with the codes it has always had
+// (tests/golden/rnnt_abi_rejections.json), a Call and a body.
+// ---------------------------------------------------------------------------------------------
+extern "C" {
+
+int pika_amd_abi_version(void) { return 25; }
+
+// padded layout (B,T,U1,V)
+size_t pika_rnnt_workspace_bytes(int B, int T, int U1) {
+    if (check_lattice_dims(B, T, U1)) return 0;
+    return workspace_bytes(B, T, U1, false);
+}
+
+int pika_rnnt_loss_forward(const float *log_probs, const int *labels, const int *frames_lengths,
+                           const int *labels_lengths, int B, int T, int U1, int V, int blank,
+                           float *costs, void *workspace, void *stream) {
+    if (int rc = forward_args_ok(B, T, U1, V, blank, log_probs && frames_lengths && labels_lengths && costs && workspace, labels))
+        return rc;
+    return loss_forward(padded_call(labels, frames_lengths, labels_lengths, B, T, U1, V, blank, stream), log_probs, costs,
+                        workspace);
+}
 
 int pika_rnnt_loss_backward_fe(const int *labels, const int *frames_lengths, const int *labels_lengths,
                                int B, int T, int U1, int V, int blank, const float *grad_costs,
@@ -1871,13 +2063,8 @@ int pika_rnnt_loss_backward_fe(const int *labels, const int *frames_lengths, con
     if (int rc = check_dims(B, T, U1, V, blank)) return rc;
     if (!frames_lengths || !labels_lengths || !workspace) return PIKA_EINVAL;
     if (U1 > 1 && !labels) return PIKA_EINVAL;
-    float lscale;
-    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
-    launch_rowmeta(L, labels, frames_lengths, labels_lengths, B, T, U1, V, grad_costs, lscale, s);
-    if (!grads) return (int)hipGetLastError();   // row metadata only (pika_rnnt.h)
-    return write_dense_grads(L, (size_t)B * T * U1, V, blank, grads, s);
+    return loss_backward(padded_call(labels, frames_lengths, labels_lengths, B, T, U1, V, blank, stream), grad_costs,
+                         fastemit_lambda, workspace, grads);
 }
 
 int pika_rnnt_loss_backward(const int *labels, const int *frames_lengths, const int *labels_lengths,
@@ -1930,54 +2117,6 @@ int pika_rnnt_dlogits_compact_bf16(const float *log_probs, const float *lse, con
                                          ld_out, scale, colsum, nullptr, nullptr, 0, stream);
 }
 
-int pika_rnnt_fused_forward(const float *logits, const int *labels, const int *frames_lengths,
-                            const int *labels_lengths, int B, int T, int U1, int V, int blank, float *costs,
-                            float *lse, void *workspace, void *stream) {
-    long long rows;
-    if (int rc = forward_args_ok(B, T, U1, V, blank, logits && frames_lengths && labels_lengths && costs && lse && workspace &&
-                                 logits_ok(logits, V), labels, &rows))
-        return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Lattice L = carve(workspace, B, T, U1);
-    PIKA_CQ(V, hipLaunchKernelGGL(rnnt_lse_gather_kernel<CQ>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, labels,
-                                  frames_lengths, labels_lengths, rows, T, U1, V, blank, lse, L.lpb, L.lpe, L.Wp, L.D));
-    return finish_forward(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
-}
-
-int pika_rnnt_fused_forward_partials(const float *logits, const float *pmax, const float *psum, int n_part,
-                                     const int *labels, const int *frames_lengths, const int *labels_lengths, int B,
-                                     int T, int U1, int V, int blank, float *costs, float *lse, void *workspace,
-                                     void *stream) {
-    long long rows;
-    if (int rc = forward_args_ok(B, T, U1, V, blank, logits && pmax && psum && n_part > 0 && frames_lengths && labels_lengths &&
-                                 costs && lse && workspace, labels, &rows))
-        return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Lattice L = carve(workspace, B, T, U1);
-    hipLaunchKernelGGL(rnnt_lse_merge_gather_kernel<false>, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s, logits,
-                       pmax, psum, n_part, labels, frames_lengths, labels_lengths, rows, T, U1, V, blank, lse, L.lpb, L.lpe,
-                       L.Wp, L.D, static_cast<const _Float16 *>(nullptr), 0LL, static_cast<const float *>(nullptr),
-                       static_cast<const int *>(nullptr), 0);
-    return finish_forward(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
-}
-
-int pika_rnnt_fused_forward_gathered(const void *logits16, long long ld16, const float *gathered, const int *g_labels,
-                                     int g_blank, const float *pmax, const float *psum, int n_part, const int *labels,
-                                     const int *frames_lengths, const int *labels_lengths, int B, int T, int U1, int V,
-                                     int blank, float *costs, float *lse, void *workspace, void *stream) {
-    long long rows;
-    if (int rc = forward_args_ok(B, T, U1, V, blank, logits16 && ld16 >= V && gathered && pmax && psum && n_part > 0 &&
-                                 frames_lengths && labels_lengths && costs && lse && workspace, labels, &rows))
-        return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Lattice L = carve(workspace, B, T, U1);
-    hipLaunchKernelGGL(rnnt_lse_merge_gather_kernel<true>, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s,
-                       static_cast<const float *>(nullptr), pmax, psum, n_part, labels, frames_lengths, labels_lengths, rows,
-                       T, U1, V, blank, lse, L.lpb, L.lpe, L.Wp, L.D, static_cast<const _Float16 *>(logits16), ld16, gathered,
-                       g_labels, g_blank);
-    return finish_forward(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
-}
-
 int pika_rnnt_dlogits_compact_bf16_f16in(const void *logits16, long long ld_in, const float *lse, const void *workspace,
                                          int B, int T, int U1, int V, int blank, void *out, long long ld_out, float scale,
                                          float *colsum, const float *gathered, const int *g_labels, int g_blank,
@@ -1992,28 +2131,51 @@ int pika_rnnt_dlogits_compact_bf16_f16in(const void *logits16, long long ld_in, 
                                             blank, out, ld_out, scale, colsum, gathered, g_labels, g_blank, stream);
 }
 
-namespace {
-// d(logits) of the fused route over `rows` rows, from the row metadata in L
-int launch_dlogits_fused(const Lattice &L, const float *logits, const float *lse, long long rows, int V, int blank,
-                         void *grad_logits, int out_dtype, long long ld_out, hipStream_t s) {
-    const dim3 grid((unsigned)((rows + 3) / 4));
-    if (out_dtype == 0)
-        PIKA_CQ(ld_out, hipLaunchKernelGGL((rnnt_dlogits_fused_kernel<float, CQ>), grid, dim3(256), 0, s, logits, lse, L.meta,
-                                           static_cast<float *>(grad_logits), rows, V, ld_out, blank));
-    else
-        PIKA_CQ(ld_out, hipLaunchKernelGGL((rnnt_dlogits_fused_kernel<__bf16, CQ>), grid, dim3(256), 0, s, logits, lse, L.meta,
-                                           static_cast<__bf16 *>(grad_logits), rows, V, ld_out, blank));
-    return (int)hipGetLastError();
+int pika_rnnt_fused_forward(const float *logits, const int *labels, const int *frames_lengths,
+                            const int *labels_lengths, int B, int T, int U1, int V, int blank, float *costs,
+                            float *lse, void *workspace, void *stream) {
+    long long rows;
+    if (int rc = forward_args_ok(B, T, U1, V, blank, logits && frames_lengths && labels_lengths && costs && lse && workspace &&
+                                 logits_ok(logits, V), labels, &rows))
+        return rc;
+    return fused_forward(padded_call(labels, frames_lengths, labels_lengths, B, T, U1, V, blank, stream), logits, costs, lse,
+                         workspace);
 }
 
-// the d(logits) arguments of the fused backward calls
-int check_dlogits_out(const float *logits, int V, const void *grad_logits, int out_dtype, long long ld_out) {
-    if (!logits_ok(logits, V) || ld_out < V || (ld_out & 3) || ld_out > V_MAX) return PIKA_EINVAL;
-    if (out_dtype != 0 && out_dtype != 1) return PIKA_EINVAL;   // PIKA_F32 / PIKA_BF16 (pika_gemm.h)
-    if (reinterpret_cast<uintptr_t>(grad_logits) & (out_dtype == 0 ? 15 : 7)) return PIKA_EINVAL;
-    return PIKA_OK;
+// (the partials and gathered forwards: their own fill launch, the padded layout only)
+int pika_rnnt_fused_forward_partials(const float *logits, const float *pmax, const float *psum, int n_part,
+                                     const int *labels, const int *frames_lengths, const int *labels_lengths, int B,
+                                     int T, int U1, int V, int blank, float *costs, float *lse, void *workspace,
+                                     void *stream) {
+    long long rows;
+    if (int rc = forward_args_ok(B, T, U1, V, blank, logits && pmax && psum && n_part > 0 && frames_lengths && labels_lengths &&
+                                 costs && lse && workspace, labels, &rows))
+        return rc;
+    const Call c = padded_call(labels, frames_lengths, labels_lengths, B, T, U1, V, blank, stream);
+    const Lattice L = carve(workspace, B, T, U1);
+    hipLaunchKernelGGL(rnnt_lse_merge_gather_kernel<false>, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, c.s, logits,
+                       pmax, psum, n_part, labels, frames_lengths, labels_lengths, rows, T, U1, V, blank, lse, L.lpb, L.lpe,
+                       L.Wp, L.D, static_cast<const _Float16 *>(nullptr), 0LL, static_cast<const float *>(nullptr),
+                       static_cast<const int *>(nullptr), 0);
+    return finish_forward(c, L, costs);
 }
-}  // namespace
+
+int pika_rnnt_fused_forward_gathered(const void *logits16, long long ld16, const float *gathered, const int *g_labels,
+                                     int g_blank, const float *pmax, const float *psum, int n_part, const int *labels,
+                                     const int *frames_lengths, const int *labels_lengths, int B, int T, int U1, int V,
+                                     int blank, float *costs, float *lse, void *workspace, void *stream) {
+    long long rows;
+    if (int rc = forward_args_ok(B, T, U1, V, blank, logits16 && ld16 >= V && gathered && pmax && psum && n_part > 0 &&
+                                 frames_lengths && labels_lengths && costs && lse && workspace, labels, &rows))
+        return rc;
+    const Call c = padded_call(labels, frames_lengths, labels_lengths, B, T, U1, V, blank, stream);
+    const Lattice L = carve(workspace, B, T, U1);
+    hipLaunchKernelGGL(rnnt_lse_merge_gather_kernel<true>, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, c.s,
+                       static_cast<const float *>(nullptr), pmax, psum, n_part, labels, frames_lengths, labels_lengths, rows,
+                       T, U1, V, blank, lse, L.lpb, L.lpe, L.Wp, L.D, static_cast<const _Float16 *>(logits16), ld16, gathered,
+                       g_labels, g_blank);
+    return finish_forward(c, L, costs);
+}
 
 int pika_rnnt_fused_backward_fe(const float *logits, const float *lse, const int *labels,
                                 const int *frames_lengths, const int *labels_lengths, int B, int T, int U1, int V,
@@ -2022,15 +2184,8 @@ int pika_rnnt_fused_backward_fe(const float *logits, const float *lse, const int
     if (int rc = check_dims(B, T, U1, V, blank)) return rc;
     if (!logits || !lse || !frames_lengths || !labels_lengths || !workspace || !grad_logits) return PIKA_EINVAL;
     if (U1 > 1 && !labels) return PIKA_EINVAL;
-    if (int rc = check_dlogits_out(logits, V, grad_logits, out_dtype, ld_out)) return rc;
-    float lscale;
-    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
-    const long long rows = (long long)B * T * U1;
-    if (rows > ROWS_MAX) return PIKA_ETOOBIG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
-    launch_rowmeta(L, labels, frames_lengths, labels_lengths, B, T, U1, V, grad_costs, lscale, s);
-    return launch_dlogits_fused(L, logits, lse, rows, V, blank, grad_logits, out_dtype, ld_out, s);
+    return fused_backward(padded_call(labels, frames_lengths, labels_lengths, B, T, U1, V, blank, stream), logits, lse,
+                          grad_costs, fastemit_lambda, workspace, grad_logits, out_dtype, ld_out);
 }
 
 int pika_rnnt_fused_backward(const float *logits, const float *lse, const int *labels,
@@ -2041,10 +2196,7 @@ int pika_rnnt_fused_backward(const float *logits, const float *lse, const int *l
                                        workspace, grad_logits, out_dtype, ld_out, 0.0f, stream);
 }
 
-// ---------------------------------------------------------------------------------------------
-// packed layout (pika_rnnt.h): the lattice planes, alpha/beta and the workspace of a padded
-// (B, T_max, U1_max) batch; gather, row metadata and the row passes address the N packed rows
-// ---------------------------------------------------------------------------------------------
+// packed layout (N, V): the lattice planes, alpha/beta and the workspace of a padded (B, T_max, U1_max) batch
 int pika_rnnt_packed_forward(const float *log_probs, const int *labels, const int *frames_lengths,
                              const int *labels_lengths, const int *row_offsets, const int *label_offsets, int B,
                              int T_max, int U1_max, long long N, int V, int blank, float *costs, void *workspace,
@@ -2053,13 +2205,8 @@ int pika_rnnt_packed_forward(const float *log_probs, const int *labels, const in
                               label_offsets))
         return rc;
     if (!log_probs || !costs || !workspace) return PIKA_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Lattice L = carve(workspace, B, T_max, U1_max);
-    const dim3 grid((unsigned)((L.D + 4 * GATHER_ROWS - 1) / (4 * GATHER_ROWS)), (unsigned)(L.Wp / 64),
-                    (unsigned)B);
-    hipLaunchKernelGGL(rnnt_gather_kernel<PACKED>, grid, dim3(256), 0, s, log_probs, labels, frames_lengths,
-                       labels_lengths, B, T_max, U1_max, V, blank, L.lpb, L.lpe, L.Wp, L.D, row_offsets, label_offsets);
-    return finish_forward(L, frames_lengths, labels_lengths, costs, B, T_max, U1_max, s);
+    return loss_forward(packed_call(labels, frames_lengths, labels_lengths, row_offsets, label_offsets, B, T_max, U1_max, N, V,
+                                    blank, stream), log_probs, costs, workspace);
 }
 
 int pika_rnnt_packed_backward(const int *labels, const int *frames_lengths, const int *labels_lengths,
@@ -2070,14 +2217,8 @@ int pika_rnnt_packed_backward(const int *labels, const int *frames_lengths, cons
                               label_offsets))
         return rc;
     if (!workspace) return PIKA_EINVAL;
-    float lscale;
-    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Lattice L = carve(const_cast<void *>(workspace), B, T_max, U1_max);
-    launch_rowmeta_packed(L, labels, frames_lengths, labels_lengths, row_offsets, label_offsets, B, T_max, U1_max, N, V,
-                          grad_costs, lscale, s);
-    if (!grads) return (int)hipGetLastError();
-    return write_dense_grads(L, (size_t)N, V, blank, grads, s);
+    return loss_backward(packed_call(labels, frames_lengths, labels_lengths, row_offsets, label_offsets, B, T_max, U1_max, N, V,
+                                     blank, stream), grad_costs, fastemit_lambda, workspace, grads);
 }
 
 int pika_rnnt_packed_fused_forward(const float *logits, const int *labels, const int *frames_lengths,
@@ -2088,12 +2229,8 @@ int pika_rnnt_packed_fused_forward(const float *logits, const int *labels, const
                               label_offsets))
         return rc;
     if (!logits || !costs || !lse || !workspace || !logits_ok(logits, V)) return PIKA_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Lattice L = carve(workspace, B, T_max, U1_max);
-    PIKA_CQ(V, hipLaunchKernelGGL((rnnt_lse_gather_kernel<CQ, PACKED>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, logits,
-                                  labels, frames_lengths, labels_lengths, N, T_max, U1_max, V, blank, lse, L.lpb, L.lpe, L.Wp,
-                                  L.D, row_offsets, label_offsets, B));
-    return finish_forward(L, frames_lengths, labels_lengths, costs, B, T_max, U1_max, s);
+    return fused_forward(packed_call(labels, frames_lengths, labels_lengths, row_offsets, label_offsets, B, T_max, U1_max, N, V,
+                                     blank, stream), logits, costs, lse, workspace);
 }
 
 int pika_rnnt_packed_fused_backward(const float *logits, const float *lse, const int *labels,
@@ -2105,19 +2242,12 @@ int pika_rnnt_packed_fused_backward(const float *logits, const float *lse, const
                               label_offsets))
         return rc;
     if (!logits || !lse || !workspace || !grad_logits) return PIKA_EINVAL;
-    if (int rc = check_dlogits_out(logits, V, grad_logits, out_dtype, ld_out)) return rc;
-    float lscale;
-    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Lattice L = carve(const_cast<void *>(workspace), B, T_max, U1_max);
-    launch_rowmeta_packed(L, labels, frames_lengths, labels_lengths, row_offsets, label_offsets, B, T_max, U1_max, N, V,
-                          grad_costs, lscale, s);
-    return launch_dlogits_fused(L, logits, lse, N, V, blank, grad_logits, out_dtype, ld_out, s);
+    return fused_backward(packed_call(labels, frames_lengths, labels_lengths, row_offsets, label_offsets, B, T_max, U1_max, N,
+                                      V, blank, stream), logits, lse, grad_costs, fastemit_lambda, workspace, grad_logits,
+                          out_dtype, ld_out);
 }
 
-// ---------------------------------------------------------------------------------------------
-// forced alignment (pika_rnnt.h): Viterbi over the lpb / lpe planes any forward call left
-// ---------------------------------------------------------------------------------------------
+// forced alignment: Viterbi over the lpb / lpe planes any forward call of the regular topology left
 size_t pika_rnnt_align_scratch_bytes(int B, int T, int U1) {
     if (check_lattice_dims(B, T, U1)) return 0;
     return (size_t)B * (size_t)(T + U1 - 1) * (size_t)(lattice_width(U1) / 64) * sizeof(unsigned long long);
@@ -2139,254 +2269,95 @@ int pika_rnnt_align(const void *workspace, const int *frames_lengths, const int 
     return ok ? (int)hipGetLastError() : PIKA_ETOOBIG;
 }
 
-// ---------------------------------------------------------------------------------------------
-// pruned (banded) lattice (pika_rnnt.h): the planes, alpha/beta and the workspace of the padded (B, T, U1) batch; gather,
-// row metadata and the row passes address the B*T*S band rows
-// ---------------------------------------------------------------------------------------------
-namespace {
-// the banded calls' shared checks: (B, T, U1, V, blank) as check_dims, 1 <= S <= U1, the lengths, the band starts and --
-// when some utterance can have a label -- the labels; B*T*S rows index the row kernels as an int
-int check_banded(int B, int T, int U1, int S, int V, int blank, const int *labels, const int *ranges,
-                 const int *frames_lengths, const int *labels_lengths) {
-    if (V <= 0 || blank < 0 || blank >= V || B <= 0 || T <= 0 || U1 <= 0) return PIKA_EINVAL;
-    if (S < 1 || S > U1) return PIKA_EINVAL;
-    if (U1 > 1024) return PIKA_ETOOBIG;
-    if (!frames_lengths || !labels_lengths || !ranges || (U1 > 1 && !labels)) return PIKA_EINVAL;
-    if ((long long)B * T * S > ROWS_MAX) return PIKA_ETOOBIG;
-    return PIKA_OK;
-}
-
-void launch_rowmeta_banded(const Lattice &L, const int *labels, const int *Tn, const int *Un, const int *ranges, int B,
-                           int T, int U1, int S, int V, const float *grad_costs, float lscale, hipStream_t s) {
-    const size_t nrows = (size_t)B * T * S;
-    hipLaunchKernelGGL(rnnt_rowmeta_kernel<BANDED>, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s, labels, Tn, Un,
-                       B, T, U1, V, grad_costs, L.lpb, L.lpe, L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, L.meta,
-                       lscale, static_cast<const int *>(nullptr), static_cast<const int *>(nullptr), 0L, ranges, S);
-}
-}  // namespace
-
+// pruned (banded) lattice (B,T,S,V): the planes, alpha/beta and the workspace of the padded (B, T, U1) batch
 int pika_prnnt_forward(const float *log_probs, const int *frames_lengths, const int *labels_lengths, const int *labels,
                        const int *ranges, int B, int T, int U1, int S, int V, int blank, float *costs, void *workspace,
                        void *stream) {
-    if (int rc = check_banded(B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
-    if (!log_probs || !costs || !workspace) return PIKA_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Lattice L = carve(workspace, B, T, U1);
-    const dim3 grid((unsigned)((L.D + 4 * GATHER_ROWS - 1) / (4 * GATHER_ROWS)), (unsigned)(L.Wp / 64), (unsigned)B);
-    hipLaunchKernelGGL(rnnt_gather_kernel<BANDED>, grid, dim3(256), 0, s, log_probs, labels, frames_lengths, labels_lengths,
-                       B, T, U1, V, blank, L.lpb, L.lpe, L.Wp, L.D, static_cast<const int *>(nullptr),
-                       static_cast<const int *>(nullptr), ranges, S);
-    return finish_forward(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
+    return banded_forward(false, log_probs, frames_lengths, labels_lengths, labels, ranges, B, T, U1, S, V, blank, costs,
+                          workspace, stream);
 }
 
 int pika_prnnt_backward(const int *frames_lengths, const int *labels_lengths, const int *labels, const int *ranges, int B,
                         int T, int U1, int S, int V, int blank, const float *grad_costs, const void *workspace,
                         float *grads, float fastemit_lambda, void *stream) {
-    if (int rc = check_banded(B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
-    if (!workspace) return PIKA_EINVAL;
-    float lscale;
-    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
-    launch_rowmeta_banded(L, labels, frames_lengths, labels_lengths, ranges, B, T, U1, S, V, grad_costs, lscale, s);
-    if (!grads) return (int)hipGetLastError();
-    return write_dense_grads(L, (size_t)B * T * S, V, blank, grads, s);
+    return banded_backward(false, frames_lengths, labels_lengths, labels, ranges, B, T, U1, S, V, blank, grad_costs, workspace,
+                           grads, fastemit_lambda, stream);
 }
 
 int pika_prnnt_fused_forward(const float *logits, const int *frames_lengths, const int *labels_lengths, const int *labels,
                              const int *ranges, int B, int T, int U1, int S, int V, int blank, float *costs, float *lse,
                              void *workspace, void *stream) {
-    if (int rc = check_banded(B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
-    if (!logits || !costs || !lse || !workspace || !logits_ok(logits, V)) return PIKA_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Lattice L = carve(workspace, B, T, U1);
-    const size_t n4 = 2 * plane_elems(B, T, U1) / 4;     // lpb and lpe are adjacent; a plane is a multiple of 64 floats
-    hipLaunchKernelGGL(rnnt_fill_neg_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s,
-                       reinterpret_cast<v4f *>(L.lpb), n4);
-    const long long rows = (long long)B * T * S;
-    PIKA_CQ(V, hipLaunchKernelGGL((rnnt_lse_gather_kernel<CQ, BANDED>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,
-                                  logits, labels, frames_lengths, labels_lengths, rows, T, U1, V, blank, lse, L.lpb, L.lpe,
-                                  L.Wp, L.D, static_cast<const int *>(nullptr), static_cast<const int *>(nullptr), B, ranges,
-                                  S));
-    return finish_forward(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
+    return banded_fused_forward(false, logits, frames_lengths, labels_lengths, labels, ranges, B, T, U1, S, V, blank, costs,
+                                lse, workspace, stream);
 }
 
 int pika_prnnt_fused_backward(const float *logits, const float *lse, const int *frames_lengths, const int *labels_lengths,
                               const int *labels, const int *ranges, int B, int T, int U1, int S, int V, int blank,
                               const float *grad_costs, const void *workspace, void *grad_logits, int out_dtype,
                               long long ld_out, float fastemit_lambda, void *stream) {
-    if (int rc = check_banded(B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
-    if (!logits || !lse || !workspace || !grad_logits) return PIKA_EINVAL;
-    if (int rc = check_dlogits_out(logits, V, grad_logits, out_dtype, ld_out)) return rc;
-    float lscale;
-    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
-    launch_rowmeta_banded(L, labels, frames_lengths, labels_lengths, ranges, B, T, U1, S, V, grad_costs, lscale, s);
-    return launch_dlogits_fused(L, logits, lse, (long long)B * T * S, V, blank, grad_logits, out_dtype, ld_out, s);
+    return banded_fused_backward(false, logits, lse, frames_lengths, labels_lengths, labels, ranges, B, T, U1, S, V, blank,
+                                 grad_costs, workspace, grad_logits, out_dtype, ld_out, fastemit_lambda, stream);
 }
 
 int pika_prnnt_planes_forward(const float *blank_lp, const float *label_lp, const int *frames_lengths,
                               const int *labels_lengths, int B, int T, int U1, float *costs, float *blank_occ,
                               float *label_occ, void *workspace, void *stream) {
-    if (int rc = check_lattice_dims(B, T, U1)) return rc;
-    if (!blank_lp || !label_lp || !frames_lengths || !labels_lengths || !costs || !blank_occ || !label_occ || !workspace)
-        return PIKA_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Lattice L = carve(workspace, B, T, U1);
-    hipLaunchKernelGGL(rnnt_skew_planes_kernel<false>, dim3((unsigned)((L.D + 3) / 4), (unsigned)(L.Wp / 64), (unsigned)B), dim3(256),
-                       0, s, blank_lp, label_lp, frames_lengths, labels_lengths, T, U1, L.lpb, L.lpe, L.Wp, L.D);
-    if (int rc = finish_forward(L, frames_lengths, labels_lengths, costs, B, T, U1, s)) return rc;
-    const size_t cells = (size_t)B * T * U1;
-    hipLaunchKernelGGL(rnnt_occupancy_kernel<false>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, frames_lengths,
-                       labels_lengths, B, T, U1, L.lpb, L.lpe, L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, blank_occ,
-                       label_occ);
-    return (int)hipGetLastError();
+    return planes_forward<false>(blank_lp, label_lp, frames_lengths, labels_lengths, B, T, U1, costs, blank_occ, label_occ,
+                                 workspace, stream);
 }
 
 int pika_prnnt_prune_ranges(const float *blank_occ, const float *label_occ, const int *frames_lengths,
                             const int *labels_lengths, int B, int T, int U1, int S, int *ranges, void *stream) {
-    if (B <= 0 || T <= 0 || U1 <= 0 || S < 1 || S > U1) return PIKA_EINVAL;
-    if (U1 > 1024) return PIKA_ETOOBIG;
-    if (!blank_occ || !label_occ || !frames_lengths || !labels_lengths || !ranges) return PIKA_EINVAL;
-    hipLaunchKernelGGL(rnnt_prune_ranges_kernel, dim3((unsigned)B), dim3(PRUNE_THREADS), 0, static_cast<hipStream_t>(stream),
-                       blank_occ, label_occ, frames_lengths, labels_lengths, T, U1, S, S - 1, ranges);
-    return (int)hipGetLastError();
+    return prune_ranges(S - 1, blank_occ, label_occ, frames_lengths, labels_lengths, B, T, U1, S, ranges, stream);
 }
 
-// ---------------------------------------------------------------------------------------------
-// modified topology (pika_rnnt.h): un-skewed planes and their own alpha/beta over a workspace of
-// pika_prnnt_mod_workspace_bytes; the row metadata is the regular RowMeta, so the flat writer and the fused d(logits)
-// kernel run unchanged.  ranges == NULL: the padded (B, T, U1, V) layout (S must be U1); else the banded (B, T, S, V) one.
-// ---------------------------------------------------------------------------------------------
-namespace {
-int check_mod(int B, int T, int U1, int S, int V, int blank, const int *labels, const int *ranges, const int *frames_lengths,
-              const int *labels_lengths) {
-    static const int some = 0;  // a padded call has no ranges to test
-    if (int rc = check_banded(B, T, U1, S, V, blank, labels, ranges ? ranges : &some, frames_lengths, labels_lengths)) return rc;
-    return (!ranges && S != U1) ? PIKA_EINVAL : PIKA_OK;
-}
-
-void launch_rowmeta_mod(const Lattice &L, const int *labels, const int *Tn, const int *Un, const int *ranges, int B, int T,
-                        int U1, int S, int V, const float *grad_costs, float lscale, hipStream_t s) {
-    const size_t nrows = (size_t)B * T * S;
-    const dim3 grid((unsigned)((nrows + 255) / 256));
-    if (ranges)
-        hipLaunchKernelGGL((rnnt_rowmeta_kernel<BANDED, true>), grid, dim3(256), 0, s, labels, Tn, Un, B, T, U1, V, grad_costs,
-                           L.lpb, L.lpe, L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, L.meta, lscale,
-                           static_cast<const int *>(nullptr), static_cast<const int *>(nullptr), 0L, ranges, S);
-    else
-        hipLaunchKernelGGL((rnnt_rowmeta_kernel<PADDED, true>), grid, dim3(256), 0, s, labels, Tn, Un, B, T, U1, V, grad_costs,
-                           L.lpb, L.lpe, L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, L.meta, lscale,
-                           static_cast<const int *>(nullptr), static_cast<const int *>(nullptr), 0L,
-                           static_cast<const int *>(nullptr), 0);
-}
-}  // namespace
-
+// modified topology: un-skewed planes and their own alpha/beta over a workspace of pika_prnnt_mod_workspace_bytes; the row
+// metadata is the regular RowMeta, so the flat writer and the fused d(logits) kernel run unchanged.  ranges == NULL: the
+// padded (B, T, U1, V) layout (S must be U1); else the banded (B, T, S, V) one.
 size_t pika_prnnt_mod_workspace_bytes(int B, int T, int U1) {
     if (check_lattice_dims(B, T, U1)) return 0;
-    return workspace_bytes_mod(B, T, U1);
+    return workspace_bytes(B, T, U1, true);
 }
 
 int pika_prnnt_mod_forward(const float *log_probs, const int *frames_lengths, const int *labels_lengths, const int *labels,
                            const int *ranges, int B, int T, int U1, int S, int V, int blank, float *costs, void *workspace,
                            void *stream) {
-    if (int rc = check_mod(B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
-    if (!log_probs || !costs || !workspace) return PIKA_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const ModLattice L = carve_mod(workspace, B, T, U1);
-    const dim3 grid((unsigned)((L.D + 4 * GATHER_ROWS - 1) / (4 * GATHER_ROWS)), (unsigned)(L.Wp / 64), (unsigned)B);
-    if (ranges)
-        hipLaunchKernelGGL((rnnt_gather_kernel<BANDED, true>), grid, dim3(256), 0, s, log_probs, labels, frames_lengths,
-                           labels_lengths, B, T, U1, V, blank, L.lpb, L.lpe, L.Wp, L.D, static_cast<const int *>(nullptr),
-                           static_cast<const int *>(nullptr), ranges, S);
-    else
-        hipLaunchKernelGGL((rnnt_gather_kernel<PADDED, true>), grid, dim3(256), 0, s, log_probs, labels, frames_lengths,
-                           labels_lengths, B, T, U1, V, blank, L.lpb, L.lpe, L.Wp, L.D, static_cast<const int *>(nullptr),
-                           static_cast<const int *>(nullptr), static_cast<const int *>(nullptr), 0);
-    return finish_forward_mod(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
+    return banded_forward(true, log_probs, frames_lengths, labels_lengths, labels, ranges, B, T, U1, S, V, blank, costs,
+                          workspace, stream);
 }
 
 int pika_prnnt_mod_backward(const int *frames_lengths, const int *labels_lengths, const int *labels, const int *ranges, int B,
                             int T, int U1, int S, int V, int blank, const float *grad_costs, const void *workspace,
                             float *grads, float fastemit_lambda, void *stream) {
-    if (int rc = check_mod(B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
-    if (!workspace) return PIKA_EINVAL;
-    float lscale;
-    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const ModLattice L = carve_mod(const_cast<void *>(workspace), B, T, U1);
-    launch_rowmeta_mod(L, labels, frames_lengths, labels_lengths, ranges, B, T, U1, S, V, grad_costs, lscale, s);
-    if (!grads) return (int)hipGetLastError();
-    return write_dense_grads(L, (size_t)B * T * S, V, blank, grads, s);
+    return banded_backward(true, frames_lengths, labels_lengths, labels, ranges, B, T, U1, S, V, blank, grad_costs, workspace,
+                           grads, fastemit_lambda, stream);
 }
 
 int pika_prnnt_mod_fused_forward(const float *logits, const int *frames_lengths, const int *labels_lengths,
                                  const int *labels, const int *ranges, int B, int T, int U1, int S, int V, int blank,
                                  float *costs, float *lse, void *workspace, void *stream) {
-    if (int rc = check_mod(B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
-    if (!logits || !costs || !lse || !workspace || !logits_ok(logits, V)) return PIKA_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const ModLattice L = carve_mod(workspace, B, T, U1);
-    const long long rows = (long long)B * T * S;
-    const dim3 grid((unsigned)((rows + 3) / 4));
-    if (ranges) {
-        const size_t n4 = 2 * ((size_t)B * L.D * L.Wp) / 4;  // lpb and lpe are adjacent; a plane is a multiple of 64 floats
-        hipLaunchKernelGGL(rnnt_fill_neg_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s,
-                           reinterpret_cast<v4f *>(L.lpb), n4);
-        PIKA_CQ(V, hipLaunchKernelGGL((rnnt_lse_gather_kernel<CQ, BANDED, true>), grid, dim3(256), 0, s, logits, labels,
-                                      frames_lengths, labels_lengths, rows, T, U1, V, blank, lse, L.lpb, L.lpe, L.Wp, L.D,
-                                      static_cast<const int *>(nullptr), static_cast<const int *>(nullptr), B, ranges, S));
-    } else {
-        PIKA_CQ(V, hipLaunchKernelGGL((rnnt_lse_gather_kernel<CQ, PADDED, true>), grid, dim3(256), 0, s, logits, labels,
-                                      frames_lengths, labels_lengths, rows, T, U1, V, blank, lse, L.lpb, L.lpe, L.Wp, L.D,
-                                      static_cast<const int *>(nullptr), static_cast<const int *>(nullptr), B,
-                                      static_cast<const int *>(nullptr), 0));
-    }
-    return finish_forward_mod(L, frames_lengths, labels_lengths, costs, B, T, U1, s);
+    return banded_fused_forward(true, logits, frames_lengths, labels_lengths, labels, ranges, B, T, U1, S, V, blank, costs, lse,
+                                workspace, stream);
 }
 
 int pika_prnnt_mod_fused_backward(const float *logits, const float *lse, const int *frames_lengths,
                                   const int *labels_lengths, const int *labels, const int *ranges, int B, int T, int U1, int S,
                                   int V, int blank, const float *grad_costs, const void *workspace, void *grad_logits,
                                   int out_dtype, long long ld_out, float fastemit_lambda, void *stream) {
-    if (int rc = check_mod(B, T, U1, S, V, blank, labels, ranges, frames_lengths, labels_lengths)) return rc;
-    if (!logits || !lse || !workspace || !grad_logits) return PIKA_EINVAL;
-    if (int rc = check_dlogits_out(logits, V, grad_logits, out_dtype, ld_out)) return rc;
-    float lscale;
-    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const ModLattice L = carve_mod(const_cast<void *>(workspace), B, T, U1);
-    launch_rowmeta_mod(L, labels, frames_lengths, labels_lengths, ranges, B, T, U1, S, V, grad_costs, lscale, s);
-    return launch_dlogits_fused(L, logits, lse, (long long)B * T * S, V, blank, grad_logits, out_dtype, ld_out, s);
+    return banded_fused_backward(true, logits, lse, frames_lengths, labels_lengths, labels, ranges, B, T, U1, S, V, blank,
+                                 grad_costs, workspace, grad_logits, out_dtype, ld_out, fastemit_lambda, stream);
 }
 
 int pika_prnnt_mod_planes_forward(const float *blank_lp, const float *label_lp, const int *frames_lengths,
                                   const int *labels_lengths, int B, int T, int U1, float *costs, float *blank_occ,
                                   float *label_occ, void *workspace, void *stream) {
-    if (int rc = check_lattice_dims(B, T, U1)) return rc;
-    if (!blank_lp || !label_lp || !frames_lengths || !labels_lengths || !costs || !blank_occ || !label_occ || !workspace)
-        return PIKA_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const ModLattice L = carve_mod(workspace, B, T, U1);
-    hipLaunchKernelGGL(rnnt_skew_planes_kernel<true>, dim3((unsigned)((L.D + 3) / 4), (unsigned)(L.Wp / 64), (unsigned)B),
-                       dim3(256), 0, s, blank_lp, label_lp, frames_lengths, labels_lengths, T, U1, L.lpb, L.lpe, L.Wp, L.D);
-    if (int rc = finish_forward_mod(L, frames_lengths, labels_lengths, costs, B, T, U1, s)) return rc;
-    const size_t cells = (size_t)B * T * U1;
-    hipLaunchKernelGGL(rnnt_occupancy_kernel<true>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, frames_lengths,
-                       labels_lengths, B, T, U1, L.lpb, L.lpe, L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, blank_occ,
-                       label_occ);
-    return (int)hipGetLastError();
+    return planes_forward<true>(blank_lp, label_lp, frames_lengths, labels_lengths, B, T, U1, costs, blank_occ, label_occ,
+                                workspace, stream);
 }
 
 int pika_prnnt_mod_prune_ranges(const float *blank_occ, const float *label_occ, const int *frames_lengths,
                                 const int *labels_lengths, int B, int T, int U1, int S, int *ranges, void *stream) {
-    if (B <= 0 || T <= 0 || U1 <= 0 || S < 1 || S > U1) return PIKA_EINVAL;
-    if (U1 > 1024) return PIKA_ETOOBIG;
-    if (!blank_occ || !label_occ || !frames_lengths || !labels_lengths || !ranges) return PIKA_EINVAL;
-    hipLaunchKernelGGL(rnnt_prune_ranges_kernel, dim3((unsigned)B), dim3(PRUNE_THREADS), 0, static_cast<hipStream_t>(stream),
-                       blank_occ, label_occ, frames_lengths, labels_lengths, T, U1, S, 1, ranges);
-    return (int)hipGetLastError();
+    return prune_ranges(1, blank_occ, label_occ, frames_lengths, labels_lengths, B, T, U1, S, ranges, stream);
 }
 
 }  // extern "C"

@@ -465,56 +465,37 @@ def _fill_packed(x, labels, frames_lengths, labels_lengths, blank, caller=None, 
 
 
 class _PackedLossFn(torch.autograd.Function):
-    """RNN-T costs of a packed batch of log-probs (N, V); gradient (N, V)."""
+    """RNN-T costs of a packed batch (N, V) of log-probs or -- `caller`, the *_from_logits form's name -- of raw logits
+    (_FusedLogitsLossFn on the packed layout); gradient (N, V)."""
 
     @staticmethod
-    def forward(ctx, log_probs, labels, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0):
-        p, (lp, labels, frames_lengths, labels_lengths), costs, ws, _ = _fill_packed(
-            log_probs, labels, frames_lengths, labels_lengths, blank, loss=True)
-        ctx.save_for_backward(labels, frames_lengths, labels_lengths, ws, p.roff, p.loff)
-        ctx.dims = (p.B, p.T, p.U1, p.N, lp.shape[1], blank)
-        ctx.fastemit_lambda = fastemit_lambda
-        return costs
-
-    @staticmethod
-    def backward(ctx, grad_costs):
-        labels, frames_lengths, labels_lengths, ws, roff, loff = ctx.saved_tensors
-        B, T, U1, N, V, blank = ctx.dims
-        gc = grad_costs.to(torch.float32).contiguous()
-        with torch.cuda.device(ws.device):
-            grads = torch.empty((N, V), dtype=torch.float32, device=ws.device)
-            with _timed("bwd"):
-                _lib.check(_lib.lib().pika_rnnt_packed_backward(
-                    _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(roff), _ptr(loff), B, T, U1, N, V,
-                    blank, _ptr(gc), _ptr(ws), _ptr(grads), ctx.fastemit_lambda, _stream()), "pika_rnnt_packed_backward")
-        return grads, None, None, None, None, None
-
-
-class _PackedLogitsLossFn(torch.autograd.Function):
-    """_FusedLogitsLossFn on a packed batch of raw logits (N, V)."""
-
-    @staticmethod
-    def forward(ctx, logits, labels, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0):
+    def forward(ctx, x, labels, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0, caller=None):
         p, (x, labels, frames_lengths, labels_lengths), costs, ws, lse = _fill_packed(
-            logits, labels, frames_lengths, labels_lengths, blank, caller="rnnt_loss_from_logits", loss=True)
-        ctx.save_for_backward(x, labels, frames_lengths, labels_lengths, ws, lse, p.roff, p.loff)
+            x, labels, frames_lengths, labels_lengths, blank, caller=caller, loss=True)
+        # (log-probs are not kept: their gradient comes from the workspace alone; lse is None for them)
+        ctx.save_for_backward(labels, frames_lengths, labels_lengths, ws, p.roff, p.loff, x if caller else None, lse)
         ctx.dims = (p.B, p.T, p.U1, p.N, x.shape[1], blank)
         ctx.fastemit_lambda = fastemit_lambda
         return costs
 
     @staticmethod
     def backward(ctx, grad_costs):
-        x, labels, frames_lengths, labels_lengths, ws, lse, roff, loff = ctx.saved_tensors
+        labels, frames_lengths, labels_lengths, ws, roff, loff, x, lse = ctx.saved_tensors
         B, T, U1, N, V, blank = ctx.dims
         gc = grad_costs.to(torch.float32).contiguous()
-        with torch.cuda.device(x.device):
-            grads = torch.empty_like(x)
+        head = (_ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(roff), _ptr(loff), B, T, U1, N, V, blank,
+                _ptr(gc), _ptr(ws))
+        with torch.cuda.device(ws.device):
+            grads = torch.empty((N, V), dtype=torch.float32, device=ws.device)
             with _timed("bwd"):
-                _lib.check(_lib.lib().pika_rnnt_packed_fused_backward(
-                    _ptr(x), _ptr(lse), _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(roff), _ptr(loff),
-                    B, T, U1, N, V, blank, _ptr(gc), _ptr(ws), _ptr(grads), 0, V, ctx.fastemit_lambda, _stream()),
-                    "pika_rnnt_packed_fused_backward")
-        return grads, None, None, None, None, None
+                if x is None:
+                    _lib.check(_lib.lib().pika_rnnt_packed_backward(*head, _ptr(grads), ctx.fastemit_lambda, _stream()),
+                               "pika_rnnt_packed_backward")
+                else:
+                    _lib.check(_lib.lib().pika_rnnt_packed_fused_backward(
+                        _ptr(x), _ptr(lse), *head, _ptr(grads), 0, V, ctx.fastemit_lambda, _stream()),
+                        "pika_rnnt_packed_fused_backward")
+        return grads, None, None, None, None, None, None
 
 
 def rnnt_loss_from_logits(logits, labels, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0,
@@ -525,8 +506,9 @@ def rnnt_loss_from_logits(logits, labels, frames_lengths, labels_lengths, blank=
     fastemit_lambda: FastEmit (module docstring); d(logits) = g~ - softmax * sum(g~) with the scaled gradient g~.
     compact=True: packed raw logits (N, V) and labels (sum U_n,) as in `rnnt_loss`, one host sync."""
     lam = _check_lambda(fastemit_lambda)
-    fn = _PackedLogitsLossFn if compact else _FusedLogitsLossFn
-    return fn.apply(logits, labels, frames_lengths, labels_lengths, blank, lam)
+    if compact:
+        return _PackedLossFn.apply(logits, labels, frames_lengths, labels_lengths, blank, lam, "rnnt_loss_from_logits")
+    return _FusedLogitsLossFn.apply(logits, labels, frames_lengths, labels_lengths, blank, lam)
 
 
 def rnnt_loss(log_probs, labels, frames_lengths, labels_lengths, average_frames=False,
@@ -647,80 +629,90 @@ def _check_pruned(x, what, labels, ranges, frames_lengths, labels_lengths, blank
     return B, T, U1, S, V
 
 
-class _PrunedLossFn(torch.autograd.Function):
-    """RNN-T costs on the banded lattice from log-probs (B,T,S,V); dense gradient (B,T,S,V)."""
+def _check_full(x, what, labels, frames_lengths, labels_lengths, blank):
+    """`_check_pruned` for a call without ranges, on the full lattice (B,T,U+1,V): the band is every column, S = U + 1."""
+    _check_tensors(x, what, labels, frames_lengths, labels_lengths, " (there is no CPU path)")
+    if x.dim() != 4:
+        raise ValueError("%s must be (B,T,U+1,V), got %s" % (what, tuple(x.shape)))
+    B, T, U1, V = x.shape
+    if labels.dim() != 2 or labels.shape[0] != B or labels.shape[1] != U1 - 1:
+        raise ValueError("labels must be (B,U)=(%d,%d), got %s" % (B, U1 - 1, tuple(labels.shape)))
+    if frames_lengths.shape != (B,) or labels_lengths.shape != (B,):
+        raise ValueError("frames_lengths / labels_lengths must be (B,)")
+    if not 0 <= blank < V:
+        raise ValueError("blank=%d outside [0,%d)" % (blank, V))
+    if U1 > 1024:
+        raise ValueError("U+1=%d > 1024 not supported" % U1)
+    if B * T * U1 > 0x7fffffff:
+        raise ValueError("B*T*(U+1) = %d rows > 2^31 - 1" % (B * T * U1))
+    return B, T, U1, U1, V
+
+
+# (modified, logits) -> the forward and the backward entry of the (B,T,S,V) / (B,T,U1,V) calls and their workspace size
+_BANDED_ENTRIES = {
+    (False, False): ("pika_prnnt_forward", "pika_prnnt_backward", "pika_rnnt_workspace_bytes"),
+    (False, True): ("pika_prnnt_fused_forward", "pika_prnnt_fused_backward", "pika_rnnt_workspace_bytes"),
+    (True, False): ("pika_prnnt_mod_forward", "pika_prnnt_mod_backward", "pika_prnnt_mod_workspace_bytes"),
+    (True, True): ("pika_prnnt_mod_fused_forward", "pika_prnnt_mod_fused_backward", "pika_prnnt_mod_workspace_bytes"),
+}
+
+
+class _BandedLossFn(torch.autograd.Function):
+    """RNN-T costs from log-probs or raw logits (`logits`: no log-prob tensor, d(logits) out), in the regular or the
+    `modified` topology, on the band (B,T,S,V) of `ranges` or -- ranges None, the modified topology only -- on the full
+    lattice (B,T,U1,V); the gradient is dense and has the input's shape."""
 
     @staticmethod
-    def forward(ctx, log_probs, labels, ranges, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0):
-        B, T, U1, S, V = _check_pruned(log_probs, "log_probs", labels, ranges, frames_lengths, labels_lengths, blank)
+    def forward(ctx, x, labels, ranges, frames_lengths, labels_lengths, blank, fastemit_lambda, logits, caller, modified):
+        what = "logits" if logits else "log_probs"
+        if ranges is None:
+            B, T, U1, S, V = _check_full(x, what, labels, frames_lengths, labels_lengths, blank)
+        else:
+            B, T, U1, S, V = _check_pruned(x, what, labels, ranges, frames_lengths, labels_lengths, blank)
+            ranges = ranges.contiguous()
+        if logits and not _fused_v_ok(V):
+            raise ValueError("%s: V = %d must be a multiple of 4 and <= %d" % (caller, V, MAX_FUSED_V))
         lib = _lib.lib()
-        x = log_probs.detach().contiguous()
-        labels, ranges, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, ranges, frames_lengths,
-                                                                                   labels_lengths))
+        fwd, ctx.bwd, ws_bytes = _BANDED_ENTRIES[modified, logits]
+        x = x.detach().contiguous()
+        labels, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, frames_lengths, labels_lengths))
         with torch.cuda.device(x.device):
             costs = torch.empty(B, dtype=torch.float32, device=x.device)
-            ws = torch.empty(lib.pika_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8, device=x.device)
+            lse = torch.empty(B * T * S, dtype=torch.float32, device=x.device) if logits else None
+            ws = torch.empty(getattr(lib, ws_bytes)(B, T, U1), dtype=torch.uint8, device=x.device)
             with _timed("fwd"):
-                _lib.check(lib.pika_prnnt_forward(_ptr(x), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(labels),
-                                                  _ptr(ranges), B, T, U1, S, V, blank, _ptr(costs), _ptr(ws), _stream()),
-                           "pika_prnnt_forward")
-        ctx.save_for_backward(labels, ranges, frames_lengths, labels_lengths, ws)
+                _lib.check(getattr(lib, fwd)(_ptr(x), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(labels), _ptr(ranges),
+                                             B, T, U1, S, V, blank, _ptr(costs), *((_ptr(lse),) if logits else ()), _ptr(ws),
+                                             _stream()), fwd)
+        # (ranges None on the full lattice; log-probs are not kept: their gradient comes from the workspace alone)
+        ctx.save_for_backward(labels, ranges, frames_lengths, labels_lengths, ws, x if logits else None, lse)
         ctx.dims = (B, T, U1, S, V, blank)
         ctx.fastemit_lambda = fastemit_lambda
+        ctx.shape = tuple(x.shape)
         return costs
 
     @staticmethod
     def backward(ctx, grad_costs):
-        labels, ranges, frames_lengths, labels_lengths, ws = ctx.saved_tensors
+        labels, ranges, frames_lengths, labels_lengths, ws, x, lse = ctx.saved_tensors
         B, T, U1, S, V, blank = ctx.dims
         gc = grad_costs.to(torch.float32).contiguous()
         with torch.cuda.device(ws.device):
-            grads = torch.empty((B, T, S, V), dtype=torch.float32, device=ws.device)
+            grads = torch.empty(ctx.shape, dtype=torch.float32, device=ws.device)
             with _timed("bwd"):
-                _lib.check(_lib.lib().pika_prnnt_backward(
-                    _ptr(frames_lengths), _ptr(labels_lengths), _ptr(labels), _ptr(ranges), B, T, U1, S, V, blank, _ptr(gc),
-                    _ptr(ws), _ptr(grads), ctx.fastemit_lambda, _stream()), "pika_prnnt_backward")
-        return grads, None, None, None, None, None, None
+                _lib.check(getattr(_lib.lib(), ctx.bwd)(
+                    *((_ptr(x), _ptr(lse)) if x is not None else ()), _ptr(frames_lengths), _ptr(labels_lengths),
+                    _ptr(labels), _ptr(ranges), B, T, U1, S, V, blank, _ptr(gc), _ptr(ws), _ptr(grads),
+                    *((0, V) if x is not None else ()), ctx.fastemit_lambda, _stream()), ctx.bwd)
+        return (grads,) + (None,) * 9
 
 
-class _PrunedLogitsLossFn(torch.autograd.Function):
-    """_FusedLogitsLossFn on the banded lattice: raw logits (B,T,S,V) in, d(logits) out, no log-prob tensor."""
-
-    @staticmethod
-    def forward(ctx, logits, labels, ranges, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0):
-        B, T, U1, S, V = _check_pruned(logits, "logits", labels, ranges, frames_lengths, labels_lengths, blank)
-        if not _fused_v_ok(V):
-            raise ValueError("rnnt_loss_pruned_from_logits: V = %d must be a multiple of 4 and <= %d" % (V, MAX_FUSED_V))
-        lib = _lib.lib()
-        x = logits.detach().contiguous()
-        labels, ranges, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, ranges, frames_lengths,
-                                                                                   labels_lengths))
-        with torch.cuda.device(x.device):
-            costs = torch.empty(B, dtype=torch.float32, device=x.device)
-            lse = torch.empty(B * T * S, dtype=torch.float32, device=x.device)
-            ws = torch.empty(lib.pika_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8, device=x.device)
-            with _timed("fwd"):
-                _lib.check(lib.pika_prnnt_fused_forward(_ptr(x), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(labels),
-                                                        _ptr(ranges), B, T, U1, S, V, blank, _ptr(costs), _ptr(lse),
-                                                        _ptr(ws), _stream()), "pika_prnnt_fused_forward")
-        ctx.save_for_backward(x, labels, ranges, frames_lengths, labels_lengths, ws, lse)
-        ctx.dims = (B, T, U1, S, V, blank)
-        ctx.fastemit_lambda = fastemit_lambda
-        return costs
-
-    @staticmethod
-    def backward(ctx, grad_costs):
-        x, labels, ranges, frames_lengths, labels_lengths, ws, lse = ctx.saved_tensors
-        B, T, U1, S, V, blank = ctx.dims
-        gc = grad_costs.to(torch.float32).contiguous()
-        with torch.cuda.device(x.device):
-            grads = torch.empty_like(x)
-            with _timed("bwd"):
-                _lib.check(_lib.lib().pika_prnnt_fused_backward(
-                    _ptr(x), _ptr(lse), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(labels), _ptr(ranges), B, T, U1, S,
-                    V, blank, _ptr(gc), _ptr(ws), _ptr(grads), 0, V, ctx.fastemit_lambda, _stream()),
-                    "pika_prnnt_fused_backward")
-        return grads, None, None, None, None, None, None
+def _banded_loss(x, labels, ranges, frames_lengths, labels_lengths, average_frames, reduction, blank, fastemit_lambda,
+                 logits, caller, modified):
+    lam = _check_lambda(fastemit_lambda)
+    if modified:
+        blank = int(blank)
+    costs = _BandedLossFn.apply(x, labels, ranges, frames_lengths, labels_lengths, blank, lam, logits, caller, modified)
+    return _reduce(costs, frames_lengths, average_frames, reduction)
 
 
 def rnnt_loss_pruned(log_probs, labels, ranges, frames_lengths, labels_lengths, average_frames=False, reduction=None,
@@ -732,18 +724,16 @@ def rnnt_loss_pruned(log_probs, labels, ranges, frames_lengths, labels_lengths, 
     the band carry probability: the cost is that of `rnnt_loss` on a (B, T, U+1, V) tensor holding the band's rows at
     their cells and -1e30 elsewhere.  The gradient is dense (B, T, S, V); rows past T_n or U_n are zero.  With S = U + 1
     and all-zero ranges this is `rnnt_loss`, bit for bit.  Keywords as in `rnnt_loss`; no host synchronisation."""
-    lam = _check_lambda(fastemit_lambda)
-    costs = _PrunedLossFn.apply(log_probs, labels, ranges, frames_lengths, labels_lengths, blank, lam)
-    return _reduce(costs, frames_lengths, average_frames, reduction)
+    return _banded_loss(log_probs, labels, ranges, frames_lengths, labels_lengths, average_frames, reduction, blank,
+                        fastemit_lambda, False, "rnnt_loss_pruned", False)
 
 
 def rnnt_loss_pruned_from_logits(logits, labels, ranges, frames_lengths, labels_lengths, average_frames=False,
                                  reduction=None, blank=0, fastemit_lambda=0.0):
     """`rnnt_loss_pruned` of log_softmax(logits) for raw logits (B, T, S, V), V % 4 == 0 and V <= 8192, differentiable
     w.r.t. the logits: the log-probabilities and their dense gradient never exist."""
-    lam = _check_lambda(fastemit_lambda)
-    costs = _PrunedLogitsLossFn.apply(logits, labels, ranges, frames_lengths, labels_lengths, blank, lam)
-    return _reduce(costs, frames_lengths, average_frames, reduction)
+    return _banded_loss(logits, labels, ranges, frames_lengths, labels_lengths, average_frames, reduction, blank,
+                        fastemit_lambda, True, "rnnt_loss_pruned_from_logits", False)
 
 
 def _check_planes(a, b, frames_lengths, labels_lengths, names):
@@ -768,22 +758,24 @@ def _check_planes(a, b, frames_lengths, labels_lengths, names):
 
 
 class _PlanesLossFn(torch.autograd.Function):
-    """RNN-T costs of a lattice given by its blank and label planes; also returns the two occupancy planes (detached)."""
+    """RNN-T costs of a lattice given by its blank and label planes, in the regular or the `modified` topology; also
+    returns the two occupancy planes (detached)."""
 
     @staticmethod
-    def forward(ctx, blank_lp, label_lp, frames_lengths, labels_lengths):
+    def forward(ctx, blank_lp, label_lp, frames_lengths, labels_lengths, modified=False):
         B, T, U1 = _check_planes(blank_lp, label_lp, frames_lengths, labels_lengths, ("blank_lp", "label_lp"))
         lib = _lib.lib()
+        fn, ws_bytes = (("pika_prnnt_mod_planes_forward", "pika_prnnt_mod_workspace_bytes") if modified else
+                        ("pika_prnnt_planes_forward", "pika_rnnt_workspace_bytes"))
         pb, pl = blank_lp.detach().contiguous(), label_lp.detach().contiguous()
         frames_lengths, labels_lengths = frames_lengths.contiguous(), labels_lengths.contiguous()
         with torch.cuda.device(pb.device):
             costs = torch.empty(B, dtype=torch.float32, device=pb.device)
             occ_b, occ_l = torch.empty_like(pb), torch.empty_like(pb)
-            ws = torch.empty(lib.pika_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8, device=pb.device)
+            ws = torch.empty(getattr(lib, ws_bytes)(B, T, U1), dtype=torch.uint8, device=pb.device)
             with _timed(None):
-                _lib.check(lib.pika_prnnt_planes_forward(_ptr(pb), _ptr(pl), _ptr(frames_lengths), _ptr(labels_lengths), B, T,
-                                                         U1, _ptr(costs), _ptr(occ_b), _ptr(occ_l), _ptr(ws), _stream()),
-                           "pika_prnnt_planes_forward")
+                _lib.check(getattr(lib, fn)(_ptr(pb), _ptr(pl), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1,
+                                            _ptr(costs), _ptr(occ_b), _ptr(occ_l), _ptr(ws), _stream()), fn)
         ctx.save_for_backward(occ_b, occ_l)
         ctx.mark_non_differentiable(occ_b, occ_l)
         return costs, occ_b, occ_l
@@ -792,7 +784,7 @@ class _PlanesLossFn(torch.autograd.Function):
     def backward(ctx, grad_costs, _gb, _gl):
         occ_b, occ_l = ctx.saved_tensors
         g = -grad_costs.to(torch.float32).view(-1, 1, 1)
-        return occ_b * g, occ_l * g, None, None
+        return occ_b * g, occ_l * g, None, None, None
 
 
 def rnnt_loss_from_planes(blank_lp, label_lp, frames_lengths, labels_lengths, reduction=None, return_occupancy=False):
@@ -815,6 +807,11 @@ def rnnt_prune_ranges(blank_occ, label_occ, frames_lengths, labels_lengths, s_ra
     minimum, f(0) = 0, f(t) = min(m(t), f(t-1) + S - 1), and s_t = max(f(t), s_max - (T_n - 1 - t)(S - 1)); s_max for
     t >= T_n.  The band connects (0, 0) with (T_n - 1, U_n) -- s_0 = 0, s_{T_n-1} = s_max, steps in [0, S-1] -- whenever
     (T_n - 1)(S - 1) >= s_max; otherwise none of that width does and s_0 > 0."""
+    return _prune_ranges("pika_prnnt_prune_ranges", blank_occ, label_occ, frames_lengths, labels_lengths, s_range)
+
+
+def _prune_ranges(entry, blank_occ, label_occ, frames_lengths, labels_lengths, s_range):
+    # the band search of either topology: `entry` is pika_prnnt_prune_ranges or pika_prnnt_mod_prune_ranges
     S = int(s_range)
     B, T, U1 = _check_planes(blank_occ, label_occ, frames_lengths, labels_lengths, ("blank_occ", "label_occ"))
     if not 1 <= S <= U1:
@@ -823,8 +820,8 @@ def rnnt_prune_ranges(blank_occ, label_occ, frames_lengths, labels_lengths, s_ra
     frames_lengths, labels_lengths = frames_lengths.contiguous(), labels_lengths.contiguous()
     with torch.cuda.device(ob.device):
         ranges = torch.empty((B, T), dtype=torch.int32, device=ob.device)
-        _lib.check(_lib.lib().pika_prnnt_prune_ranges(_ptr(ob), _ptr(ol), _ptr(frames_lengths), _ptr(labels_lengths), B, T,
-                                                      U1, S, _ptr(ranges), _stream()), "pika_prnnt_prune_ranges")
+        _lib.check(getattr(_lib.lib(), entry)(_ptr(ob), _ptr(ol), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, S,
+                                              _ptr(ranges), _stream()), entry)
     return ranges
 
 
@@ -1107,86 +1104,13 @@ def rnnt_pruned_joint_loss_smoothed(enc, pred, labels, frames_lengths, labels_le
 # ---------------------------------------------------------------------------------------------------------------------
 # Modified topology (k2's rnnt_loss / rnnt_loss_pruned with modified=True; include/pika_rnnt.h "Modified topology"): every
 # frame emits exactly one symbol, the label edge runs (t, u) -> (t+1, u+1).  The same surface as the regular functions
-# above, name for name with a `_modified` in it, over the pika_prnnt_mod_* entries; feasible iff U_n <= T_n, an utterance
-# without a path costs +inf and has a zero gradient.  Nothing reads a length on the host.
+# above, name for name with a `_modified` in it, over the same classes and the pika_prnnt_mod_* entries; feasible iff
+# U_n <= T_n, an utterance without a path costs +inf and has a zero gradient.  Nothing reads a length on the host.
 # ---------------------------------------------------------------------------------------------------------------------
-class _ModifiedLossFn(torch.autograd.Function):
-    """Modified-topology costs from log-probs or raw logits (`logits`), on the band (B,T,S,V) of `ranges` or -- ranges None
-    -- on the full lattice (B,T,U1,V); the gradient has the input's shape."""
-
-    @staticmethod
-    def forward(ctx, x, labels, ranges, frames_lengths, labels_lengths, blank, fastemit_lambda, logits, caller):
-        what = "logits" if logits else "log_probs"
-        if ranges is None:
-            _check_tensors(x, what, labels, frames_lengths, labels_lengths, " (there is no CPU path)")
-            if x.dim() != 4:
-                raise ValueError("%s must be (B,T,U+1,V), got %s" % (what, tuple(x.shape)))
-            B, T, U1, V = x.shape
-            S = U1
-            if labels.dim() != 2 or labels.shape[0] != B or labels.shape[1] != U1 - 1:
-                raise ValueError("labels must be (B,U)=(%d,%d), got %s" % (B, U1 - 1, tuple(labels.shape)))
-            if frames_lengths.shape != (B,) or labels_lengths.shape != (B,):
-                raise ValueError("frames_lengths / labels_lengths must be (B,)")
-            if not 0 <= blank < V:
-                raise ValueError("blank=%d outside [0,%d)" % (blank, V))
-            if U1 > 1024:
-                raise ValueError("U+1=%d > 1024 not supported" % U1)
-            if B * T * U1 > 0x7fffffff:
-                raise ValueError("B*T*(U+1) = %d rows > 2^31 - 1" % (B * T * U1))
-        else:
-            B, T, U1, S, V = _check_pruned(x, what, labels, ranges, frames_lengths, labels_lengths, blank)
-            ranges = ranges.contiguous()
-        if logits and not _fused_v_ok(V):
-            raise ValueError("%s: V = %d must be a multiple of 4 and <= %d" % (caller, V, MAX_FUSED_V))
-        lib = _lib.lib()
-        x = x.detach().contiguous()
-        labels, frames_lengths, labels_lengths = (t.contiguous() for t in (labels, frames_lengths, labels_lengths))
-        with torch.cuda.device(x.device):
-            costs = torch.empty(B, dtype=torch.float32, device=x.device)
-            ws = torch.empty(lib.pika_prnnt_mod_workspace_bytes(B, T, U1), dtype=torch.uint8, device=x.device)
-            head = (_ptr(x), _ptr(frames_lengths), _ptr(labels_lengths), _ptr(labels), _ptr(ranges), B, T, U1, S, V, blank,
-                    _ptr(costs))
-            with _timed("fwd"):
-                if logits:
-                    lse = torch.empty(B * T * S, dtype=torch.float32, device=x.device)
-                    _lib.check(lib.pika_prnnt_mod_fused_forward(*head, _ptr(lse), _ptr(ws), _stream()),
-                               "pika_prnnt_mod_fused_forward")
-                else:
-                    lse = None
-                    _lib.check(lib.pika_prnnt_mod_forward(*head, _ptr(ws), _stream()), "pika_prnnt_mod_forward")
-        ctx.save_for_backward(labels, frames_lengths, labels_lengths, ws, *((x, lse) if logits else ()))
-        ctx.ranges = ranges          # (not a differentiable input; None on the full lattice)
-        ctx.dims = (B, T, U1, S, V, blank)
-        ctx.fastemit_lambda = fastemit_lambda
-        ctx.shape = tuple(x.shape)
-        return costs
-
-    @staticmethod
-    def backward(ctx, grad_costs):
-        labels, frames_lengths, labels_lengths, ws = ctx.saved_tensors[:4]
-        B, T, U1, S, V, blank = ctx.dims
-        gc = grad_costs.to(torch.float32).contiguous()
-        tail = (_ptr(frames_lengths), _ptr(labels_lengths), _ptr(labels), _ptr(ctx.ranges), B, T, U1, S, V, blank, _ptr(gc),
-                _ptr(ws))
-        with torch.cuda.device(ws.device):
-            grads = torch.empty(ctx.shape, dtype=torch.float32, device=ws.device)
-            with _timed("bwd"):
-                if len(ctx.saved_tensors) > 4:
-                    x, lse = ctx.saved_tensors[4:]
-                    _lib.check(_lib.lib().pika_prnnt_mod_fused_backward(_ptr(x), _ptr(lse), *tail, _ptr(grads), 0, V,
-                                                                        ctx.fastemit_lambda, _stream()),
-                               "pika_prnnt_mod_fused_backward")
-                else:
-                    _lib.check(_lib.lib().pika_prnnt_mod_backward(*tail, _ptr(grads), ctx.fastemit_lambda, _stream()),
-                               "pika_prnnt_mod_backward")
-        return (grads,) + (None,) * 8
-
-
 def _modified_loss(x, labels, ranges, frames_lengths, labels_lengths, average_frames, reduction, blank, fastemit_lambda,
                    logits, caller):
-    lam = _check_lambda(fastemit_lambda)
-    costs = _ModifiedLossFn.apply(x, labels, ranges, frames_lengths, labels_lengths, int(blank), lam, logits, caller)
-    return _reduce(costs, frames_lengths, average_frames, reduction)
+    return _banded_loss(x, labels, ranges, frames_lengths, labels_lengths, average_frames, reduction, blank,
+                        fastemit_lambda, logits, caller, True)
 
 
 def rnnt_loss_modified(log_probs, labels, frames_lengths, labels_lengths, average_frames=False, reduction=None, blank=0,
@@ -1228,41 +1152,13 @@ def rnnt_loss_pruned_modified_from_logits(logits, labels, ranges, frames_lengths
                           fastemit_lambda, True, "rnnt_loss_pruned_modified_from_logits")
 
 
-class _ModifiedPlanesLossFn(torch.autograd.Function):
-    """`_PlanesLossFn` in the modified topology."""
-
-    @staticmethod
-    def forward(ctx, blank_lp, label_lp, frames_lengths, labels_lengths):
-        B, T, U1 = _check_planes(blank_lp, label_lp, frames_lengths, labels_lengths, ("blank_lp", "label_lp"))
-        lib = _lib.lib()
-        pb, pl = blank_lp.detach().contiguous(), label_lp.detach().contiguous()
-        frames_lengths, labels_lengths = frames_lengths.contiguous(), labels_lengths.contiguous()
-        with torch.cuda.device(pb.device):
-            costs = torch.empty(B, dtype=torch.float32, device=pb.device)
-            occ_b, occ_l = torch.empty_like(pb), torch.empty_like(pb)
-            ws = torch.empty(lib.pika_prnnt_mod_workspace_bytes(B, T, U1), dtype=torch.uint8, device=pb.device)
-            with _timed(None):
-                _lib.check(lib.pika_prnnt_mod_planes_forward(_ptr(pb), _ptr(pl), _ptr(frames_lengths), _ptr(labels_lengths),
-                                                             B, T, U1, _ptr(costs), _ptr(occ_b), _ptr(occ_l), _ptr(ws),
-                                                             _stream()), "pika_prnnt_mod_planes_forward")
-        ctx.save_for_backward(occ_b, occ_l)
-        ctx.mark_non_differentiable(occ_b, occ_l)
-        return costs, occ_b, occ_l
-
-    @staticmethod
-    def backward(ctx, grad_costs, _gb, _gl):
-        occ_b, occ_l = ctx.saved_tensors
-        g = -grad_costs.to(torch.float32).view(-1, 1, 1)
-        return occ_b * g, occ_l * g, None, None
-
-
 def rnnt_loss_from_planes_modified(blank_lp, label_lp, frames_lengths, labels_lengths, reduction=None,
                                    return_occupancy=False):
     """`rnnt_loss_from_planes` in the modified topology: blank_lp[b, t, u] is the edge (t, u) -> (t+1, u), label_lp[b, t, u]
     the edge (t, u) -> (t+1, u+1), ll = alpha(T_n, U_n).  The planes of `rnnt_simple_planes` / `rnnt_smoothed_planes` are
     topology-independent and are what this takes.  An utterance with U_n > T_n costs +inf; its gradient and occupancies
     are zero."""
-    costs, occ_b, occ_l = _ModifiedPlanesLossFn.apply(blank_lp, label_lp, frames_lengths, labels_lengths)
+    costs, occ_b, occ_l = _PlanesLossFn.apply(blank_lp, label_lp, frames_lengths, labels_lengths, True)
     costs = _reduce(costs, frames_lengths, False, reduction)
     return (costs, occ_b, occ_l) if return_occupancy else costs
 
@@ -1273,17 +1169,7 @@ def rnnt_prune_ranges_modified(blank_occ, label_occ, frames_lengths, labels_leng
     raw and m as in `rnnt_prune_ranges`; f(0) = 0, f(t) = min(m(t), f(t-1) + 1), s_t = max(f(t), s_max - (T_n - 1 - t));
     s_max for t >= T_n.  s_0 = 0, 0 <= s_{t+1} - s_t <= 1 and s_{T_n-1} = s_max whenever T_n - 1 >= s_max (otherwise
     s_0 > 0); such a band holds the path u_t = min(t, s_t + S - 1) whenever U_n <= T_n."""
-    S = int(s_range)
-    B, T, U1 = _check_planes(blank_occ, label_occ, frames_lengths, labels_lengths, ("blank_occ", "label_occ"))
-    if not 1 <= S <= U1:
-        raise ValueError("s_range=%d must be in [1, U+1=%d]" % (S, U1))
-    ob, ol = blank_occ.detach().contiguous(), label_occ.detach().contiguous()
-    frames_lengths, labels_lengths = frames_lengths.contiguous(), labels_lengths.contiguous()
-    with torch.cuda.device(ob.device):
-        ranges = torch.empty((B, T), dtype=torch.int32, device=ob.device)
-        _lib.check(_lib.lib().pika_prnnt_mod_prune_ranges(_ptr(ob), _ptr(ol), _ptr(frames_lengths), _ptr(labels_lengths), B,
-                                                          T, U1, S, _ptr(ranges), _stream()), "pika_prnnt_mod_prune_ranges")
-    return ranges
+    return _prune_ranges("pika_prnnt_mod_prune_ranges", blank_occ, label_occ, frames_lengths, labels_lengths, s_range)
 
 
 def rnnt_pruned_joint_loss_modified(enc, pred, labels, frames_lengths, labels_lengths, fc1, fc_gate, fc2, simple_am,

@@ -102,6 +102,9 @@ def source_instantiations():
     fused = set(re.findall(r"rnnt_dlogits_fused_kernel<(\w+), CQ>", src))
     merge = set(re.findall(r"rnnt_lse_merge_gather_kernel<(true|false)>", src))
     assert "rnnt_lse_gather_kernel<CQ>" in src
+    # one launch site for every layout; the padded layout of the regular topology -- the routes' -- is in its list
+    assert len(re.findall(r"hipLaunchKernelGGL\(\(rnnt_lse_gather_kernel<CQ, P::layout, P::mod>\),", src)) == 1
+    assert len(re.findall(r"hipLaunchKernelGGL\(\(?rnnt_lse_gather_kernel<", src)) == 1 and "LayoutOf<PADDED, false>{}" in src
     names = {R.AB(w) for w in waves}
     names |= {R.LG(c) for c in cq}
     names |= {"rnnt_lse_merge_gather_kernel<%s>" % m for m in merge}

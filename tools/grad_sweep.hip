@@ -318,7 +318,7 @@ int main(int argc, char **argv) {
     // reported and left out of the timing
     {
         // make the lattice non-trivial: alpha/beta planes = small pseudo-random values
-        std::vector<float> h(4 * plane_elems(B, T, U1));
+        std::vector<float> h(4 * plane_elems(B, T, U1, false));
         for (size_t i = 0; i < h.size(); ++i) h[i] = -0.001f * (float)((i * 2654435761u) % 4096);
         CK(hipMemcpy(ws, h.data(), h.size() * 4, hipMemcpyHostToDevice));
         float *ref; CK(hipMalloc(&ref, (n + 64) * 4));
