@@ -79,6 +79,9 @@ _RNNT_EXPORTS = ("rnnt_loss_pruned", "rnnt_loss_pruned_from_logits", "rnnt_loss_
 # The joint network on the band (pika_amd/model/ops.py).
 _OPS_EXPORTS = ("joint_pruned",)
 
+# The one-symbol-per-frame beam search (pika_amd/decoder/modified_search.py).
+_MSEARCH_EXPORTS = ("ModifiedBeamState", "modified_beam_search")
+
 
 def __getattr__(name):
     if name in _CTC_EXPORTS:
@@ -90,8 +93,12 @@ def __getattr__(name):
     if name in _OPS_EXPORTS:
         from .model import ops
         return getattr(ops, name)
+    if name in _MSEARCH_EXPORTS:
+        from .decoder import modified_search
+        return getattr(modified_search, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
 def __dir__():
-    return sorted(list(globals()) + list(_CTC_EXPORTS) + list(_RNNT_EXPORTS) + list(_OPS_EXPORTS))
+    return sorted(list(globals()) + list(_CTC_EXPORTS) + list(_RNNT_EXPORTS) + list(_OPS_EXPORTS)
+                  + list(_MSEARCH_EXPORTS))

@@ -56,6 +56,12 @@ SIGNATURES = {
     "pika_prnnt_mod_prune_ranges": (_i, [_vp] * 4 + [_i] * 4 + [_vp] * 2),
     "pika_mrnnt_align_scratch_bytes": (_sz, [_i, _i, _i]),
     "pika_mrnnt_align": (_i, [_vp] * 3 + [_i] * 3 + [_vp] * 4),
+    # include/pika_msearch.h
+    "pika_msearch_state_bytes": (_sz, [_i, _i, _i]),
+    "pika_msearch_reset": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "pika_msearch_advance": (_i, [_vp, _vp, _ll, _vp] + [_i] * 5 + [_f, _f] + [_vp] * 3),
+    "pika_msearch_results": (_i, [_vp] + [_i] * 5 + [_vp] * 4),
+    "pika_msearch_hyps": (_i, [_vp] + [_i] * 4 + [_vp] * 3),
     # include/pika_ctc.h
     "pika_ctc_workspace_bytes": (_sz, [_i, _i, _i]),
     "pika_ctc_align_scratch_bytes": (_sz, [_i, _i, _i]),

@@ -1,0 +1,383 @@
+"""One-symbol-per-frame ("modified") transducer beam search: the search that belongs to the modified topology of
+`rnnt_loss_modified` / `rnnt_pruned_joint_loss_modified`, in which every frame emits exactly one symbol -- blank or a
+label (k2's `modified=True`, icefall's `modified_beam_search`).  Every hypothesis consumes one frame per step, so an
+utterance of T_n frames takes T_n steps, a batch max(T_n), known before the first launch: the loop reads nothing back.
+
+`ModifiedBeamState` is the search state and its frame step (include/pika_msearch.h, csrc/msearch.hip);
+`modified_beam_search` drives a transducer model through it.  The definition of a step is in the header and in DESIGN.md
+section 3, "Modified beam search"; `_torch_step` below spells it in plain torch.
+"""
+import torch
+
+from .. import _lib
+
+MAX_BEAM = 64
+ROOT = 0x7ffffffe
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _torch_step(scores, logits, blank, sm_scale, blank_penalty):
+    """The step's definition on one utterance, in the dtype of `logits`: scores (K,), logits (K,V) ->
+    [(merged score, representative's slot k, its v, [(k, v) of the members in rank order])] in the new beam's order."""
+    K, V = logits.shape
+    x = sm_scale * logits
+    x[:, blank] = x[:, blank] - blank_penalty
+    m = x.max(dim=1, keepdim=True).values
+    dead = ~(m > -float("inf"))
+    m = torch.where(dead, torch.zeros_like(m), m)
+    lp = (x - m) - torch.log(torch.exp(x - m).sum(dim=1, keepdim=True))
+    lp = torch.where(dead.expand_as(lp), torch.full_like(lp, -float("inf")), lp)
+    cand = scores.to(logits.dtype).unsqueeze(1) + lp
+    cand = torch.where((scores > -float("inf")).unsqueeze(1).expand_as(cand), cand, torch.full_like(cand, -float("inf")))
+    # the total order: larger value, then lower k, then lower v -- a stable descending sort of the (k, v)-major array
+    val, idx = torch.sort(cand.reshape(-1), descending=True, stable=True)
+    sel = [(val[r], int(idx[r]) // V, int(idx[r]) % V) for r in range(min(K, K * V)) if val[r] > -float("inf")]
+    return sel
+
+
+class ModifiedBeamState(object):
+    """The state of a one-symbol-per-frame beam search over `batch` utterances of at most `max_frames` frames with
+    `beam` slots each, and its frame step.
+
+    advance(logits, num_frames, sm_scale=1.0, blank_penalty=0.0) -> (parent, token), both (batch, beam) int64
+        logits (batch * beam, V): row b * beam + k is the joint network's output for slot k of utterance b at frame
+        frames[b]; any row stride >= V (the class stride must be 1).  num_frames (batch,) int64: utterance b is ACTIVE
+        while frames[b] < min(num_frames[b], max_frames).  For an active utterance the beam's candidates
+        score[k] + log_softmax(sm_scale * logits[k] - blank_penalty [blank])[v] are cut to the `beam` best, candidates
+        that spell the same token sequence are merged (log-sum-exp), and slot j of the new beam came from slot
+        parent[b, j] by token[b, j] (blank: the sequence did not grow).  An inactive utterance keeps its state and
+        gets parent[b, j] = j, token = blank, so a caller that re-orders its prediction-network state by `parent` and
+        steps it where token != blank leaves it alone.  Empty slots (fewer than `beam` candidates exist) have score
+        -inf, parent 0, token blank.
+    results(nbest=1, max_len=None) -> (tokens (batch, nbest, L) int64, -1 beyond the length; lengths (batch, nbest)
+        int64, -1 for a missing entry; scores (batch, nbest), -inf for a missing entry), the beam's order (best
+        first).  L = max_len or max_frames; a longer entry reports its true length and its first L tokens.
+    hyps(max_len=None) -> (tokens (batch, beam, L), lengths (batch, beam)): the same for the current slots.
+    reset(which=None)   every utterance, or those selected by `which` ((batch,) bool / int), back to the empty sequence.
+    frames, scores, overflowed   live views of the state: (batch,) int32, (batch, beam) float, (batch,) bool
+        (overflowed: num_frames[b] > max_frames and the state is full; the further frames are ignored).
+
+    On a HIP device the state is one blob of device memory and every call is a HIP kernel launch with no host
+    synchronisation, capturable in a `torch.cuda.graph`; logits must then be float32 on that device -- anything else
+    raises.  On the CPU, or with dtype=torch.float64, the same definition runs in plain torch (per-utterance Python
+    loops: a spelling of the definition, not a fast path)."""
+
+    def __init__(self, batch, max_frames, beam=4, blank=0, device=None, dtype=None):
+        batch, max_frames, beam, blank = int(batch), int(max_frames), int(beam), int(blank)
+        if not 1 <= beam <= MAX_BEAM:
+            raise ValueError("need 1 <= beam <= %d, got beam=%d" % (MAX_BEAM, beam))
+        if batch < 1 or max_frames < 1 or blank < 0:
+            raise ValueError("need batch >= 1, max_frames >= 1 and blank >= 0, got %d, %d, %d" % (batch, max_frames, blank))
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.float64):
+            raise TypeError("dtype must be float32 or float64, got %s" % dtype)
+        self.batch, self.max_frames, self.beam, self.blank = batch, max_frames, beam, blank
+        self.device, self.dtype = dev, dtype
+        self.native = dev.type == "cuda" and dtype == torch.float32
+        if self.native:
+            lib = _lib.lib()
+            nbytes = lib.pika_msearch_state_bytes(batch, beam, max_frames)
+            if nbytes == 0:
+                raise ValueError("(batch,max_frames,beam) = (%d,%d,%d) not supported" % (batch, max_frames, beam))
+            with torch.cuda.device(dev):
+                self._state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            BK = batch * beam       # the layout of include/pika_msearch.h
+            self._scores = self._state[:4 * BK].view(torch.float32).view(batch, beam)
+            self._frames = self._state[12 * BK:12 * BK + 4 * batch].view(torch.int32)
+            self._over = self._state[12 * BK + 4 * batch:12 * BK + 8 * batch].view(torch.int32)
+        else:
+            self._scores = torch.empty((batch, beam), dtype=dtype, device=dev)
+            self._frames = torch.empty(batch, dtype=torch.int32, device=dev)
+            self._over = torch.empty(batch, dtype=torch.int32, device=dev)
+            self._node = [[0] * beam for _ in range(batch)]       # per slot: the node of its token sequence, 0 = root
+            self._tries = [None] * batch                          # per utterance: ({(parent, token): node}, [(parent, token)])
+        self.reset()
+
+    @property
+    def frames(self):
+        return self._frames
+
+    @property
+    def scores(self):
+        return self._scores
+
+    @property
+    def overflowed(self):
+        return self._over != 0
+
+    def _which(self, which):
+        if which is not None:
+            which = torch.as_tensor(which)
+            if which.dtype not in (torch.bool, torch.int32, torch.int64):
+                raise TypeError("which must be bool, int32 or int64, got %s" % which.dtype)
+            which = which.reshape(-1).to(self.device, torch.int32).contiguous()
+            if which.numel() != self.batch:
+                raise ValueError("which must hold batch = %d entries" % self.batch)
+        return which
+
+    def reset(self, which=None):
+        which = self._which(which)
+        if self.native:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().pika_msearch_reset(_ptr(self._state), self.batch, self.beam, self.max_frames,
+                                                         _ptr(which), _stream()), "pika_msearch_reset")
+            return
+        sel = range(self.batch) if which is None else [b for b, w in enumerate(which.tolist()) if w]
+        for b in sel:
+            self._scores[b] = -float("inf")
+            self._scores[b, 0] = 0.0
+            self._frames[b] = 0
+            self._over[b] = 0
+            self._node[b] = [0] * self.beam
+            self._tries[b] = ({}, [(-1, -1)])
+
+    def _check_logits(self, logits, num_frames):
+        if not isinstance(logits, torch.Tensor):
+            raise TypeError("logits must be a tensor")
+        if self.native and not logits.is_cuda:
+            raise RuntimeError("pika_amd ModifiedBeamState: logits must live on a HIP device (the state does)")
+        if logits.dtype != self.dtype:
+            raise TypeError("logits must be %s, got %s" % (self.dtype, logits.dtype))
+        if logits.device != self.device:
+            raise ValueError("the state lives on %s, logits on %s" % (self.device, logits.device))
+        if logits.dim() != 2 or logits.shape[0] != self.batch * self.beam:
+            raise ValueError("logits must be (batch * beam, V) = (%d, V), got %s" % (self.batch * self.beam,
+                                                                                 tuple(logits.shape)))
+        V = logits.shape[1]
+        if V < 2 or not 0 <= self.blank < V:
+            raise ValueError("need V >= 2 and 0 <= blank < V, got V=%d, blank=%d" % (V, self.blank))
+        if logits.stride(1) != 1 or logits.stride(0) < V:
+            raise ValueError("logits rows must be contiguous (class stride 1, row stride >= V), got strides %s"
+                             % (tuple(logits.stride()),))
+        num_frames = torch.as_tensor(num_frames)
+        if num_frames.dtype not in (torch.int32, torch.int64) or num_frames.numel() != self.batch:
+            raise ValueError("num_frames must be (batch,) int32 or int64")
+        return logits, num_frames.reshape(-1).to(self.device, torch.int64).contiguous()
+
+    def advance(self, logits, num_frames, sm_scale=1.0, blank_penalty=0.0):
+        sm_scale, blank_penalty = float(sm_scale), float(blank_penalty)
+        if sm_scale != sm_scale or sm_scale in (float("inf"), -float("inf")) or blank_penalty != blank_penalty \
+                or blank_penalty in (float("inf"), -float("inf")):
+            raise ValueError("sm_scale and blank_penalty must be finite")
+        logits, num_frames = self._check_logits(logits, num_frames)
+        B, K, V = self.batch, self.beam, logits.shape[1]
+        if self.native:
+            with torch.cuda.device(self.device):
+                parent = torch.empty((B, K), dtype=torch.int64, device=self.device)
+                token = torch.empty((B, K), dtype=torch.int64, device=self.device)
+                _lib.check(_lib.lib().pika_msearch_advance(
+                    _ptr(self._state), _ptr(logits), logits.stride(0), _ptr(num_frames), B, K, self.max_frames, V,
+                    self.blank, sm_scale, blank_penalty, _ptr(parent), _ptr(token), _stream()), "pika_msearch_advance")
+            return parent, token
+        parent = torch.arange(K, dtype=torch.int64).repeat(B, 1)
+        token = torch.full((B, K), self.blank, dtype=torch.int64)
+        nf = num_frames.tolist()
+        for b in range(B):
+            frames = int(self._frames[b])
+            if frames < min(max(nf[b], 0), self.max_frames):
+                self._advance_one(b, logits[b * K:(b + 1) * K].clone(), sm_scale, blank_penalty, parent[b], token[b])
+                frames += 1
+                self._frames[b] = frames
+            if frames >= self.max_frames and nf[b] > self.max_frames:
+                self._over[b] = 1
+        return parent.to(self.device), token.to(self.device)
+
+    def _advance_one(self, b, logits, sm_scale, blank_penalty, parent, token):
+        K, blank, ninf = self.beam, self.blank, -float("inf")
+        index, nodes = self._tries[b]
+        scores = self._scores[b].clone()
+        groups, by_key = [], {}
+        for c, k, v in _torch_step(scores, logits, blank, sm_scale, blank_penalty):
+            pn = self._node[b][k]
+            if v == blank:
+                key = pn
+            else:
+                key = index.get((pn, v))
+                if key is None:
+                    key = index[(pn, v)] = len(nodes)
+                    nodes.append((pn, v))
+            if key not in by_key:
+                by_key[key] = len(groups)
+                groups.append([key, k, v, [c]])
+            else:
+                groups[by_key[key]][3].append(c)
+        merged = []
+        for rank, (key, k, v, cs) in enumerate(groups):
+            s = torch.zeros((), dtype=logits.dtype)
+            for c in cs:                                    # in rank order, from the group's largest value
+                s = s + torch.exp(c - cs[0])
+            merged.append((cs[0] + torch.log(s), rank, key, k, v))
+        merged.sort(key=lambda g: (-float(g[0]), g[1]))     # (exact: a float64 holds every float32)
+        new_nodes = [0] * K
+        for j in range(K):
+            if j < len(merged):
+                sc, _, key, k, v = merged[j]
+                self._scores[b, j] = sc
+                new_nodes[j], parent[j], token[j] = key, k, v
+            else:
+                self._scores[b, j] = ninf
+                parent[j], token[j] = 0, blank
+        self._node[b] = new_nodes
+
+    def _read(self, n, max_len):
+        L = self.max_frames if max_len is None else int(max_len)
+        if L < 1:
+            raise ValueError("max_len must be >= 1, got %d" % L)
+        B, K = self.batch, self.beam
+        if self.native:
+            with torch.cuda.device(self.device):
+                tokens = torch.empty((B, n, L), dtype=torch.int64, device=self.device)
+                lengths = torch.empty((B, n), dtype=torch.int64, device=self.device)
+            return tokens, lengths, L
+        tokens = torch.full((B, n, L), -1, dtype=torch.int64)
+        lengths = torch.full((B, n), -1, dtype=torch.int64)
+        for b in range(B):
+            nodes = self._tries[b][1]
+            for j in range(n):
+                if self._scores[b, j] > -float("inf"):
+                    seq, node = [], self._node[b][j]
+                    while node != 0:
+                        node, tok = nodes[node]
+                        seq.append(tok)
+                    seq.reverse()
+                    lengths[b, j] = len(seq)
+                    tokens[b, j, :min(len(seq), L)] = torch.tensor(seq[:L], dtype=torch.int64)
+        return tokens.to(self.device), lengths.to(self.device), L
+
+    def results(self, nbest=1, max_len=None):
+        nbest = int(nbest)
+        if not 1 <= nbest <= self.beam:
+            raise ValueError("need 1 <= nbest <= beam = %d, got nbest=%d" % (self.beam, nbest))
+        tokens, lengths, L = self._read(nbest, max_len)
+        if self.native:
+            with torch.cuda.device(self.device):
+                scores = torch.empty((self.batch, nbest), dtype=torch.float32, device=self.device)
+                _lib.check(_lib.lib().pika_msearch_results(
+                    _ptr(self._state), self.batch, self.beam, self.max_frames, nbest, L, _ptr(tokens), _ptr(lengths),
+                    _ptr(scores), _stream()), "pika_msearch_results")
+            return tokens, lengths, scores
+        return tokens, lengths, self._scores[:, :nbest].clone()
+
+    def hyps(self, max_len=None):
+        tokens, lengths, L = self._read(self.beam, max_len)
+        if self.native:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().pika_msearch_hyps(
+                    _ptr(self._state), self.batch, self.beam, self.max_frames, L, _ptr(tokens), _ptr(lengths),
+                    _stream()), "pika_msearch_hyps")
+        return tokens, lengths
+
+
+@torch.no_grad()
+def modified_beam_search(model, x, x_len, beam=4, nbest=1, sm_scale=1.0, blank_penalty=0.0, use_graph=True, blank=0,
+                         precision="fp16x2"):
+    """Decode a batch with a transducer model (`pika_amd.model.transducer.Net`) under the modified topology: at most --
+    exactly -- one symbol per frame.  -> (tokens (B, nbest, T) int64, lengths (B, nbest) int64, scores (B, nbest) f32,
+    enc_out (B, T, H)) with the conventions of `ModifiedBeamState.results`.
+
+    x (B, T_in, D) features; x_len (B,) the utterances' numbers of ENCODER frames (as `TransducerDecoder.decode_batch`
+    takes them), host or device, clamped to [0, T].  The encoder runs once; the joint's encoder halves are computed
+    once; per frame step the rows of the frame frames[b] are gathered, the prediction half is added, gate and fc2 give
+    the (B * beam, V) logits, `ModifiedBeamState.advance` cuts and merges, the prediction-network state is re-ordered by
+    `parent` and stepped on the rows whose token is a label (every row is computed and masked: fixed shapes).  The
+    loop runs exactly min(max(x_len), T) steps and reads nothing back.  use_graph (HIP only): two steps run eagerly,
+    the next is captured once and replayed for the rest.
+
+    Prediction networks: the LSTM of the shipped recipes (`decoder_type == 'rnn'`) is stepped on its (h, c) state.  The
+    conv-transformer prediction network is re-run every step on [blank] + hyps() padded to T + 1 positions: correct, not
+    fast (the incremental cache of `TransducerDecoder` is not wired in).
+
+    Scores are the summed log-probabilities of the paths the beam kept, NOT length-normalised, and the entries come in
+    the beam's order by that score; normalising by length and picking the entry to return is the caller's:
+    nbest=beam gives every entry's score and length.  Token time stamps: `rnnt_align_modified*` on the returned
+    hypotheses.  precision: `pika_amd.gemm.PRECISION` for the products of the call on a HIP device ("fp32": exact)."""
+    from .. import gemm as G
+    from ..model import ops
+    K, blank = int(beam), int(blank)
+    old = G.PRECISION
+    if x.is_cuda:
+        if precision not in G.PRECISIONS:
+            raise ValueError("unknown precision %r" % (precision,))
+        G.PRECISION = precision
+    try:
+        if model.pack_seq and x_len is not None:
+            enc_out = model.encode(x, x_len)
+        else:
+            enc_out = model.encoder(x)
+        B, T, H = enc_out.shape
+        dev = enc_out.device
+        x_len = torch.as_tensor(x_len)
+        steps = min(max(int(x_len.max()), 0), T)               # (the one host read, before the first launch)
+        num_frames = x_len.to(dev).long().clamp(0, T)
+        rnn = model.decoder_type == 'rnn'
+        state = ModifiedBeamState(B, T, K, blank, dev, enc_out.dtype)
+
+        w1, wg = model.fc1, model.fc_gate
+        e1_all = ops.linear(enc_out, w1.weight[:, :H].contiguous(), w1.bias)
+        eg_all = ops.linear(enc_out, wg.weight[:, :H].contiguous(), wg.bias)
+        e_all = torch.cat((e1_all, eg_all), dim=2).reshape(B * T, 2 * H)          # row b*T + t = [e1 | eg]
+        wp = torch.cat((w1.weight[:, H:], wg.weight[:, H:]), dim=0).contiguous()  # (2H, H)
+        brow = torch.arange(B, device=dev) * T
+        flat0 = (torch.arange(B, device=dev) * K).unsqueeze(1)
+
+        sos = torch.full((B * K, 1), blank, dtype=torch.long, device=dev)
+        if rnn:
+            _, st = model.decoder(model.embed(sos))
+            pred = [st[0].contiguous(), st[1].contiguous()]
+        else:
+            pred = [model.decoder(sos)[:, -1, :].contiguous()]
+            pad = model.embed.padding_idx
+            pos = torch.arange(1, T + 1, device=dev).unsqueeze(0)
+
+        def step():
+            tg = state.frames.long().clamp(max=T - 1)
+            rows = (brow + tg).unsqueeze(1).expand(B, K).reshape(-1)
+            dec_hid = pred[0][-1] if rnn else pred[0]
+            z = e_all.index_select(0, rows) + ops.linear(dec_hid, wp)
+            h = torch.tanh(z[:, :H]) * torch.sigmoid(z[:, H:])
+            logits = ops.linear(h, model.fc2.weight, model.fc2.bias).contiguous()
+            parent, token = state.advance(logits, num_frames, sm_scale, blank_penalty)
+            flat = (flat0 + parent).reshape(-1)
+            for s_ in pred:
+                s_.copy_(s_.index_select(1 if rnn else 0, flat))
+            label = token.reshape(-1).ne(blank)
+            if rnn:
+                hh, cc = pred
+                _, (h2, c2) = model.decoder(model.embed(token.reshape(-1, 1)), (hh, cc))
+                m = label.view(1, -1, 1)
+                hh.copy_(torch.where(m, h2, hh))
+                cc.copy_(torch.where(m, c2, cc))
+            else:
+                hyp, ln = state.hyps(max_len=T)
+                hyp, ln = hyp.view(B * K, T), ln.view(-1).clamp(min=0)
+                body = torch.where(pos <= ln.unsqueeze(1), hyp, torch.full_like(hyp, pad))
+                out = model.decoder(torch.cat((sos, body), dim=1))
+                last = out.gather(1, ln.view(-1, 1, 1).expand(-1, 1, out.shape[2])).squeeze(1)
+                pred[0].copy_(torch.where(label.unsqueeze(1), last, pred[0]))
+
+        graph = None
+        for i in range(steps):
+            if use_graph and enc_out.is_cuda and i >= 2:
+                if graph is None:
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph):
+                        step()
+                graph.replay()
+            else:
+                step()
+        tokens, lengths, scores = state.results(nbest=nbest)
+    finally:
+        G.PRECISION = old
+    return tokens, lengths, scores, enc_out
