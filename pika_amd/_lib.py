@@ -62,6 +62,13 @@ SIGNATURES = {
     "pika_msearch_advance": (_i, [_vp, _vp, _ll, _vp] + [_i] * 5 + [_f, _f] + [_vp] * 3),
     "pika_msearch_results": (_i, [_vp] + [_i] * 5 + [_vp] * 4),
     "pika_msearch_hyps": (_i, [_vp] + [_i] * 4 + [_vp] * 3),
+    # include/pika_msearch_lm.h
+    "pika_msearch_lm_state_bytes": (_sz, [_i, _i, _i, _i]),
+    "pika_msearch_lm_reset": (_i, [_vp] + [_i] * 8 + [_vp, _vp]),
+    "pika_msearch_lm_advance": (_i, [_vp, _vp, _ll, _vp] + [_i] * 6 + [_f, _f] + ([_vp] * 5 + [_i] * 4) * 2 + [_f] * 3
+                                + [_vp] * 3),
+    "pika_msearch_lm_results": (_i, [_vp] + [_i] * 4 + ([_vp] * 5 + [_i] * 5) * 2 + [_f, _f] + [_i] * 3 + [_vp] * 5),
+    "pika_msearch_lm_hyps": (_i, [_vp] + [_i] * 5 + [_vp] * 3),
     # include/pika_ctc.h
     "pika_ctc_workspace_bytes": (_sz, [_i, _i, _i]),
     "pika_ctc_align_scratch_bytes": (_sz, [_i, _i, _i]),

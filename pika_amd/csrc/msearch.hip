@@ -14,12 +14,19 @@
 //      are taken one at a time instead, K arg-max passes: slow, exact, bounded.
 //   4  keys, merge, sort: at most 64 entries, wave 0.
 // Every comparison is in the total order (value, k, v), so ties cost nothing and the result is a function of the input.
+//
+// The step with n-gram LM / hotword fusion (include/pika_msearch_lm.h) is the same kernel template with NFST = 1 or 2
+// automata: stages 1-3 select C = candidates >= K entries by F[k] + lp[k,v]; in stage 4 thread j walks the automata for
+// entry j (fst_walk.h), entries merge by key on their acoustic scores and the groups are ordered by the fused score.
+// The plain instantiation (NFST = 0) has no trace of it (if constexpr).
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <stdint.h>
 
 #include "ctc_search_core.h"
+#include "fst_walk.h"
 #include "pika_msearch.h"
+#include "pika_msearch_lm.h"
 
 static_assert(ROOT == PIKA_MSEARCH_ROOT && MAX_BEAM == PIKA_MSEARCH_MAX_BEAM, "the constants the C ABI documents");
 
@@ -29,11 +36,15 @@ constexpr int THREADS = 256, WAVES = THREADS / 64;
 constexpr int LIST_CAP = 1024;  // entries the collect pass can hold
 constexpr float NINF = -INFINITY;
 
-// where the parts of the blob lie
+// where the parts of the blob lie; score is the value the step ranks by (the fused search's F).  The fused search's
+// blob has am, bonus and the automata's states as well
 struct Blob {
     float *score;
     int *node, *len, *frames, *overflowed;
     unsigned long long *tables;
+    float *am;
+    double *bonus;
+    int *lmst, *lmst2;
 };
 
 __host__ __device__ inline size_t head_bytes(int B, int K) {
@@ -49,7 +60,48 @@ __host__ __device__ inline Blob blob_of(void *state, int B, int K) {
     s.frames = reinterpret_cast<int *>(p + 12 * (size_t)B * K);
     s.overflowed = s.frames + B;
     s.tables = reinterpret_cast<unsigned long long *>(p + head_bytes(B, K));
+    s.am = nullptr; s.bonus = nullptr; s.lmst = nullptr; s.lmst2 = nullptr;
     return s;
+}
+
+// the fused search's blob (pika_msearch_lm.h)
+__host__ __device__ inline size_t lm_head_bytes(int B, int K) {
+    return (32 * (size_t)B * K + 8 * (size_t)B + 15) & ~(size_t)15;
+}
+
+__host__ __device__ inline Blob lm_blob_of(void *state, int B, int K) {
+    char *p = static_cast<char *>(state);
+    const size_t BK = (size_t)B * K;
+    Blob s;
+    s.bonus = reinterpret_cast<double *>(p);
+    s.score = reinterpret_cast<float *>(p + 8 * BK);
+    s.am = reinterpret_cast<float *>(p + 12 * BK);
+    s.node = reinterpret_cast<int *>(p + 16 * BK);
+    s.len = reinterpret_cast<int *>(p + 20 * BK);
+    s.lmst = reinterpret_cast<int *>(p + 24 * BK);
+    s.lmst2 = reinterpret_cast<int *>(p + 28 * BK);
+    s.frames = reinterpret_cast<int *>(p + 32 * BK);
+    s.overflowed = s.frames + B;
+    s.tables = reinterpret_cast<unsigned long long *>(p + lm_head_bytes(B, K));
+    return s;
+}
+
+// what a launch of the fused search takes beside the plain one's arguments: the automata, the weights and C.  The plain
+// search takes the empty one.
+template <int NFST>
+struct Fused {
+    Fst f[NFST];
+    float lmw, bw, lb;
+    int C;
+};
+
+template <>
+struct Fused<0> {};
+
+template <int NFST>
+__host__ __device__ inline Blob blob_of(void *state, int B, int K) {
+    if constexpr (NFST == 0) return blob_of(state, B, K);
+    else return lm_blob_of(state, B, K);
 }
 
 // a candidate: its value and where it came from
@@ -98,11 +150,13 @@ __device__ __forceinline__ float cand_of(float score, float x, float m, float lo
     return __fadd_rn(score, __fsub_rn(__fsub_rn(x, m), logs));
 }
 
+// LM: the fused search's blob; slot 0 starts in the automata's start states
+template <bool LM>
 __global__ __launch_bounds__(THREADS) void msearch_reset_kernel(void *state, int B, int K, size_t slots,
-                                                                 const int *__restrict__ which) {
+                                                                 const int *__restrict__ which, int start, int start2) {
     const int b = blockIdx.x;
     if (which && which[b] == 0) return;  // workgroup-uniform
-    const Blob s = blob_of(state, B, K);
+    const Blob s = blob_of<LM ? 1 : 0>(state, B, K);
     unsigned long long *table = s.tables + (size_t)b * slots;
     for (size_t i = (size_t)blockIdx.y * THREADS + threadIdx.x; i < slots; i += (size_t)gridDim.y * THREADS)
         table[i] = EMPTY;
@@ -112,17 +166,32 @@ __global__ __launch_bounds__(THREADS) void msearch_reset_kernel(void *state, int
             s.score[(size_t)b * K + k] = k == 0 ? 0.0f : NINF;
             s.node[(size_t)b * K + k] = ROOT;
             s.len[(size_t)b * K + k] = 0;
+            if constexpr (LM) {
+                s.am[(size_t)b * K + k] = k == 0 ? 0.0f : NINF;
+                s.bonus[(size_t)b * K + k] = 0.0;
+                s.lmst[(size_t)b * K + k] = start;
+                s.lmst2[(size_t)b * K + k] = start2;
+            }
         }
         if (k == 0) { s.frames[b] = 0; s.overflowed[b] = 0; }
     }
 }
 
+// NFST: the automata fused in (0: the plain step of pika_msearch.h; 1, 2: the step of pika_msearch_lm.h).  NSEL is the
+// number of entries stages 1-3 select: K, or the fused step's C.
+template <int NFST>
 __global__ __launch_bounds__(THREADS) void msearch_advance_kernel(void *state, const float *__restrict__ logits,
                                                                    long long ld, const long long *__restrict__ num_frames,
                                                                    int B, int K, int max_frames, int V, int blank,
                                                                    float sm_scale, float penalty, unsigned mask, int vec,
                                                                    long long *__restrict__ parent_out,
-                                                                   long long *__restrict__ token_out) {
+                                                                   long long *__restrict__ token_out,
+                                                                   const Fused<NFST> fu) {
+    constexpr bool LM = NFST > 0;
+    constexpr int NL = LM ? MAX_BEAM : 1;  // the fused step's arrays: per old slot, and per selected entry
+    __shared__ float s_am[NL], s_G[NL];
+    __shared__ double s_bonus[NL], s_cbonus[NL];
+    __shared__ int s_st[NL], s_st2[NL], s_cst[NL], s_cst2[NL];
     __shared__ float s_score[MAX_BEAM], s_m[MAX_BEAM], s_logs[MAX_BEAM];
     __shared__ int s_node[MAX_BEAM], s_len[MAX_BEAM];
     __shared__ float pool_c[MAX_BEAM][64];  // per row, the lane maxima in order
@@ -134,8 +203,10 @@ __global__ __launch_bounds__(THREADS) void msearch_advance_kernel(void *state, c
     __shared__ float s_merged[MAX_BEAM];
 
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const Blob st = blob_of(state, B, K);
+    const Blob st = blob_of<NFST>(state, B, K);
     const size_t bk = (size_t)b * K;
+    int NSEL = K;
+    if constexpr (LM) NSEL = clampi(fu.C, K, MAX_BEAM);
     const long long nf_raw = num_frames[b];
     const int nf = (int)(nf_raw < 0 ? 0 : (nf_raw > max_frames ? max_frames : nf_raw));
     const int frames = st.frames[b];
@@ -149,6 +220,12 @@ __global__ __launch_bounds__(THREADS) void msearch_advance_kernel(void *state, c
         s_score[tid] = st.score[bk + tid];
         s_node[tid] = st.node[bk + tid];
         s_len[tid] = clampi(st.len[bk + tid], 0, max_frames);
+        if constexpr (LM) {  // (a state outside its table: lm_step finds no child; clamped all the same)
+            s_am[tid] = st.am[bk + tid];
+            s_bonus[tid] = st.bonus[bk + tid];
+            s_st[tid] = clampi(st.lmst[bk + tid], 0, fu.f[0].S - 1);
+            if constexpr (NFST == 2) s_st2[tid] = clampi(st.lmst2[bk + tid], 0, fu.f[1].S - 1);
+        }
     }
     if (tid == 0) { s_cnt = 0; s_all = 0; }
     __syncthreads();
@@ -204,7 +281,7 @@ __global__ __launch_bounds__(THREADS) void msearch_advance_kernel(void *state, c
         int head = 0;
         Cand thr = {NINF, 0, 0};
         bool all = false;
-        for (int r = 0; r < K; ++r) {
+        for (int r = 0; r < NSEL; ++r) {
             Cand h = {NINF, lane, 0x7fffffff};
             if (row_live && head < 64) { h.c = pool_c[lane][head]; h.v = pool_v[lane][head]; }
             const Cand w = wave_best(h);
@@ -243,15 +320,15 @@ __global__ __launch_bounds__(THREADS) void msearch_advance_kernel(void *state, c
                 const Cand o = {list_c[j], list_kv[j][0], list_kv[j][1]};
                 rank += cand_before(o, e) ? 1 : 0;
             }
-            if (rank < K) s_sel[rank] = e;
+            if (rank < NSEL) s_sel[rank] = e;
         }
-        if (tid == 0) s_nsel = n < K ? n : K;
+        if (tid == 0) s_nsel = n < NSEL ? n : NSEL;
         __syncthreads();
     } else {
         // the list overflowed: the K best one at a time, each the best of what comes after the one before
         Cand prev = {INFINITY, -1, -1};
         int got = 0;
-        for (int r = 0; r < K; ++r) {
+        for (int r = 0; r < NSEL; ++r) {
             Cand best = {NINF, 0x7fffffff, 0x7fffffff};
             for (int k = wave; k < K; k += WAVES) {
                 const float score = s_score[k];
@@ -282,18 +359,48 @@ __global__ __launch_bounds__(THREADS) void msearch_advance_kernel(void *state, c
 
     // 4  keys, merge, order: entry j of the selection is thread j's
     const int nsel = s_nsel;
-    if (tid < K) { s_key[tid] = NONE; s_lead[tid] = 0; }
+    if (tid < NSEL) { s_key[tid] = NONE; s_lead[tid] = 0; }
     __syncthreads();
     Cand me = {NINF, 0, blank};
     if (tid < nsel) {
         me = s_sel[tid];
         me.k = clampi(me.k, 0, K - 1);
         const int pn = s_node[me.k];
-        s_key[tid] = me.v == blank ? pn : trie_node(table, mask, pn, me.v);
-        s_klen[tid] = s_len[me.k] + (me.v == blank ? 0 : 1);
+        bool exists = true;
+        if constexpr (LM) {
+            // the entry's acoustic score a' = am[k] + lp[k,v] (the one logit again, from the cache), then the walks: an
+            // entry that an automaton does not reach keeps the key NONE and the value -inf, and makes no node
+            me.v = clampi(me.v, 0, V - 1);
+            const float x = scaled(logits[(bk + me.k) * ld + me.v], me.v, blank, sm_scale, penalty);
+            me.c = __fadd_rn(s_am[me.k], __fsub_rn(__fsub_rn(x, s_m[me.k]), s_logs[me.k]));
+            double bonus = s_bonus[me.k];
+            int n1 = s_st[me.k], n2 = 0;
+            if constexpr (NFST == 2) n2 = s_st2[me.k];
+            if (me.v != blank) {
+                float inc = 0.0f;
+                exists = lm_step(fu.f[0], n1, me.v, inc, n1) && inc - inc == 0.0f;  // (false for +-inf and NaN)
+                bonus = __dadd_rn(bonus, __dmul_rn((double)fu.lmw, (double)inc));
+                if constexpr (NFST == 2) {
+                    float inc2 = 0.0f;
+                    exists = exists && lm_step(fu.f[1], n2, me.v, inc2, n2) && inc2 - inc2 == 0.0f;
+                    bonus = __dadd_rn(bonus, __dmul_rn((double)fu.bw, (double)inc2));
+                }
+                bonus = __dadd_rn(bonus, (double)fu.lb);
+            }
+            exists = exists && me.c > NINF;
+            if (!exists) me.c = NINF;
+            s_sel[tid].c = me.c;  // the merge below sums the acoustic scores
+            s_cbonus[tid] = bonus;
+            s_cst[tid] = n1;
+            s_cst2[tid] = n2;
+        }
+        if (exists) {
+            s_key[tid] = me.v == blank ? pn : trie_node(table, mask, pn, me.v);
+            s_klen[tid] = s_len[me.k] + (me.v == blank ? 0 : 1);
+        }
     }
     __syncthreads();
-    if (tid < nsel) {
+    if (tid < nsel && (!LM || me.c > NINF)) {  // (fused: an entry that does not exist joins no group)
         const int key = s_key[tid];
         int rep = tid;
         for (int i = tid - 1; i >= 0; --i)
@@ -303,6 +410,7 @@ __global__ __launch_bounds__(THREADS) void msearch_advance_kernel(void *state, c
             for (int i = tid; i < nsel; ++i)
                 if (s_key[i] == key) s += expf(s_sel[i].c - me.c);
             s_merged[tid] = __fadd_rn(me.c, logf(s));
+            if constexpr (LM) s_G[tid] = (float)__dadd_rn((double)s_merged[tid], s_cbonus[tid]);
             s_lead[tid] = 1;
         }
     }
@@ -310,20 +418,29 @@ __global__ __launch_bounds__(THREADS) void msearch_advance_kernel(void *state, c
     // the new beam: every group finds its place (s_from[j]: the entry that fills slot j), slot j's thread writes it
     if (tid < K) s_from[tid] = -1;
     __syncthreads();
+    const float *s_order = s_merged;  // what orders the groups: the merged score, or the fused one
+    if constexpr (LM) s_order = s_G;
     if (tid < nsel && s_lead[tid]) {
-        const float mine = s_merged[tid];
+        const float mine = s_order[tid];
         int pos = 0;
         for (int i = 0; i < nsel; ++i)
-            if (s_lead[i] && i != tid && (s_merged[i] > mine || (s_merged[i] == mine && i < tid))) ++pos;
-        if (mine > NINF) s_from[pos] = tid;  // (pos < the number of groups <= K)
+            if (s_lead[i] && i != tid && (s_order[i] > mine || (s_order[i] == mine && i < tid))) ++pos;
+        // (plain: pos < the number of groups <= K; fused: up to C groups, the K best stay)
+        if (mine > NINF && (!LM || pos < K)) s_from[pos] = tid;
     }
     __syncthreads();
     if (tid < K) {
         const int j = s_from[tid];
         const bool full = j >= 0;
-        st.score[bk + tid] = full ? s_merged[j] : NINF;
+        st.score[bk + tid] = full ? s_order[j] : NINF;
         st.node[bk + tid] = full ? s_key[j] : ROOT;
         st.len[bk + tid] = full ? s_klen[j] : 0;
+        if constexpr (LM) {
+            st.am[bk + tid] = full ? s_merged[j] : NINF;
+            st.bonus[bk + tid] = full ? s_cbonus[j] : 0.0;
+            st.lmst[bk + tid] = full ? s_cst[j] : 0;
+            st.lmst2[bk + tid] = full ? s_cst2[j] : 0;
+        }
         parent_out[bk + tid] = full ? clampi(s_sel[j].k, 0, K - 1) : 0;
         token_out[bk + tid] = full ? s_sel[j].v : blank;
     }
@@ -333,31 +450,83 @@ __global__ __launch_bounds__(THREADS) void msearch_advance_kernel(void *state, c
     }
 }
 
-// the token sequences of `n` slots per utterance, slot j of the output from slot j of the beam
+// the token sequences of `n` entries per utterance, entry j of the output from slot j of the beam.  The fused search's
+// results with use_final (lane = slot) score every slot first -- am + bonus + the automata's final terms, no final state:
+// the slot drops out -- and entry j is the j-th slot by that score, ties by the slot.  The state is only read.
+template <int NFST>
 __global__ __launch_bounds__(64) void msearch_read_kernel(const void *state, int B, int K, int max_frames, unsigned mask,
                                                            int n, int L, long long *__restrict__ tokens,
-                                                           long long *__restrict__ lengths, float *__restrict__ scores) {
+                                                           long long *__restrict__ lengths, float *__restrict__ scores,
+                                                           float *__restrict__ am_scores, const Fused<NFST> fu,
+                                                           int use_final) {
+    constexpr bool LM = NFST > 0;
+    __shared__ float s_sc[LM ? MAX_BEAM : 1];
+    __shared__ int s_src[LM ? MAX_BEAM : 1];
     const int b = blockIdx.x, lane = threadIdx.x;
-    const Blob st = blob_of(const_cast<void *>(state), B, K);
+    const Blob st = blob_of<NFST>(const_cast<void *>(state), B, K);
     const unsigned long long *table = st.tables + (size_t)b * ((size_t)mask + 1);
     const size_t bk = (size_t)b * K;
+    if constexpr (LM) {
+        float sc = NINF;
+        if (lane < K) {
+            sc = st.score[bk + lane];
+            if (use_final && sc > NINF) {
+                double s = __dadd_rn((double)st.am[bk + lane], st.bonus[bk + lane]);
+                float inc = 0.0f;
+                bool live = lm_final(fu.f[0], clampi(st.lmst[bk + lane], 0, fu.f[0].S - 1), inc);
+                if (live) s = __dadd_rn(s, __dmul_rn((double)fu.lmw, (double)inc));
+                if constexpr (NFST == 2) {
+                    if (live) {
+                        live = lm_final(fu.f[1], clampi(st.lmst2[bk + lane], 0, fu.f[1].S - 1), inc);
+                        if (live) s = __dadd_rn(s, __dmul_rn((double)fu.bw, (double)inc));
+                    }
+                }
+                sc = live ? (float)s : NINF;
+            }
+            if (!(sc > NINF)) sc = NINF;  // (a NaN is not alive)
+        }
+        s_sc[lane] = sc;
+        __syncthreads();
+        if (lane < K) {
+            int rank = lane;
+            if (use_final) {
+                rank = 0;
+                for (int q = 0; q < K; ++q) rank += (s_sc[q] > sc || (s_sc[q] == sc && q < lane)) ? 1 : 0;
+            }
+            s_src[rank] = lane;
+        }
+        __syncthreads();
+    }
+    // entry j: its slot and its score
+    auto slot_of = [&](int j) __attribute__((always_inline)) {
+        if constexpr (LM) return s_src[j];
+        else return j;
+    };
+    auto score_of = [&](int slot) __attribute__((always_inline)) {
+        if constexpr (LM) return s_sc[slot];
+        else return st.score[bk + slot];
+    };
     for (int j = 0; j < n; ++j) {  // (no entry is longer than max_frames: the rows are short, the lanes pad them)
-        const float sc = st.score[bk + j];
+        const int src = slot_of(j);
+        const float sc = score_of(src);
         const bool live = sc > NINF;
-        const int len = live ? clampi(st.len[bk + j], 0, max_frames) : -1;
+        const int len = live ? clampi(st.len[bk + src], 0, max_frames) : -1;
         long long *out = tokens + ((size_t)b * n + j) * L;
         for (int p = lane; p < L; p += 64)
             if (p >= len) out[p] = -1;
         if (lane == 0) {
             lengths[(size_t)b * n + j] = len;
             if (scores) scores[(size_t)b * n + j] = live ? sc : NINF;
+            if constexpr (LM)
+                if (am_scores) am_scores[(size_t)b * n + j] = live ? st.am[bk + src] : NINF;
         }
     }
     if (lane < n) {
-        const bool live = st.score[bk + lane] > NINF;
-        const int len = live ? clampi(st.len[bk + lane], 0, max_frames) : 0;
+        const int src = slot_of(lane);
+        const bool live = score_of(src) > NINF;
+        const int len = live ? clampi(st.len[bk + src], 0, max_frames) : 0;
         long long *out = tokens + ((size_t)b * n + lane) * L;
-        int node = st.node[bk + lane];
+        int node = st.node[bk + src];
         for (int p = len - 1; p >= 0; --p) {  // bounded by len whatever the table holds
             long long tok = -1;
             if (node != ROOT) {
@@ -370,21 +539,82 @@ __global__ __launch_bounds__(64) void msearch_read_kernel(const void *state, int
     }
 }
 
-static inline int check_dims(int B, int K, int max_frames) {
-    if (B <= 0 || K <= 0 || max_frames <= 0) return PIKA_EINVAL;
-    if (K > MAX_BEAM || B > 65535 || 2ll * max_frames * K > (1ll << 28)) return PIKA_ETOOBIG;
+// ---------------------------------------------------------------------------------------------
+// host.  C: what sizes the trie's tables -- the entries a step can select: K, or the fused search's candidates
+// ---------------------------------------------------------------------------------------------
+static inline int check_dims(int B, int K, int C, int max_frames) {
+    if (B <= 0 || K <= 0 || C <= 0 || max_frames <= 0 || K > C) return PIKA_EINVAL;
+    if (C > MAX_BEAM || B > 65535 || 2ll * max_frames * C > (1ll << 28)) return PIKA_ETOOBIG;
     return PIKA_OK;
 }
 
-static int read_out(const void *state, int B, int K, int max_frames, int n, int L, long long *tokens, long long *lengths,
-                    float *scores, bool want_scores, void *stream) {
+static inline int check_dims(int B, int K, int max_frames) { return check_dims(B, K, K, max_frames); }
+
+static inline int check_read(int B, int K, int C, int max_frames, int n, int L) {
     if (n <= 0 || L <= 0) return PIKA_EINVAL;
-    if (int rc = check_dims(B, K, max_frames)) return rc;
+    if (int rc = check_dims(B, K, C, max_frames)) return rc;
     if (n > K || (long long)n * L > 0x7fffffffll) return PIKA_ETOOBIG;
-    if (!state || !tokens || !lengths || (want_scores && !scores)) return PIKA_EINVAL;
-    hipLaunchKernelGGL(msearch_read_kernel, dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream), state, B,
-                       K, max_frames, (unsigned)(table_slots(max_frames, K) - 1), n, L, tokens, lengths, scores);
+    return PIKA_OK;
+}
+
+template <int NFST>
+static int read_out(const void *state, int B, int K, int C, int max_frames, int n, int L, long long *tokens,
+                    long long *lengths, float *scores, float *am_scores, const Fused<NFST> &fu, int use_final,
+                    void *stream) {
+    hipLaunchKernelGGL((msearch_read_kernel<NFST>), dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       state, B, K, max_frames, (unsigned)(table_slots(max_frames, C) - 1), n, L, tokens, lengths, scores,
+                       am_scores, fu, use_final);
     return (int)hipGetLastError();
+}
+
+static int read_plain(const void *state, int B, int K, int max_frames, int n, int L, long long *tokens,
+                      long long *lengths, float *scores, bool want_scores, void *stream) {
+    if (int rc = check_read(B, K, K, max_frames, n, L)) return rc;
+    if (!state || !tokens || !lengths || (want_scores && !scores)) return PIKA_EINVAL;
+    return read_out<0>(state, B, K, K, max_frames, n, L, tokens, lengths, scores, nullptr, Fused<0>{}, 0, stream);
+}
+
+template <bool LM>
+static int reset(void *state, int B, int K, int C, int max_frames, const int *which, int start, int start2, void *stream) {
+    const size_t slots = table_slots(max_frames, C), y = slots / 4096;  // 16 keys per thread
+    hipLaunchKernelGGL((msearch_reset_kernel<LM>), dim3((unsigned)B, (unsigned)(y < 1 ? 1 : (y > 256 ? 256 : y))),
+                       dim3(THREADS), 0, static_cast<hipStream_t>(stream), state, B, K, slots, which, start, start2);
+    return (int)hipGetLastError();
+}
+
+template <int NFST>
+static int advance(void *state, const float *logits, long long ld, const long long *num_frames, int B, int K, int C,
+                   int max_frames, int V, int blank, float sm_scale, float blank_penalty, long long *parent_out,
+                   long long *token_out, const Fused<NFST> &fu, void *stream) {
+    const int vec = ld % 4 == 0 && reinterpret_cast<uintptr_t>(logits) % 16 == 0;
+    hipLaunchKernelGGL((msearch_advance_kernel<NFST>), dim3((unsigned)B), dim3(THREADS), 0,
+                       static_cast<hipStream_t>(stream), state, logits, ld, num_frames, B, K, max_frames, V, blank,
+                       sm_scale, blank_penalty, (unsigned)(table_slots(max_frames, C) - 1), vec, parent_out, token_out, fu);
+    return (int)hipGetLastError();
+}
+
+// ---- the automata of a fused call, checked as pika_ctc_lm.h states it
+static inline bool bad_start(int S, int start) { return S <= 0 || start < 0 || start >= S; }
+
+static inline int check_fst(const Fst &f, int start) {
+    if (f.A < 0 || bad_start(f.S, start)) return PIKA_EINVAL;
+    if (!f.off || !f.fin || (f.A > 0 && (!f.il || !f.w || !f.ns))) return PIKA_EINVAL;
+    return PIKA_OK;
+}
+
+// the optional second automaton: 0 none (no states, no arcs, no arrays), 1 present and sound, < 0 refused
+static inline int second_fst(const Fst &g, int start2) {
+    if (g.S == 0) return (g.A == 0 && !g.off && !g.il && !g.w && !g.ns && !g.fin) ? 0 : PIKA_EINVAL;
+    return check_fst(g, start2) ? PIKA_EINVAL : 1;
+}
+
+template <int NFST>
+static inline Fused<NFST> fused(const Fst &f, const Fst &g, float lmw, float bw, float lb, int C) {
+    Fused<NFST> fu;
+    fu.f[0] = f;
+    if constexpr (NFST == 2) fu.f[1] = g;
+    fu.lmw = lmw; fu.bw = bw; fu.lb = lb; fu.C = C;
+    return fu;
 }
 
 }  // namespace
@@ -399,10 +629,7 @@ size_t pika_msearch_state_bytes(int B, int K, int max_frames) {
 int pika_msearch_reset(void *state, int B, int K, int max_frames, const int *which, void *stream) {
     if (int rc = check_dims(B, K, max_frames)) return rc;
     if (!state) return PIKA_EINVAL;
-    const size_t slots = table_slots(max_frames, K), y = slots / 4096;  // 16 keys per thread
-    hipLaunchKernelGGL(msearch_reset_kernel, dim3((unsigned)B, (unsigned)(y < 1 ? 1 : (y > 256 ? 256 : y))),
-                       dim3(THREADS), 0, static_cast<hipStream_t>(stream), state, B, K, slots, which);
-    return (int)hipGetLastError();
+    return reset<false>(state, B, K, K, max_frames, which, 0, 0, stream);
 }
 
 int pika_msearch_advance(void *state, const float *logits, long long ld, const long long *num_frames, int B, int K,
@@ -411,21 +638,94 @@ int pika_msearch_advance(void *state, const float *logits, long long ld, const l
     if (V < 2 || blank < 0 || blank >= V || ld < V || !std::isfinite(sm_scale) || !std::isfinite(blank_penalty)) return PIKA_EINVAL;
     if (int rc = check_dims(B, K, max_frames)) return rc;
     if (!state || !logits || !num_frames || !parent_out || !token_out) return PIKA_EINVAL;
-    const int vec = ld % 4 == 0 && reinterpret_cast<uintptr_t>(logits) % 16 == 0;
-    hipLaunchKernelGGL(msearch_advance_kernel, dim3((unsigned)B), dim3(THREADS), 0, static_cast<hipStream_t>(stream),
-                       state, logits, ld, num_frames, B, K, max_frames, V, blank, sm_scale, blank_penalty,
-                       (unsigned)(table_slots(max_frames, K) - 1), vec, parent_out, token_out);
-    return (int)hipGetLastError();
+    return advance<0>(state, logits, ld, num_frames, B, K, K, max_frames, V, blank, sm_scale, blank_penalty, parent_out,
+                      token_out, Fused<0>{}, stream);
 }
 
 int pika_msearch_results(const void *state, int B, int K, int max_frames, int nbest, int L, long long *tokens,
                          long long *lengths, float *scores, void *stream) {
-    return read_out(state, B, K, max_frames, nbest, L, tokens, lengths, scores, true, stream);
+    return read_plain(state, B, K, max_frames, nbest, L, tokens, lengths, scores, true, stream);
 }
 
 int pika_msearch_hyps(const void *state, int B, int K, int max_frames, int L, long long *tokens, long long *lengths,
                       void *stream) {
-    return read_out(state, B, K, max_frames, K, L, tokens, lengths, nullptr, false, stream);
+    return read_plain(state, B, K, max_frames, K, L, tokens, lengths, nullptr, false, stream);
+}
+
+// ---- the search with one or two automata fused in (pika_msearch_lm.h) ------------------------------------------------
+
+size_t pika_msearch_lm_state_bytes(int B, int K, int C, int max_frames) {
+    if (check_dims(B, K, C, max_frames)) return 0;
+    return lm_head_bytes(B, K) + table_bytes(B, max_frames, C);
+}
+
+int pika_msearch_lm_reset(void *state, int B, int K, int C, int max_frames, int num_states, int start, int num_states2,
+                          int start2, const int *which, void *stream) {
+    if (bad_start(num_states, start) || num_states2 < 0 || (num_states2 > 0 && bad_start(num_states2, start2)))
+        return PIKA_EINVAL;
+    if (int rc = check_dims(B, K, C, max_frames)) return rc;
+    if (!state) return PIKA_EINVAL;
+    return reset<true>(state, B, K, C, max_frames, which, start, num_states2 > 0 ? start2 : 0, stream);
+}
+
+int pika_msearch_lm_advance(void *state, const float *logits, long long ld, const long long *num_frames, int B, int K,
+                            int C, int max_frames, int V, int blank, float sm_scale, float blank_penalty,
+                            const long long *fst_offsets, const int *fst_ilabel, const float *fst_weight,
+                            const int *fst_nextstate, const float *fst_final, int num_states, int num_arcs,
+                            int backoff_id, int label_offset, const long long *fst2_offsets, const int *fst2_ilabel,
+                            const float *fst2_weight, const int *fst2_nextstate, const float *fst2_final,
+                            int num_states2, int num_arcs2, int backoff_id2, int label_offset2, float lm_weight,
+                            float bias_weight, float length_bonus, long long *parent_out, long long *token_out,
+                            void *stream) {
+    const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
+                   label_offset};
+    const Fst g = {fst2_offsets, fst2_ilabel, fst2_weight, fst2_nextstate, fst2_final, num_states2, num_arcs2,
+                   backoff_id2, label_offset2};
+    if (V < 2 || blank < 0 || blank >= V || ld < V || !std::isfinite(sm_scale) || !std::isfinite(blank_penalty) ||
+        !std::isfinite(lm_weight) || !std::isfinite(bias_weight) || !std::isfinite(length_bonus))
+        return PIKA_EINVAL;
+    const int two = second_fst(g, 0);
+    if (two < 0 || check_fst(f, 0)) return PIKA_EINVAL;
+    if (int rc = check_dims(B, K, C, max_frames)) return rc;
+    if (!state || !logits || !num_frames || !parent_out || !token_out) return PIKA_EINVAL;
+    if (two)
+        return advance<2>(state, logits, ld, num_frames, B, K, C, max_frames, V, blank, sm_scale, blank_penalty,
+                          parent_out, token_out, fused<2>(f, g, lm_weight, bias_weight, length_bonus, C), stream);
+    return advance<1>(state, logits, ld, num_frames, B, K, C, max_frames, V, blank, sm_scale, blank_penalty, parent_out,
+                      token_out, fused<1>(f, g, lm_weight, bias_weight, length_bonus, C), stream);
+}
+
+int pika_msearch_lm_results(const void *state, int B, int K, int C, int max_frames, const long long *fst_offsets,
+                            const int *fst_ilabel, const float *fst_weight, const int *fst_nextstate,
+                            const float *fst_final, int num_states, int num_arcs, int start, int backoff_id,
+                            int label_offset, const long long *fst2_offsets, const int *fst2_ilabel,
+                            const float *fst2_weight, const int *fst2_nextstate, const float *fst2_final,
+                            int num_states2, int num_arcs2, int start2, int backoff_id2, int label_offset2,
+                            float lm_weight, float bias_weight, int use_final, int nbest, int L, long long *tokens,
+                            long long *lengths, float *scores, float *am_scores, void *stream) {
+    const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
+                   label_offset};
+    const Fst g = {fst2_offsets, fst2_ilabel, fst2_weight, fst2_nextstate, fst2_final, num_states2, num_arcs2,
+                   backoff_id2, label_offset2};
+    if (!std::isfinite(lm_weight) || !std::isfinite(bias_weight)) return PIKA_EINVAL;
+    const int two = second_fst(g, start2);
+    if (two < 0 || check_fst(f, start)) return PIKA_EINVAL;
+    if (int rc = check_read(B, K, C, max_frames, nbest, L)) return rc;
+    if (!state || !tokens || !lengths || !scores || !am_scores) return PIKA_EINVAL;
+    if (two)
+        return read_out<2>(state, B, K, C, max_frames, nbest, L, tokens, lengths, scores, am_scores,
+                           fused<2>(f, g, lm_weight, bias_weight, 0.0f, C), use_final != 0, stream);
+    return read_out<1>(state, B, K, C, max_frames, nbest, L, tokens, lengths, scores, am_scores,
+                       fused<1>(f, g, lm_weight, bias_weight, 0.0f, C), use_final != 0, stream);
+}
+
+int pika_msearch_lm_hyps(const void *state, int B, int K, int C, int max_frames, int L, long long *tokens,
+                         long long *lengths, void *stream) {
+    if (int rc = check_read(B, K, C, max_frames, K, L)) return rc;
+    if (!state || !tokens || !lengths) return PIKA_EINVAL;
+    // (the slots in the beam's order: no automaton is walked, the kernel takes an empty one)
+    return read_out<1>(state, B, K, C, max_frames, K, L, tokens, lengths, nullptr, nullptr,
+                       fused<1>(Fst{}, Fst{}, 0.0f, 0.0f, 0.0f, C), 0, stream);
 }
 
 }  // extern "C"

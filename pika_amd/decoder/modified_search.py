@@ -6,6 +6,10 @@ utterance of T_n frames takes T_n steps, a batch max(T_n), known before the firs
 `ModifiedBeamState` is the search state and its frame step (include/pika_msearch.h, csrc/msearch.hip);
 `modified_beam_search` drives a transducer model through it.  The definition of a step is in the header and in DESIGN.md
 section 3, "Modified beam search"; `_torch_step` below spells it in plain torch.
+
+`ModifiedLmBeamState` / `modified_beam_search_lm` are the same with an n-gram LM, a hotword list or both fused into the
+ranking (include/pika_msearch_lm.h; DESIGN.md section 3, "Modified beam search with an LM"): the `lm` is what the CTC
+searches take -- a `CtcNgramLm`, a `CtcHotwords` alone, or a `CtcBiasedLm` pair.
 """
 import torch
 
@@ -42,7 +46,95 @@ def _torch_step(scores, logits, blank, sm_scale, blank_penalty):
     return sel
 
 
-class ModifiedBeamState(object):
+class _BeamState(object):
+    """What the search states share: the views of the state, and the checks and the allocation of a call's tensors."""
+
+    @property
+    def frames(self):
+        return self._frames
+
+    @property
+    def scores(self):
+        return self._scores
+
+    @property
+    def overflowed(self):
+        return self._over != 0
+
+    def _which(self, which):
+        if which is not None:
+            which = torch.as_tensor(which)
+            if which.dtype not in (torch.bool, torch.int32, torch.int64):
+                raise TypeError("which must be bool, int32 or int64, got %s" % which.dtype)
+            which = which.reshape(-1).to(self.device, torch.int32).contiguous()
+            if which.numel() != self.batch:
+                raise ValueError("which must hold batch = %d entries" % self.batch)
+        return which
+
+    def _check_logits(self, logits, num_frames):
+        if not isinstance(logits, torch.Tensor):
+            raise TypeError("logits must be a tensor")
+        if self.native and not logits.is_cuda:
+            raise RuntimeError("pika_amd %s: logits must live on a HIP device (the state does)" % type(self).__name__)
+        if logits.dtype != self.dtype:
+            raise TypeError("logits must be %s, got %s" % (self.dtype, logits.dtype))
+        if logits.device != self.device:
+            raise ValueError("the state lives on %s, logits on %s" % (self.device, logits.device))
+        if logits.dim() != 2 or logits.shape[0] != self.batch * self.beam:
+            raise ValueError("logits must be (batch * beam, V) = (%d, V), got %s" % (self.batch * self.beam,
+                                                                                 tuple(logits.shape)))
+        V = logits.shape[1]
+        if V < 2 or not 0 <= self.blank < V:
+            raise ValueError("need V >= 2 and 0 <= blank < V, got V=%d, blank=%d" % (V, self.blank))
+        if logits.stride(1) != 1 or logits.stride(0) < V:
+            raise ValueError("logits rows must be contiguous (class stride 1, row stride >= V), got strides %s"
+                             % (tuple(logits.stride()),))
+        num_frames = torch.as_tensor(num_frames)
+        if num_frames.dtype not in (torch.int32, torch.int64) or num_frames.numel() != self.batch:
+            raise ValueError("num_frames must be (batch,) int32 or int64")
+        return logits, num_frames.reshape(-1).to(self.device, torch.int64).contiguous()
+
+    @staticmethod
+    def _finite(sm_scale, blank_penalty):
+        sm_scale, blank_penalty = float(sm_scale), float(blank_penalty)
+        if sm_scale != sm_scale or sm_scale in (float("inf"), -float("inf")) or blank_penalty != blank_penalty \
+                or blank_penalty in (float("inf"), -float("inf")):
+            raise ValueError("sm_scale and blank_penalty must be finite")
+        return sm_scale, blank_penalty
+
+    def _nbest(self, nbest):
+        nbest = int(nbest)
+        if not 1 <= nbest <= self.beam:
+            raise ValueError("need 1 <= nbest <= beam = %d, got nbest=%d" % (self.beam, nbest))
+        return nbest
+
+    def _read(self, n, max_len):
+        L = self.max_frames if max_len is None else int(max_len)
+        if L < 1:
+            raise ValueError("max_len must be >= 1, got %d" % L)
+        B, K = self.batch, self.beam
+        if self.native:
+            with torch.cuda.device(self.device):
+                tokens = torch.empty((B, n, L), dtype=torch.int64, device=self.device)
+                lengths = torch.empty((B, n), dtype=torch.int64, device=self.device)
+            return tokens, lengths, L
+        tokens = torch.full((B, n, L), -1, dtype=torch.int64)
+        lengths = torch.full((B, n), -1, dtype=torch.int64)
+        for b in range(B):
+            nodes = self._tries[b][1]
+            for j in range(n):
+                if self._scores[b, j] > -float("inf"):
+                    seq, node = [], self._node[b][j]
+                    while node != 0:
+                        node, tok = nodes[node]
+                        seq.append(tok)
+                    seq.reverse()
+                    lengths[b, j] = len(seq)
+                    tokens[b, j, :min(len(seq), L)] = torch.tensor(seq[:L], dtype=torch.int64)
+        return tokens.to(self.device), lengths.to(self.device), L
+
+
+class ModifiedBeamState(_BeamState):
     """The state of a one-symbol-per-frame beam search over `batch` utterances of at most `max_frames` frames with
     `beam` slots each, and its frame step.
 
@@ -105,28 +197,6 @@ class ModifiedBeamState(object):
             self._tries = [None] * batch                          # per utterance: ({(parent, token): node}, [(parent, token)])
         self.reset()
 
-    @property
-    def frames(self):
-        return self._frames
-
-    @property
-    def scores(self):
-        return self._scores
-
-    @property
-    def overflowed(self):
-        return self._over != 0
-
-    def _which(self, which):
-        if which is not None:
-            which = torch.as_tensor(which)
-            if which.dtype not in (torch.bool, torch.int32, torch.int64):
-                raise TypeError("which must be bool, int32 or int64, got %s" % which.dtype)
-            which = which.reshape(-1).to(self.device, torch.int32).contiguous()
-            if which.numel() != self.batch:
-                raise ValueError("which must hold batch = %d entries" % self.batch)
-        return which
-
     def reset(self, which=None):
         which = self._which(which)
         if self.native:
@@ -143,34 +213,8 @@ class ModifiedBeamState(object):
             self._node[b] = [0] * self.beam
             self._tries[b] = ({}, [(-1, -1)])
 
-    def _check_logits(self, logits, num_frames):
-        if not isinstance(logits, torch.Tensor):
-            raise TypeError("logits must be a tensor")
-        if self.native and not logits.is_cuda:
-            raise RuntimeError("pika_amd ModifiedBeamState: logits must live on a HIP device (the state does)")
-        if logits.dtype != self.dtype:
-            raise TypeError("logits must be %s, got %s" % (self.dtype, logits.dtype))
-        if logits.device != self.device:
-            raise ValueError("the state lives on %s, logits on %s" % (self.device, logits.device))
-        if logits.dim() != 2 or logits.shape[0] != self.batch * self.beam:
-            raise ValueError("logits must be (batch * beam, V) = (%d, V), got %s" % (self.batch * self.beam,
-                                                                                 tuple(logits.shape)))
-        V = logits.shape[1]
-        if V < 2 or not 0 <= self.blank < V:
-            raise ValueError("need V >= 2 and 0 <= blank < V, got V=%d, blank=%d" % (V, self.blank))
-        if logits.stride(1) != 1 or logits.stride(0) < V:
-            raise ValueError("logits rows must be contiguous (class stride 1, row stride >= V), got strides %s"
-                             % (tuple(logits.stride()),))
-        num_frames = torch.as_tensor(num_frames)
-        if num_frames.dtype not in (torch.int32, torch.int64) or num_frames.numel() != self.batch:
-            raise ValueError("num_frames must be (batch,) int32 or int64")
-        return logits, num_frames.reshape(-1).to(self.device, torch.int64).contiguous()
-
     def advance(self, logits, num_frames, sm_scale=1.0, blank_penalty=0.0):
-        sm_scale, blank_penalty = float(sm_scale), float(blank_penalty)
-        if sm_scale != sm_scale or sm_scale in (float("inf"), -float("inf")) or blank_penalty != blank_penalty \
-                or blank_penalty in (float("inf"), -float("inf")):
-            raise ValueError("sm_scale and blank_penalty must be finite")
+        sm_scale, blank_penalty = self._finite(sm_scale, blank_penalty)
         logits, num_frames = self._check_logits(logits, num_frames)
         B, K, V = self.batch, self.beam, logits.shape[1]
         if self.native:
@@ -231,35 +275,8 @@ class ModifiedBeamState(object):
                 parent[j], token[j] = 0, blank
         self._node[b] = new_nodes
 
-    def _read(self, n, max_len):
-        L = self.max_frames if max_len is None else int(max_len)
-        if L < 1:
-            raise ValueError("max_len must be >= 1, got %d" % L)
-        B, K = self.batch, self.beam
-        if self.native:
-            with torch.cuda.device(self.device):
-                tokens = torch.empty((B, n, L), dtype=torch.int64, device=self.device)
-                lengths = torch.empty((B, n), dtype=torch.int64, device=self.device)
-            return tokens, lengths, L
-        tokens = torch.full((B, n, L), -1, dtype=torch.int64)
-        lengths = torch.full((B, n), -1, dtype=torch.int64)
-        for b in range(B):
-            nodes = self._tries[b][1]
-            for j in range(n):
-                if self._scores[b, j] > -float("inf"):
-                    seq, node = [], self._node[b][j]
-                    while node != 0:
-                        node, tok = nodes[node]
-                        seq.append(tok)
-                    seq.reverse()
-                    lengths[b, j] = len(seq)
-                    tokens[b, j, :min(len(seq), L)] = torch.tensor(seq[:L], dtype=torch.int64)
-        return tokens.to(self.device), lengths.to(self.device), L
-
     def results(self, nbest=1, max_len=None):
-        nbest = int(nbest)
-        if not 1 <= nbest <= self.beam:
-            raise ValueError("need 1 <= nbest <= beam = %d, got nbest=%d" % (self.beam, nbest))
+        nbest = self._nbest(nbest)
         tokens, lengths, L = self._read(nbest, max_len)
         if self.native:
             with torch.cuda.device(self.device):
@@ -277,6 +294,116 @@ class ModifiedBeamState(object):
                 _lib.check(_lib.lib().pika_msearch_hyps(
                     _ptr(self._state), self.batch, self.beam, self.max_frames, L, _ptr(tokens), _ptr(lengths),
                     _stream()), "pika_msearch_hyps")
+        return tokens, lengths
+
+
+class ModifiedLmBeamState(_BeamState):
+    """`ModifiedBeamState` with an n-gram LM, a hotword list or both fused into the ranking (include/pika_msearch_lm.h).
+
+    lm   a `CtcNgramLm` -- which includes a `CtcHotwords` phrase list alone (use lm_weight=1.0) -- or a `CtcBiasedLm`
+         pair; anything else is a TypeError.  The object is what the CTC searches take: one upload serves both.
+    A slot carries am, the log-sum of the paths kept, and bonus = lm_weight * LM(l) + bias_weight * BIAS(l) +
+    length_bonus * |l| of its token sequence l; the beam is ranked by the fused score F = am + bonus.  Per step the
+    `candidates` best of F[k] + log_softmax(...)[v] are taken first (None: min(2 * beam, 64); beam <= candidates <= 64:
+    `candidates=beam` is icefall's rule, more lets the LM rescue what the acoustic cut would drop), each label walks
+    the automata -- a token an automaton does not reach is dropped whatever the weights -- equal sequences merge their
+    am, and the `beam` best by fused score stay.  With zero weights, candidates=beam and automata that reach every
+    class it is `ModifiedBeamState` bit for bit.
+
+    advance(logits, num_frames, sm_scale=1.0, blank_penalty=0.0) -> (parent, token)   as `ModifiedBeamState.advance`
+    results(nbest=1, max_len=None, use_final=True) -> (tokens, lengths, scores, am_scores): use_final adds lm_weight *
+        final(state) + bias_weight * final2(state2), drops the entries without a final state and sorts again (a
+        `CtcHotwords` refunds the match in progress there); the state is only read.
+    hyps(max_len=None), reset(which=None)   as `ModifiedBeamState`'s
+    frames, scores (F), am_scores, overflowed   live views of the state.
+
+    HIP float32 only: there is no CPU path (RuntimeError), as for `CtcNgramLm`.  Every call is a kernel launch with no
+    host synchronisation, capturable in a `torch.cuda.graph`."""
+
+    def __init__(self, batch, max_frames, lm, beam=4, blank=0, lm_weight=0.5, length_bonus=0.0, candidates=None,
+                 device=None):
+        from ..ctc import _Search, _hip_device
+        batch, max_frames, beam, blank = int(batch), int(max_frames), int(beam), int(blank)
+        if not 1 <= beam <= MAX_BEAM:
+            raise ValueError("need 1 <= beam <= %d, got beam=%d" % (MAX_BEAM, beam))
+        if batch < 1 or max_frames < 1 or blank < 0:
+            raise ValueError("need batch >= 1, max_frames >= 1 and blank >= 0, got %d, %d, %d" % (batch, max_frames, blank))
+        candidates = min(2 * beam, MAX_BEAM) if candidates is None else int(candidates)
+        if not beam <= candidates <= MAX_BEAM:
+            raise ValueError("need beam <= candidates <= %d, got beam=%d, candidates=%d" % (MAX_BEAM, beam, candidates))
+        v = _Search(lm, lm_weight, length_bonus, True)              # (TypeError unless an LM or a pair)
+        for name, w in (("lm_weight", v.lm_weight), ("bias_weight", v.bias_weight), ("length_bonus", v.length_bonus)):
+            if w != w or w in (float("inf"), -float("inf")):
+                raise ValueError("%s must be finite" % name)
+        self.device = _hip_device(device if device is not None else v.lm.device, "cuda", "ModifiedLmBeamState")
+        v.check_against(0, self.device, "the state")                # (no class yet: the devices alone)
+        self.batch, self.max_frames, self.beam, self.blank, self.candidates = batch, max_frames, beam, blank, candidates
+        self.dtype, self.native, self._v = torch.float32, True, v
+        self._dims = (batch, beam, candidates, max_frames)
+        nbytes = _lib.lib().pika_msearch_lm_state_bytes(*self._dims)
+        if nbytes == 0:
+            raise ValueError("(batch,max_frames,beam,candidates) = (%d,%d,%d,%d) not supported"
+                             % (batch, max_frames, beam, candidates))
+        with torch.cuda.device(self.device):
+            self._state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        BK = batch * beam           # the layout of include/pika_msearch_lm.h
+        self._scores = self._state[8 * BK:12 * BK].view(torch.float32).view(batch, beam)
+        self._am = self._state[12 * BK:16 * BK].view(torch.float32).view(batch, beam)
+        self._frames = self._state[32 * BK:32 * BK + 4 * batch].view(torch.int32)
+        self._over = self._state[32 * BK + 4 * batch:32 * BK + 8 * batch].view(torch.int32)
+        self.reset()
+
+    @property
+    def am_scores(self):
+        return self._am
+
+    def _fsts(self, start):
+        """The automata as the C ABI takes them; "none" for the second where there is one alone."""
+        none = (None,) * 5 + (0, 0) + ((0,) if start else ()) + (0, 0)
+        return self._v.fsts(start) + (none if self._v.bias is None else ())
+
+    def _weights(self):
+        return (self._v.lm_weight, self._v.bias_weight if self._v.bias is not None else 0.0)
+
+    def reset(self, which=None):
+        which = self._which(which)
+        starts = self._v.starts() + ((0, 0) if self._v.bias is None else ())
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().pika_msearch_lm_reset(*((_ptr(self._state),) + self._dims + starts
+                                                          + (_ptr(which), _stream()))), "pika_msearch_lm_reset")
+
+    def advance(self, logits, num_frames, sm_scale=1.0, blank_penalty=0.0):
+        sm_scale, blank_penalty = self._finite(sm_scale, blank_penalty)
+        logits, num_frames = self._check_logits(logits, num_frames)
+        B, K, V = self.batch, self.beam, logits.shape[1]
+        self._v.check_against(V, self.device, "the state")
+        with torch.cuda.device(self.device):
+            parent = torch.empty((B, K), dtype=torch.int64, device=self.device)
+            token = torch.empty((B, K), dtype=torch.int64, device=self.device)
+            _lib.check(_lib.lib().pika_msearch_lm_advance(*(
+                (_ptr(self._state), _ptr(logits), logits.stride(0), _ptr(num_frames)) + self._dims
+                + (V, self.blank, sm_scale, blank_penalty) + self._fsts(False) + self._weights()
+                + (self._v.length_bonus, _ptr(parent), _ptr(token), _stream()))), "pika_msearch_lm_advance")
+        return parent, token
+
+    def results(self, nbest=1, max_len=None, use_final=True):
+        nbest = self._nbest(nbest)
+        tokens, lengths, L = self._read(nbest, max_len)
+        with torch.cuda.device(self.device):
+            scores = torch.empty((self.batch, nbest), dtype=torch.float32, device=self.device)
+            am_scores = torch.empty((self.batch, nbest), dtype=torch.float32, device=self.device)
+            _lib.check(_lib.lib().pika_msearch_lm_results(*(
+                (_ptr(self._state),) + self._dims + self._fsts(True) + self._weights()
+                + (1 if use_final else 0, nbest, L, _ptr(tokens), _ptr(lengths), _ptr(scores), _ptr(am_scores),
+                   _stream()))), "pika_msearch_lm_results")
+        return tokens, lengths, scores, am_scores
+
+    def hyps(self, max_len=None):
+        tokens, lengths, L = self._read(self.beam, max_len)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().pika_msearch_lm_hyps(*((_ptr(self._state),) + self._dims
+                                                         + (L, _ptr(tokens), _ptr(lengths), _stream()))),
+                       "pika_msearch_lm_hyps")
         return tokens, lengths
 
 
@@ -303,6 +430,28 @@ def modified_beam_search(model, x, x_len, beam=4, nbest=1, sm_scale=1.0, blank_p
     the beam's order by that score; normalising by length and picking the entry to return is the caller's:
     nbest=beam gives every entry's score and length.  Token time stamps: `rnnt_align_modified*` on the returned
     hypotheses.  precision: `pika_amd.gemm.PRECISION` for the products of the call on a HIP device ("fp32": exact)."""
+    return _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, precision,
+                  lambda B, T, dev, dtype: ModifiedBeamState(B, T, int(beam), int(blank), dev, dtype),
+                  lambda state: state.results(nbest=nbest))
+
+
+@torch.no_grad()
+def modified_beam_search_lm(model, x, x_len, lm, beam=4, nbest=1, sm_scale=1.0, blank_penalty=0.0, use_graph=True,
+                            blank=0, precision="fp16x2", lm_weight=0.5, length_bonus=0.0, candidates=None,
+                            use_final=True):
+    """`modified_beam_search` with an n-gram LM, a hotword list or both fused into the ranking: `lm`, `lm_weight`,
+    `length_bonus` and `candidates` are `ModifiedLmBeamState`'s, `use_final` its `results`'.  HIP only.
+    -> (tokens, lengths, scores, am_scores, enc_out): scores are the fused scores the entries are ordered by, am_scores
+    the summed log-probabilities of the paths kept alone (what `modified_beam_search` calls scores)."""
+    return _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, precision,
+                  lambda B, T, dev, dtype: ModifiedLmBeamState(B, T, lm, int(beam), int(blank), lm_weight, length_bonus,
+                                                               candidates, dev),
+                  lambda state: state.results(nbest=nbest, use_final=use_final))
+
+
+def _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, precision, make_state, results):
+    """The loop of `modified_beam_search` around a search state: make_state(B, T, device, dtype) -> the state,
+    results(state) -> what the call returns ahead of enc_out."""
     from .. import gemm as G
     from ..model import ops
     K, blank = int(beam), int(blank)
@@ -322,7 +471,7 @@ def modified_beam_search(model, x, x_len, beam=4, nbest=1, sm_scale=1.0, blank_p
         steps = min(max(int(x_len.max()), 0), T)               # (the one host read, before the first launch)
         num_frames = x_len.to(dev).long().clamp(0, T)
         rnn = model.decoder_type == 'rnn'
-        state = ModifiedBeamState(B, T, K, blank, dev, enc_out.dtype)
+        state = make_state(B, T, dev, enc_out.dtype)
 
         w1, wg = model.fc1, model.fc_gate
         e1_all = ops.linear(enc_out, w1.weight[:, :H].contiguous(), w1.bias)
@@ -377,7 +526,7 @@ def modified_beam_search(model, x, x_len, beam=4, nbest=1, sm_scale=1.0, blank_p
                 graph.replay()
             else:
                 step()
-        tokens, lengths, scores = state.results(nbest=nbest)
+        out = tuple(results(state))
     finally:
         G.PRECISION = old
-    return tokens, lengths, scores, enc_out
+    return out + (enc_out,)
