@@ -80,7 +80,8 @@ _RNNT_EXPORTS = ("rnnt_loss_pruned", "rnnt_loss_pruned_from_logits", "rnnt_loss_
 _OPS_EXPORTS = ("joint_pruned",)
 
 # The one-symbol-per-frame beam search (pika_amd/decoder/modified_search.py).
-_MSEARCH_EXPORTS = ("ModifiedBeamState", "modified_beam_search", "ModifiedLmBeamState", "modified_beam_search_lm")
+_MSEARCH_EXPORTS = ("ModifiedBeamState", "modified_beam_search", "ModifiedLmBeamState", "modified_beam_search_lm",
+                    "ModifiedBeamStream", "ModifiedStreamDecoder")
 
 
 def __getattr__(name):

@@ -69,6 +69,12 @@ SIGNATURES = {
                                 + [_vp] * 3),
     "pika_msearch_lm_results": (_i, [_vp] + [_i] * 4 + ([_vp] * 5 + [_i] * 5) * 2 + [_f, _f] + [_i] * 3 + [_vp] * 5),
     "pika_msearch_lm_hyps": (_i, [_vp] + [_i] * 5 + [_vp] * 3),
+    # include/pika_msearch_stream.h
+    "pika_msearch_stream_side_bytes": (_sz, [_i]),
+    "pika_msearch_stream_reset": (_i, [_vp, _i, _vp, _vp]),
+    "pika_msearch_commit_scratch_bytes": (_sz, [_i, _i, _i]),
+    "pika_msearch_commit": (_i, [_vp, _vp] + [_i] * 3 + [_vp] + [_i] * 3 + [_vp] * 5),
+    "pika_msearch_lm_commit": (_i, [_vp, _vp] + [_i] * 4 + [_vp] + [_i] * 3 + [_vp] * 5),
     # include/pika_ctc.h
     "pika_ctc_workspace_bytes": (_sz, [_i, _i, _i]),
     "pika_ctc_align_scratch_bytes": (_sz, [_i, _i, _i]),

@@ -19,6 +19,9 @@
 // automata: stages 1-3 select C = candidates >= K entries by F[k] + lp[k,v]; in stage 4 thread j walks the automata for
 // entry j (fst_walk.h), entries merge by key on their acoustic scores and the groups are ordered by the fused score.
 // The plain instantiation (NFST = 0) has no trace of it (if constexpr).
+//
+// Streaming (include/pika_msearch_stream.h): the side record and msearch_commit_kernel, one template for the two blobs,
+// which emits the labels every slot shares, re-roots and rebuilds the trie and lowers `frames`.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <stdint.h>
@@ -27,6 +30,7 @@
 #include "fst_walk.h"
 #include "pika_msearch.h"
 #include "pika_msearch_lm.h"
+#include "pika_msearch_stream.h"
 
 static_assert(ROOT == PIKA_MSEARCH_ROOT && MAX_BEAM == PIKA_MSEARCH_MAX_BEAM, "the constants the C ABI documents");
 
@@ -540,6 +544,194 @@ __global__ __launch_bounds__(64) void msearch_read_kernel(const void *state, int
 }
 
 // ---------------------------------------------------------------------------------------------
+// streaming (pika_msearch_stream.h): the side record and the commit
+// ---------------------------------------------------------------------------------------------
+struct Side {
+    int *retired;
+    double *offset, *boff;
+};
+
+__host__ __device__ inline Side side_of(void *side, int B) {
+    char *p = static_cast<char *>(side);
+    Side s;
+    s.retired = reinterpret_cast<int *>(p + PIKA_MSEARCH_STREAM_RETIRED_OFFSET(B));
+    s.offset = reinterpret_cast<double *>(p + PIKA_MSEARCH_STREAM_OFFSET_OFFSET(B));
+    s.boff = reinterpret_cast<double *>(p + PIKA_MSEARCH_STREAM_BONUS_OFFSET_OFFSET(B));
+    return s;
+}
+
+__global__ __launch_bounds__(THREADS) void msearch_side_reset_kernel(Side sd, int B, const int *__restrict__ which) {
+    const int b = blockIdx.x * THREADS + threadIdx.x;
+    if (b >= B || (which && which[b] == 0)) return;
+    sd.retired[b] = 0; sd.offset[b] = 0.0; sd.boff[b] = 0.0;
+}
+
+// Commit, one kernel for the two blobs; grid = B, block = 256, as ctc_stream_commit_kernel (ctc_search_core.h), whose walk
+// this is: wave 0's lane r owns slot r and holds what the slot carries in its registers.  The lanes find the live slots'
+// common ancestor -- every slot up to the depth of the shallowest, then all in step until they meet --, lane 0 writes the
+// labels above it, every lane leaves the labels between the new root and its slot in paths[b][r][0, tail), root side
+// first; the table is cleared by the workgroup; the lanes replay their labels through trie_node from ROOT (a node's
+// identity is the table slot of its key, so the parents come first; lanes that share a prefix find each other's keys)
+// and write their slot where it now stands.  Then the keys are counted and `frames` is lowered.  frames, every len and
+// every node bound loops and index the table through its mask: a blob that was never reset ends inside its own memory.
+// NSEL: the keys a step can add (K, or the fused search's C).
+template <bool LM>
+__global__ __launch_bounds__(THREADS) void msearch_commit_kernel(void *state, Side sd, int B, int K, int NSEL,
+                                                                  int max_frames, unsigned mask,
+                                                                  const int *__restrict__ which, int max_tail, int rebase,
+                                                                  int L, long long *__restrict__ tokens,
+                                                                  long long *__restrict__ lengths,
+                                                                  long long *__restrict__ slot_map,
+                                                                  int *__restrict__ paths) {
+    __shared__ int s_depth, s_live, s_tail, s_n;
+    const int b = blockIdx.x, tid = threadIdx.x, r = tid;
+    const size_t bk = (size_t)b * K;
+    long long *out = tokens + (size_t)b * L;
+    if (which && which[b] == 0) {  // workgroup-uniform
+        for (int p = tid; p < L; p += THREADS) out[p] = -1;
+        if (tid < K) slot_map[bk + tid] = tid;
+        if (tid == 0) lengths[b] = 0;
+        return;
+    }
+    const Blob st = blob_of<LM ? 1 : 0>(state, B, K);
+    unsigned long long *table = st.tables + (size_t)b * ((size_t)mask + 1);
+    const int frames = clampi(st.frames[b], 0, max_frames);
+    // one step towards the root; whatever a node holds, the load stays inside the table
+    auto up = [&](int node) __attribute__((always_inline)) {
+        return node == ROOT ? ROOT : (int)(unsigned)(trie_load(table, mask, node) >> 32);
+    };
+    int tail = -1, j = 0, n = 0;  // wave 0, lane r: the labels slot r keeps (-1: it does not stay), its slot afterwards
+    float score = NINF, am = NINF;
+    double bonus = 0.0;
+    int st1 = 0, st2 = 0;
+    if (tid < 64) {
+        if (r < K) {
+            score = st.score[bk + r];
+            if constexpr (LM) {
+                am = st.am[bk + r]; bonus = st.bonus[bk + r]; st1 = st.lmst[bk + r]; st2 = st.lmst2[bk + r];
+            }
+        }
+        // the live slots: the front slots with a score (lanes at and beyond K have none)
+        const unsigned long long dead = __ballot(!(r < K && score > NINF));
+        n = dead ? __ffsll(dead) - 1 : 64;
+        const bool act = r < n;
+        const int node = act ? st.node[bk + r] : ROOT;
+        const int len = act ? clampi(st.len[bk + r], 0, frames) : 0;
+        int lmin = act ? len : 0x7fffffff;
+        for (int o = 32; o > 0; o >>= 1) lmin = min(lmin, __shfl_xor(lmin, o));
+        if (n == 0) lmin = 0;
+        int cur = node;
+        for (int k = len - lmin; k > 0; --k) cur = up(cur);  // (no slot: len = 0, no step)
+        int steps = 0, first;
+        bool same;
+        for (;; ++steps) {  // wave-uniform
+            first = __shfl(cur, 0);
+            same = __all(!act || cur == first);
+            if (same || steps >= lmin) break;
+            cur = up(cur);
+        }
+        int depth = same ? lmin - steps : 0;  // labels from the root to the new root
+        int root = same ? first : ROOT;       // (no meeting point within lmin steps: not a trie; nothing is shared)
+        const int len0 = __shfl(len, 0);
+        if (max_tail >= 0 && n > 0 && len0 - depth > max_tail) {  // wave-uniform: forced
+            int c = node;
+            if (r == 0)
+                for (int k = 0; k < max_tail; ++k) c = up(c);  // max_tail < len0 <= frames
+            root = __shfl(c, 0);
+            depth = len0 - max_tail;
+        }
+        if (r == 0) {  // the committed labels, back from the new root; L may be narrower than the prefix
+            int c = root;
+            for (int p = depth - 1; p >= 0; --p) {
+                long long tok = -1;
+                if (c != ROOT) {
+                    const unsigned long long key = trie_load(table, mask, c);
+                    tok = (long long)(int)(unsigned)(key & 0xffffffffull);
+                    c = (int)(unsigned)(key >> 32);
+                }
+                if (p < L) out[p] = tok;
+            }
+            lengths[b] = depth;
+            s_depth = depth;
+            s_live = 0;
+        }
+        // the labels between the new root and the slot; a slot stays if that walk ends at the new root
+        if (act && len >= depth) {
+            const int tl = len - depth;  // <= frames <= max_frames
+            int *path = paths + (bk + r) * max_frames;
+            int c = node;
+            for (int k = 0; k < tl; ++k) {
+                const unsigned long long key = trie_load(table, mask, c);
+                path[tl - 1 - k] = (int)(unsigned)(key & 0xffffffffull);
+                c = c == ROOT ? ROOT : (int)(unsigned)(key >> 32);
+            }
+            if (c == root) tail = tl;
+        }
+        const unsigned long long kept = __ballot(tail >= 0);
+        j = __popcll(kept & ((1ull << r) - 1ull));
+        int tmax = tail;
+        for (int o = 32; o > 0; o >>= 1) tmax = max(tmax, __shfl_xor(tmax, o));
+        if (r == 0) { s_n = __popcll(kept); s_tail = max(tmax, 0); }
+    }
+    __syncthreads();  // every walk through the old table is over; the slots are in wave 0's registers
+    for (int p = s_depth + tid; p < L; p += THREADS) out[p] = -1;
+    for (size_t i = tid; i <= (size_t)mask; i += THREADS) table[i] = EMPTY;
+    __syncthreads();  // the table is empty
+    if (tid < 64) {
+        const int kept_n = s_n;
+        int node = ROOT;
+        if (tail >= 0) {
+            const int *path = paths + (bk + r) * max_frames;
+            for (int k = 0; k < tail; ++k) node = trie_node(table, mask, node, path[k]);
+        }
+        if (rebase && kept_n > 0) {  // wave-uniform: the new slot 0 is the first slot that stays
+            const int r0 = __ffsll(__ballot(tail >= 0)) - 1;
+            if constexpr (LM) {
+                const float c = __shfl(am, r0);
+                const double e = __shfl(bonus, r0);
+                if (tail >= 0) {
+                    am = __fsub_rn(am, c);
+                    bonus = __dsub_rn(bonus, e);
+                    score = (float)__dadd_rn((double)am, bonus);
+                }
+                if (r == 0) { sd.offset[b] += (double)c; sd.boff[b] += e; }
+            } else {
+                const float c = __shfl(score, r0);
+                if (tail >= 0) score = __fsub_rn(score, c);
+                if (r == 0) sd.offset[b] += (double)c;
+            }
+        }
+        if (tail >= 0) {  // (j <= r, and every lane read its slot before the barrier)
+            st.score[bk + j] = score; st.node[bk + j] = node; st.len[bk + j] = tail;
+            if constexpr (LM) {
+                st.am[bk + j] = am; st.bonus[bk + j] = bonus; st.lmst[bk + j] = st1; st.lmst2[bk + j] = st2;
+            }
+            slot_map[bk + j] = r;
+        }
+        if (r >= kept_n && r < K) {
+            if (r < n) {  // vacated
+                st.score[bk + r] = NINF; st.node[bk + r] = ROOT; st.len[bk + r] = 0;
+                if constexpr (LM) {
+                    st.am[bk + r] = NINF; st.bonus[bk + r] = 0.0; st.lmst[bk + r] = 0; st.lmst2[bk + r] = 0;
+                }
+            }
+            slot_map[bk + r] = r;
+        }
+    }
+    __syncthreads();  // the table holds the live keys
+    int live = 0;
+    for (size_t i = tid; i <= (size_t)mask; i += THREADS) live += trie_load(table, mask, (int)i) != EMPTY;
+    if (live) atomicAdd(&s_live, live);
+    __syncthreads();
+    if (tid == 0) {
+        // the fewest frames that account for the live keys (NSEL per frame) and for the longest tail; never more than before
+        const int fnew = min(max((s_live + NSEL - 1) / NSEL, s_tail), frames);
+        st.frames[b] = fnew;
+        sd.retired[b] += frames - fnew;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host.  C: what sizes the trie's tables -- the entries a step can select: K, or the fused search's candidates
 // ---------------------------------------------------------------------------------------------
 static inline int check_dims(int B, int K, int C, int max_frames) {
@@ -590,6 +782,20 @@ static int advance(void *state, const float *logits, long long ld, const long lo
     hipLaunchKernelGGL((msearch_advance_kernel<NFST>), dim3((unsigned)B), dim3(THREADS), 0,
                        static_cast<hipStream_t>(stream), state, logits, ld, num_frames, B, K, max_frames, V, blank,
                        sm_scale, blank_penalty, (unsigned)(table_slots(max_frames, C) - 1), vec, parent_out, token_out, fu);
+    return (int)hipGetLastError();
+}
+
+static inline int check_streams(int B) { return B <= 0 ? PIKA_EINVAL : (B > 65535 ? PIKA_ETOOBIG : PIKA_OK); }
+
+template <bool LM>
+static int commit(void *state, void *side, int B, int K, int C, int max_frames, const int *which, int max_tail, int rebase,
+                  int L, long long *tokens, long long *lengths, long long *slot_map, void *scratch, void *stream) {
+    if (L <= 0) return PIKA_EINVAL;
+    if (int rc = check_dims(B, K, C, max_frames)) return rc;
+    if (!state || !side || !tokens || !lengths || !slot_map || !scratch) return PIKA_EINVAL;
+    hipLaunchKernelGGL((msearch_commit_kernel<LM>), dim3((unsigned)B), dim3(THREADS), 0, static_cast<hipStream_t>(stream),
+                       state, side_of(side, B), B, K, C, max_frames, (unsigned)(table_slots(max_frames, C) - 1), which,
+                       max_tail, rebase, L, tokens, lengths, slot_map, static_cast<int *>(scratch));
     return (int)hipGetLastError();
 }
 
@@ -726,6 +932,40 @@ int pika_msearch_lm_hyps(const void *state, int B, int K, int C, int max_frames,
     // (the slots in the beam's order: no automaton is walked, the kernel takes an empty one)
     return read_out<1>(state, B, K, C, max_frames, K, L, tokens, lengths, nullptr, nullptr,
                        fused<1>(Fst{}, Fst{}, 0.0f, 0.0f, 0.0f, C), 0, stream);
+}
+
+// ---- streaming: the side record and the commit of either blob (pika_msearch_stream.h) --------------------------------
+
+size_t pika_msearch_stream_side_bytes(int B) {
+    if (check_streams(B)) return 0;
+    return PIKA_MSEARCH_STREAM_BONUS_OFFSET_OFFSET(B) + PIKA_MSEARCH_STREAM_ROUND16(8 * (size_t)B);
+}
+
+int pika_msearch_stream_reset(void *side, int B, const int *which, void *stream) {
+    if (int rc = check_streams(B)) return rc;
+    if (!side) return PIKA_EINVAL;
+    hipLaunchKernelGGL(msearch_side_reset_kernel, dim3((unsigned)((B + THREADS - 1) / THREADS)), dim3(THREADS), 0,
+                       static_cast<hipStream_t>(stream), side_of(side, B), B, which);
+    return (int)hipGetLastError();
+}
+
+size_t pika_msearch_commit_scratch_bytes(int B, int K, int max_frames) {
+    if (check_dims(B, K, max_frames)) return 0;
+    return sizeof(int) * (size_t)B * K * max_frames;
+}
+
+int pika_msearch_commit(void *state, void *side, int B, int K, int max_frames, const int *which, int max_tail,
+                        int rebase, int L, long long *tokens, long long *lengths, long long *slot_map, void *scratch,
+                        void *stream) {
+    return commit<false>(state, side, B, K, K, max_frames, which, max_tail, rebase, L, tokens, lengths, slot_map, scratch,
+                         stream);
+}
+
+int pika_msearch_lm_commit(void *state, void *side, int B, int K, int C, int max_frames, const int *which, int max_tail,
+                           int rebase, int L, long long *tokens, long long *lengths, long long *slot_map, void *scratch,
+                           void *stream) {
+    return commit<true>(state, side, B, K, C, max_frames, which, max_tail, rebase, L, tokens, lengths, slot_map, scratch,
+                        stream);
 }
 
 }  // extern "C"

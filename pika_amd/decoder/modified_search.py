@@ -10,6 +10,10 @@ section 3, "Modified beam search"; `_torch_step` below spells it in plain torch.
 `ModifiedLmBeamState` / `modified_beam_search_lm` are the same with an n-gram LM, a hotword list or both fused into the
 ranking (include/pika_msearch_lm.h; DESIGN.md section 3, "Modified beam search with an LM"): the `lm` is what the CTC
 searches take -- a `CtcNgramLm`, a `CtcHotwords` alone, or a `CtcBiasedLm` pair.
+
+`ModifiedBeamStream` wraps either state into a stream that outlives `max_frames` (include/pika_msearch_stream.h;
+DESIGN.md section 3, "Streaming modified beam search"): `commit` emits the labels every hypothesis shares and gives the
+capacity back.  `ModifiedStreamDecoder` drives a model with the LSTM prediction network through it chunk by chunk.
 """
 import torch
 
@@ -405,6 +409,321 @@ class ModifiedLmBeamState(_BeamState):
                                                          + (L, _ptr(tokens), _ptr(lengths), _stream()))),
                        "pika_msearch_lm_hyps")
         return tokens, lengths
+
+
+class ModifiedBeamStream(object):
+    """A one-symbol-per-frame beam search that outlives its buffer (include/pika_msearch_stream.h; DESIGN.md section 3,
+    "Streaming modified beam search"): a `ModifiedBeamState` (lm is None) or a `ModifiedLmBeamState` (`lm`, `lm_weight`,
+    `length_bonus`, `candidates` are its arguments), exposed as `.state`, with a side record per stream -- the frames the
+    commits gave back and the fp64 offsets of the scores -- and `commit`.
+
+    advance(logits, num_frames, sm_scale=1.0, blank_penalty=0.0) -> (parent, token)   the state's step; num_frames
+        (batch,) is the ABSOLUTE number of frames offered to each stream so far (the stream passes num_frames - retired on,
+        a device subtraction), and the rows of stream b are those of its frame consumed[b].
+    commit(which=None, max_tail=None, rebase=False, max_len=None) -> (tokens (batch, L) int64, -1 beyond the length;
+        lengths (batch,) int64; slot_map (batch, beam) int64).  The labels that every live hypothesis of a stream shares can
+        never change again: they are returned, the trie is re-rooted below them and rebuilt with what the slots still
+        need, and `frames` drops to what that takes, so `room` grows.  max_tail=m forces it: when the best hypothesis
+        would keep more than m labels, everything but its last m is committed and the hypotheses that disagree are
+        dropped; slot_map[b, j] is the old slot of new slot j (the identity otherwise): re-order a prediction network's
+        state by it as by advance's `parent`.  rebase=True moves the best slot's score (LM: its am and its bonus) into
+        `offset` (`bonus_offset`), float64: absolute scores are scores + offset (LM: am_scores + offset and
+        scores + offset + bonus_offset).  Without rebase a stream equals the one-shot search bit for bit; a rebase changes
+        the rounding of what follows.  Unselected streams (`which`) get length 0 and are not touched.
+        L = max_len or max_frames.
+    results(...), hyps(max_len=None)   the state's own: the UNCOMMITTED tails, scores relative to the offsets.
+    reset(which=None)   the state and the side record.
+    frames (held capacity), retired, consumed = frames + retired, room = max_frames - frames, offset, bonus_offset
+        (float64, zero until a rebase), scores, overflowed   live views or device expressions, no host read.
+
+    On a HIP device every call is a kernel launch with no host synchronisation, capturable in a `torch.cuda.graph`.  On
+    the CPU or with dtype=torch.float64 (plain search only) `commit` runs in Python on the state's dict tries, by the
+    same definition, in the state's dtype."""
+
+    def __init__(self, batch, max_frames, beam=4, blank=0, lm=None, lm_weight=0.5, length_bonus=0.0, candidates=None,
+                 device=None, dtype=None):
+        if lm is None:
+            if candidates is not None or lm_weight != 0.5 or length_bonus != 0.0:
+                raise ValueError("candidates, lm_weight and length_bonus belong to the search with an LM (lm is None)")
+            self.state = ModifiedBeamState(batch, max_frames, beam, blank, device, dtype)
+        else:
+            if dtype not in (None, torch.float32):
+                raise TypeError("the search with an LM is float32 only, got dtype=%s" % dtype)
+            self.state = ModifiedLmBeamState(batch, max_frames, lm, beam, blank, lm_weight, length_bonus, candidates,
+                                             device)
+        s = self.state
+        self.batch, self.max_frames, self.beam, self.blank = s.batch, s.max_frames, s.beam, s.blank
+        self.device, self.dtype, self.native, self.lm = s.device, s.dtype, s.native, lm is not None
+        B = self.batch
+        if self.native:
+            lib = _lib.lib()
+            self._dims = s._dims if self.lm else (B, self.beam, self.max_frames)
+            o1 = (4 * B + 15) & ~15                   # the layout of include/pika_msearch_stream.h
+            o2 = o1 + ((8 * B + 15) & ~15)
+            with torch.cuda.device(self.device):
+                self._side = torch.empty(lib.pika_msearch_stream_side_bytes(B), dtype=torch.uint8, device=self.device)
+                self._scratch = torch.empty(lib.pika_msearch_commit_scratch_bytes(B, self.beam, self.max_frames),
+                                            dtype=torch.uint8, device=self.device)
+            self._retired = self._side[:4 * B].view(torch.int32)
+            self._offset = self._side[o1:o1 + 8 * B].view(torch.float64)
+            self._boff = self._side[o2:o2 + 8 * B].view(torch.float64)
+        else:
+            self._retired = torch.empty(B, dtype=torch.int32, device=self.device)
+            self._offset = torch.empty(B, dtype=torch.float64, device=self.device)
+            self._boff = torch.empty(B, dtype=torch.float64, device=self.device)
+        self._reset_side(None)
+
+    frames = property(lambda self: self.state.frames)
+    retired = property(lambda self: self._retired)
+    consumed = property(lambda self: self.state.frames + self._retired)
+    room = property(lambda self: self.max_frames - self.state.frames)
+    offset = property(lambda self: self._offset)
+    bonus_offset = property(lambda self: self._boff)
+    scores = property(lambda self: self.state.scores)
+    overflowed = property(lambda self: self.state.overflowed)
+
+    def _reset_side(self, which):
+        if self.native:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().pika_msearch_stream_reset(_ptr(self._side), self.batch, _ptr(which), _stream()),
+                           "pika_msearch_stream_reset")
+            return
+        sel = slice(None) if which is None else which.bool()
+        self._retired[sel] = 0
+        self._offset[sel] = 0.0
+        self._boff[sel] = 0.0
+
+    def reset(self, which=None):
+        which = self.state._which(which)
+        self.state.reset(which)
+        self._reset_side(which)
+
+    def advance(self, logits, num_frames, sm_scale=1.0, blank_penalty=0.0):
+        num_frames = torch.as_tensor(num_frames)
+        if num_frames.dtype not in (torch.int32, torch.int64) or num_frames.numel() != self.batch:
+            raise ValueError("num_frames must be (batch,) int32 or int64")
+        held = num_frames.reshape(-1).to(self.device, torch.int64) - self._retired.to(torch.int64)
+        return self.state.advance(logits, held, sm_scale, blank_penalty)
+
+    def results(self, *args, **kwargs):
+        return self.state.results(*args, **kwargs)
+
+    def hyps(self, max_len=None):
+        return self.state.hyps(max_len)
+
+    def commit(self, which=None, max_tail=None, rebase=False, max_len=None):
+        which = self.state._which(which)
+        max_tail = -1 if max_tail is None else int(max_tail)
+        if max_tail < 0 and max_tail != -1:
+            raise ValueError("max_tail must be None or >= 0, got %d" % max_tail)
+        L = self.max_frames if max_len is None else int(max_len)
+        if L < 1:
+            raise ValueError("max_len must be >= 1, got %d" % L)
+        B, K = self.batch, self.beam
+        if not self.native:
+            return self._commit_cpu(which, max_tail, bool(rebase), L)
+        with torch.cuda.device(self.device):
+            tokens = torch.empty((B, L), dtype=torch.int64, device=self.device)
+            lengths = torch.empty(B, dtype=torch.int64, device=self.device)
+            slot_map = torch.empty((B, K), dtype=torch.int64, device=self.device)
+            fn, name = ((_lib.lib().pika_msearch_lm_commit, "pika_msearch_lm_commit") if self.lm else
+                        (_lib.lib().pika_msearch_commit, "pika_msearch_commit"))
+            _lib.check(fn(*((_ptr(self.state._state), _ptr(self._side)) + self._dims
+                            + (_ptr(which), max_tail, 1 if rebase else 0, L, _ptr(tokens), _ptr(lengths), _ptr(slot_map),
+                               _ptr(self._scratch), _stream()))), name)
+        return tokens, lengths, slot_map
+
+    def _commit_cpu(self, which, max_tail, rebase, L):
+        """The commit's definition on the dict tries of `ModifiedBeamState`."""
+        s, B, K, ninf = self.state, self.batch, self.beam, -float("inf")
+        tokens = torch.full((B, L), -1, dtype=torch.int64)
+        lengths = torch.zeros(B, dtype=torch.int64)
+        slot_map = torch.arange(K, dtype=torch.int64).repeat(B, 1)
+        sel = range(B) if which is None else [b for b, w in enumerate(which.tolist()) if w]
+        for b in sel:
+            nodes = s._tries[b][1]
+            n = 0                                               # the live slots: the front slots with a score
+            while n < K and s._scores[b, n] > ninf:
+                n += 1
+            seqs = []
+            for j in range(n):
+                seq, node = [], s._node[b][j]
+                while node != 0:
+                    node, tok = nodes[node]
+                    seq.append(tok)
+                seqs.append(seq[::-1])
+            d = min(len(q) for q in seqs) if n else 0           # the depth of the common ancestor
+            while d > 0 and any(q[:d] != seqs[0][:d] for q in seqs):
+                d -= 1
+            if max_tail >= 0 and n and len(seqs[0]) - d > max_tail:
+                d = len(seqs[0]) - max_tail
+            keep = [j for j in range(n) if seqs[j][:d] == seqs[0][:d] and len(seqs[j]) >= d]
+            if n:
+                lengths[b] = d
+                tokens[b, :min(d, L)] = torch.tensor(seqs[0][:min(d, L)], dtype=torch.int64)
+            index, new_nodes = {}, [(-1, -1)]                   # the trie again, parents first
+            old = s._scores[b].clone()
+            for jn, j in enumerate(keep):
+                node = 0
+                for tok in seqs[j][d:]:
+                    nxt = index.get((node, tok))
+                    if nxt is None:
+                        nxt = index[(node, tok)] = len(new_nodes)
+                        new_nodes.append((node, tok))
+                    node = nxt
+                s._node[b][jn] = node
+                s._scores[b, jn] = old[j]
+                slot_map[b, jn] = j
+            for jn in range(len(keep), n):                      # vacated: as a reset leaves an empty slot
+                s._node[b][jn] = 0
+                s._scores[b, jn] = ninf
+                slot_map[b, jn] = jn
+            s._tries[b] = (index, new_nodes)
+            frames = int(s._frames[b])
+            tail = max([len(seqs[j]) - d for j in keep] + [0])
+            fnew = min(frames, max((len(new_nodes) - 1 + K - 1) // K, tail))
+            s._frames[b] = fnew
+            self._retired[b] += frames - fnew
+            if rebase and keep:
+                c = s._scores[b, 0].clone()
+                live = s._scores[b] > ninf
+                s._scores[b] = torch.where(live, s._scores[b] - c, s._scores[b])
+                self._offset[b] += c.double()
+        return tokens.to(self.device), lengths.to(self.device), slot_map.to(self.device)
+
+
+class ModifiedStreamDecoder(object):
+    """`modified_beam_search` chunk by chunk, for audio without an end: a transducer model (`pika_amd.model.transducer.
+    Net`) with the LSTM prediction network (`decoder_type == 'rnn'`; anything else raises NotImplementedError -- the
+    conv-transformer cache is its own item) around a `ModifiedBeamStream` (`.stream`) of `batch` streams.  `lm`,
+    `lm_weight`, `length_bonus`, `candidates` are the stream's.
+
+    advance(enc_chunk (batch, Tc, H), lengths=None)   Tc frame steps on a chunk of ENCODER output; lengths (batch,): the
+        chunk's frames that count for each stream (None: Tc).  The joint's encoder halves are computed once per chunk;
+        per step the rows are gathered by consumed - chunk start, `(h, c)` is re-ordered by `parent` and stepped where
+        token != blank.  Between two commits a stream takes at most `room` frames (`stream.overflowed` otherwise).
+    commit(which=None, max_tail=None, rebase=False) -> (tokens, lengths, slot_map)   the stream's commit; `(h, c)` is
+        re-ordered by slot_map and the new labels join the streams' committed text (one host read).
+    results(nbest=1, max_len=None, **kw) -> (committed tokens (batch, Lc) int64, -1 beyond the length; committed lengths
+        (batch,); tail tokens (batch, nbest, L); tail lengths (batch, nbest); scores (batch, nbest), relative to the
+        stream's offsets): a hypothesis is the committed text followed by its tail.
+    reset(which=None)   the stream, `(h, c)` and the committed text of the selected streams."""
+
+    def __init__(self, model, batch, max_frames, beam=4, lm=None, lm_weight=0.5, length_bonus=0.0, candidates=None,
+                 sm_scale=1.0, blank_penalty=0.0, blank=0, precision="fp16x2"):
+        from .. import gemm as G
+        if getattr(model, "decoder_type", None) != 'rnn':
+            raise NotImplementedError("ModifiedStreamDecoder steps the LSTM prediction network (decoder_type == 'rnn') "
+                                      "only; the conv-transformer cache is not wired in")
+        if precision not in G.PRECISIONS:
+            raise ValueError("unknown precision %r" % (precision,))
+        p = next(model.parameters())
+        self.model, self.precision = model, precision
+        self.sm_scale, self.blank_penalty = _BeamState._finite(sm_scale, blank_penalty)
+        self.stream = ModifiedBeamStream(batch, max_frames, beam, blank, lm, lm_weight, length_bonus, candidates,
+                                         p.device, None if lm is not None else p.dtype)
+        s = self.stream
+        self.batch, self.beam, self.blank, self.device = s.batch, s.beam, s.blank, s.device
+        w1, wg = model.fc1, model.fc_gate
+        H = self.H = w1.weight.shape[1] - model.decoder.hidden_size       # the encoder's share of the joint's input
+        self.J = w1.weight.shape[0]
+        self._we = torch.cat((w1.weight[:, :H], wg.weight[:, :H]), dim=0).contiguous()    # enc -> [e1 | eg]
+        self._be = torch.cat((w1.bias, wg.bias), dim=0).contiguous()
+        self._wp = torch.cat((w1.weight[:, H:], wg.weight[:, H:]), dim=0).contiguous()    # pred -> [p1 | pg]
+        self._flat0 = (torch.arange(self.batch, device=self.device) * self.beam).unsqueeze(1)
+        self._offered = torch.zeros(self.batch, dtype=torch.int64, device=self.device)
+        self._pred = None
+        self._text = [[] for _ in range(self.batch)]
+        self.reset()
+
+    def _precision(self):
+        from .. import gemm as G
+        old = G.PRECISION
+        if self.device.type == "cuda":
+            G.PRECISION = self.precision
+        return G, old
+
+    @torch.no_grad()
+    def reset(self, which=None):
+        which = self.stream.state._which(which)
+        self.stream.reset(which)
+        G, old = self._precision()
+        try:
+            sos = torch.full((self.batch * self.beam, 1), self.blank, dtype=torch.long, device=self.device)
+            _, st = self.model.decoder(self.model.embed(sos))
+        finally:
+            G.PRECISION = old
+        fresh = [st[0].contiguous(), st[1].contiguous()]
+        if which is None or self._pred is None:
+            self._pred = fresh
+            self._offered.zero_()
+            self._text = [[] for _ in range(self.batch)]
+            return
+        rows = which.bool().repeat_interleave(self.beam).view(1, -1, 1)
+        for cur, new in zip(self._pred, fresh):
+            cur.copy_(torch.where(rows, new, cur))
+        self._offered.masked_fill_(which.bool(), 0)
+        for b, w in enumerate(which.tolist()):
+            if w:
+                self._text[b] = []
+
+    @torch.no_grad()
+    def advance(self, enc_chunk, lengths=None):
+        from ..model import ops
+        B, K, H, model = self.batch, self.beam, self.H, self.model
+        if enc_chunk.dim() != 3 or enc_chunk.shape[0] != B or enc_chunk.shape[2] != H:
+            raise ValueError("enc_chunk must be (batch, Tc, H) = (%d, Tc, %d), got %s" % (B, H, tuple(enc_chunk.shape)))
+        Tc = enc_chunk.shape[1]
+        if Tc == 0:
+            return
+        if lengths is None:
+            lengths = torch.full((B,), Tc, dtype=torch.int64, device=self.device)
+        else:
+            lengths = torch.as_tensor(lengths)
+            if lengths.dtype not in (torch.int32, torch.int64) or lengths.numel() != B:
+                raise ValueError("lengths must be (batch,) int32 or int64")
+            lengths = lengths.reshape(-1).to(self.device, torch.int64).clamp(0, Tc)
+        G, old = self._precision()
+        try:
+            start = self._offered.clone()
+            self._offered += lengths
+            J = self.J
+            e_all = ops.linear(enc_chunk.contiguous(), self._we, self._be).reshape(B * Tc, 2 * J)   # row b*Tc + t
+            brow = torch.arange(B, device=self.device) * Tc
+            hh, cc = self._pred
+            for _ in range(Tc):
+                tg = (self.stream.consumed.long() - start).clamp(0, Tc - 1)
+                rows = (brow + tg).unsqueeze(1).expand(B, K).reshape(-1)
+                z = e_all.index_select(0, rows) + ops.linear(hh[-1], self._wp)
+                h = torch.tanh(z[:, :J]) * torch.sigmoid(z[:, J:])
+                logits = ops.linear(h, model.fc2.weight, model.fc2.bias).contiguous()
+                parent, token = self.stream.advance(logits, self._offered, self.sm_scale, self.blank_penalty)
+                flat = (self._flat0 + parent).reshape(-1)
+                hh.copy_(hh.index_select(1, flat))
+                cc.copy_(cc.index_select(1, flat))
+                _, (h2, c2) = model.decoder(model.embed(token.reshape(-1, 1)), (hh, cc))
+                m = token.reshape(-1).ne(self.blank).view(1, -1, 1)
+                hh.copy_(torch.where(m, h2, hh))
+                cc.copy_(torch.where(m, c2, cc))
+        finally:
+            G.PRECISION = old
+
+    @torch.no_grad()
+    def commit(self, which=None, max_tail=None, rebase=False):
+        tokens, lengths, slot_map = self.stream.commit(which, max_tail, rebase)
+        flat = (self._flat0 + slot_map).reshape(-1)
+        for s_ in self._pred:
+            s_.copy_(s_.index_select(1, flat))
+        for b, (row, n) in enumerate(zip(tokens.tolist(), lengths.tolist())):
+            self._text[b] += row[:n]
+        return tokens, lengths, slot_map
+
+    def results(self, nbest=1, max_len=None, **kwargs):
+        out = self.stream.results(nbest, max_len, **kwargs)
+        Lc = max([len(t) for t in self._text] + [1])
+        committed = torch.tensor([t + [-1] * (Lc - len(t)) for t in self._text], dtype=torch.int64, device=self.device)
+        clen = torch.tensor([len(t) for t in self._text], dtype=torch.int64, device=self.device)
+        return committed, clen, out[0], out[1], out[2]
 
 
 @torch.no_grad()
