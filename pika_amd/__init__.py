@@ -81,7 +81,7 @@ _OPS_EXPORTS = ("joint_pruned",)
 
 # The one-symbol-per-frame beam search (pika_amd/decoder/modified_search.py).
 _MSEARCH_EXPORTS = ("ModifiedBeamState", "modified_beam_search", "ModifiedLmBeamState", "modified_beam_search_lm",
-                    "ModifiedBeamStream", "ModifiedStreamDecoder")
+                    "ModifiedBeamStream", "ModifiedStreamDecoder", "ModifiedBeamTimes", "modified_beam_search_timed")
 
 
 def __getattr__(name):

@@ -75,6 +75,13 @@ SIGNATURES = {
     "pika_msearch_commit_scratch_bytes": (_sz, [_i, _i, _i]),
     "pika_msearch_commit": (_i, [_vp, _vp] + [_i] * 3 + [_vp] + [_i] * 3 + [_vp] * 5),
     "pika_msearch_lm_commit": (_i, [_vp, _vp] + [_i] * 4 + [_vp] + [_i] * 3 + [_vp] * 5),
+    # include/pika_msearch_times.h
+    "pika_msearch_times_bytes": (_sz, [_i, _i, _i]),
+    "pika_msearch_times_reset": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "pika_msearch_times_step": (_i, [_vp] * 3 + [_i] * 4 + [_vp, _vp, _i, _vp]),
+    "pika_msearch_times_hyps": (_i, [_vp, _vp] + [_i] * 5 + [_vp, _vp]),
+    "pika_msearch_times_results": (_i, [_vp, _vp] + [_i] * 6 + [_vp] * 4),
+    "pika_msearch_times_commit": (_i, [_vp, _vp] + [_i] * 4 + [_vp] * 3 + [_i] + [_vp] * 2),
     # include/pika_ctc.h
     "pika_ctc_workspace_bytes": (_sz, [_i, _i, _i]),
     "pika_ctc_align_scratch_bytes": (_sz, [_i, _i, _i]),

@@ -22,6 +22,9 @@
 //
 // Streaming (include/pika_msearch_stream.h): the side record and msearch_commit_kernel, one template for the two blobs,
 // which emits the labels every slot shares, re-roots and rebuilds the trie and lowers `frames`.
+//
+// Time stamps (include/pika_msearch_times.h): a record of emission frames per slot that lives beside either blob and
+// follows the (parent, token) pairs of the step; its kernels only read the blobs.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <stdint.h>
@@ -31,6 +34,7 @@
 #include "pika_msearch.h"
 #include "pika_msearch_lm.h"
 #include "pika_msearch_stream.h"
+#include "pika_msearch_times.h"
 
 static_assert(ROOT == PIKA_MSEARCH_ROOT && MAX_BEAM == PIKA_MSEARCH_MAX_BEAM, "the constants the C ABI documents");
 
@@ -732,6 +736,190 @@ __global__ __launch_bounds__(THREADS) void msearch_commit_kernel(void *state, Si
 }
 
 // ---------------------------------------------------------------------------------------------
+// time stamps (pika_msearch_times.h): the record beside a blob.  The kernels read the blob -- score, len, node, frames,
+// the table -- and never write it.
+// ---------------------------------------------------------------------------------------------
+struct Times {
+    int *seen, *lost, *cur;
+    int *planes;   // two planes of [B][K][max_frames]
+    size_t plane;  // elements of one
+};
+
+__host__ __device__ inline Times times_of(void *times, int B, int K, int max_frames) {
+    char *p = static_cast<char *>(times);
+    Times t;
+    t.seen = reinterpret_cast<int *>(p + PIKA_MSEARCH_TIMES_SEEN_OFFSET(B));
+    t.lost = reinterpret_cast<int *>(p + PIKA_MSEARCH_TIMES_LOST_OFFSET(B));
+    t.cur = reinterpret_cast<int *>(p + PIKA_MSEARCH_TIMES_CUR_OFFSET(B));
+    t.planes = reinterpret_cast<int *>(p + PIKA_MSEARCH_TIMES_PLANES_OFFSET(B));
+    t.plane = (size_t)B * K * max_frames;
+    return t;
+}
+
+// row (b, k) of plane p
+__device__ __forceinline__ int *times_row(const Times &t, int p, int b, int K, int k, int max_frames) {
+    return t.planes + (size_t)p * t.plane + ((size_t)b * K + k) * max_frames;
+}
+
+__device__ __forceinline__ int clampll(long long v, int lo, int hi) {
+    return v < lo ? lo : (v > hi ? hi : (int)v);
+}
+
+// n entries from src to dst by one wave; `vec` (wave-uniform): both rows are 16-byte aligned
+__device__ __forceinline__ void times_copy(int *__restrict__ dst, const int *__restrict__ src, int n, int lane, bool vec) {
+    int done = 0;
+    if (vec) {
+        const int n4 = n >> 2;
+        for (int i = lane; i < n4; i += 64) reinterpret_cast<int4 *>(dst)[i] = reinterpret_cast<const int4 *>(src)[i];
+        done = 4 * n4;
+    }
+    for (int p = done + lane; p < n; p += 64) dst[p] = src[p];
+}
+
+// grid = (B, y), block = 256: the workgroups (b, *) fill both planes of utterance b with -1, (b, 0) writes its head
+__global__ __launch_bounds__(THREADS) void msearch_times_reset_kernel(Times tm, int K, int max_frames,
+                                                                       const int *__restrict__ which) {
+    const int b = blockIdx.x;
+    if (which && which[b] == 0) return;  // workgroup-uniform
+    const size_t n = (size_t)K * max_frames;
+    for (int p = 0; p < 2; ++p) {
+        int *row = times_row(tm, p, b, K, 0, max_frames);
+        for (size_t i = (size_t)blockIdx.y * THREADS + threadIdx.x; i < n; i += (size_t)gridDim.y * THREADS) row[i] = -1;
+    }
+    if (blockIdx.y == 0 && threadIdx.x == 0) { tm.seen[b] = 0; tm.lost[b] = 0; tm.cur[b] = 0; }
+}
+
+// The step; grid = B, block = 256: wave w moves the rows of the new slots w, w + 4, ...
+template <bool LM>
+__global__ __launch_bounds__(THREADS) void msearch_times_step_kernel(Times tm, const void *state,
+                                                                      const int *__restrict__ retired, int B, int K,
+                                                                      int max_frames, const long long *__restrict__ parent,
+                                                                      const long long *__restrict__ token, int blank,
+                                                                      int vec) {
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const Blob st = blob_of<LM ? 1 : 0>(const_cast<void *>(state), B, K);
+    const unsigned now = (unsigned)st.frames[b] + (retired ? (unsigned)retired[b] : 0u);  // consumed[b]
+    const unsigned seen = (unsigned)tm.seen[b];
+    const int lost = tm.lost[b], cur = tm.cur[b] & 1;
+    __syncthreads();  // every thread has read the head that thread 0 writes below
+    if (lost != 0 || now == seen) return;  // workgroup-uniform, as what follows
+    if (now != seen + 1u) {
+        if (tid == 0) tm.lost[b] = 1;
+        return;
+    }
+    const int stamp = (int)(now - 1u);
+    for (int j = wave; j < K; j += WAVES) {
+        const size_t bk = (size_t)b * K + j;
+        const int p = clampll(parent[bk], 0, K - 1);
+        const bool label = token[bk] != (long long)blank;
+        const int len = clampi(st.len[bk], 0, max_frames);
+        const int n = label ? max(len - 1, 0) : len;
+        int *dst = times_row(tm, cur ^ 1, b, K, j, max_frames);
+        times_copy(dst, times_row(tm, cur, b, K, p, max_frames), n, lane, vec != 0);
+        if (label && len > 0 && lane == 0) dst[len - 1] = stamp;
+    }
+    if (tid == 0) { tm.cur[b] = cur ^ 1; tm.seen[b] = (int)now; }
+}
+
+// The slots' times; grid = B, block = 256: a wave per slot
+template <bool LM>
+__global__ __launch_bounds__(THREADS) void msearch_times_hyps_kernel(Times tm, const void *state, int B, int K,
+                                                                      int max_frames, int L, long long *__restrict__ out) {
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const Blob st = blob_of<LM ? 1 : 0>(const_cast<void *>(state), B, K);
+    const bool lost = tm.lost[b] != 0;
+    const int cur = tm.cur[b] & 1;
+    for (int j = wave; j < K; j += WAVES) {
+        const size_t bk = (size_t)b * K + j;
+        const bool live = !lost && st.score[bk] > NINF;
+        const int len = live ? clampi(st.len[bk], 0, max_frames) : 0;
+        const int *row = times_row(tm, cur, b, K, j, max_frames);
+        long long *o = out + bk * L;
+        for (int p = lane; p < L; p += 64) o[p] = p < len ? (long long)row[p] : -1ll;
+    }
+}
+
+// The times of an entry of a results call; grid = (B, N), block = 64: lane k walks slot k's path up the trie against the
+// entry's tokens, the first slot that spells them gives its row
+template <bool LM>
+__global__ __launch_bounds__(64) void msearch_times_results_kernel(Times tm, const void *state, int B, int K,
+                                                                    int max_frames, unsigned mask, int N, int L,
+                                                                    const long long *__restrict__ tokens,
+                                                                    const long long *__restrict__ lengths,
+                                                                    long long *__restrict__ out) {
+    const int b = blockIdx.x, e = blockIdx.y, lane = threadIdx.x;
+    const Blob st = blob_of<LM ? 1 : 0>(const_cast<void *>(state), B, K);
+    const unsigned long long *table = st.tables + (size_t)b * ((size_t)mask + 1);
+    const size_t bk = (size_t)b * K, be = (size_t)b * N + e;
+    const long long *tok = tokens + be * L;
+    const long long le = lengths[be];
+    const bool ok = tm.lost[b] == 0 && le >= 0 && le <= (long long)L && le <= (long long)max_frames;  // wave-uniform
+    const int n = ok ? (int)le : 0;
+    bool match = false;
+    if (ok && lane < K && st.score[bk + lane] > NINF && clampi(st.len[bk + lane], 0, max_frames) == n) {
+        int node = st.node[bk + lane];
+        match = true;
+        for (int p = n - 1; p >= 0 && match; --p) {  // bounded by n <= max_frames whatever the table holds
+            if (node == ROOT) { match = false; break; }
+            const unsigned long long key = trie_load(table, mask, node);
+            match = (long long)(int)(unsigned)(key & 0xffffffffull) == tok[p];
+            node = (int)(unsigned)(key >> 32);
+        }
+        match = match && node == ROOT;
+    }
+    const unsigned long long found = __ballot(match);
+    const int slot = found ? __ffsll(found) - 1 : -1;  // < K
+    const int len = slot >= 0 ? n : 0;
+    const int *row = times_row(tm, tm.cur[b] & 1, b, K, slot >= 0 ? slot : 0, max_frames);
+    long long *o = out + be * L;
+    for (int p = lane; p < L; p += 64) o[p] = p < len ? (long long)row[p] : -1ll;
+}
+
+// The commit; grid = B, block = 256.  The threads take the committed positions -- the minimum over the live slots' old
+// rows, which the threads of a wave read side by side --, the waves move the tails.
+template <bool LM>
+__global__ __launch_bounds__(THREADS) void msearch_times_commit_kernel(Times tm, const void *state, int B, int K,
+                                                                        int max_frames, const int *__restrict__ which,
+                                                                        const long long *__restrict__ lengths,
+                                                                        const long long *__restrict__ slot_map, int L,
+                                                                        long long *__restrict__ out, int vec) {
+    __shared__ int s_src[MAX_BEAM], s_len[MAX_BEAM], s_n;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t bk = (size_t)b * K;
+    long long *o = out + (size_t)b * L;
+    const int lost = tm.lost[b], cur = tm.cur[b] & 1;
+    __syncthreads();  // every thread has read the head that thread 0 writes below
+    if ((which && which[b] == 0) || lost != 0) {  // workgroup-uniform
+        for (int p = tid; p < L; p += THREADS) o[p] = -1;
+        return;
+    }
+    const Blob st = blob_of<LM ? 1 : 0>(const_cast<void *>(state), B, K);
+    const int d = clampll(lengths[b], 0, max_frames);
+    if (tid < 64) {
+        // the live slots: the front slots with a score (lanes at and beyond K have none)
+        const unsigned long long dead = __ballot(!(tid < K && st.score[bk + (tid < K ? tid : 0)] > NINF));
+        if (tid < K) {
+            s_src[tid] = clampll(slot_map[bk + tid], 0, K - 1);
+            s_len[tid] = min(clampi(st.len[bk + tid], 0, max_frames), max_frames - d);
+        }
+        if (tid == 0) s_n = dead ? __ffsll(dead) - 1 : 64;
+    }
+    __syncthreads();
+    const int n = s_n;  // <= K
+    const int *old = times_row(tm, cur, b, K, 0, max_frames);
+    for (int i = tid; i < min(d, L); i += THREADS) {
+        int t = n > 0 ? 0x7fffffff : -1;
+        for (int j = 0; j < n; ++j) t = min(t, old[(size_t)s_src[j] * max_frames + i]);
+        o[i] = t;
+    }
+    for (int p = d + tid; p < L; p += THREADS) o[p] = -1;
+    for (int j = wave; j < K; j += WAVES)
+        times_copy(times_row(tm, cur ^ 1, b, K, j, max_frames), old + (size_t)s_src[j] * max_frames + d, s_len[j], lane,
+                   vec != 0 && (d & 3) == 0);
+    if (tid == 0) tm.cur[b] = cur ^ 1;
+}
+
+// ---------------------------------------------------------------------------------------------
 // host.  C: what sizes the trie's tables -- the entries a step can select: K, or the fused search's candidates
 // ---------------------------------------------------------------------------------------------
 static inline int check_dims(int B, int K, int C, int max_frames) {
@@ -821,6 +1009,20 @@ static inline Fused<NFST> fused(const Fst &f, const Fst &g, float lmw, float bw,
     if constexpr (NFST == 2) fu.f[1] = g;
     fu.lmw = lmw; fu.bw = bw; fu.lb = lb; fu.C = C;
     return fu;
+}
+
+// ---- the time record: C = 0 names the plain blob, K <= C the fused search's
+static inline int check_times(int B, int K, int C, int max_frames) {
+    if (C < 0) return PIKA_EINVAL;
+    return check_dims(B, K, C == 0 ? K : C, max_frames);
+}
+
+static inline unsigned times_mask(int K, int C, int max_frames) {
+    return (unsigned)(table_slots(max_frames, C == 0 ? K : C) - 1);
+}
+
+static inline int times_vec(const void *times, int max_frames) {
+    return max_frames % 4 == 0 && reinterpret_cast<uintptr_t>(times) % 16 == 0;
 }
 
 }  // namespace
@@ -966,6 +1168,93 @@ int pika_msearch_lm_commit(void *state, void *side, int B, int K, int C, int max
                            void *stream) {
     return commit<true>(state, side, B, K, C, max_frames, which, max_tail, rebase, L, tokens, lengths, slot_map, scratch,
                         stream);
+}
+
+// ---- time stamps: the record beside either blob (pika_msearch_times.h) ------------------------------------------------
+
+size_t pika_msearch_times_bytes(int B, int K, int max_frames) {
+    if (check_dims(B, K, max_frames)) return 0;
+    return PIKA_MSEARCH_TIMES_PLANES_OFFSET(B) + 2 * sizeof(int) * (size_t)B * K * max_frames;
+}
+
+int pika_msearch_times_reset(void *times, int B, int K, int max_frames, const int *which, void *stream) {
+    if (int rc = check_dims(B, K, max_frames)) return rc;
+    if (!times) return PIKA_EINVAL;
+    const size_t y = ((size_t)K * max_frames) / 4096;  // 16 entries per thread and plane
+    hipLaunchKernelGGL(msearch_times_reset_kernel, dim3((unsigned)B, (unsigned)(y < 1 ? 1 : (y > 256 ? 256 : y))),
+                       dim3(THREADS), 0, static_cast<hipStream_t>(stream), times_of(times, B, K, max_frames), K,
+                       max_frames, which);
+    return (int)hipGetLastError();
+}
+
+int pika_msearch_times_step(void *times, const void *state, const void *side, int B, int K, int C, int max_frames,
+                            const long long *parent, const long long *token, int blank, void *stream) {
+    if (blank < 0) return PIKA_EINVAL;
+    if (int rc = check_times(B, K, C, max_frames)) return rc;
+    if (!times || !state || !parent || !token) return PIKA_EINVAL;
+    const Times tm = times_of(times, B, K, max_frames);
+    const int *retired = side ? side_of(const_cast<void *>(side), B).retired : nullptr;
+    const int vec = times_vec(times, max_frames);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (C)
+        hipLaunchKernelGGL((msearch_times_step_kernel<true>), dim3((unsigned)B), dim3(THREADS), 0, s, tm, state, retired,
+                           B, K, max_frames, parent, token, blank, vec);
+    else
+        hipLaunchKernelGGL((msearch_times_step_kernel<false>), dim3((unsigned)B), dim3(THREADS), 0, s, tm, state, retired,
+                           B, K, max_frames, parent, token, blank, vec);
+    return (int)hipGetLastError();
+}
+
+int pika_msearch_times_hyps(const void *times, const void *state, int B, int K, int C, int max_frames, int L,
+                            long long *out, void *stream) {
+    if (L <= 0) return PIKA_EINVAL;
+    if (int rc = check_times(B, K, C, max_frames)) return rc;
+    if ((long long)K * L > 0x7fffffffll) return PIKA_ETOOBIG;
+    if (!times || !state || !out) return PIKA_EINVAL;
+    const Times tm = times_of(const_cast<void *>(times), B, K, max_frames);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (C)
+        hipLaunchKernelGGL((msearch_times_hyps_kernel<true>), dim3((unsigned)B), dim3(THREADS), 0, s, tm, state, B, K,
+                           max_frames, L, out);
+    else
+        hipLaunchKernelGGL((msearch_times_hyps_kernel<false>), dim3((unsigned)B), dim3(THREADS), 0, s, tm, state, B, K,
+                           max_frames, L, out);
+    return (int)hipGetLastError();
+}
+
+int pika_msearch_times_results(const void *times, const void *state, int B, int K, int C, int max_frames, int N, int L,
+                               const long long *tokens, const long long *lengths, long long *out, void *stream) {
+    if (N <= 0 || L <= 0) return PIKA_EINVAL;
+    if (int rc = check_times(B, K, C, max_frames)) return rc;
+    if (N > K || (long long)N * L > 0x7fffffffll) return PIKA_ETOOBIG;
+    if (!times || !state || !tokens || !lengths || !out) return PIKA_EINVAL;
+    const Times tm = times_of(const_cast<void *>(times), B, K, max_frames);
+    const unsigned mask = times_mask(K, C, max_frames);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (C)
+        hipLaunchKernelGGL((msearch_times_results_kernel<true>), dim3((unsigned)B, (unsigned)N), dim3(64), 0, s, tm, state,
+                           B, K, max_frames, mask, N, L, tokens, lengths, out);
+    else
+        hipLaunchKernelGGL((msearch_times_results_kernel<false>), dim3((unsigned)B, (unsigned)N), dim3(64), 0, s, tm,
+                           state, B, K, max_frames, mask, N, L, tokens, lengths, out);
+    return (int)hipGetLastError();
+}
+
+int pika_msearch_times_commit(void *times, const void *state, int B, int K, int C, int max_frames, const int *which,
+                              const long long *lengths, const long long *slot_map, int L, long long *out, void *stream) {
+    if (L <= 0) return PIKA_EINVAL;
+    if (int rc = check_times(B, K, C, max_frames)) return rc;
+    if (!times || !state || !lengths || !slot_map || !out) return PIKA_EINVAL;
+    const Times tm = times_of(times, B, K, max_frames);
+    const int vec = times_vec(times, max_frames);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (C)
+        hipLaunchKernelGGL((msearch_times_commit_kernel<true>), dim3((unsigned)B), dim3(THREADS), 0, s, tm, state, B, K,
+                           max_frames, which, lengths, slot_map, L, out, vec);
+    else
+        hipLaunchKernelGGL((msearch_times_commit_kernel<false>), dim3((unsigned)B), dim3(THREADS), 0, s, tm, state, B, K,
+                           max_frames, which, lengths, slot_map, L, out, vec);
+    return (int)hipGetLastError();
 }
 
 }  // extern "C"

@@ -14,6 +14,10 @@ searches take -- a `CtcNgramLm`, a `CtcHotwords` alone, or a `CtcBiasedLm` pair.
 `ModifiedBeamStream` wraps either state into a stream that outlives `max_frames` (include/pika_msearch_stream.h;
 DESIGN.md section 3, "Streaming modified beam search"): `commit` emits the labels every hypothesis shares and gives the
 capacity back.  `ModifiedStreamDecoder` drives a model with the LSTM prediction network through it chunk by chunk.
+
+`ModifiedBeamTimes` keeps the token time stamps of any of the three next to it (include/pika_msearch_times.h; DESIGN.md
+section 3, "Time stamps of the modified beam search"); `modified_beam_search_timed` and
+`ModifiedStreamDecoder.track_times` are its drivers.
 """
 import torch
 
@@ -592,6 +596,228 @@ class ModifiedBeamStream(object):
         return tokens.to(self.device), lengths.to(self.device), slot_map.to(self.device)
 
 
+class ModifiedBeamTimes(object):
+    """The token time stamps of a one-symbol-per-frame beam search (include/pika_msearch_times.h; DESIGN.md section 3,
+    "Time stamps of the modified beam search"): a record kept NEXT TO `search` -- a `ModifiedBeamState`, a
+    `ModifiedLmBeamState` or a `ModifiedBeamStream`, whose batch, beam, max_frames, blank and device it takes -- that
+    holds, for every slot and every label of the slot's current token sequence, the ABSOLUTE index of the frame at which
+    the slot's lineage emitted the label.  A slot's lineage is its representative's: the best-ranked member of every
+    merged group, whose old slot and token `advance` returns as (parent, token).  Integers only: exact, bit for bit.
+
+    step(parent, token)   after EVERY `advance` of the search, with what it returned.  An utterance that the advance left
+        alone is left alone; an utterance whose `consumed` moved by anything but one frame since the last step -- a step
+        was skipped, or the search was reset without the record -- is LOST: `lost[b]` is set and its read-outs give -1
+        until `reset` selects it.
+    hyps(max_len=None) -> (batch, beam, L) int64: the times of the current slots, in the order of the search's `hyps`;
+        -1 beyond the length and for empty slots.
+    results(tokens, lengths) -> (batch, N, L) int64: the times of the entries that any `results(...)` call of the search
+        returned, each found by its tokens among the live slots (`ModifiedLmBeamState.results(use_final=True)` re-ranks
+        and drops slots); -1 for a missing entry, for an entry longer than L and for one no live slot spells.
+    commit(lengths, slot_map, which=None, max_len=None) -> (batch, L) int64: right after `ModifiedBeamStream.commit`,
+        with that call's lengths, slot_map and `which`: the times of the committed labels, -1 beyond the length, and
+        the record re-rooted as the search was.  The time of a committed label is the EARLIEST over the hypotheses that
+        are live after the commit -- they share the labels, not necessarily their lineages --, which keeps a stream's
+        committed times followed by any live tail's times strictly increasing under every schedule.
+    reset(which=None)   with the search's reset.
+    lost   live view, (batch,) bool.
+
+    Tokens are bit for bit the one-shot search's under any commit schedule; times equal the one-shot search's without
+    commits, under any chunking.  With commits the committed times are final by definition: the one-shot search's best
+    hypothesis may carry another member's lineage for a label that a stream committed earlier.
+
+    Where the search runs its HIP kernels so does the record (no host synchronisation, capturable in a
+    `torch.cuda.graph`); where the search runs in plain torch (CPU, float64) the record runs in numpy by the same
+    definition."""
+
+    def __init__(self, search):
+        if isinstance(search, ModifiedBeamStream):
+            state = search.state
+        elif isinstance(search, (ModifiedBeamState, ModifiedLmBeamState)):
+            state = search
+        else:
+            raise TypeError("search must be a ModifiedBeamState, a ModifiedLmBeamState or a ModifiedBeamStream, got %s"
+                            % type(search).__name__)
+        self.search, self._st = search, state
+        self._stream = search if state is not search else None
+        self.batch, self.beam, self.max_frames, self.blank = state.batch, state.beam, state.max_frames, state.blank
+        self.device, self.native = state.device, state.native
+        B, K, mf = self.batch, self.beam, self.max_frames
+        if self.native:
+            self._C = state.candidates if isinstance(state, ModifiedLmBeamState) else 0
+            nbytes = _lib.lib().pika_msearch_times_bytes(B, K, mf)
+            if nbytes == 0:
+                raise ValueError("(batch,max_frames,beam) = (%d,%d,%d) not supported" % (B, mf, K))
+            with torch.cuda.device(self.device):
+                self._rec = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._seen = self._rec[:4 * B].view(torch.int32)        # the layout of include/pika_msearch_times.h
+            self._lost = self._rec[4 * B:8 * B].view(torch.int32)
+            self._dims = (B, K, self._C, mf)
+        else:
+            import numpy as np
+            self._seen = np.zeros(B, np.int64)
+            self._lost = torch.zeros(B, dtype=torch.int32)
+            self._rows = [[[] for _ in range(K)] for _ in range(B)]
+        self.reset()
+
+    @property
+    def lost(self):
+        return self._lost != 0
+
+    def _side(self):
+        return _ptr(self._stream._side) if self._stream is not None else None
+
+    def _length(self, max_len):
+        L = self.max_frames if max_len is None else int(max_len)
+        if L < 1:
+            raise ValueError("max_len must be >= 1, got %d" % L)
+        return L
+
+    def _pairs(self, a, b, shape, names):
+        out = []
+        for t, name in zip((a, b), names):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int64:
+                raise TypeError("%s must be an int64 tensor" % name)
+            if t.device != self.device:
+                raise ValueError("the record lives on %s, %s on %s" % (self.device, name, t.device))
+            out.append(t.contiguous())
+        if tuple(out[1].shape) != shape:
+            raise ValueError("%s must be %s, got %s" % (names[1], shape, tuple(out[1].shape)))
+        return out
+
+    # ---- the plain spelling of the definition (CPU, float64) --------------------------------------------------------
+    def _consumed(self):
+        at = self._st.frames.cpu().long()
+        if self._stream is not None:
+            at = at + self._stream.retired.cpu().long()
+        return at.tolist()
+
+    def _lens(self, b):
+        """len of every slot of utterance b: the depth of its node in the state's dict trie."""
+        nodes, out = self._st._tries[b][1], []
+        for node in self._st._node[b]:
+            n = 0
+            while node != 0:
+                node, n = nodes[node][0], n + 1
+            out.append(n)
+        return out
+
+    def _live(self, b):
+        return [bool(s > -float("inf")) for s in self._st.scores[b].cpu()]
+
+    def reset(self, which=None):
+        which = self._st._which(which)
+        if self.native:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().pika_msearch_times_reset(_ptr(self._rec), self.batch, self.beam, self.max_frames,
+                                                               _ptr(which), _stream()), "pika_msearch_times_reset")
+            return
+        for b in (range(self.batch) if which is None else [b for b, w in enumerate(which.tolist()) if w]):
+            self._seen[b], self._lost[b] = 0, 0
+            self._rows[b] = [[] for _ in range(self.beam)]
+
+    def step(self, parent, token):
+        B, K = self.batch, self.beam
+        parent, token = self._pairs(parent, token, (B, K), ("parent", "token"))
+        if tuple(parent.shape) != (B, K):
+            raise ValueError("parent must be (%d, %d), got %s" % (B, K, tuple(parent.shape)))
+        if self.native:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().pika_msearch_times_step(*(
+                    (_ptr(self._rec), _ptr(self._st._state), self._side()) + self._dims
+                    + (_ptr(parent), _ptr(token), self.blank, _stream()))), "pika_msearch_times_step")
+            return
+        parent, token = parent.cpu().tolist(), token.cpu().tolist()
+        for b, now in enumerate(self._consumed()):
+            if self._lost[b] or now == self._seen[b]:
+                continue
+            if now != self._seen[b] + 1:
+                self._lost[b] = 1
+                continue
+            old, lens, new = self._rows[b], self._lens(b), []
+            for j in range(K):
+                label = token[b][j] != self.blank
+                n = max(lens[j] - 1, 0) if label else lens[j]
+                row = list(old[min(max(parent[b][j], 0), K - 1)][:n])
+                if label and lens[j] > 0:
+                    row.append(now - 1)
+                new.append(row)
+            self._rows[b], self._seen[b] = new, now
+
+    def hyps(self, max_len=None):
+        L = self._length(max_len)
+        B, K = self.batch, self.beam
+        if self.native:
+            with torch.cuda.device(self.device):
+                out = torch.empty((B, K, L), dtype=torch.int64, device=self.device)
+                _lib.check(_lib.lib().pika_msearch_times_hyps(*(
+                    (_ptr(self._rec), _ptr(self._st._state)) + self._dims + (L, _ptr(out), _stream()))),
+                    "pika_msearch_times_hyps")
+            return out
+        out = torch.full((B, K, L), -1, dtype=torch.int64)
+        for b in range(B):
+            if not self._lost[b]:
+                for k, (live, n) in enumerate(zip(self._live(b), self._lens(b))):
+                    if live:
+                        row = self._rows[b][k][:min(n, L)]
+                        out[b, k, :len(row)] = torch.tensor(row, dtype=torch.int64)
+        return out.to(self.device)
+
+    def results(self, tokens, lengths):
+        if not isinstance(tokens, torch.Tensor) or tokens.dim() != 3 or tokens.shape[0] != self.batch \
+                or not 1 <= tokens.shape[1] <= self.beam or tokens.shape[2] < 1:
+            raise ValueError("tokens must be (batch, N, L) with 1 <= N <= beam, as a results call returned them")
+        B, N, L = tokens.shape
+        tokens, lengths = self._pairs(tokens, lengths, (B, N), ("tokens", "lengths"))
+        if self.native:
+            with torch.cuda.device(self.device):
+                out = torch.empty((B, N, L), dtype=torch.int64, device=self.device)
+                _lib.check(_lib.lib().pika_msearch_times_results(*(
+                    (_ptr(self._rec), _ptr(self._st._state)) + self._dims
+                    + (N, L, _ptr(tokens), _ptr(lengths), _ptr(out), _stream()))), "pika_msearch_times_results")
+            return out
+        out = torch.full((B, N, L), -1, dtype=torch.int64)
+        hyp, ln = (t.cpu() for t in self._st.hyps())
+        tokens, lengths = tokens.cpu(), lengths.cpu().tolist()
+        for b in range(B):
+            for e in range(N):
+                n = lengths[b][e]
+                if self._lost[b] or not 0 <= n <= min(L, self.max_frames):
+                    continue
+                for k in range(self.beam):
+                    if int(ln[b, k]) == n and torch.equal(hyp[b, k, :n], tokens[b, e, :n]):
+                        out[b, e, :n] = torch.tensor(self._rows[b][k][:n], dtype=torch.int64)
+                        break
+        return out.to(self.device)
+
+    def commit(self, lengths, slot_map, which=None, max_len=None):
+        L = self._length(max_len)
+        B, K = self.batch, self.beam
+        which = self._st._which(which)
+        lengths, slot_map = self._pairs(lengths, slot_map, (B, K), ("lengths", "slot_map"))
+        if tuple(lengths.shape) != (B,):
+            raise ValueError("lengths must be (%d,), got %s" % (B, tuple(lengths.shape)))
+        if self.native:
+            with torch.cuda.device(self.device):
+                out = torch.empty((B, L), dtype=torch.int64, device=self.device)
+                _lib.check(_lib.lib().pika_msearch_times_commit(*(
+                    (_ptr(self._rec), _ptr(self._st._state)) + self._dims
+                    + (_ptr(which), _ptr(lengths), _ptr(slot_map), L, _ptr(out), _stream()))),
+                    "pika_msearch_times_commit")
+            return out
+        out = torch.full((B, L), -1, dtype=torch.int64)
+        lengths, slot_map = lengths.cpu().tolist(), slot_map.cpu().tolist()
+        for b in (range(B) if which is None else [b for b, w in enumerate(which.tolist()) if w]):
+            if self._lost[b]:
+                continue
+            d, old, live = min(max(lengths[b], 0), self.max_frames), self._rows[b], self._live(b)
+            n = live.index(False) if False in live else K          # the live slots: the front slots with a score
+            src = [min(max(s, 0), K - 1) for s in slot_map[b]]
+            for i in range(min(d, L)):
+                out[b, i] = min(old[src[j]][i] for j in range(n)) if n else -1
+            self._rows[b] = [list(old[src[j]][d:d + m]) for j, m in enumerate(self._lens(b))]
+        return out.to(self.device)
+
+
 class ModifiedStreamDecoder(object):
     """`modified_beam_search` chunk by chunk, for audio without an end: a transducer model (`pika_amd.model.transducer.
     Net`) with the LSTM prediction network (`decoder_type == 'rnn'`; anything else raises NotImplementedError -- the
@@ -607,7 +833,12 @@ class ModifiedStreamDecoder(object):
     results(nbest=1, max_len=None, **kw) -> (committed tokens (batch, Lc) int64, -1 beyond the length; committed lengths
         (batch,); tail tokens (batch, nbest, L); tail lengths (batch, nbest); scores (batch, nbest), relative to the
         stream's offsets): a hypothesis is the committed text followed by its tail.
-    reset(which=None)   the stream, `(h, c)` and the committed text of the selected streams."""
+    reset(which=None)   the stream, `(h, c)` and the committed text of the selected streams.
+    track_times()   before the first `advance`: keeps a `ModifiedBeamTimes` (`.times`) next to the stream.  The step loop
+        then steps it, `commit` (same return value) appends the committed labels' times to the streams' text times, and
+    results_timed(nbest=1, max_len=None, **kw) -> `results(...)`'s tuple + (committed times (batch, Lc) int64, -1 beyond
+        the length; tail times (batch, nbest, L)): absolute encoder frames; committed followed by any tail is strictly
+        increasing.  With tracking off nothing changes."""
 
     def __init__(self, model, batch, max_frames, beam=4, lm=None, lm_weight=0.5, length_bonus=0.0, candidates=None,
                  sm_scale=1.0, blank_penalty=0.0, blank=0, precision="fp16x2"):
@@ -634,7 +865,16 @@ class ModifiedStreamDecoder(object):
         self._offered = torch.zeros(self.batch, dtype=torch.int64, device=self.device)
         self._pred = None
         self._text = [[] for _ in range(self.batch)]
+        self.times, self._ttext, self._started = None, None, False
         self.reset()
+
+    def track_times(self):
+        if self._started:
+            raise RuntimeError("track_times() comes before the first advance")
+        if self.times is None:
+            self.times = ModifiedBeamTimes(self.stream)
+            self._ttext = [[] for _ in range(self.batch)]
+        return self.times
 
     def _precision(self):
         from .. import gemm as G
@@ -647,6 +887,11 @@ class ModifiedStreamDecoder(object):
     def reset(self, which=None):
         which = self.stream.state._which(which)
         self.stream.reset(which)
+        if self.times is not None:
+            self.times.reset(which)
+            for b, w in enumerate([1] * self.batch if which is None else which.tolist()):
+                if w:
+                    self._ttext[b] = []
         G, old = self._precision()
         try:
             sos = torch.full((self.batch * self.beam, 1), self.blank, dtype=torch.long, device=self.device)
@@ -658,6 +903,7 @@ class ModifiedStreamDecoder(object):
             self._pred = fresh
             self._offered.zero_()
             self._text = [[] for _ in range(self.batch)]
+            self._started = False
             return
         rows = which.bool().repeat_interleave(self.beam).view(1, -1, 1)
         for cur, new in zip(self._pred, fresh):
@@ -676,6 +922,7 @@ class ModifiedStreamDecoder(object):
         Tc = enc_chunk.shape[1]
         if Tc == 0:
             return
+        self._started = True
         if lengths is None:
             lengths = torch.full((B,), Tc, dtype=torch.int64, device=self.device)
         else:
@@ -698,6 +945,8 @@ class ModifiedStreamDecoder(object):
                 h = torch.tanh(z[:, :J]) * torch.sigmoid(z[:, J:])
                 logits = ops.linear(h, model.fc2.weight, model.fc2.bias).contiguous()
                 parent, token = self.stream.advance(logits, self._offered, self.sm_scale, self.blank_penalty)
+                if self.times is not None:
+                    self.times.step(parent, token)
                 flat = (self._flat0 + parent).reshape(-1)
                 hh.copy_(hh.index_select(1, flat))
                 cc.copy_(cc.index_select(1, flat))
@@ -716,6 +965,10 @@ class ModifiedStreamDecoder(object):
             s_.copy_(s_.index_select(1, flat))
         for b, (row, n) in enumerate(zip(tokens.tolist(), lengths.tolist())):
             self._text[b] += row[:n]
+        if self.times is not None:
+            when = self.times.commit(lengths, slot_map, which)
+            for b, (row, n) in enumerate(zip(when.tolist(), lengths.tolist())):
+                self._ttext[b] += row[:n]
         return tokens, lengths, slot_map
 
     def results(self, nbest=1, max_len=None, **kwargs):
@@ -724,6 +977,14 @@ class ModifiedStreamDecoder(object):
         committed = torch.tensor([t + [-1] * (Lc - len(t)) for t in self._text], dtype=torch.int64, device=self.device)
         clen = torch.tensor([len(t) for t in self._text], dtype=torch.int64, device=self.device)
         return committed, clen, out[0], out[1], out[2]
+
+    def results_timed(self, nbest=1, max_len=None, **kwargs):
+        if self.times is None:
+            raise RuntimeError("results_timed() needs track_times() before the first advance")
+        out = self.results(nbest, max_len, **kwargs)
+        Lc = out[0].shape[1]
+        when = torch.tensor([t + [-1] * (Lc - len(t)) for t in self._ttext], dtype=torch.int64, device=self.device)
+        return out + (when, self.times.results(out[2], out[3]))
 
 
 @torch.no_grad()
@@ -747,8 +1008,8 @@ def modified_beam_search(model, x, x_len, beam=4, nbest=1, sm_scale=1.0, blank_p
 
     Scores are the summed log-probabilities of the paths the beam kept, NOT length-normalised, and the entries come in
     the beam's order by that score; normalising by length and picking the entry to return is the caller's:
-    nbest=beam gives every entry's score and length.  Token time stamps: `rnnt_align_modified*` on the returned
-    hypotheses.  precision: `pika_amd.gemm.PRECISION` for the products of the call on a HIP device ("fp32": exact)."""
+    nbest=beam gives every entry's score and length.  Token time stamps: `modified_beam_search_timed` returns the frames
+    at which this search emitted the labels.  precision: `pika_amd.gemm.PRECISION` for the products of the call on a HIP device ("fp32": exact)."""
     return _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, precision,
                   lambda B, T, dev, dtype: ModifiedBeamState(B, T, int(beam), int(blank), dev, dtype),
                   lambda state: state.results(nbest=nbest))
@@ -768,9 +1029,43 @@ def modified_beam_search_lm(model, x, x_len, lm, beam=4, nbest=1, sm_scale=1.0, 
                   lambda state: state.results(nbest=nbest, use_final=use_final))
 
 
-def _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, precision, make_state, results):
+@torch.no_grad()
+def modified_beam_search_timed(model, x, x_len, lm=None, beam=4, nbest=1, sm_scale=1.0, blank_penalty=0.0,
+                               use_graph=True, blank=0, precision="fp16x2", lm_weight=0.5, length_bonus=0.0,
+                               candidates=None, use_final=True):
+    """`modified_beam_search` -- `modified_beam_search_lm` when `lm` is given, with its `lm_weight`, `length_bonus`,
+    `candidates` and `use_final`; they must be left alone otherwise -- with token time stamps.
+    -> (tokens, lengths, scores[, am_scores], times, enc_out): times (B, nbest, T) int64, times[b, j, i] the encoder
+    frame at which this search emitted label i of entry j (the lineage of the hypothesis' representative, see
+    `ModifiedBeamTimes`), -1 beyond the length and for a missing entry.  Tokens, lengths and scores are those of the
+    untimed call bit for bit: the record's step sits behind the search's in the same captured graph and only reads."""
+    if lm is None:
+        if candidates is not None or lm_weight != 0.5 or length_bonus != 0.0 or use_final is not True:
+            raise ValueError("lm_weight, length_bonus, candidates and use_final belong to the search with an LM")
+
+        def make_state(B, T, dev, dtype):
+            return ModifiedBeamState(B, T, int(beam), int(blank), dev, dtype)
+        kw = {}
+    else:
+        def make_state(B, T, dev, dtype):
+            return ModifiedLmBeamState(B, T, lm, int(beam), int(blank), lm_weight, length_bonus, candidates, dev)
+        kw = {"use_final": use_final}
+    rec = []
+
+    def hook(state):
+        rec.append(ModifiedBeamTimes(state))
+        return rec[0].step
+
+    def results(state):
+        out = tuple(state.results(nbest=nbest, **kw))
+        return out + (rec[0].results(out[0], out[1]),)
+    return _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, precision, make_state, results, hook)
+
+
+def _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, precision, make_state, results, hook=None):
     """The loop of `modified_beam_search` around a search state: make_state(B, T, device, dtype) -> the state,
-    results(state) -> what the call returns ahead of enc_out."""
+    results(state) -> what the call returns ahead of enc_out, hook(state) -> a callable that every step hands its
+    (parent, token) right after the advance (None: there is none)."""
     from .. import gemm as G
     from ..model import ops
     K, blank = int(beam), int(blank)
@@ -791,6 +1086,7 @@ def _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, pre
         num_frames = x_len.to(dev).long().clamp(0, T)
         rnn = model.decoder_type == 'rnn'
         state = make_state(B, T, dev, enc_out.dtype)
+        after = hook(state) if hook is not None else None
 
         w1, wg = model.fc1, model.fc_gate
         e1_all = ops.linear(enc_out, w1.weight[:, :H].contiguous(), w1.bias)
@@ -817,6 +1113,8 @@ def _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, pre
             h = torch.tanh(z[:, :H]) * torch.sigmoid(z[:, H:])
             logits = ops.linear(h, model.fc2.weight, model.fc2.bias).contiguous()
             parent, token = state.advance(logits, num_frames, sm_scale, blank_penalty)
+            if after is not None:
+                after(parent, token)
             flat = (flat0 + parent).reshape(-1)
             for s_ in pred:
                 s_.copy_(s_.index_select(1 if rnn else 0, flat))
