@@ -81,7 +81,11 @@ _OPS_EXPORTS = ("joint_pruned",)
 
 # The one-symbol-per-frame beam search (pika_amd/decoder/modified_search.py).
 _MSEARCH_EXPORTS = ("ModifiedBeamState", "modified_beam_search", "ModifiedLmBeamState", "modified_beam_search_lm",
-                    "ModifiedBeamStream", "ModifiedStreamDecoder", "ModifiedBeamTimes", "modified_beam_search_timed")
+                    "ModifiedBeamStream", "ModifiedStreamDecoder", "ModifiedBeamTimes", "modified_beam_search_timed",
+                    "ModifiedNnLmBeamState", "modified_beam_search_nnlm")
+
+# The neural LM the search above fuses (pika_amd/model/lm.py).
+_LM_EXPORTS = ("LstmLm",)
 
 
 def __getattr__(name):
@@ -97,9 +101,12 @@ def __getattr__(name):
     if name in _MSEARCH_EXPORTS:
         from .decoder import modified_search
         return getattr(modified_search, name)
+    if name in _LM_EXPORTS:
+        from .model import lm
+        return getattr(lm, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
 def __dir__():
     return sorted(list(globals()) + list(_CTC_EXPORTS) + list(_RNNT_EXPORTS) + list(_OPS_EXPORTS)
-                  + list(_MSEARCH_EXPORTS))
+                  + list(_MSEARCH_EXPORTS) + list(_LM_EXPORTS))

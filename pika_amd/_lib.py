@@ -69,6 +69,11 @@ SIGNATURES = {
                                 + [_vp] * 3),
     "pika_msearch_lm_results": (_i, [_vp] + [_i] * 4 + ([_vp] * 5 + [_i] * 5) * 2 + [_f, _f] + [_i] * 3 + [_vp] * 5),
     "pika_msearch_lm_hyps": (_i, [_vp] + [_i] * 5 + [_vp] * 3),
+    # include/pika_msearch_nn.h
+    "pika_msearch_nn_reset": (_i, [_vp] + [_i] * 8 + [_vp, _vp]),
+    "pika_msearch_nn_advance": (_i, [_vp, _vp, _ll, _vp] + [_i] * 6 + [_f, _f] + ([_vp] * 5 + [_i] * 4) * 2 + [_f] * 3
+                                + [_vp, _ll, _i, _i, _f, _f] + [_vp] * 3),
+    "pika_msearch_nn_results": (_i, [_vp] + [_i] * 4 + ([_vp] * 5 + [_i] * 5) * 2 + [_f, _f] + [_i] * 3 + [_vp] * 5),
     # include/pika_msearch_stream.h
     "pika_msearch_stream_side_bytes": (_sz, [_i]),
     "pika_msearch_stream_reset": (_i, [_vp, _i, _vp, _vp]),

@@ -20,6 +20,10 @@
 // entry j (fst_walk.h), entries merge by key on their acoustic scores and the groups are ordered by the fused score.
 // The plain instantiation (NFST = 0) has no trace of it (if constexpr).
 //
+// The step with a neural LM (include/pika_msearch_nn.h) is the same template again with DENSE: a row of LM logits per old
+// slot.  The wave that takes acoustic row k in stage 1 takes LM row k right behind it, the same pass (row_stats) for the
+// row's max and log-sum-exp; stage 4 adds the third increment.  The fused search's blob, with or without automata.
+//
 // Streaming (include/pika_msearch_stream.h): the side record and msearch_commit_kernel, one template for the two blobs,
 // which emits the labels every slot shares, re-roots and rebuilds the trie and lowers `frames`.
 //
@@ -33,6 +37,7 @@
 #include "fst_walk.h"
 #include "pika_msearch.h"
 #include "pika_msearch_lm.h"
+#include "pika_msearch_nn.h"
 #include "pika_msearch_stream.h"
 #include "pika_msearch_times.h"
 
@@ -106,6 +111,20 @@ struct Fused {
 template <>
 struct Fused<0> {};
 
+// ... and with DENSE the rows of the neural LM (pika_msearch_nn.h).  lb and C are the dense launch's own -- there may be
+// no automaton to carry them -- and hide Fused's: the kernel reads fu.lb and fu.C whatever the variant.
+template <int NFST, bool DENSE>
+struct Step : Fused<NFST> {};
+
+template <int NFST>
+struct Step<NFST, true> : Fused<NFST> {
+    const float *rows;
+    long long rld;
+    int VL, off, rvec;
+    float scale, nnw, lb;
+    int C;
+};
+
 template <int NFST>
 __host__ __device__ inline Blob blob_of(void *state, int B, int K) {
     if constexpr (NFST == 0) return blob_of(state, B, K);
@@ -158,6 +177,37 @@ __device__ __forceinline__ float cand_of(float score, float x, float m, float lo
     return __fadd_rn(score, __fsub_rn(__fsub_rn(x, m), logs));
 }
 
+// One pass of a wave over a row: x = xf(v, logit) for every element, each(v, x) sees it behind the sums.  -> the row's
+// max and log(sum exp(x - max)) in every lane: each lane folds its own elements online, in the order it reads them, the
+// 64 lanes are combined by lane 0's xor tree.  Elements that are -inf or NaN take no part.
+template <class X, class E>
+__device__ __forceinline__ void row_stats(const float *__restrict__ row, int V, int lane, bool vec, X xf, E each,
+                                          float &m_out, float &logs_out) {
+    float m = NINF, s = 0.0f;
+    for_row(row, V, lane, vec, [&](int v, float l) {
+        const float x = xf(v, l);
+        if (x > m) {
+            s = __fadd_rn(__fmul_rn(s, expf(m - x)), 1.0f);
+            m = x;
+        } else if (x > NINF) {
+            s += expf(x - m);
+        }
+        each(v, x);
+    });
+    for (int o = 32; o > 0; o >>= 1) {
+        const float m2 = __shfl_xor(m, o), s2 = __shfl_xor(s, o);
+        const float M = fmaxf(m, m2);
+        if (M > NINF) {
+            const float a = m > NINF ? __fmul_rn(s, expf(m - M)) : 0.0f;
+            const float c = m2 > NINF ? __fmul_rn(s2, expf(m2 - M)) : 0.0f;
+            s = __fadd_rn(a, c);
+        }
+        m = M;
+    }
+    m_out = __shfl(m, 0);
+    logs_out = logf(__shfl(s, 0));
+}
+
 // LM: the fused search's blob; slot 0 starts in the automata's start states
 template <bool LM>
 __global__ __launch_bounds__(THREADS) void msearch_reset_kernel(void *state, int B, int K, size_t slots,
@@ -185,19 +235,20 @@ __global__ __launch_bounds__(THREADS) void msearch_reset_kernel(void *state, int
     }
 }
 
-// NFST: the automata fused in (0: the plain step of pika_msearch.h; 1, 2: the step of pika_msearch_lm.h).  NSEL is the
-// number of entries stages 1-3 select: K, or the fused step's C.
-template <int NFST>
+// NFST: the automata fused in (0: the plain step of pika_msearch.h; 1, 2: the step of pika_msearch_lm.h); DENSE: the
+// rows of a neural LM beside them (pika_msearch_nn.h; NFST = 0, 1, 2).  NSEL is the number of entries stages 1-3 select:
+// K, or the fused step's C.
+template <int NFST, bool DENSE>
 __global__ __launch_bounds__(THREADS) void msearch_advance_kernel(void *state, const float *__restrict__ logits,
                                                                    long long ld, const long long *__restrict__ num_frames,
                                                                    int B, int K, int max_frames, int V, int blank,
                                                                    float sm_scale, float penalty, unsigned mask, int vec,
                                                                    long long *__restrict__ parent_out,
                                                                    long long *__restrict__ token_out,
-                                                                   const Fused<NFST> fu) {
-    constexpr bool LM = NFST > 0;
+                                                                   const Step<NFST, DENSE> fu) {
+    constexpr bool LM = NFST > 0 || DENSE;
     constexpr int NL = LM ? MAX_BEAM : 1;  // the fused step's arrays: per old slot, and per selected entry
-    __shared__ float s_am[NL], s_G[NL];
+    __shared__ float s_am[NL], s_G[NL], s_nm[DENSE ? MAX_BEAM : 1], s_ns[DENSE ? MAX_BEAM : 1];
     __shared__ double s_bonus[NL], s_cbonus[NL];
     __shared__ int s_st[NL], s_st2[NL], s_cst[NL], s_cst2[NL];
     __shared__ float s_score[MAX_BEAM], s_m[MAX_BEAM], s_logs[MAX_BEAM];
@@ -211,7 +262,7 @@ __global__ __launch_bounds__(THREADS) void msearch_advance_kernel(void *state, c
     __shared__ float s_merged[MAX_BEAM];
 
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const Blob st = blob_of<NFST>(state, B, K);
+    const Blob st = blob_of<LM ? 1 : 0>(state, B, K);
     const size_t bk = (size_t)b * K;
     int NSEL = K;
     if constexpr (LM) NSEL = clampi(fu.C, K, MAX_BEAM);
@@ -231,7 +282,7 @@ __global__ __launch_bounds__(THREADS) void msearch_advance_kernel(void *state, c
         if constexpr (LM) {  // (a state outside its table: lm_step finds no child; clamped all the same)
             s_am[tid] = st.am[bk + tid];
             s_bonus[tid] = st.bonus[bk + tid];
-            s_st[tid] = clampi(st.lmst[bk + tid], 0, fu.f[0].S - 1);
+            if constexpr (NFST >= 1) s_st[tid] = clampi(st.lmst[bk + tid], 0, fu.f[0].S - 1);
             if constexpr (NFST == 2) s_st2[tid] = clampi(st.lmst2[bk + tid], 0, fu.f[1].S - 1);
         }
     }
@@ -243,32 +294,14 @@ __global__ __launch_bounds__(THREADS) void msearch_advance_kernel(void *state, c
         const float score = s_score[k];
         if (!(score > NINF)) continue;  // wave-uniform: an empty slot
         const float *row = logits + (bk + k) * ld;
-        float m = NINF, s = 0.0f, bx = NINF;
+        float m, logs, bx = NINF;
         int bv = 0x7fffffff;
-        for_row(row, V, lane, vec != 0, [&](int v, float l) {
-            const float x = scaled(l, v, blank, sm_scale, penalty);
-            if (x > m) {
-                s = __fadd_rn(__fmul_rn(s, expf(m - x)), 1.0f);
-                m = x;
-            } else if (x > NINF) {
-                s += expf(x - m);
-            }
-            if (x > bx) { bx = x; bv = v; }
-        });
-        // the row's (max, sum): lane 0's tree, handed to every lane
-        for (int o = 32; o > 0; o >>= 1) {
-            const float m2 = __shfl_xor(m, o), s2 = __shfl_xor(s, o);
-            const float M = fmaxf(m, m2);
-            if (M > NINF) {
-                const float a = m > NINF ? __fmul_rn(s, expf(m - M)) : 0.0f;
-                const float c = m2 > NINF ? __fmul_rn(s2, expf(m2 - M)) : 0.0f;
-                s = __fadd_rn(a, c);
-            }
-            m = M;
-        }
-        m = __shfl(m, 0);
-        s = __shfl(s, 0);
-        const float logs = logf(s);
+        row_stats(
+            row, V, lane, vec != 0, [&](int v, float l) { return scaled(l, v, blank, sm_scale, penalty); },
+            [&](int v, float x) {
+                if (x > bx) { bx = x; bv = v; }
+            },
+            m, logs);
         if (lane == 0) { s_m[k] = m; s_logs[k] = logs; }
         // the lane maxima in the total order, by counting; lanes that read nothing hold equal keys and keep their own
         // order, so the ranks are a permutation and every entry of the row's list is written
@@ -280,6 +313,13 @@ __global__ __launch_bounds__(THREADS) void msearch_advance_kernel(void *state, c
         }
         pool_c[k][rank] = mine.c;
         pool_v[k][rank] = mine.v;
+        if constexpr (DENSE) {  // the LM's row of the same slot: M and S of y = nn_scale * lm_logits (a dead slot's is not read)
+            float M, S;
+            row_stats(
+                fu.rows + (bk + k) * fu.rld, fu.VL, lane, fu.rvec != 0, [&](int, float l) { return __fmul_rn(fu.scale, l); },
+                [](int, float) {}, M, S);
+            if (lane == 0) { s_nm[k] = M; s_ns[k] = S; }
+        }
     }
     __syncthreads();
 
@@ -382,16 +422,29 @@ __global__ __launch_bounds__(THREADS) void msearch_advance_kernel(void *state, c
             const float x = scaled(logits[(bk + me.k) * ld + me.v], me.v, blank, sm_scale, penalty);
             me.c = __fadd_rn(s_am[me.k], __fsub_rn(__fsub_rn(x, s_m[me.k]), s_logs[me.k]));
             double bonus = s_bonus[me.k];
-            int n1 = s_st[me.k], n2 = 0;
+            int n1 = 0, n2 = 0;
+            if constexpr (NFST >= 1) n1 = s_st[me.k];
             if constexpr (NFST == 2) n2 = s_st2[me.k];
             if (me.v != blank) {
-                float inc = 0.0f;
-                exists = lm_step(fu.f[0], n1, me.v, inc, n1) && inc - inc == 0.0f;  // (false for +-inf and NaN)
-                bonus = __dadd_rn(bonus, __dmul_rn((double)fu.lmw, (double)inc));
+                if constexpr (NFST >= 1) {
+                    float inc = 0.0f;
+                    exists = lm_step(fu.f[0], n1, me.v, inc, n1) && inc - inc == 0.0f;  // (false for +-inf and NaN)
+                    bonus = __dadd_rn(bonus, __dmul_rn((double)fu.lmw, (double)inc));
+                }
                 if constexpr (NFST == 2) {
                     float inc2 = 0.0f;
                     exists = exists && lm_step(fu.f[1], n2, me.v, inc2, n2) && inc2 - inc2 == 0.0f;
                     bonus = __dadd_rn(bonus, __dmul_rn((double)fu.bw, (double)inc2));
+                }
+                if constexpr (DENSE) {
+                    // the label's class in the LM's row: outside it, a row without a finite maximum or a non-finite
+                    // increment and the entry does not exist; the one logit comes from the cache, the index clamped
+                    const int c = me.v + fu.off;
+                    const float M = s_nm[me.k];
+                    const float y = __fmul_rn(fu.scale, fu.rows[(bk + me.k) * fu.rld + clampi(c, 0, fu.VL - 1)]);
+                    const float inc3 = __fsub_rn(__fsub_rn(y, M), s_ns[me.k]);
+                    exists = exists && c >= 0 && c < fu.VL && M - M == 0.0f && inc3 - inc3 == 0.0f;
+                    bonus = __dadd_rn(bonus, __dmul_rn((double)fu.nnw, (double)inc3));
                 }
                 bonus = __dadd_rn(bonus, (double)fu.lb);
             }
@@ -461,24 +514,24 @@ __global__ __launch_bounds__(THREADS) void msearch_advance_kernel(void *state, c
 // the token sequences of `n` entries per utterance, entry j of the output from slot j of the beam.  The fused search's
 // results with use_final (lane = slot) score every slot first -- am + bonus + the automata's final terms, no final state:
 // the slot drops out -- and entry j is the j-th slot by that score, ties by the slot.  The state is only read.
-template <int NFST>
+template <int NFST, bool DENSE>
 __global__ __launch_bounds__(64) void msearch_read_kernel(const void *state, int B, int K, int max_frames, unsigned mask,
                                                            int n, int L, long long *__restrict__ tokens,
                                                            long long *__restrict__ lengths, float *__restrict__ scores,
                                                            float *__restrict__ am_scores, const Fused<NFST> fu,
                                                            int use_final) {
-    constexpr bool LM = NFST > 0;
+    constexpr bool LM = NFST > 0 || DENSE;  // (DENSE: the fused search's blob, even with no automaton)
     __shared__ float s_sc[LM ? MAX_BEAM : 1];
     __shared__ int s_src[LM ? MAX_BEAM : 1];
     const int b = blockIdx.x, lane = threadIdx.x;
-    const Blob st = blob_of<NFST>(const_cast<void *>(state), B, K);
+    const Blob st = blob_of<LM ? 1 : 0>(const_cast<void *>(state), B, K);
     const unsigned long long *table = st.tables + (size_t)b * ((size_t)mask + 1);
     const size_t bk = (size_t)b * K;
     if constexpr (LM) {
         float sc = NINF;
         if (lane < K) {
             sc = st.score[bk + lane];
-            if (use_final && sc > NINF) {
+            if constexpr (NFST > 0) if (use_final && sc > NINF) {
                 double s = __dadd_rn((double)st.am[bk + lane], st.bonus[bk + lane]);
                 float inc = 0.0f;
                 bool live = lm_final(fu.f[0], clampi(st.lmst[bk + lane], 0, fu.f[0].S - 1), inc);
@@ -937,11 +990,11 @@ static inline int check_read(int B, int K, int C, int max_frames, int n, int L) 
     return PIKA_OK;
 }
 
-template <int NFST>
+template <int NFST, bool DENSE = false>
 static int read_out(const void *state, int B, int K, int C, int max_frames, int n, int L, long long *tokens,
                     long long *lengths, float *scores, float *am_scores, const Fused<NFST> &fu, int use_final,
                     void *stream) {
-    hipLaunchKernelGGL((msearch_read_kernel<NFST>), dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL((msearch_read_kernel<NFST, DENSE>), dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream),
                        state, B, K, max_frames, (unsigned)(table_slots(max_frames, C) - 1), n, L, tokens, lengths, scores,
                        am_scores, fu, use_final);
     return (int)hipGetLastError();
@@ -962,12 +1015,16 @@ static int reset(void *state, int B, int K, int C, int max_frames, const int *wh
     return (int)hipGetLastError();
 }
 
-template <int NFST>
+static inline int row_vec(const float *rows, long long ld) {
+    return ld % 4 == 0 && reinterpret_cast<uintptr_t>(rows) % 16 == 0;
+}
+
+template <int NFST, bool DENSE = false>
 static int advance(void *state, const float *logits, long long ld, const long long *num_frames, int B, int K, int C,
                    int max_frames, int V, int blank, float sm_scale, float blank_penalty, long long *parent_out,
-                   long long *token_out, const Fused<NFST> &fu, void *stream) {
-    const int vec = ld % 4 == 0 && reinterpret_cast<uintptr_t>(logits) % 16 == 0;
-    hipLaunchKernelGGL((msearch_advance_kernel<NFST>), dim3((unsigned)B), dim3(THREADS), 0,
+                   long long *token_out, const Step<NFST, DENSE> &fu, void *stream) {
+    const int vec = row_vec(logits, ld);
+    hipLaunchKernelGGL((msearch_advance_kernel<NFST, DENSE>), dim3((unsigned)B), dim3(THREADS), 0,
                        static_cast<hipStream_t>(stream), state, logits, ld, num_frames, B, K, max_frames, V, blank,
                        sm_scale, blank_penalty, (unsigned)(table_slots(max_frames, C) - 1), vec, parent_out, token_out, fu);
     return (int)hipGetLastError();
@@ -1003,12 +1060,37 @@ static inline int second_fst(const Fst &g, int start2) {
 }
 
 template <int NFST>
-static inline Fused<NFST> fused(const Fst &f, const Fst &g, float lmw, float bw, float lb, int C) {
-    Fused<NFST> fu;
+static inline Step<NFST, false> fused(const Fst &f, const Fst &g, float lmw, float bw, float lb, int C) {
+    Step<NFST, false> fu;
     fu.f[0] = f;
     if constexpr (NFST == 2) fu.f[1] = g;
     fu.lmw = lmw; fu.bw = bw; fu.lb = lb; fu.C = C;
     return fu;
+}
+
+// the rows of a neural LM beside the automata that exist
+struct NnRows {
+    const float *rows;
+    long long ld;
+    int V, off;
+    float scale, w;
+};
+
+template <int NFST>
+static inline Step<NFST, true> dense(const Fst &f, const Fst &g, float lmw, float bw, float lb, int C, const NnRows &nn) {
+    Step<NFST, true> fu;
+    if constexpr (NFST >= 1) { fu.f[0] = f; fu.lmw = lmw; fu.bw = bw; }
+    if constexpr (NFST == 2) fu.f[1] = g;
+    fu.rows = nn.rows; fu.rld = nn.ld; fu.VL = nn.V; fu.off = nn.off; fu.rvec = row_vec(nn.rows, nn.ld);
+    fu.scale = nn.scale; fu.nnw = nn.w; fu.lb = lb; fu.C = C;
+    return fu;
+}
+
+// the automata of a call with a neural LM, either of which may be "none": the number present (0, 1, 2), < 0 refused
+static inline int nn_fsts(const Fst &f, int start, const Fst &g, int start2) {
+    const int one = second_fst(f, start), two = second_fst(g, start2);
+    if (one < 0 || two < 0 || (two && !one)) return PIKA_EINVAL;
+    return one + two;
 }
 
 // ---- the time record: C = 0 names the plain blob, K <= C the fused search's
@@ -1047,7 +1129,7 @@ int pika_msearch_advance(void *state, const float *logits, long long ld, const l
     if (int rc = check_dims(B, K, max_frames)) return rc;
     if (!state || !logits || !num_frames || !parent_out || !token_out) return PIKA_EINVAL;
     return advance<0>(state, logits, ld, num_frames, B, K, K, max_frames, V, blank, sm_scale, blank_penalty, parent_out,
-                      token_out, Fused<0>{}, stream);
+                      token_out, Step<0, false>{}, stream);
 }
 
 int pika_msearch_results(const void *state, int B, int K, int max_frames, int nbest, int L, long long *tokens,
@@ -1134,6 +1216,78 @@ int pika_msearch_lm_hyps(const void *state, int B, int K, int C, int max_frames,
     // (the slots in the beam's order: no automaton is walked, the kernel takes an empty one)
     return read_out<1>(state, B, K, C, max_frames, K, L, tokens, lengths, nullptr, nullptr,
                        fused<1>(Fst{}, Fst{}, 0.0f, 0.0f, 0.0f, C), 0, stream);
+}
+
+// ---- the search with a neural LM's rows beside up to two automata (pika_msearch_nn.h) ---------------------------------
+
+int pika_msearch_nn_reset(void *state, int B, int K, int C, int max_frames, int num_states, int start, int num_states2,
+                          int start2, const int *which, void *stream) {
+    if (num_states < 0 || num_states2 < 0 || (num_states2 > 0 && num_states == 0)) return PIKA_EINVAL;
+    if ((num_states > 0 && bad_start(num_states, start)) || (num_states2 > 0 && bad_start(num_states2, start2)))
+        return PIKA_EINVAL;
+    if (int rc = check_dims(B, K, C, max_frames)) return rc;
+    if (!state) return PIKA_EINVAL;
+    return reset<true>(state, B, K, C, max_frames, which, num_states > 0 ? start : 0, num_states2 > 0 ? start2 : 0, stream);
+}
+
+int pika_msearch_nn_advance(void *state, const float *logits, long long ld, const long long *num_frames, int B, int K,
+                            int C, int max_frames, int V, int blank, float sm_scale, float blank_penalty,
+                            const long long *fst_offsets, const int *fst_ilabel, const float *fst_weight,
+                            const int *fst_nextstate, const float *fst_final, int num_states, int num_arcs,
+                            int backoff_id, int label_offset, const long long *fst2_offsets, const int *fst2_ilabel,
+                            const float *fst2_weight, const int *fst2_nextstate, const float *fst2_final,
+                            int num_states2, int num_arcs2, int backoff_id2, int label_offset2, float lm_weight,
+                            float bias_weight, float length_bonus, const float *lm_logits, long long lm_ld, int V_lm,
+                            int nn_label_offset, float nn_scale, float nn_weight, long long *parent_out,
+                            long long *token_out, void *stream) {
+    const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
+                   label_offset};
+    const Fst g = {fst2_offsets, fst2_ilabel, fst2_weight, fst2_nextstate, fst2_final, num_states2, num_arcs2,
+                   backoff_id2, label_offset2};
+    if (V < 2 || blank < 0 || blank >= V || ld < V || !std::isfinite(sm_scale) || !std::isfinite(blank_penalty) ||
+        !std::isfinite(lm_weight) || !std::isfinite(bias_weight) || !std::isfinite(length_bonus))
+        return PIKA_EINVAL;
+    if (V_lm < 1 || lm_ld < V_lm || !std::isfinite(nn_scale) || !std::isfinite(nn_weight)) return PIKA_EINVAL;
+    const int n = nn_fsts(f, 0, g, 0);
+    if (n < 0) return PIKA_EINVAL;
+    if (int rc = check_dims(B, K, C, max_frames)) return rc;
+    if (!state || !logits || !lm_logits || !num_frames || !parent_out || !token_out) return PIKA_EINVAL;
+    const NnRows nn = {lm_logits, lm_ld, V_lm, nn_label_offset, nn_scale, nn_weight};
+    if (n == 2)
+        return advance<2, true>(state, logits, ld, num_frames, B, K, C, max_frames, V, blank, sm_scale, blank_penalty,
+                                parent_out, token_out, dense<2>(f, g, lm_weight, bias_weight, length_bonus, C, nn), stream);
+    if (n == 1)
+        return advance<1, true>(state, logits, ld, num_frames, B, K, C, max_frames, V, blank, sm_scale, blank_penalty,
+                                parent_out, token_out, dense<1>(f, g, lm_weight, bias_weight, length_bonus, C, nn), stream);
+    return advance<0, true>(state, logits, ld, num_frames, B, K, C, max_frames, V, blank, sm_scale, blank_penalty,
+                            parent_out, token_out, dense<0>(f, g, lm_weight, bias_weight, length_bonus, C, nn), stream);
+}
+
+int pika_msearch_nn_results(const void *state, int B, int K, int C, int max_frames, const long long *fst_offsets,
+                            const int *fst_ilabel, const float *fst_weight, const int *fst_nextstate,
+                            const float *fst_final, int num_states, int num_arcs, int start, int backoff_id,
+                            int label_offset, const long long *fst2_offsets, const int *fst2_ilabel,
+                            const float *fst2_weight, const int *fst2_nextstate, const float *fst2_final,
+                            int num_states2, int num_arcs2, int start2, int backoff_id2, int label_offset2,
+                            float lm_weight, float bias_weight, int use_final, int nbest, int L, long long *tokens,
+                            long long *lengths, float *scores, float *am_scores, void *stream) {
+    const Fst f = {fst_offsets, fst_ilabel, fst_weight, fst_nextstate, fst_final, num_states, num_arcs, backoff_id,
+                   label_offset};
+    const Fst g = {fst2_offsets, fst2_ilabel, fst2_weight, fst2_nextstate, fst2_final, num_states2, num_arcs2,
+                   backoff_id2, label_offset2};
+    if (!std::isfinite(lm_weight) || !std::isfinite(bias_weight)) return PIKA_EINVAL;
+    const int n = nn_fsts(f, start, g, start2);
+    if (n < 0) return PIKA_EINVAL;
+    if (int rc = check_read(B, K, C, max_frames, nbest, L)) return rc;
+    if (!state || !tokens || !lengths || !scores || !am_scores) return PIKA_EINVAL;
+    if (n == 2)
+        return read_out<2>(state, B, K, C, max_frames, nbest, L, tokens, lengths, scores, am_scores,
+                           fused<2>(f, g, lm_weight, bias_weight, 0.0f, C), use_final != 0, stream);
+    if (n == 1)
+        return read_out<1>(state, B, K, C, max_frames, nbest, L, tokens, lengths, scores, am_scores,
+                           fused<1>(f, g, lm_weight, bias_weight, 0.0f, C), use_final != 0, stream);
+    // (no automaton: no final term, the beam as it stands)
+    return read_out<0, true>(state, B, K, C, max_frames, nbest, L, tokens, lengths, scores, am_scores, Fused<0>{}, 0, stream);
 }
 
 // ---- streaming: the side record and the commit of either blob (pika_msearch_stream.h) --------------------------------

@@ -11,6 +11,10 @@ section 3, "Modified beam search"; `_torch_step` below spells it in plain torch.
 ranking (include/pika_msearch_lm.h; DESIGN.md section 3, "Modified beam search with an LM"): the `lm` is what the CTC
 searches take -- a `CtcNgramLm`, a `CtcHotwords` alone, or a `CtcBiasedLm` pair.
 
+`ModifiedNnLmBeamState` / `modified_beam_search_nnlm` fuse a NEURAL LM -- a dense row of LM logits per hypothesis and
+frame (include/pika_msearch_nn.h; DESIGN.md section 3, "Modified beam search with a neural LM"), such as
+`pika_amd.model.lm.LstmLm` -- alone or beside those automata; a low-order n-gram on a negative weight beside it is LODR.
+
 `ModifiedBeamStream` wraps either state into a stream that outlives `max_frames` (include/pika_msearch_stream.h;
 DESIGN.md section 3, "Streaming modified beam search"): `commit` emits the labels every hypothesis shares and gives the
 capacity back.  `ModifiedStreamDecoder` drives a model with the LSTM prediction network through it chunk by chunk.
@@ -330,6 +334,11 @@ class ModifiedLmBeamState(_BeamState):
 
     def __init__(self, batch, max_frames, lm, beam=4, blank=0, lm_weight=0.5, length_bonus=0.0, candidates=None,
                  device=None):
+        self._setup(batch, max_frames, lm, beam, blank, lm_weight, length_bonus, candidates, device, True, ())
+        self.reset()
+
+    def _setup(self, batch, max_frames, lm, beam, blank, lm_weight, length_bonus, candidates, device, need_lm, more):
+        """The checks and the blob; need_lm: `lm` may not be None; more: further (name, weight) pairs to be finite."""
         from ..ctc import _Search, _hip_device
         batch, max_frames, beam, blank = int(batch), int(max_frames), int(beam), int(blank)
         if not 1 <= beam <= MAX_BEAM:
@@ -339,11 +348,14 @@ class ModifiedLmBeamState(_BeamState):
         candidates = min(2 * beam, MAX_BEAM) if candidates is None else int(candidates)
         if not beam <= candidates <= MAX_BEAM:
             raise ValueError("need beam <= candidates <= %d, got beam=%d, candidates=%d" % (MAX_BEAM, beam, candidates))
-        v = _Search(lm, lm_weight, length_bonus, True)              # (TypeError unless an LM or a pair)
-        for name, w in (("lm_weight", v.lm_weight), ("bias_weight", v.bias_weight), ("length_bonus", v.length_bonus)):
+        v = _Search(lm, lm_weight, length_bonus, need_lm)           # (TypeError unless an LM or a pair)
+        for name, w in (("lm_weight", v.lm_weight), ("bias_weight", v.bias_weight),
+                        ("length_bonus", v.length_bonus)) + tuple(more):
             if w != w or w in (float("inf"), -float("inf")):
                 raise ValueError("%s must be finite" % name)
-        self.device = _hip_device(device if device is not None else v.lm.device, "cuda", "ModifiedLmBeamState")
+        if device is None and v.lm is not None:
+            device = v.lm.device
+        self.device = _hip_device(device, "cuda", type(self).__name__)
         v.check_against(0, self.device, "the state")                # (no class yet: the devices alone)
         self.batch, self.max_frames, self.beam, self.blank, self.candidates = batch, max_frames, beam, blank, candidates
         self.dtype, self.native, self._v = torch.float32, True, v
@@ -359,39 +371,47 @@ class ModifiedLmBeamState(_BeamState):
         self._am = self._state[12 * BK:16 * BK].view(torch.float32).view(batch, beam)
         self._frames = self._state[32 * BK:32 * BK + 4 * batch].view(torch.int32)
         self._over = self._state[32 * BK + 4 * batch:32 * BK + 8 * batch].view(torch.int32)
-        self.reset()
+        self._bonus = self._state[:8 * BK].view(torch.float64).view(batch, beam)
 
     @property
     def am_scores(self):
         return self._am
 
     def _fsts(self, start):
-        """The automata as the C ABI takes them; "none" for the second where there is one alone."""
+        """The automata as the C ABI takes them; "none" for those there are not."""
         none = (None,) * 5 + (0, 0) + ((0,) if start else ()) + (0, 0)
-        return self._v.fsts(start) + (none if self._v.bias is None else ())
+        return self._v.fsts(start) + none * (2 - len(self._v.automata))
 
     def _weights(self):
         return (self._v.lm_weight, self._v.bias_weight if self._v.bias is not None else 0.0)
 
     def reset(self, which=None):
         which = self._which(which)
-        starts = self._v.starts() + ((0, 0) if self._v.bias is None else ())
+        starts = self._v.starts() + (0, 0) * (2 - len(self._v.automata))
+        name = self._abi + "reset"
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().pika_msearch_lm_reset(*((_ptr(self._state),) + self._dims + starts
-                                                          + (_ptr(which), _stream()))), "pika_msearch_lm_reset")
+            _lib.check(getattr(_lib.lib(), name)(*((_ptr(self._state),) + self._dims + starts
+                                                   + (_ptr(which), _stream()))), name)
+
+    _abi = "pika_msearch_lm_"          # the entry points of reset, advance and results
 
     def advance(self, logits, num_frames, sm_scale=1.0, blank_penalty=0.0):
+        return self._advance(logits, num_frames, sm_scale, blank_penalty, ())
+
+    def _advance(self, logits, num_frames, sm_scale, blank_penalty, dense):
+        """dense: what the step takes between length_bonus and the outputs (the rows of a neural LM, or nothing)."""
         sm_scale, blank_penalty = self._finite(sm_scale, blank_penalty)
         logits, num_frames = self._check_logits(logits, num_frames)
         B, K, V = self.batch, self.beam, logits.shape[1]
         self._v.check_against(V, self.device, "the state")
+        name = self._abi + "advance"
         with torch.cuda.device(self.device):
             parent = torch.empty((B, K), dtype=torch.int64, device=self.device)
             token = torch.empty((B, K), dtype=torch.int64, device=self.device)
-            _lib.check(_lib.lib().pika_msearch_lm_advance(*(
+            _lib.check(getattr(_lib.lib(), name)(*(
                 (_ptr(self._state), _ptr(logits), logits.stride(0), _ptr(num_frames)) + self._dims
                 + (V, self.blank, sm_scale, blank_penalty) + self._fsts(False) + self._weights()
-                + (self._v.length_bonus, _ptr(parent), _ptr(token), _stream()))), "pika_msearch_lm_advance")
+                + (self._v.length_bonus,) + dense + (_ptr(parent), _ptr(token), _stream()))), name)
         return parent, token
 
     def results(self, nbest=1, max_len=None, use_final=True):
@@ -400,10 +420,10 @@ class ModifiedLmBeamState(_BeamState):
         with torch.cuda.device(self.device):
             scores = torch.empty((self.batch, nbest), dtype=torch.float32, device=self.device)
             am_scores = torch.empty((self.batch, nbest), dtype=torch.float32, device=self.device)
-            _lib.check(_lib.lib().pika_msearch_lm_results(*(
+            _lib.check(getattr(_lib.lib(), self._abi + "results")(*(
                 (_ptr(self._state),) + self._dims + self._fsts(True) + self._weights()
                 + (1 if use_final else 0, nbest, L, _ptr(tokens), _ptr(lengths), _ptr(scores), _ptr(am_scores),
-                   _stream()))), "pika_msearch_lm_results")
+                   _stream()))), self._abi + "results")
         return tokens, lengths, scores, am_scores
 
     def hyps(self, max_len=None):
@@ -413,6 +433,62 @@ class ModifiedLmBeamState(_BeamState):
                                                          + (L, _ptr(tokens), _ptr(lengths), _stream()))),
                        "pika_msearch_lm_hyps")
         return tokens, lengths
+
+
+class ModifiedNnLmBeamState(ModifiedLmBeamState):
+    """`ModifiedLmBeamState` with a NEURAL LM fused into the ranking (include/pika_msearch_nn.h): per step the caller
+    hands `advance` a dense row of LM logits for every slot, as it hands it the joint network's; the LM's own state lives
+    with the caller, as the prediction network's does.
+
+    nn_weight, nn_scale, nn_label_offset   a pre-selected label v of slot k adds nn_weight * log_softmax(nn_scale *
+         lm_logits[k])[v + nn_label_offset] to the slot's bonus; a label whose class falls outside the LM's vocabulary or
+         whose term is not finite (a -inf or NaN logit, a row of -inf) is dropped whatever the weights are, as a label an
+         automaton does not reach.  Blank is untouched.  The LM does not enter the pre-selection (`candidates`).
+    lm   optional: what `ModifiedLmBeamState` takes, fused beside the neural LM with `lm_weight`.  A low-order n-gram
+         with a NEGATIVE weight -- `lm=CtcBiasedLm(ngram, low_order, bias_weight=-0.2)`, or the low-order LM alone with
+         lm_weight < 0 -- is LODR (icefall's modified_beam_search_LODR).
+    Equal token sequences merge and the group takes its best-ranked member's bonus: give equal rows to equal sequences
+    (an LM that is a function of the tokens does).  With nn_weight = 0 the step is `ModifiedLmBeamState`'s bit for bit.
+
+    advance(logits, lm_logits, num_frames, sm_scale=1.0, blank_penalty=0.0) -> (parent, token)   lm_logits
+        (batch * beam, V_lm) float32, row b * beam + k for slot k as it stands BEFORE the step; any row stride >= V_lm.
+    results(nbest=1, max_len=None, use_final=True) -> (tokens, lengths, scores, am_scores)   use_final adds the final
+        terms of the automata there are; the neural LM has none.
+    hyps(max_len=None), reset(which=None)   as `ModifiedLmBeamState`'s
+    frames, scores (F), am_scores, bonus (float64: scores = float32(am_scores + bonus)), overflowed   live views.
+
+    HIP float32 only: there is no CPU path (RuntimeError).  Every call is a kernel launch with no host synchronisation,
+    capturable in a `torch.cuda.graph`; `ModifiedBeamTimes` takes the state as it takes a `ModifiedLmBeamState`."""
+
+    _abi = "pika_msearch_nn_"
+
+    def __init__(self, batch, max_frames, beam=4, blank=0, nn_weight=0.3, nn_scale=1.0, nn_label_offset=0, lm=None,
+                 lm_weight=0.5, length_bonus=0.0, candidates=None, device=None):
+        self.nn_weight, self.nn_scale, self.nn_label_offset = float(nn_weight), float(nn_scale), int(nn_label_offset)
+        self._setup(batch, max_frames, lm, beam, blank, lm_weight, length_bonus, candidates, device, False,
+                    (("nn_weight", self.nn_weight), ("nn_scale", self.nn_scale)))
+        self.reset()
+
+    @property
+    def bonus(self):
+        return self._bonus
+
+    def advance(self, logits, lm_logits, num_frames, sm_scale=1.0, blank_penalty=0.0):
+        if not isinstance(lm_logits, torch.Tensor):
+            raise TypeError("lm_logits must be a tensor")
+        if lm_logits.dtype != torch.float32:
+            raise TypeError("lm_logits must be float32, got %s" % lm_logits.dtype)
+        if lm_logits.device != self.device:
+            raise ValueError("the state lives on %s, lm_logits on %s" % (self.device, lm_logits.device))
+        if lm_logits.dim() != 2 or lm_logits.shape[0] != self.batch * self.beam or lm_logits.shape[1] < 1:
+            raise ValueError("lm_logits must be (batch * beam, V_lm) = (%d, V_lm), got %s" % (self.batch * self.beam,
+                                                                                          tuple(lm_logits.shape)))
+        if lm_logits.stride(1) != 1 or lm_logits.stride(0) < lm_logits.shape[1]:
+            raise ValueError("lm_logits rows must be contiguous (class stride 1, row stride >= V_lm), got strides %s"
+                             % (tuple(lm_logits.stride()),))
+        return self._advance(logits, num_frames, sm_scale, blank_penalty,
+                             (_ptr(lm_logits), lm_logits.stride(0), lm_logits.shape[1], self.nn_label_offset,
+                              self.nn_scale, self.nn_weight))
 
 
 class ModifiedBeamStream(object):
@@ -1059,13 +1135,70 @@ def modified_beam_search_timed(model, x, x_len, lm=None, beam=4, nbest=1, sm_sca
     def results(state):
         out = tuple(state.results(nbest=nbest, **kw))
         return out + (rec[0].results(out[0], out[1]),)
-    return _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, precision, make_state, results, hook)
+    return _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, precision, make_state, results,
+                  hook=hook)
 
 
-def _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, precision, make_state, results, hook=None):
+@torch.no_grad()
+def modified_beam_search_nnlm(model, x, x_len, nnlm, beam=4, nbest=1, sm_scale=1.0, blank_penalty=0.0, use_graph=True,
+                              blank=0, precision="fp16x2", nn_weight=0.3, nn_scale=1.0, nn_label_offset=0, lm=None,
+                              lm_weight=0.5, length_bonus=0.0, candidates=None, use_final=True):
+    """`modified_beam_search` with a neural LM fused into the ranking (icefall's modified_beam_search_lm_shallow_fusion):
+    `nnlm` is a `pika_amd.model.lm.LstmLm` or any object with its four methods (the protocol is in that module's
+    docstring), on the model's device; `nn_weight`, `nn_scale`, `nn_label_offset`, `lm`, `lm_weight`, `length_bonus` and
+    `candidates` are `ModifiedNnLmBeamState`'s, `use_final` its `results`'.  HIP only.
+    -> (tokens, lengths, scores, am_scores, enc_out) as `modified_beam_search_lm`.
+
+    Per frame step `nnlm.logits` is computed fresh on the LM's output for all B * beam rows, the step takes it beside the
+    joint network's logits, the LM's state is re-ordered by `parent` with the prediction network's, and the LM is stepped
+    on every row with token + nn_label_offset and kept where the token is a label: fixed shapes, nothing read back, two
+    eager steps and one captured step replayed for the rest, as for the prediction network.
+
+    LODR (icefall's modified_beam_search_LODR): give the low-order n-gram as `lm` with a negative weight -- alone with
+    lm_weight < 0, or as the `bias` of a `CtcBiasedLm(ngram, low_order, bias_weight < 0)` beside a full n-gram."""
+    def make_state(B, T, dev, dtype):
+        return ModifiedNnLmBeamState(B, T, int(beam), int(blank), nn_weight, nn_scale, nn_label_offset, lm, lm_weight,
+                                     length_bonus, candidates, dev)
+    return _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, precision, make_state,
+                  lambda state: state.results(nbest=nbest, use_final=use_final),
+                  side=lambda rows: _LmRows(nnlm, rows, int(nn_label_offset)))
+
+
+class _LmRows(object):
+    """A neural LM beside the loop of `_drive`: its output and state for the B * beam rows, in buffers that stay where
+    they are (a captured step reads and writes the same memory at every replay)."""
+
+    def __init__(self, nnlm, rows, offset):
+        for name in ("start", "step", "logits", "select"):
+            if not callable(getattr(nnlm, name, None)):
+                raise TypeError("nnlm must have start, step, logits and select (pika_amd.model.lm), got %s"
+                                % type(nnlm).__name__)
+        self.nnlm, self.offset = nnlm, offset
+        out, state = nnlm.start(rows)
+        self.out, self.state = out.clone(), tuple(s.clone() for s in state)
+
+    def rows(self):
+        """What `advance` takes behind the joint's logits: the LM's logits for the slots as they stand."""
+        self.last = self.nnlm.logits(self.out).float().contiguous()
+        return (self.last,)
+
+    def follow(self, flat, token, label):
+        """flat (rows,): the old row of every new row; token (rows,); label (rows,) bool: the token is a label."""
+        out = self.out.index_select(0, flat)
+        state = self.nnlm.select(self.state, flat)
+        ids = (token + self.offset).clamp(0, self.last.shape[1] - 1)      # (blank's class may lie outside: masked below)
+        out2, state2 = self.nnlm.step(ids, state)
+        self.out.copy_(torch.where(label.view(-1, 1), out2, out))
+        for buf, new, old in zip(self.state, state2, state):
+            buf.copy_(torch.where(label.view((1, -1) + (1,) * (buf.dim() - 2)), new, old))
+
+
+def _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, precision, make_state, results, side=None,
+           hook=None):
     """The loop of `modified_beam_search` around a search state: make_state(B, T, device, dtype) -> the state,
-    results(state) -> what the call returns ahead of enc_out, hook(state) -> a callable that every step hands its
-    (parent, token) right after the advance (None: there is none)."""
+    results(state) -> what the call returns ahead of enc_out, side(B * beam) -> a `_LmRows`: what `advance` takes behind
+    the logits, re-ordered and stepped with the prediction network (None: nothing), hook(state) -> a callable that every
+    step hands its (parent, token) right after the advance (None: there is none)."""
     from .. import gemm as G
     from ..model import ops
     K, blank = int(beam), int(blank)
@@ -1087,6 +1220,7 @@ def _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, pre
         rnn = model.decoder_type == 'rnn'
         state = make_state(B, T, dev, enc_out.dtype)
         after = hook(state) if hook is not None else None
+        beside = side(B * K) if side is not None else None
 
         w1, wg = model.fc1, model.fc_gate
         e1_all = ops.linear(enc_out, w1.weight[:, :H].contiguous(), w1.bias)
@@ -1112,13 +1246,16 @@ def _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, pre
             z = e_all.index_select(0, rows) + ops.linear(dec_hid, wp)
             h = torch.tanh(z[:, :H]) * torch.sigmoid(z[:, H:])
             logits = ops.linear(h, model.fc2.weight, model.fc2.bias).contiguous()
-            parent, token = state.advance(logits, num_frames, sm_scale, blank_penalty)
+            extra = beside.rows() if beside is not None else ()
+            parent, token = state.advance(logits, *(extra + (num_frames, sm_scale, blank_penalty)))
             if after is not None:
                 after(parent, token)
             flat = (flat0 + parent).reshape(-1)
             for s_ in pred:
                 s_.copy_(s_.index_select(1 if rnn else 0, flat))
             label = token.reshape(-1).ne(blank)
+            if beside is not None:
+                beside.follow(flat, token.reshape(-1), label)
             if rnn:
                 hh, cc = pred
                 _, (h2, c2) = model.decoder(model.embed(token.reshape(-1, 1)), (hh, cc))
