@@ -85,6 +85,28 @@ int pika_rnnt_loss_backward_fe(const int *labels, const int *frames_lengths, con
 int pika_rnnt_loss_dense_grads(const void *workspace, int B, int T, int U1, int V, int blank,
                                float *grads, void *stream);
 
+/* pika_rnnt_loss_dense_grads into a tensor that may already hold a gradient this library wrote.  Every V-row of the
+ * gradient has at most two non-zeros, in column `blank` and in the row's label column; the call leaves the label
+ * column of every row (-1: none) in cols_out (B*T*U1 ints).
+ * prev_cols == NULL: nothing is known about `grads`; the streaming pass of pika_rnnt_loss_dense_grads writes every
+ * word, then a small pass writes cols_out.
+ * prev_cols != NULL: the caller guarantees that `grads` holds, unmodified, what an earlier call of this entry wrote
+ * with the same V: rows [0, prev_rows) with non-zeros in column prev_blank and column prev_cols[r] only, and +0.0f in
+ * every other word of its first max(prev_rows, B*T*U1) rows.  One small kernel then stores +0.0f over the old
+ * non-zeros and the new values where they belong: about four dword stores per row, not the V-row.  Rows from B*T*U1
+ * up to prev_rows are left all zero.  The words are bit for bit those of the streaming pass.  cols_out may be
+ * prev_cols.  prev_rows < 0 or prev_blank outside [0, V): PIKA_EINVAL; prev_rows >= 2^31: PIKA_ETOOBIG. */
+int pika_rgrad_dense_grads_update(const void *workspace, int B, int T, int U1, int V, int blank, float *grads,
+                                  const int *prev_cols, long long prev_rows, int prev_blank, int *cols_out,
+                                  void *stream);
+
+/* pika_rnnt_loss_backward_fe (grads required) with pika_rgrad_dense_grads_update as its writer: one host call per
+ * backward. */
+int pika_rgrad_backward_fe(const int *labels, const int *frames_lengths, const int *labels_lengths,
+                           int B, int T, int U1, int V, int blank, const float *grad_costs,
+                           const void *workspace, float *grads, float fastemit_lambda, const int *prev_cols,
+                           long long prev_rows, int prev_blank, int *cols_out, void *stream);
+
 /* warp_rnnt-shaped one-shot: forward + backward with unit grad_costs. */
 int pika_rnnt_loss_fwd_bwd(const float *log_probs, const int *labels,
                            const int *frames_lengths, const int *labels_lengths,

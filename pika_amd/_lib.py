@@ -35,6 +35,10 @@ SIGNATURES = {
     "pika_rnnt_packed_fused_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _ll, _i, _i, _vp, _vp, _vp, _vp]),
     "pika_rnnt_packed_fused_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _ll, _i, _i, _vp, _vp, _vp, _i,
                                               _ll, _f, _vp]),
+    # the dense gradient written over an earlier one (a prefix of their own: tests/test_rnnt_abi_rejections.py keeps
+    # its recorded table of every pika_rnnt_* / pika_prnnt_* entry)
+    "pika_rgrad_dense_grads_update": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _ll, _i, _vp, _vp]),
+    "pika_rgrad_backward_fe": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _ll, _i, _vp, _vp]),
     "pika_rnnt_align_scratch_bytes": (_sz, [_i, _i, _i]),
     "pika_rnnt_align": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     # include/pika_rnnt.h, the pruned (banded) lattice

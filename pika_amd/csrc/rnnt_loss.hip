@@ -755,6 +755,48 @@ __global__ __launch_bounds__(256) void rnnt_grad_scalar_kernel(const RowMeta *__
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// grad, in place: the tensor already holds a gradient this library wrote -- rows [0, prev_rows) with
+// their non-zeros in column prev_blank and column prev_cols[r] (if >= 0), every other word +0.0f, rows
+// beyond all +0.0f -- so the new gradient of rows [0, rows) takes the old non-zeros out and puts the
+// new ones in: at most four dword stores per row instead of the V-row.  One thread per row over
+// max(prev_rows, rows) does both, so no store of one thread depends on another's.  A word gets ONE
+// store: the new value where a new entry lands on an old one, +0.0f where only the old one was, and
+// none where the new value is +0.0f over a word that is +0.0f already; -0.0f (an underflowed
+// -sc * exp(..)) is a value like any other, so the tensor is word for word what the streaming writer
+// leaves.  The label wins over blank (blend_row).  cols_out may be prev_cols (read before written).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rnnt_grad_update_kernel(const RowMeta *__restrict__ meta, long rows, int V,
+                                                               int blank, const int *prev_cols, long prev_rows,
+                                                               int prev_blank, float *__restrict__ grads, int *cols_out) {
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool had = r < prev_rows, live = r < rows;
+    if (!had && !live) return;
+    int cb = -1, ce = -1;   // the columns this row's new entries go to
+    float gb = 0.f, ge = 0.f;
+    if (live) {
+        const RowMeta m = meta[r];
+        ce = m.ye;
+        ge = m.ge;
+        if (m.ye != blank) { cb = blank; gb = m.gb; }
+    }
+    float *row = grads + (size_t)r * V;
+    const int ob = had ? prev_blank : -1;
+    const int oe = had ? prev_cols[r] : -1;
+    if (ob >= 0 && ob != cb && ob != ce) row[ob] = 0.f;
+    if (oe >= 0 && oe != ob && oe != cb && oe != ce) row[oe] = 0.f;
+    if (cb >= 0 && (cb == ob || cb == oe || __float_as_uint(gb) != 0u)) row[cb] = gb;
+    if (ce >= 0 && (ce == ob || ce == oe || __float_as_uint(ge) != 0u)) row[ce] = ge;
+    if (live) cols_out[r] = ce;
+}
+
+// the label column of every row (-1: none), beside a tensor the streaming writer has written
+__global__ __launch_bounds__(256) void rnnt_grad_cols_kernel(const RowMeta *__restrict__ meta, long rows,
+                                                             int *__restrict__ cols_out) {
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < rows) cols_out[r] = meta[r].ye;
+}
+
 __global__ __launch_bounds__(256) void rnnt_export_kernel(
     const float *__restrict__ alpha, const float *__restrict__ beta, const double *__restrict__ off_a,
     const double *__restrict__ off_b, const int *__restrict__ Tn_, const int *__restrict__ Un_,
@@ -1992,6 +2034,37 @@ int write_dense_grads(const Lattice &L, size_t nrows, int V, int blank, float *g
     return (int)hipGetLastError();
 }
 
+// What the tensor `grads` points into held before this call (pika_rnnt.h, pika_rgrad_*), and where the label columns of
+// what it holds afterwards go.  prev_cols null: nothing known, the streaming pass writes every word.
+struct PrevGrad {
+    const int *cols;
+    long long rows;
+    int blank;
+    int *cols_out;
+};
+
+int check_prev_grad(const PrevGrad &p, int V) {
+    if (!p.cols_out) return PIKA_EINVAL;
+    if (p.cols && (p.rows < 0 || p.blank < 0 || p.blank >= V)) return PIKA_EINVAL;
+    return (p.cols && p.rows > ROWS_MAX) ? PIKA_ETOOBIG : PIKA_OK;
+}
+
+// the dense (nrows, V) gradient and its label columns: streamed, or -- over a tensor that holds an earlier one -- updated
+int write_or_update_dense_grads(const Lattice &L, long long nrows, int V, int blank, float *grads, const PrevGrad &p,
+                                hipStream_t s) {
+    if (nrows > ROWS_MAX) return PIKA_ETOOBIG;
+    if (!p.cols) {
+        if (int rc = write_dense_grads(L, (size_t)nrows, V, blank, grads, s)) return rc;
+        hipLaunchKernelGGL(rnnt_grad_cols_kernel, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s, L.meta, (long)nrows,
+                           p.cols_out);
+        return (int)hipGetLastError();
+    }
+    const long long n = nrows > p.rows ? nrows : p.rows;
+    hipLaunchKernelGGL(rnnt_grad_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, L.meta, (long)nrows, V,
+                       blank, p.cols, (long)p.rows, p.blank, grads, p.cols_out);
+    return (int)hipGetLastError();
+}
+
 // d(logits) of the fused route over `rows` rows, from the row metadata in L
 int launch_dlogits_fused(const Lattice &L, const float *logits, const float *lse, long long rows, int V, int blank,
                          void *grad_logits, int out_dtype, long long ld_out, hipStream_t s) {
@@ -2194,6 +2267,31 @@ int pika_rnnt_loss_dense_grads(const void *workspace, int B, int T, int U1, int 
     if (!workspace || !grads) return PIKA_EINVAL;
     const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
     return write_dense_grads(L, (size_t)B * T * U1, V, blank, grads, static_cast<hipStream_t>(stream));
+}
+
+int pika_rgrad_dense_grads_update(const void *workspace, int B, int T, int U1, int V, int blank, float *grads,
+                                  const int *prev_cols, long long prev_rows, int prev_blank, int *cols_out, void *stream) {
+    if (int rc = check_dims(B, T, U1, V, blank)) return rc;
+    if (!workspace || !grads) return PIKA_EINVAL;
+    const PrevGrad p{prev_cols, prev_rows, prev_blank, cols_out};
+    if (int rc = check_prev_grad(p, V)) return rc;
+    const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
+    return write_or_update_dense_grads(L, (long long)B * T * U1, V, blank, grads, p, static_cast<hipStream_t>(stream));
+}
+
+int pika_rgrad_backward_fe(const int *labels, const int *frames_lengths, const int *labels_lengths, int B, int T, int U1,
+                           int V, int blank, const float *grad_costs, const void *workspace, float *grads,
+                           float fastemit_lambda, const int *prev_cols, long long prev_rows, int prev_blank, int *cols_out,
+                           void *stream) {
+    if (int rc = check_dims(B, T, U1, V, blank)) return rc;
+    if (!frames_lengths || !labels_lengths || !workspace || !grads) return PIKA_EINVAL;
+    if (U1 > 1 && !labels) return PIKA_EINVAL;
+    const PrevGrad p{prev_cols, prev_rows, prev_blank, cols_out};
+    if (int rc = check_prev_grad(p, V)) return rc;
+    const Call c = padded_call(labels, frames_lengths, labels_lengths, B, T, U1, V, blank, stream);
+    if (c.rows > ROWS_MAX) return PIKA_ETOOBIG;
+    if (int rc = loss_backward(c, grad_costs, fastemit_lambda, workspace, nullptr)) return rc;   // the row metadata
+    return write_or_update_dense_grads(carve(const_cast<void *>(workspace), B, T, U1), c.rows, V, blank, grads, p, c.s);
 }
 
 int pika_rnnt_loss_fwd_bwd(const float *log_probs, const int *labels, const int *frames_lengths,

@@ -556,6 +556,9 @@ class LogSoftmaxFn(torch.autograd.Function):
             _lib.check(_lib.lib().pika_log_softmax_bwd_rows(lp.data_ptr(), g.data_ptr(), rows, cols,
                                                             cols, ctx.scale, _stream()),
                        "pika_log_softmax_bwd_rows")
+        # a write torch did not see: whoever keeps track of this storage by its version counter (the RNN-T loss, which
+        # writes its next dense gradient over the non-zeros of the last one -- pika_amd.rnnt._dense_backward) must know
+        torch.autograd.graph.increment_version(g)
         return g, None
 
 

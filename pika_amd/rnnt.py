@@ -27,6 +27,8 @@ Two options of warp_rnnt's keyword surface (README "RNN-T loss"):
                    under stream capture; the padded layout never synchronises.
 """
 import math
+import os
+import threading
 
 import torch
 
@@ -311,6 +313,92 @@ def _fill_padded(x, labels, frames_lengths, labels_lengths, blank, logits=False,
     return costs, ws, lse, V, width
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The dense gradient, written over the one returned before (DESIGN.md "RNN-T loss: the reused dense gradient").
+# Every V-row of it has at most two non-zeros.  The backward keeps the STORAGE of the tensor it returned (an alias that
+# shares storage and version counter, not the tensor: autograd still adopts the returned tensor as `.grad` without a
+# copy) and the label column of every row.  When the next backward finds that storage owned by nobody else and unwritten
+# since, the tensor is zero except where this module put something, so the kernel clears those words and stores the new
+# ones (pika_rgrad_backward_fe) instead of streaming B*T*U1*V floats.  One record per device.
+# ---------------------------------------------------------------------------------------------------------------------
+GRAD_REUSE_STATS = {"reused": 0, "full": 0}
+_retained = {}                    # device index -> _Retained
+_retained_lock = threading.Lock()
+_private_owners = []              # what _storage_Use_Count answers for a tensor nobody else holds: measured once
+
+
+class _Retained(object):
+    __slots__ = ("alias", "version", "cap_rows", "rows", "V", "blank", "cols", "stream")
+
+
+def _grad_reuse_enabled():
+    return os.environ.get("PIKA_RNNT_GRAD_REUSE", "1") != "0"
+
+
+def _owners(t):
+    return torch._C._storage_Use_Count(t.untyped_storage()._cdata)
+
+
+def release_grad_buffer(device=None):
+    """Free what the dense backward retains between calls (every device's, or one's): the storage of the last gradient
+    it returned -- if nothing else holds it -- and the row columns beside it."""
+    with _retained_lock:
+        if device is None:
+            _retained.clear()
+        else:
+            index = torch.device(device).index
+            _retained.pop(torch.cuda.current_device() if index is None else index, None)
+
+
+def _reusable(rec, rows, V, stream):
+    if rec is None or rec.V != V or rows > rec.cap_rows or rec.stream != stream or rec.alias._version != rec.version:
+        return False
+    if not _private_owners:
+        _private_owners.append(_owners(torch.empty(1, dtype=torch.float32, device=rec.alias.device)))
+    return _owners(rec.alias) == _private_owners[0]
+
+
+def _dense_backward(lib, ws, dims, labels, frames_lengths, labels_lengths, gc, lam):
+    """The dense (B,T,U1,V) gradient of the padded loss: into the retained storage where that is safe, else into a new
+    tensor, which is retained in its place.  (Called with the workspace's device current.)"""
+    B, T, U1, V, blank = dims
+    rows, stream = B * T * U1, _stream()
+    capturing = torch.cuda.is_current_stream_capturing()
+    if capturing or not _grad_reuse_enabled():      # the plain path; a capture leaves the retention as it is
+        if not capturing:
+            release_grad_buffer(ws.device)
+        GRAD_REUSE_STATS["full"] += 1
+        grads = torch.empty((B, T, U1, V), dtype=torch.float32, device=ws.device)
+        with _timed("bwd"):
+            _lib.check(lib.pika_rnnt_loss_backward_fe(
+                _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank,
+                _ptr(gc), _ptr(ws), _ptr(grads), lam, stream), "pika_rnnt_loss_backward_fe")
+        return grads
+    with _retained_lock:
+        rec = _retained.get(ws.device.index)
+        if _reusable(rec, rows, V, stream):
+            grads = rec.alias.view(-1)[:rows * V].view(B, T, U1, V)
+            prev = (_ptr(rec.cols), rec.rows, rec.blank)
+            GRAD_REUSE_STATS["reused"] += 1
+        else:
+            del rec
+            _retained.pop(ws.device.index, None)      # first: two gradient-sized buffers never coexist
+            grads = torch.empty((B, T, U1, V), dtype=torch.float32, device=ws.device)
+            rec = _Retained()
+            rec.alias, rec.cap_rows, rec.V = grads.detach(), rows, V
+            rec.cols = torch.empty(rows, dtype=torch.int32, device=ws.device)
+            prev = (None, 0, 0)
+            GRAD_REUSE_STATS["full"] += 1
+        with _timed("bwd"):
+            _lib.check(lib.pika_rgrad_backward_fe(
+                _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank,
+                _ptr(gc), _ptr(ws), _ptr(grads), lam, prev[0], prev[1], prev[2], _ptr(rec.cols), stream),
+                "pika_rgrad_backward_fe")
+        rec.version, rec.rows, rec.blank, rec.stream = rec.alias._version, rows, blank, stream
+        _retained[ws.device.index] = rec
+    return grads
+
+
 class _RNNTLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, log_probs, labels, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0):
@@ -350,11 +438,7 @@ class _RNNTLossFn(torch.autograd.Function):
             lazy.lse = lse
             return lazy, None, None, None, None, None
         with torch.cuda.device(ws.device):
-            grads = torch.empty((B, T, U1, V), dtype=torch.float32, device=ws.device)
-            with _timed("bwd"):
-                _lib.check(lib.pika_rnnt_loss_backward_fe(
-                    _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank,
-                    _ptr(gc), _ptr(ws), _ptr(grads), lam, _stream()), "pika_rnnt_loss_backward_fe")
+            grads = _dense_backward(lib, ws, ctx.dims, labels, frames_lengths, labels_lengths, gc, lam)
         grads._pika_compact = CompactGrad(ws, (B, T, U1, V, blank), grads)
         return grads, None, None, None, None, None
 
