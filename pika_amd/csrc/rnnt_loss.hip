@@ -575,44 +575,56 @@ __device__ inline int packed_utterance(const int *__restrict__ roff, int B, long
     return lo;
 }
 
+// What a row's metadata is computed from: the call's labels and lengths, the lattice planes and, per layout, the offsets
+// (PACKED) or the band (BANDED).  An instantiation does not read what its layout does not have.
+struct MetaArgs {
+    const int *labels, *Tn, *Un;
+    int B, T, U1, V;
+    const float *grad_costs;  // null: ones
+    const float *lpb, *lpe, *alpha, *beta;
+    const double *off_a, *off_b, *ll;
+    int Wp, D;
+    float lscale;
+    const int *roff, *loff;
+    long npacked;
+    const int *ranges;
+    int S;
+};
+
+// The metadata of row `row` (< the layout's row count): THE definition, for rnnt_rowmeta_kernel and for the in-place update
+// that computes it on the way (rnnt_grad_rowmeta_update_kernel).
 // MOD (the modified topology, below): un-skewed planes, both edges of cell (t, u) end in row t + 1 -- the blank edge in
 // (t+1, u), the label edge in (t+1, u+1) -- and row T_n is terminal, so the last frame has no special case.
 template <int LAYOUT = PADDED, bool MOD = false>
-__global__ __launch_bounds__(256) void rnnt_rowmeta_kernel(
-    const int *__restrict__ labels, const int *__restrict__ Tn_, const int *__restrict__ Un_,
-    int B, int T, int U1, int V, const float *__restrict__ grad_costs,
-    const float *__restrict__ lpb, const float *__restrict__ lpe, const float *__restrict__ alpha,
-    const float *__restrict__ beta, const double *__restrict__ off_a,
-    const double *__restrict__ off_b, const double *__restrict__ ll, int Wp, int D,
-    RowMeta *__restrict__ meta, float lscale, const int *__restrict__ roff = nullptr,
-    const int *__restrict__ loff = nullptr, long npacked = 0, const int *__restrict__ ranges = nullptr, int S = 0) {
+__device__ inline RowMeta row_meta(const MetaArgs &in, long row) {
     constexpr bool PACKED = LAYOUT == Layout::PACKED, BANDED = LAYOUT == Layout::BANDED;
-    const long row = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long nrows = PACKED ? npacked : BANDED ? (long)B * T * S : (long)B * T * U1;
-    if (row >= nrows) return;
+    const int B = in.B, T = in.T, U1 = in.U1, V = in.V, Wp = in.Wp, D = in.D, S = in.S;
+    const float *lpb = in.lpb, *lpe = in.lpe, *alpha = in.alpha, *beta = in.beta, *grad_costs = in.grad_costs;
+    const double *off_a = in.off_a, *off_b = in.off_b, *ll = in.ll;
+    const float lscale = in.lscale;
     float gb = 0.f, ge = 0.f;
     int ye = -1;
     int u, t, b;
     const int *lab;
     if constexpr (PACKED) {
-        b = packed_utterance(roff, B, row);
-        const int w = clampi(Un_[b], 0, U1 - 1) + 1;
-        const int i = (int)(row - roff[b]);
+        b = packed_utterance(in.roff, B, row);
+        const int w = clampi(in.Un[b], 0, U1 - 1) + 1;
+        const int i = (int)(row - in.roff[b]);
         t = i / w;
         u = i - t * w;
-        lab = labels + loff[b];
+        lab = in.labels + in.loff[b];
     } else if constexpr (BANDED) {
         t = (int)((row / S) % T);
         b = (int)(row / ((long)S * T));
-        u = (int)(row % S) + band_start(ranges, b, T, t, clampi(Un_[b], 0, U1 - 1), S);
-        lab = labels + (size_t)b * (U1 - 1);
+        u = (int)(row % S) + band_start(in.ranges, b, T, t, clampi(in.Un[b], 0, U1 - 1), S);
+        lab = in.labels + (size_t)b * (U1 - 1);
     } else {
         u = (int)(row % U1);
         t = (int)((row / U1) % T);
         b = (int)(row / ((long)U1 * T));
-        lab = labels + (size_t)b * (U1 - 1);
+        lab = in.labels + (size_t)b * (U1 - 1);
     }
-    const int Tn = clampi(Tn_[b], 1, T), Un = clampi(Un_[b], 0, U1 - 1);
+    const int Tn = clampi(in.Tn[b], 1, T), Un = clampi(in.Un[b], 0, U1 - 1);
     if constexpr (MOD) {
         if (t < Tn && u <= Un) {
             const size_t o = ((size_t)b * D + t) * Wp + u;
@@ -649,7 +661,16 @@ __global__ __launch_bounds__(256) void rnnt_rowmeta_kernel(
             }
         }
     }
-    meta[row] = RowMeta{gb, ge, ye, 0};
+    return RowMeta{gb, ge, ye, 0};
+}
+
+template <int LAYOUT = PADDED, bool MOD = false>
+__global__ __launch_bounds__(256) void rnnt_rowmeta_kernel(MetaArgs in, RowMeta *__restrict__ meta) {
+    const long row = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long nrows = LAYOUT == Layout::PACKED ? in.npacked : LAYOUT == Layout::BANDED ? (long)in.B * in.T * in.S
+                                                                                       : (long)in.B * in.T * in.U1;
+    if (row >= nrows) return;
+    meta[row] = row_meta<LAYOUT, MOD>(in, row);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -766,28 +787,52 @@ __global__ __launch_bounds__(256) void rnnt_grad_scalar_kernel(const RowMeta *__
 // -sc * exp(..)) is a value like any other, so the tensor is word for word what the streaming writer
 // leaves.  The label wins over blank (blend_row).  cols_out may be prev_cols (read before written).
 // ---------------------------------------------------------------------------------------------
+// One V-row: its old entries sat in columns ob and oe (-1: none), its new ones are m's (live) or none.
+__device__ inline void update_row(float *__restrict__ row, bool live, const RowMeta &m, int blank, int ob, int oe) {
+    int cb = -1, ce = -1;   // the columns this row's new entries go to
+    float gb = 0.f, ge = 0.f;
+    if (live) {
+        ce = m.ye;
+        ge = m.ge;
+        if (m.ye != blank) { cb = blank; gb = m.gb; }
+    }
+    if (ob >= 0 && ob != cb && ob != ce) row[ob] = 0.f;
+    if (oe >= 0 && oe != ob && oe != cb && oe != ce) row[oe] = 0.f;
+    if (cb >= 0 && (cb == ob || cb == oe || __float_as_uint(gb) != 0u)) row[cb] = gb;
+    if (ce >= 0 && (ce == ob || ce == oe || __float_as_uint(ge) != 0u)) row[ce] = ge;
+}
+
 __global__ __launch_bounds__(256) void rnnt_grad_update_kernel(const RowMeta *__restrict__ meta, long rows, int V,
                                                                int blank, const int *prev_cols, long prev_rows,
                                                                int prev_blank, float *__restrict__ grads, int *cols_out) {
     const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const bool had = r < prev_rows, live = r < rows;
     if (!had && !live) return;
-    int cb = -1, ce = -1;   // the columns this row's new entries go to
-    float gb = 0.f, ge = 0.f;
-    if (live) {
-        const RowMeta m = meta[r];
-        ce = m.ye;
-        ge = m.ge;
-        if (m.ye != blank) { cb = blank; gb = m.gb; }
-    }
-    float *row = grads + (size_t)r * V;
-    const int ob = had ? prev_blank : -1;
     const int oe = had ? prev_cols[r] : -1;
-    if (ob >= 0 && ob != cb && ob != ce) row[ob] = 0.f;
-    if (oe >= 0 && oe != ob && oe != cb && oe != ce) row[oe] = 0.f;
-    if (cb >= 0 && (cb == ob || cb == oe || __float_as_uint(gb) != 0u)) row[cb] = gb;
-    if (ce >= 0 && (ce == ob || ce == oe || __float_as_uint(ge) != 0u)) row[ce] = ge;
-    if (live) cols_out[r] = ce;
+    RowMeta m{0.f, 0.f, -1, 0};
+    if (live) m = meta[r];
+    update_row(grads + (size_t)r * V, live, m, blank, had ? prev_blank : -1, oe);
+    if (live) cols_out[r] = m.ye;
+}
+
+// The same update with the row metadata computed on the way (padded layout, regular topology): a row of this call gets
+// its RowMeta from row_meta, stores it -- the workspace stays complete for the readers of the compact gradient -- and
+// updates its V-row from the registers.  The plane loads and the two exponentials of a wave run under the scattered
+// stores of the others, so the backward over a reused tensor is this one launch.  Workgroups of 512: measured at the
+// benchmark shape against 64 / 128 / 256 threads and 2 / 4 rows per thread (DESIGN.md has the table).
+constexpr int UPDATE_FUSED_THREADS = 512;
+
+__global__ __launch_bounds__(UPDATE_FUSED_THREADS) void rnnt_grad_rowmeta_update_kernel(
+    MetaArgs in, RowMeta *__restrict__ meta, long rows, int blank, const int *prev_cols, long prev_rows, int prev_blank,
+    float *__restrict__ grads, int *cols_out) {
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool had = r < prev_rows, live = r < rows;
+    if (!had && !live) return;
+    const int oe = had ? prev_cols[r] : -1;
+    RowMeta m{0.f, 0.f, -1, 0};
+    if (live) meta[r] = m = row_meta<>(in, r);
+    update_row(grads + (size_t)r * in.V, live, m, blank, had ? prev_blank : -1, oe);
+    if (live) cols_out[r] = m.ye;
 }
 
 // the label column of every row (-1: none), beside a tensor the streaming writer has written
@@ -1972,14 +2017,17 @@ int launch_lse_gather(const Call &c, const Lattice &L, const float *logits, floa
     return ok ? PIKA_OK : PIKA_EINVAL;
 }
 
+MetaArgs meta_args(const Call &c, const Lattice &L, const float *grad_costs, float lscale) {
+    return MetaArgs{c.labels, c.frames_lengths, c.labels_lengths, c.B, c.T, c.U1, c.V, grad_costs, L.lpb, L.lpe, L.alpha,
+                    L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, lscale, c.roff, c.loff, (long)c.rows, c.ranges, c.S};
+}
+
 // row metadata of the call's rows
 int launch_rowmeta(const Call &c, const Lattice &L, const float *grad_costs, float lscale) {
     const bool ok = dispatch_layout(c, [&](auto pair) {
         using P = decltype(pair);
         hipLaunchKernelGGL((rnnt_rowmeta_kernel<P::layout, P::mod>), dim3((unsigned)((c.rows + 255) / 256)), dim3(256), 0, c.s,
-                           c.labels, c.frames_lengths, c.labels_lengths, c.B, c.T, c.U1, c.V, grad_costs, L.lpb, L.lpe,
-                           L.alpha, L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, L.meta, lscale, c.roff, c.loff, (long)c.rows,
-                           c.ranges, c.S);
+                           meta_args(c, L, grad_costs, lscale), L.meta);
     });
     return ok ? PIKA_OK : PIKA_EINVAL;
 }
@@ -2083,6 +2131,20 @@ int label_scale(float fastemit_lambda, float *lscale) {
     if (!(fastemit_lambda >= 0.0f && fastemit_lambda <= 3.4e38f)) return PIKA_EINVAL;
     *lscale = 1.0f + fastemit_lambda;
     return PIKA_OK;
+}
+
+// The padded call's row metadata and, in the same launch, the update of a tensor that holds an earlier gradient (p.cols
+// set, the row counts checked): what launch_rowmeta and then write_or_update_dense_grads do, word for word.
+int rowmeta_and_update_dense_grads(const Call &c, const Lattice &L, const float *grad_costs, float fastemit_lambda,
+                                   float *grads, const PrevGrad &p) {
+    float lscale;
+    if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
+    const long long n = c.rows > p.rows ? c.rows : p.rows;
+    constexpr int NT = UPDATE_FUSED_THREADS;
+    hipLaunchKernelGGL(rnnt_grad_rowmeta_update_kernel, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, c.s,
+                       meta_args(c, L, grad_costs, lscale), L.meta, (long)c.rows, c.blank, p.cols, (long)p.rows, p.blank,
+                       grads, p.cols_out);
+    return (int)hipGetLastError();
 }
 
 // the d(logits) arguments of the fused backward calls
@@ -2290,8 +2352,10 @@ int pika_rgrad_backward_fe(const int *labels, const int *frames_lengths, const i
     if (int rc = check_prev_grad(p, V)) return rc;
     const Call c = padded_call(labels, frames_lengths, labels_lengths, B, T, U1, V, blank, stream);
     if (c.rows > ROWS_MAX) return PIKA_ETOOBIG;
+    const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
+    if (p.cols) return rowmeta_and_update_dense_grads(c, L, grad_costs, fastemit_lambda, grads, p);   // one launch
     if (int rc = loss_backward(c, grad_costs, fastemit_lambda, workspace, nullptr)) return rc;   // the row metadata
-    return write_or_update_dense_grads(carve(const_cast<void *>(workspace), B, T, U1), c.rows, V, blank, grads, p, c.s);
+    return write_or_update_dense_grads(L, c.rows, V, blank, grads, p, c.s);
 }
 
 int pika_rnnt_loss_fwd_bwd(const float *log_probs, const int *labels, const int *frames_lengths,
