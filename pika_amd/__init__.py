@@ -87,6 +87,9 @@ _MSEARCH_EXPORTS = ("ModifiedBeamState", "modified_beam_search", "ModifiedLmBeam
 # The neural LM the search above fuses (pika_amd/model/lm.py).
 _LM_EXPORTS = ("LstmLm",)
 
+# The stateless prediction network and its search context (pika_amd/model/stateless.py).
+_STATELESS_EXPORTS = ("StatelessPredNet", "StatelessContext")
+
 
 def __getattr__(name):
     if name in _CTC_EXPORTS:
@@ -104,9 +107,12 @@ def __getattr__(name):
     if name in _LM_EXPORTS:
         from .model import lm
         return getattr(lm, name)
+    if name in _STATELESS_EXPORTS:
+        from .model import stateless
+        return getattr(stateless, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
 def __dir__():
     return sorted(list(globals()) + list(_CTC_EXPORTS) + list(_RNNT_EXPORTS) + list(_OPS_EXPORTS)
-                  + list(_MSEARCH_EXPORTS) + list(_LM_EXPORTS))
+                  + list(_MSEARCH_EXPORTS) + list(_LM_EXPORTS) + list(_STATELESS_EXPORTS))

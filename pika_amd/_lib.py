@@ -91,6 +91,11 @@ SIGNATURES = {
     "pika_msearch_times_hyps": (_i, [_vp, _vp] + [_i] * 5 + [_vp, _vp]),
     "pika_msearch_times_results": (_i, [_vp, _vp] + [_i] * 6 + [_vp] * 4),
     "pika_msearch_times_commit": (_i, [_vp, _vp] + [_i] * 4 + [_vp] * 3 + [_i] + [_vp] * 2),
+    # include/pika_stateless.h
+    "pika_stateless_forward": (_i, [_vp, _ll, _vp, _vp] + [_i] * 6 + [_vp, _ll, _vp]),
+    "pika_stateless_backward_workspace_bytes": (_sz, [_i] * 5),
+    "pika_stateless_backward": (_i, [_vp, _ll] + [_vp] * 5 + [_ll, _vp, _ll] + [_i] * 6 + [_vp] * 4),
+    "pika_stateless_step": (_i, [_vp] * 3 + [_i] * 4 + [_vp, _vp] + [_i] * 3 + [_vp, _ll, _vp]),
     # include/pika_ctc.h
     "pika_ctc_workspace_bytes": (_sz, [_i, _i, _i]),
     "pika_ctc_align_scratch_bytes": (_sz, [_i, _i, _i]),

@@ -896,8 +896,10 @@ class ModifiedBeamTimes(object):
 
 class ModifiedStreamDecoder(object):
     """`modified_beam_search` chunk by chunk, for audio without an end: a transducer model (`pika_amd.model.transducer.
-    Net`) with the LSTM prediction network (`decoder_type == 'rnn'`; anything else raises NotImplementedError -- the
-    conv-transformer cache is its own item) around a `ModifiedBeamStream` (`.stream`) of `batch` streams.  `lm`,
+    Net`) with the LSTM prediction network (`decoder_type == 'rnn'`) or the stateless one (`'stateless'`: a
+    `StatelessContext` stands where `(h, c)` does below, followed by one kernel per step, re-ordered by a commit's slot_map
+    and reset with the streams; the conv-transformer raises NotImplementedError -- its cache is its own item) around a
+    `ModifiedBeamStream` (`.stream`) of `batch` streams.  `lm`,
     `lm_weight`, `length_bonus`, `candidates` are the stream's.
 
     advance(enc_chunk (batch, Tc, H), lengths=None)   Tc frame steps on a chunk of ENCODER output; lengths (batch,): the
@@ -919,9 +921,10 @@ class ModifiedStreamDecoder(object):
     def __init__(self, model, batch, max_frames, beam=4, lm=None, lm_weight=0.5, length_bonus=0.0, candidates=None,
                  sm_scale=1.0, blank_penalty=0.0, blank=0, precision="fp16x2"):
         from .. import gemm as G
-        if getattr(model, "decoder_type", None) != 'rnn':
+        if getattr(model, "decoder_type", None) not in ('rnn', 'stateless'):
             raise NotImplementedError("ModifiedStreamDecoder steps the LSTM prediction network (decoder_type == 'rnn') "
-                                      "only; the conv-transformer cache is not wired in")
+                                      "and the stateless one ('stateless') only; the conv-transformer cache is not "
+                                      "wired in")
         if precision not in G.PRECISIONS:
             raise ValueError("unknown precision %r" % (precision,))
         p = next(model.parameters())
@@ -932,7 +935,9 @@ class ModifiedStreamDecoder(object):
         s = self.stream
         self.batch, self.beam, self.blank, self.device = s.batch, s.beam, s.blank, s.device
         w1, wg = model.fc1, model.fc_gate
-        H = self.H = w1.weight.shape[1] - model.decoder.hidden_size       # the encoder's share of the joint's input
+        stateless = model.decoder_type == 'stateless'
+        H = self.H = w1.weight.shape[1] - (model.decoder.dim if stateless else model.decoder.hidden_size)   # the encoder's
+        #                                                                                         share of the joint's input
         self.J = w1.weight.shape[0]
         self._we = torch.cat((w1.weight[:, :H], wg.weight[:, :H]), dim=0).contiguous()    # enc -> [e1 | eg]
         self._be = torch.cat((w1.bias, wg.bias), dim=0).contiguous()
@@ -940,6 +945,10 @@ class ModifiedStreamDecoder(object):
         self._flat0 = (torch.arange(self.batch, device=self.device) * self.beam).unsqueeze(1)
         self._offered = torch.zeros(self.batch, dtype=torch.int64, device=self.device)
         self._pred = None
+        self._context = None            # the stateless network's (h, c): every slot's last tokens and the rows for them
+        if stateless:
+            from ..model.stateless import StatelessContext
+            self._context = StatelessContext(model.decoder, self.batch, self.beam, self.blank)
         self._text = [[] for _ in range(self.batch)]
         self.times, self._ttext, self._started = None, None, False
         self.reset()
@@ -968,13 +977,17 @@ class ModifiedStreamDecoder(object):
             for b, w in enumerate([1] * self.batch if which is None else which.tolist()):
                 if w:
                     self._ttext[b] = []
-        G, old = self._precision()
-        try:
-            sos = torch.full((self.batch * self.beam, 1), self.blank, dtype=torch.long, device=self.device)
-            _, st = self.model.decoder(self.model.embed(sos))
-        finally:
-            G.PRECISION = old
-        fresh = [st[0].contiguous(), st[1].contiguous()]
+        if self._context is not None:
+            self._context.reset(which)
+            fresh = []
+        else:
+            G, old = self._precision()
+            try:
+                sos = torch.full((self.batch * self.beam, 1), self.blank, dtype=torch.long, device=self.device)
+                _, st = self.model.decoder(self.model.embed(sos))
+            finally:
+                G.PRECISION = old
+            fresh = [st[0].contiguous(), st[1].contiguous()]
         if which is None or self._pred is None:
             self._pred = fresh
             self._offered.zero_()
@@ -1013,16 +1026,21 @@ class ModifiedStreamDecoder(object):
             J = self.J
             e_all = ops.linear(enc_chunk.contiguous(), self._we, self._be).reshape(B * Tc, 2 * J)   # row b*Tc + t
             brow = torch.arange(B, device=self.device) * Tc
-            hh, cc = self._pred
+            context = self._context
+            if context is None:
+                hh, cc = self._pred
             for _ in range(Tc):
                 tg = (self.stream.consumed.long() - start).clamp(0, Tc - 1)
                 rows = (brow + tg).unsqueeze(1).expand(B, K).reshape(-1)
-                z = e_all.index_select(0, rows) + ops.linear(hh[-1], self._wp)
+                z = e_all.index_select(0, rows) + ops.linear(hh[-1] if context is None else context.rows, self._wp)
                 h = torch.tanh(z[:, :J]) * torch.sigmoid(z[:, J:])
                 logits = ops.linear(h, model.fc2.weight, model.fc2.bias).contiguous()
                 parent, token = self.stream.advance(logits, self._offered, self.sm_scale, self.blank_penalty)
                 if self.times is not None:
                     self.times.step(parent, token)
+                if context is not None:
+                    context.follow(parent, token)
+                    continue
                 flat = (self._flat0 + parent).reshape(-1)
                 hh.copy_(hh.index_select(1, flat))
                 cc.copy_(cc.index_select(1, flat))
@@ -1036,6 +1054,8 @@ class ModifiedStreamDecoder(object):
     @torch.no_grad()
     def commit(self, which=None, max_tail=None, rebase=False):
         tokens, lengths, slot_map = self.stream.commit(which, max_tail, rebase)
+        if self._context is not None:
+            self._context.reorder(slot_map)
         flat = (self._flat0 + slot_map).reshape(-1)
         for s_ in self._pred:
             s_.copy_(s_.index_select(1, flat))
@@ -1079,6 +1099,8 @@ def modified_beam_search(model, x, x_len, beam=4, nbest=1, sm_scale=1.0, blank_p
     the next is captured once and replayed for the rest.
 
     Prediction networks: the LSTM of the shipped recipes (`decoder_type == 'rnn'`) is stepped on its (h, c) state.  The
+    stateless network (`'stateless'`, `pika_amd.model.stateless`) keeps a `StatelessContext`: one kernel per step turns
+    (parent, token) into the next prediction rows; there is no state to re-order.  The
     conv-transformer prediction network is re-run every step on [blank] + hyps() padded to T + 1 positions: correct, not
     fast (the incremental cache of `TransducerDecoder` is not wired in).
 
@@ -1218,6 +1240,7 @@ def _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, pre
         steps = min(max(int(x_len.max()), 0), T)               # (the one host read, before the first launch)
         num_frames = x_len.to(dev).long().clamp(0, T)
         rnn = model.decoder_type == 'rnn'
+        stateless = model.decoder_type == 'stateless'
         state = make_state(B, T, dev, enc_out.dtype)
         after = hook(state) if hook is not None else None
         beside = side(B * K) if side is not None else None
@@ -1231,7 +1254,11 @@ def _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, pre
         flat0 = (torch.arange(B, device=dev) * K).unsqueeze(1)
 
         sos = torch.full((B * K, 1), blank, dtype=torch.long, device=dev)
-        if rnn:
+        if stateless:
+            from ..model.stateless import StatelessContext
+            context = StatelessContext(model.decoder, B, K, blank)
+            pred = [context.rows]                   # the joint's prediction half: rewritten in place by every follow
+        elif rnn:
             _, st = model.decoder(model.embed(sos))
             pred = [st[0].contiguous(), st[1].contiguous()]
         else:
@@ -1251,9 +1278,12 @@ def _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, pre
             if after is not None:
                 after(parent, token)
             flat = (flat0 + parent).reshape(-1)
-            for s_ in pred:
-                s_.copy_(s_.index_select(1 if rnn else 0, flat))
             label = token.reshape(-1).ne(blank)
+            if stateless:                           # one launch: no state to re-order, no hyps() walk
+                context.follow(parent, token)
+            else:
+                for s_ in pred:
+                    s_.copy_(s_.index_select(1 if rnn else 0, flat))
             if beside is not None:
                 beside.follow(flat, token.reshape(-1), label)
             if rnn:
@@ -1262,7 +1292,7 @@ def _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, pre
                 m = label.view(1, -1, 1)
                 hh.copy_(torch.where(m, h2, hh))
                 cc.copy_(torch.where(m, c2, cc))
-            else:
+            elif not stateless:
                 hyp, ln = state.hyps(max_len=T)
                 hyp, ln = hyp.view(B * K, T), ln.view(-1).clamp(min=0)
                 body = torch.where(pos <= ln.unsqueeze(1), hyp, torch.full_like(hyp, pad))

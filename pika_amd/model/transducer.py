@@ -7,6 +7,7 @@ from torch.nn.utils.rnn import pack_padded_sequence, pad_packed_sequence
 from . import ops
 from .encoder import Net as TdnnTransformerEncoder
 from .prednet import Net as ConvTransformerPredNet
+from .stateless import StatelessPredNet
 
 
 def _lstm_forward(rnn, x):
@@ -40,7 +41,10 @@ def _lstm_forward(rnn, x):
 
 class Net(nn.Module):
     """`opt` supplies rnn_size, local_rank, decoder_type, brnn, encoder_type, dropout,
-    enc_layers, dec_layers, embd_dim, padding_idx (transducer.py:27-68)."""
+    enc_layers, dec_layers, embd_dim, padding_idx (transducer.py:27-68).  decoder_type 'rnn' and the conv-transformer are
+    the reference's; 'stateless' (no counterpart there) is the embedding + grouped causal conv + ReLU prediction network of
+    pika_amd/model/stateless.py, of width rnn_size, with opt.context_size (2) and opt.decoder_groups (rnn_size // 4) where
+    `opt` has them; `embed` is then the decoder's own embedding."""
 
     def __init__(self, opt, input_dim, output_dim):
         super().__init__()
@@ -60,15 +64,22 @@ class Net(nn.Module):
                                                   output_dim=self.hid_dim, tdnn_nhid=1024,
                                                   tdnn_layers=9)
             self.pack_seq = False
-        self.embed = nn.Embedding(output_dim + 1, opt.embd_dim, padding_idx=opt.padding_idx)
-        if opt.decoder_type == 'rnn':
-            self.decoder = nn.LSTM(input_size=opt.embd_dim, hidden_size=self.hid_dim,
-                                   dropout=opt.dropout, num_layers=opt.dec_layers,
-                                   bidirectional=False, batch_first=True)
+        if opt.decoder_type == 'stateless':
+            # embedding + grouped causal conv over the last context_size labels + ReLU (pika_amd/model/stateless.py); the
+            # embedding is the decoder's own, of the decoder's width
+            self.decoder = StatelessPredNet(output_dim + 1, self.hid_dim, getattr(opt, 'context_size', 2),
+                                            getattr(opt, 'decoder_groups', None))
+            self.embed = self.decoder.embedding
         else:
-            self.decoder = ConvTransformerPredNet(embeddings=self.embed, output_dim=self.hid_dim,
-                                                  d_model=512, num_layers=opt.dec_layers, heads=8,
-                                                  d_ff=2048, dropout=opt.dropout)
+            self.embed = nn.Embedding(output_dim + 1, opt.embd_dim, padding_idx=opt.padding_idx)
+            if opt.decoder_type == 'rnn':
+                self.decoder = nn.LSTM(input_size=opt.embd_dim, hidden_size=self.hid_dim,
+                                       dropout=opt.dropout, num_layers=opt.dec_layers,
+                                       bidirectional=False, batch_first=True)
+            else:
+                self.decoder = ConvTransformerPredNet(embeddings=self.embed, output_dim=self.hid_dim,
+                                                      d_model=512, num_layers=opt.dec_layers, heads=8,
+                                                      d_ff=2048, dropout=opt.dropout)
         self.fc1 = nn.Linear(2 * self.hid_dim, self.hid_dim)
         self.fc_gate = nn.Linear(2 * self.hid_dim, self.hid_dim)
         self.fc2 = nn.Linear(self.hid_dim, output_dim)
@@ -86,7 +97,7 @@ class Net(nn.Module):
         """Prediction network on label sequences that already start with SOS (= blank = 0)."""
         if self.decoder_type == 'rnn':
             return _lstm_forward(self.decoder, self.embed(y))
-        return self.decoder(y)
+        return self.decoder(y)          # (the conv-transformer and the stateless network embed for themselves)
 
     def forward(self, x, y, x_len=None, softmax=True):
         """transducer.py:73-112.  A TRAINING call on a HIP device may be served by a hipGraph replay of this very

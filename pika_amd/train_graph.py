@@ -163,6 +163,8 @@ def wanted(model, x, softmax):
     """Does this forward call go through the graphs?  (The cheap checks; `forward` below does the rest.)"""
     if os.environ.get("PIKA_TRAIN_GRAPH", "1") == "0":
         return False
+    if getattr(model, "decoder_type", None) == 'stateless':
+        return False        # declined: the stateless prediction network trains through the eager step (DESIGN.md section 3)
     st = model.__dict__.get("_step_graphs")
     if st is None:
         if not AUTO or not (model.training and x.is_cuda and torch.is_grad_enabled()):
