@@ -90,6 +90,9 @@ _LM_EXPORTS = ("LstmLm",)
 # The stateless prediction network and its search context (pika_amd/model/stateless.py).
 _STATELESS_EXPORTS = ("StatelessPredNet", "StatelessContext")
 
+# CTC-guided frame skipping (pika_amd/frame_skip.py).
+_FSKIP_EXPORTS = ("FrameSkipPlan", "ctc_skip_plan", "frame_skip_apply", "frame_skip_times", "modified_beam_search_skip")
+
 
 def __getattr__(name):
     if name in _CTC_EXPORTS:
@@ -110,9 +113,12 @@ def __getattr__(name):
     if name in _STATELESS_EXPORTS:
         from .model import stateless
         return getattr(stateless, name)
+    if name in _FSKIP_EXPORTS:
+        from . import frame_skip
+        return getattr(frame_skip, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
 def __dir__():
     return sorted(list(globals()) + list(_CTC_EXPORTS) + list(_RNNT_EXPORTS) + list(_OPS_EXPORTS)
-                  + list(_MSEARCH_EXPORTS) + list(_LM_EXPORTS) + list(_STATELESS_EXPORTS))
+                  + list(_MSEARCH_EXPORTS) + list(_LM_EXPORTS) + list(_STATELESS_EXPORTS) + list(_FSKIP_EXPORTS))

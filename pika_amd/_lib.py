@@ -149,6 +149,10 @@ SIGNATURES = {
                                     + [_i] * 3 + [_vp] * 5),
     "pika_ctc_lm2_stream_commit_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "pika_ctc_lm2_stream_commit": (_i, [_vp] + [_i] * 4 + [_vp, _i, _i] + [_vp] * 4),
+    # include/pika_frame_skip.h
+    "pika_fskip_rows": (_i, [_vp, _ll, _ll, _vp] + [_i] * 5 + [_vp, _vp]),
+    "pika_fskip_plan": (_i, [_vp, _vp, _vp, _i, _i, _f] + [_vp] * 4),
+    "pika_fskip_apply": (_i, [_vp, _ll, _ll, _vp, _i, _i, _ll, _i, _vp, _vp]),
     # include/pika_bmuf.h
     "pika_bmuf_delta": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "pika_bmuf_nan_flag": (_i, [_vp, _sz, _vp, _vp]),

@@ -1216,11 +1216,13 @@ class _LmRows(object):
 
 
 def _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, precision, make_state, results, side=None,
-           hook=None):
+           reduce=None, hook=None):
     """The loop of `modified_beam_search` around a search state: make_state(B, T, device, dtype) -> the state,
     results(state) -> what the call returns ahead of enc_out, side(B * beam) -> a `_LmRows`: what `advance` takes behind
     the logits, re-ordered and stepped with the prediction network (None: nothing), hook(state) -> a callable that every
-    step hands its (parent, token) right after the advance (None: there is none)."""
+    step hands its (parent, token) right after the advance (None: there is none), reduce(enc_out, x_len) -> (frames, lengths):
+    what the step loop runs on instead of the encoder's output and x_len, of the same (B, T, H) shape (None: those
+    themselves; `pika_amd.frame_skip.modified_beam_search_skip`).  The call returns the encoder's own output either way."""
     from .. import gemm as G
     from ..model import ops
     K, blank = int(beam), int(blank)
@@ -1234,8 +1236,11 @@ def _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, pre
             enc_out = model.encode(x, x_len)
         else:
             enc_out = model.encoder(x)
-        B, T, H = enc_out.shape
-        dev = enc_out.device
+        frames = enc_out
+        if reduce is not None:
+            frames, x_len = reduce(enc_out, x_len)
+        B, T, H = frames.shape
+        dev = frames.device
         x_len = torch.as_tensor(x_len)
         steps = min(max(int(x_len.max()), 0), T)               # (the one host read, before the first launch)
         num_frames = x_len.to(dev).long().clamp(0, T)
@@ -1246,8 +1251,8 @@ def _drive(model, x, x_len, beam, sm_scale, blank_penalty, use_graph, blank, pre
         beside = side(B * K) if side is not None else None
 
         w1, wg = model.fc1, model.fc_gate
-        e1_all = ops.linear(enc_out, w1.weight[:, :H].contiguous(), w1.bias)
-        eg_all = ops.linear(enc_out, wg.weight[:, :H].contiguous(), wg.bias)
+        e1_all = ops.linear(frames, w1.weight[:, :H].contiguous(), w1.bias)
+        eg_all = ops.linear(frames, wg.weight[:, :H].contiguous(), wg.bias)
         e_all = torch.cat((e1_all, eg_all), dim=2).reshape(B * T, 2 * H)          # row b*T + t = [e1 | eg]
         wp = torch.cat((w1.weight[:, H:], wg.weight[:, H:]), dim=0).contiguous()  # (2H, H)
         brow = torch.arange(B, device=dev) * T
