@@ -107,6 +107,14 @@ int pika_rgrad_backward_fe(const int *labels, const int *frames_lengths, const i
                            const void *workspace, float *grads, float fastemit_lambda, const int *prev_cols,
                            long long prev_rows, int prev_blank, int *cols_out, void *stream);
 
+/* pika_rgrad_backward_fe with an element stride for grad_costs: utterance b's factor is grad_costs[b * gc_stride]
+ * (0: one expanded scalar, as `costs.sum().backward()` hands it over).  gc_stride < 0: PIKA_EINVAL, after the checks
+ * of pika_rgrad_backward_fe, which is this entry with gc_stride = 1. */
+int pika_rgrad_backward_fe_s(const int *labels, const int *frames_lengths, const int *labels_lengths,
+                             int B, int T, int U1, int V, int blank, const float *grad_costs, long long gc_stride,
+                             const void *workspace, float *grads, float fastemit_lambda, const int *prev_cols,
+                             long long prev_rows, int prev_blank, int *cols_out, void *stream);
+
 /* warp_rnnt-shaped one-shot: forward + backward with unit grad_costs. */
 int pika_rnnt_loss_fwd_bwd(const float *log_probs, const int *labels,
                            const int *frames_lengths, const int *labels_lengths,

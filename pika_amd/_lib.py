@@ -39,6 +39,7 @@ SIGNATURES = {
     # its recorded table of every pika_rnnt_* / pika_prnnt_* entry)
     "pika_rgrad_dense_grads_update": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _ll, _i, _vp, _vp]),
     "pika_rgrad_backward_fe": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _ll, _i, _vp, _vp]),
+    "pika_rgrad_backward_fe_s": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _ll, _vp, _vp, _f, _vp, _ll, _i, _vp, _vp]),
     "pika_rnnt_align_scratch_bytes": (_sz, [_i, _i, _i]),
     "pika_rnnt_align": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     # include/pika_rnnt.h, the pruned (banded) lattice

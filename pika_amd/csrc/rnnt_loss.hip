@@ -581,6 +581,7 @@ struct MetaArgs {
     const int *labels, *Tn, *Un;
     int B, T, U1, V;
     const float *grad_costs;  // null: ones
+    long gc_stride;           // utterance b's factor is grad_costs[b * gc_stride] (0: one expanded scalar)
     const float *lpb, *lpe, *alpha, *beta;
     const double *off_a, *off_b, *ll;
     int Wp, D;
@@ -591,45 +592,25 @@ struct MetaArgs {
     int S;
 };
 
-// The metadata of row `row` (< the layout's row count): THE definition, for rnnt_rowmeta_kernel and for the in-place update
-// that computes it on the way (rnnt_grad_rowmeta_update_kernel).
+// The metadata of cell (t, u) of utterance b, whose labels are lab: THE definition, for rnnt_rowmeta_kernel (through
+// row_meta, which finds the cell of a row) and for the in-place updates that compute it on the way
+// (rnnt_grad_rowmeta_update_kernel through row_meta, rnnt_grad_rowmeta_update_frames_kernel from its own (b, t, u)).
 // MOD (the modified topology, below): un-skewed planes, both edges of cell (t, u) end in row t + 1 -- the blank edge in
 // (t+1, u), the label edge in (t+1, u+1) -- and row T_n is terminal, so the last frame has no special case.
-template <int LAYOUT = PADDED, bool MOD = false>
-__device__ inline RowMeta row_meta(const MetaArgs &in, long row) {
-    constexpr bool PACKED = LAYOUT == Layout::PACKED, BANDED = LAYOUT == Layout::BANDED;
-    const int B = in.B, T = in.T, U1 = in.U1, V = in.V, Wp = in.Wp, D = in.D, S = in.S;
+template <bool MOD = false>
+__device__ inline RowMeta cell_meta(const MetaArgs &in, int b, int t, int u, const int *__restrict__ lab) {
+    const int T = in.T, U1 = in.U1, V = in.V, Wp = in.Wp, D = in.D;
     const float *lpb = in.lpb, *lpe = in.lpe, *alpha = in.alpha, *beta = in.beta, *grad_costs = in.grad_costs;
     const double *off_a = in.off_a, *off_b = in.off_b, *ll = in.ll;
     const float lscale = in.lscale;
     float gb = 0.f, ge = 0.f;
     int ye = -1;
-    int u, t, b;
-    const int *lab;
-    if constexpr (PACKED) {
-        b = packed_utterance(in.roff, B, row);
-        const int w = clampi(in.Un[b], 0, U1 - 1) + 1;
-        const int i = (int)(row - in.roff[b]);
-        t = i / w;
-        u = i - t * w;
-        lab = in.labels + in.loff[b];
-    } else if constexpr (BANDED) {
-        t = (int)((row / S) % T);
-        b = (int)(row / ((long)S * T));
-        u = (int)(row % S) + band_start(in.ranges, b, T, t, clampi(in.Un[b], 0, U1 - 1), S);
-        lab = in.labels + (size_t)b * (U1 - 1);
-    } else {
-        u = (int)(row % U1);
-        t = (int)((row / U1) % T);
-        b = (int)(row / ((long)U1 * T));
-        lab = in.labels + (size_t)b * (U1 - 1);
-    }
     const int Tn = clampi(in.Tn[b], 1, T), Un = clampi(in.Un[b], 0, U1 - 1);
     if constexpr (MOD) {
         if (t < Tn && u <= Un) {
             const size_t o = ((size_t)b * D + t) * Wp + u;
             const float a = alpha[o];
-            const float sc = grad_costs ? grad_costs[b] : 1.0f;
+            const float sc = grad_costs ? grad_costs[b * in.gc_stride] : 1.0f;
             // (ll = +inf where the utterance has no path: every exponent is -inf, every entry zero)
             const float k1 = (float)(off_a[(size_t)b * D + t] - ll[b] + off_b[(size_t)b * D + t + 1]);
             gb = -sc * __expf(k1 + (a + beta[o + Wp] + lpb[o]));
@@ -645,7 +626,7 @@ __device__ inline RowMeta row_meta(const MetaArgs &in, long row) {
         const int d = t + u;
         const size_t o = ((size_t)b * D + d) * Wp + u;
         const float a = alpha[o];
-        const float sc = grad_costs ? grad_costs[b] : 1.0f;
+        const float sc = grad_costs ? grad_costs[b * in.gc_stride] : 1.0f;
         const double base = off_a[(size_t)b * D + d] - ll[b];
         // exponent = alpha + beta' + lp - ll, with the large parts cancelled in fp64
         const float k1 = (d + 1 < D) ? (float)(base + off_b[(size_t)b * D + d + 1]) : 0.0f;
@@ -662,6 +643,37 @@ __device__ inline RowMeta row_meta(const MetaArgs &in, long row) {
         }
     }
     return RowMeta{gb, ge, ye, 0};
+}
+
+// the padded layout's labels of utterance b
+__device__ inline const int *padded_labels(const MetaArgs &in, int b) { return in.labels + (size_t)b * (in.U1 - 1); }
+
+// The metadata of row `row` (< the layout's row count): the row's cell, then cell_meta.
+template <int LAYOUT = PADDED, bool MOD = false>
+__device__ inline RowMeta row_meta(const MetaArgs &in, long row) {
+    constexpr bool PACKED = LAYOUT == Layout::PACKED, BANDED = LAYOUT == Layout::BANDED;
+    const int B = in.B, T = in.T, U1 = in.U1, S = in.S;
+    int u, t, b;
+    const int *lab;
+    if constexpr (PACKED) {
+        b = packed_utterance(in.roff, B, row);
+        const int w = clampi(in.Un[b], 0, U1 - 1) + 1;
+        const int i = (int)(row - in.roff[b]);
+        t = i / w;
+        u = i - t * w;
+        lab = in.labels + in.loff[b];
+    } else if constexpr (BANDED) {
+        t = (int)((row / S) % T);
+        b = (int)(row / ((long)S * T));
+        u = (int)(row % S) + band_start(in.ranges, b, T, t, clampi(in.Un[b], 0, U1 - 1), S);
+        lab = padded_labels(in, b);
+    } else {
+        u = (int)(row % U1);
+        t = (int)((row / U1) % T);
+        b = (int)(row / ((long)U1 * T));
+        lab = padded_labels(in, b);
+    }
+    return cell_meta<MOD>(in, b, t, u, lab);
 }
 
 template <int LAYOUT = PADDED, bool MOD = false>
@@ -693,12 +705,16 @@ __global__ __launch_bounds__(256) void rnnt_rowmeta_kernel(MetaArgs in, RowMeta 
 // ---------------------------------------------------------------------------------------------
 constexpr int GRAD_RUN_SHIFT = 6;  // GRAD_RUN = 64 chunks
 
-__device__ inline unsigned grad_chunk(unsigned b, unsigned nblocks) {
-    constexpr unsigned gmask = (8u << GRAD_RUN_SHIFT) - 1;
+// the map itself, for runs of 1 << RUN_SHIFT chunks (shared with the frame runs of rnnt_grad_rowmeta_update_frames_kernel)
+template <int RUN_SHIFT>
+__device__ inline unsigned xcd_run_chunk(unsigned b, unsigned nblocks) {
+    constexpr unsigned gmask = (8u << RUN_SHIFT) - 1;
     if ((b | gmask) >= nblocks) return b;  // the last group is partial: linear
     const unsigned j = b & gmask;
-    return (b & ~gmask) | ((j & 7u) << GRAD_RUN_SHIFT) | (j >> 3);
+    return (b & ~gmask) | ((j & 7u) << RUN_SHIFT) | (j >> 3);
 }
+
+__device__ inline unsigned grad_chunk(unsigned b, unsigned nblocks) { return xcd_run_chunk<GRAD_RUN_SHIFT>(b, nblocks); }
 
 __device__ inline v4f blend_row(int q, int qb, int cb, float gb, float ge, int ye) {
     const int qe = ye >> 2, ce = ye & 3;  // ye = -1 -> qe = -1: never matches
@@ -819,7 +835,9 @@ __global__ __launch_bounds__(256) void rnnt_grad_update_kernel(const RowMeta *__
 // its RowMeta from row_meta, stores it -- the workspace stays complete for the readers of the compact gradient -- and
 // updates its V-row from the registers.  The plane loads and the two exponentials of a wave run under the scattered
 // stores of the others, so the backward over a reused tensor is this one launch.  Workgroups of 512: measured at the
-// benchmark shape against 64 / 128 / 256 threads and 2 / 4 rows per thread (DESIGN.md has the table).
+// benchmark shape against 64 / 128 / 256 threads and 2 / 4 rows per thread (DESIGN.md has the table).  This is the
+// linear map, row = workgroup * 512 + thread, with row_meta's divisions: what runs when more than 512 columns, or the
+// tail of a far larger earlier gradient, keep a call off the frame map below.
 constexpr int UPDATE_FUSED_THREADS = 512;
 
 __global__ __launch_bounds__(UPDATE_FUSED_THREADS) void rnnt_grad_rowmeta_update_kernel(
@@ -831,6 +849,50 @@ __global__ __launch_bounds__(UPDATE_FUSED_THREADS) void rnnt_grad_rowmeta_update
     const int oe = had ? prev_cols[r] : -1;
     RowMeta m{0.f, 0.f, -1, 0};
     if (live) meta[r] = m = row_meta<>(in, r);
+    update_row(grads + (size_t)r * in.V, live, m, blank, had ? prev_blank : -1, oe);
+    if (live) cols_out[r] = m.ye;
+}
+
+// The same kernel with a thread-to-row map that needs no division by a run-time number: a workgroup with
+// blockIdx.y < B owns F = UPDATE_FUSED_THREADS / U1 consecutive frames of utterance blockIdx.y (U1 <= the workgroup), thread
+// i < F * U1 is cell (t0 + i / U1, i % U1), and i / U1 is a multiply by the host's recip = ceil(2^20 / U1) and a shift
+// (exact for i < 512 and U1 <= 512: 512 * (recip * U1 - 2^20) < 512 * 512 < 2^20).  Threads past F * U1, and past frame T
+// in an utterance's last workgroup, have no row.  Rows [rows, prev_rows) of a larger earlier gradient belong to no
+// utterance of this call: the workgroups with blockIdx.y >= B take them, 512 consecutive rows each.  So every row below
+// max(prev_rows, rows) has exactly one thread, as in the linear map, and no store of one thread depends on another's.
+// The frame chunk of a workgroup is not blockIdx.x itself: a line of the lattice planes (32 columns of one diagonal) is
+// read by 32 consecutive frames, that is by three or four consecutive chunks at the benchmark shape, and under the
+// linear map those run on different XCDs, each of which pulls the line into its own L2.  xcd_run_chunk hands the
+// workgroups blockIdx.x, blockIdx.x + 8, .. (one XCD, whatever the row's first one is) runs of 1 << FRAME_RUN_SHIFT
+// consecutive chunks of the utterance; a bijection for any grid, the partial last group linear.
+struct FrameMap {
+    int F;           // frames per workgroup
+    unsigned recip;  // ceil(2^20 / U1)
+};
+
+constexpr int FRAME_RUN_SHIFT = 2;  // runs of 4 frame chunks
+
+__global__ __launch_bounds__(UPDATE_FUSED_THREADS) void rnnt_grad_rowmeta_update_frames_kernel(
+    MetaArgs in, RowMeta *__restrict__ meta, FrameMap fm, long rows, int blank, const int *prev_cols, long prev_rows,
+    int prev_blank, float *__restrict__ grads, int *cols_out) {
+    const unsigned i = threadIdx.x;
+    const bool live = blockIdx.y < (unsigned)in.B;
+    long r;
+    int t = 0, u = 0;
+    if (live) {
+        const unsigned f = (i * fm.recip) >> 20;
+        t = (int)(xcd_run_chunk<FRAME_RUN_SHIFT>(blockIdx.x, gridDim.x) * (unsigned)fm.F + f);
+        u = (int)(i - f * (unsigned)in.U1);
+        if (f >= (unsigned)fm.F || t >= in.T) return;
+        r = ((long)blockIdx.y * in.T + t) * in.U1 + u;
+    } else {
+        r = rows + ((long)(blockIdx.y - (unsigned)in.B) * gridDim.x + blockIdx.x) * UPDATE_FUSED_THREADS + i;
+        if (r >= prev_rows) return;
+    }
+    const bool had = r < prev_rows;
+    const int oe = had ? prev_cols[r] : -1;
+    RowMeta m{0.f, 0.f, -1, 0};
+    if (live) meta[r] = m = cell_meta<>(in, (int)blockIdx.y, t, u, padded_labels(in, (int)blockIdx.y));
     update_row(grads + (size_t)r * in.V, live, m, blank, had ? prev_blank : -1, oe);
     if (live) cols_out[r] = m.ye;
 }
@@ -2017,17 +2079,17 @@ int launch_lse_gather(const Call &c, const Lattice &L, const float *logits, floa
     return ok ? PIKA_OK : PIKA_EINVAL;
 }
 
-MetaArgs meta_args(const Call &c, const Lattice &L, const float *grad_costs, float lscale) {
-    return MetaArgs{c.labels, c.frames_lengths, c.labels_lengths, c.B, c.T, c.U1, c.V, grad_costs, L.lpb, L.lpe, L.alpha,
+MetaArgs meta_args(const Call &c, const Lattice &L, const float *grad_costs, float lscale, long gc_stride = 1) {
+    return MetaArgs{c.labels, c.frames_lengths, c.labels_lengths, c.B, c.T, c.U1, c.V, grad_costs, gc_stride, L.lpb, L.lpe, L.alpha,
                     L.beta, L.off_a, L.off_b, L.ll, L.Wp, L.D, lscale, c.roff, c.loff, (long)c.rows, c.ranges, c.S};
 }
 
 // row metadata of the call's rows
-int launch_rowmeta(const Call &c, const Lattice &L, const float *grad_costs, float lscale) {
+int launch_rowmeta(const Call &c, const Lattice &L, const float *grad_costs, float lscale, long gc_stride = 1) {
     const bool ok = dispatch_layout(c, [&](auto pair) {
         using P = decltype(pair);
         hipLaunchKernelGGL((rnnt_rowmeta_kernel<P::layout, P::mod>), dim3((unsigned)((c.rows + 255) / 256)), dim3(256), 0, c.s,
-                           meta_args(c, L, grad_costs, lscale), L.meta);
+                           meta_args(c, L, grad_costs, lscale, gc_stride), L.meta);
     });
     return ok ? PIKA_OK : PIKA_EINVAL;
 }
@@ -2135,15 +2197,27 @@ int label_scale(float fastemit_lambda, float *lscale) {
 
 // The padded call's row metadata and, in the same launch, the update of a tensor that holds an earlier gradient (p.cols
 // set, the row counts checked): what launch_rowmeta and then write_or_update_dense_grads do, word for word.
-int rowmeta_and_update_dense_grads(const Call &c, const Lattice &L, const float *grad_costs, float fastemit_lambda,
-                                   float *grads, const PrevGrad &p) {
+int rowmeta_and_update_dense_grads(const Call &c, const Lattice &L, const float *grad_costs, long long gc_stride,
+                                   float fastemit_lambda, float *grads, const PrevGrad &p) {
     float lscale;
     if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
-    const long long n = c.rows > p.rows ? c.rows : p.rows;
     constexpr int NT = UPDATE_FUSED_THREADS;
-    hipLaunchKernelGGL(rnnt_grad_rowmeta_update_kernel, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, c.s,
-                       meta_args(c, L, grad_costs, lscale), L.meta, (long)c.rows, c.blank, p.cols, (long)p.rows, p.blank,
-                       grads, p.cols_out);
+    const MetaArgs in = meta_args(c, L, grad_costs, lscale, (long)gc_stride);
+    // the frame map: whole frames in a workgroup, and the tail of a larger earlier gradient within the grid's y range
+    // (ny > 65535 needs an earlier gradient of more than 33 million rows behind a call of one workgroup per utterance:
+    // no test builds one; that call takes the linear kernel, which the tests reach through U1 = 513 and 1024)
+    const int F = c.U1 <= NT ? NT / c.U1 : 0;
+    const long long nx = F ? (c.T + F - 1) / F : 0, tail = p.rows > c.rows ? p.rows - c.rows : 0;
+    const long long ny = F ? c.B + (tail + nx * NT - 1) / (nx * NT) : 0;
+    if (F && ny <= 65535) {
+        const FrameMap fm{F, (unsigned)(((1u << 20) + c.U1 - 1) / c.U1)};
+        hipLaunchKernelGGL(rnnt_grad_rowmeta_update_frames_kernel, dim3((unsigned)nx, (unsigned)ny), dim3(NT), 0, c.s, in, L.meta,
+                           fm, (long)c.rows, c.blank, p.cols, (long)p.rows, p.blank, grads, p.cols_out);
+        return (int)hipGetLastError();
+    }
+    const long long n = c.rows > p.rows ? c.rows : p.rows;   // the linear map: one thread per row, divisions in row_meta
+    hipLaunchKernelGGL(rnnt_grad_rowmeta_update_kernel, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, c.s, in, L.meta,
+                       (long)c.rows, c.blank, p.cols, (long)p.rows, p.blank, grads, p.cols_out);
     return (int)hipGetLastError();
 }
 
@@ -2163,11 +2237,12 @@ int loss_forward(const Call &c, const float *log_probs, float *costs, void *work
 }
 
 // grads null: row metadata only (pika_rnnt.h)
-int loss_backward(const Call &c, const float *grad_costs, float fastemit_lambda, const void *workspace, float *grads) {
+int loss_backward(const Call &c, const float *grad_costs, float fastemit_lambda, const void *workspace, float *grads,
+                  long gc_stride = 1) {
     float lscale;
     if (int rc = label_scale(fastemit_lambda, &lscale)) return rc;
     const Lattice L = carve(const_cast<void *>(workspace), c.B, c.T, c.U1, c.mod);
-    if (int rc = launch_rowmeta(c, L, grad_costs, lscale)) return rc;
+    if (int rc = launch_rowmeta(c, L, grad_costs, lscale, gc_stride)) return rc;
     if (!grads) return (int)hipGetLastError();
     return write_dense_grads(L, (size_t)c.rows, c.V, c.blank, grads, c.s);
 }
@@ -2345,6 +2420,14 @@ int pika_rgrad_backward_fe(const int *labels, const int *frames_lengths, const i
                            int V, int blank, const float *grad_costs, const void *workspace, float *grads,
                            float fastemit_lambda, const int *prev_cols, long long prev_rows, int prev_blank, int *cols_out,
                            void *stream) {
+    return pika_rgrad_backward_fe_s(labels, frames_lengths, labels_lengths, B, T, U1, V, blank, grad_costs, 1, workspace,
+                                    grads, fastemit_lambda, prev_cols, prev_rows, prev_blank, cols_out, stream);
+}
+
+int pika_rgrad_backward_fe_s(const int *labels, const int *frames_lengths, const int *labels_lengths, int B, int T, int U1,
+                             int V, int blank, const float *grad_costs, long long gc_stride, const void *workspace,
+                             float *grads, float fastemit_lambda, const int *prev_cols, long long prev_rows, int prev_blank,
+                             int *cols_out, void *stream) {
     if (int rc = check_dims(B, T, U1, V, blank)) return rc;
     if (!frames_lengths || !labels_lengths || !workspace || !grads) return PIKA_EINVAL;
     if (U1 > 1 && !labels) return PIKA_EINVAL;
@@ -2352,9 +2435,10 @@ int pika_rgrad_backward_fe(const int *labels, const int *frames_lengths, const i
     if (int rc = check_prev_grad(p, V)) return rc;
     const Call c = padded_call(labels, frames_lengths, labels_lengths, B, T, U1, V, blank, stream);
     if (c.rows > ROWS_MAX) return PIKA_ETOOBIG;
+    if (gc_stride < 0) return PIKA_EINVAL;
     const Lattice L = carve(const_cast<void *>(workspace), B, T, U1);
-    if (p.cols) return rowmeta_and_update_dense_grads(c, L, grad_costs, fastemit_lambda, grads, p);   // one launch
-    if (int rc = loss_backward(c, grad_costs, fastemit_lambda, workspace, nullptr)) return rc;   // the row metadata
+    if (p.cols) return rowmeta_and_update_dense_grads(c, L, grad_costs, gc_stride, fastemit_lambda, grads, p);   // one launch
+    if (int rc = loss_backward(c, grad_costs, fastemit_lambda, workspace, nullptr, (long)gc_stride)) return rc;   // the row metadata
     return write_or_update_dense_grads(L, c.rows, V, blank, grads, p, c.s);
 }
 

@@ -358,9 +358,11 @@ def _reusable(rec, rows, V, stream):
     return _owners(rec.alias) == _private_owners[0]
 
 
-def _dense_backward(lib, ws, dims, labels, frames_lengths, labels_lengths, gc, lam):
+def _dense_backward(lib, ws, dims, labels, frames_lengths, labels_lengths, grad_costs, lam):
     """The dense (B,T,U1,V) gradient of the padded loss: into the retained storage where that is safe, else into a new
-    tensor, which is retained in its place.  (Called with the workspace's device current.)"""
+    tensor, which is retained in its place.  (Called with the workspace's device current.)  The reuse path's kernel reads a
+    1-D fp32 grad_costs through its own stride -- 0 for the expanded scalar of `costs.sum().backward()` -- so only other
+    dtypes and layouts, and the plain path, pay for a contiguous copy."""
     B, T, U1, V, blank = dims
     rows, stream = B * T * U1, _stream()
     capturing = torch.cuda.is_current_stream_capturing()
@@ -368,12 +370,17 @@ def _dense_backward(lib, ws, dims, labels, frames_lengths, labels_lengths, gc, l
         if not capturing:
             release_grad_buffer(ws.device)
         GRAD_REUSE_STATS["full"] += 1
+        gc = grad_costs.to(torch.float32).contiguous()
         grads = torch.empty((B, T, U1, V), dtype=torch.float32, device=ws.device)
         with _timed("bwd"):
             _lib.check(lib.pika_rnnt_loss_backward_fe(
                 _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank,
                 _ptr(gc), _ptr(ws), _ptr(grads), lam, stream), "pika_rnnt_loss_backward_fe")
         return grads
+    if grad_costs.dtype == torch.float32 and grad_costs.dim() == 1:
+        gc, gc_stride = grad_costs, grad_costs.stride(0)
+    else:
+        gc, gc_stride = grad_costs.to(torch.float32).contiguous(), 1
     with _retained_lock:
         rec = _retained.get(ws.device.index)
         if _reusable(rec, rows, V, stream):
@@ -390,10 +397,10 @@ def _dense_backward(lib, ws, dims, labels, frames_lengths, labels_lengths, gc, l
             prev = (None, 0, 0)
             GRAD_REUSE_STATS["full"] += 1
         with _timed("bwd"):
-            _lib.check(lib.pika_rgrad_backward_fe(
+            _lib.check(lib.pika_rgrad_backward_fe_s(
                 _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank,
-                _ptr(gc), _ptr(ws), _ptr(grads), lam, prev[0], prev[1], prev[2], _ptr(rec.cols), stream),
-                "pika_rgrad_backward_fe")
+                _ptr(gc), gc_stride, _ptr(ws), _ptr(grads), lam, prev[0], prev[1], prev[2], _ptr(rec.cols), stream),
+                "pika_rgrad_backward_fe_s")
         rec.version, rec.rows, rec.blank, rec.stream = rec.alias._version, rows, blank, stream
         _retained[ws.device.index] = rec
     return grads
@@ -428,8 +435,8 @@ class _RNNTLossFn(torch.autograd.Function):
         B, T, U1, V, blank = ctx.dims
         lam = ctx.fastemit_lambda
         lib = _lib.lib()
-        gc = grad_costs.to(torch.float32).contiguous()
         if ctx.lazy:
+            gc = grad_costs.to(torch.float32).contiguous()
             with torch.cuda.device(ws.device):
                 _lib.check(lib.pika_rnnt_loss_backward_fe(
                     _ptr(labels), _ptr(frames_lengths), _ptr(labels_lengths), B, T, U1, V, blank,
@@ -438,7 +445,7 @@ class _RNNTLossFn(torch.autograd.Function):
             lazy.lse = lse
             return lazy, None, None, None, None, None
         with torch.cuda.device(ws.device):
-            grads = _dense_backward(lib, ws, ctx.dims, labels, frames_lengths, labels_lengths, gc, lam)
+            grads = _dense_backward(lib, ws, ctx.dims, labels, frames_lengths, labels_lengths, grad_costs, lam)
         grads._pika_compact = CompactGrad(ws, (B, T, U1, V, blank), grads)
         return grads, None, None, None, None, None
 
